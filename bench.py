@@ -159,6 +159,37 @@ def pmc_traffic(path, n, shape, kname):
     return None, None
 
 
+DUMP_SAMPLE = 1 << 20          # --dump-outputs: positions drawn for the fixed sample of SA and BWT
+DUMP_SEED = 0x20261015
+DUMP_CHUNKS = 4096             # ... and sums over this many equal chunks of the whole block
+DUMP_MAX_BYTES = 64 << 20
+
+
+def last_step_outputs(sa_t, payload_t, n):
+    """What the timed path handed its caller in its last step -- the suffix array (int32 x n, None with --no-sa) and BWT || baseId
+    (n + 4 bytes) -- as float arrays small enough to keep: the values at a fixed, seeded sample of positions, baseId, and the sums of
+    DUMP_CHUNKS equal chunks of the whole SA and BWT (exact in float64), so that a difference anywhere in the block shows."""
+    import torch
+    idx = np.unique(np.random.default_rng(DUMP_SEED).integers(0, n, min(n, DUMP_SAMPLE)))
+    idx_t = torch.from_numpy(idx).to(payload_t.device)
+    bwt_t = payload_t[:n]
+    out = {"sample_index": idx.astype(np.float64),
+           "base_id": np.array([payload_t[n:].view(torch.int32).item()], np.float64),
+           "bwt_sample": bwt_t[idx_t].cpu().numpy().astype(np.float32),
+           "bwt_chunk_sums": bwt_t.view(DUMP_CHUNKS, -1).sum(dim=1, dtype=torch.int64).cpu().numpy().astype(np.float64)}
+    if sa_t is not None:
+        out["sa_sample"] = sa_t[idx_t].cpu().numpy().astype(np.float64)
+        out["sa_chunk_sums"] = sa_t.view(DUMP_CHUNKS, -1).sum(dim=1, dtype=torch.int64).cpu().numpy().astype(np.float64)
+    return out
+
+
+def dump_outputs(path, arrays):
+    assert sum(a.nbytes for a in arrays.values()) <= DUMP_MAX_BYTES
+    os.makedirs(path, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), a)
+
+
 PATH_NAMES = {0: "7 LSB passes + refinement rounds", 1: "streaming (hist16, 2 LSB passes, in-LDS bucket sort)",
               2: "closed form (clean periodic block)"}
 EXTRA_SHAPES = ("dna", "a", "ab", "motif", "text", "prose")
@@ -307,7 +338,12 @@ def main():
     ap.add_argument("--pass-b-buckets", type=int, default=-1, help="library option pass_b_buckets (default: the library's own, 1; 0 = pass B by ranges: A/B runs)")
     ap.add_argument("--backend", default="nccl", help="nccl (= RCCL; the measured configuration) | gloo (rehearsal of the N>1 "
                     "control flow on fewer GPUs than ranks: ranks share devices, the gather is staged through host memory)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps, write what the last one computed for rank 0's "
+                    "block to DIR/<name>.npy (float32/float64): SA and BWT at a fixed, seeded sample of positions, baseId, and sums of "
+                    "%d chunks of the whole SA and BWT; under %d MB in all (e.g. DIR = bench_outputs)" % (DUMP_CHUNKS, DUMP_MAX_BYTES >> 20))
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     import torch
     import archon_synth
@@ -424,6 +460,9 @@ def main():
         run_steps(args.steps)
         fence()
         dt = time.perf_counter() - t0
+        if args.dump_outputs and rank == 0:
+            # the last timed step went to feeder (K - 1) mod F; its payload is the pipe's last (the region below overwrites both)
+            dumped = last_step_outputs(sa_f[(args.steps - 1) % in_flight], pipe.last()[0], n)
         stage_flight = [s.asdict() for lst in stage_f for s in lst]
         feeders.close()
         # every feeder's last block against the reference's digests (the one-at-a-time region's goes through the ordinary gate below)
@@ -458,6 +497,8 @@ def main():
             step()
         fence()
         dt = time.perf_counter() - t0
+        if args.dump_outputs and rank == 0:
+            dumped = last_step_outputs(sa_t, pipe.last()[0], n)
     stage[:] = [s.asdict() for s in stage]
     pass_ms[:] = [s["ms_radix_pass_sum"] for s in stage]
     pass_cnt[:] = [s["radix_pass_timed"] for s in stage]
@@ -626,6 +667,8 @@ def main():
                 line["reference_elsewhere"] = {"what": "reference a7 on the whole %d MiB block, 1 core" % (n >> 20), "unit": "MB/s",
                                                "value": round(n / 1e6 / full["reference_sa_time_s"], 3), "seconds": round(full["reference_sa_time_s"], 1),
                                                "host": "development container, recorded in tests/golden/golden_full.json -- not this machine"}
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, dumped)
         print(json.dumps(line), flush=True)
     pipe.close()
     if dist is not None:

@@ -167,6 +167,23 @@ def run_ref_lms(x, tmpdir="/tmp"):
                 os.remove(tag + ext)
 
 
+# the inputs of test_oracle's live-reference tests; tests/golden/live_reference.json holds the reference's answers to them
+# (make_live_reference.py), so the tests check the oracle against the reference also where oracle/_ref is not built
+LIVE_SHAPES = (("random", 300000, 5), ("dna", 200001, 6), ("text", 123457, 7), ("motif", 99999, 8))
+
+
+def live_lms_inputs():
+    import archon_synth as S
+    rng = np.random.default_rng(5)
+    return [rng.integers(0, 256, 5000).astype(np.uint8), rng.integers(0, 2, 777).astype(np.uint8), S.gen_text(30000),
+            np.arange(256, dtype=np.uint8).repeat(3), np.frombuffer(b"a" * 100, np.uint8), np.frombuffer(b"ba", np.uint8)]
+
+
+def sha256_bytes(a, dtype=np.uint8):
+    import hashlib
+    return hashlib.sha256(np.ascontiguousarray(a, dtype).tobytes()).hexdigest()
+
+
 def lms_digest(count, items):
     import hashlib
     return hashlib.sha256(np.ascontiguousarray(count, "<u4").tobytes() + np.ascontiguousarray(items, "<u4").tobytes()).hexdigest()

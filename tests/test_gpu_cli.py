@@ -179,6 +179,36 @@ def test_bench_default_run_keeps_two_blocks_in_flight():
         assert all(v["sa_sha256_matches_reference"] is not False for v in line["shapes"].values())
 
 
+def test_bench_dump_outputs(tmp_path):
+    """bench.py --dump-outputs: the last timed step's SA and BWT || baseId as float .npy files -- the same arrays whether the steps ran
+    with two blocks in flight or one at a time, sums over the whole block that match its input, under 64 MB.  Not a measurement."""
+    import json
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    mib = 16
+    n = mib << 20
+    dumps = []
+    for extra in ([], ["--in-flight", "1"]):
+        d = tmp_path / ("out%d" % len(dumps))
+        r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--block-mib", str(mib),
+                            "--no-cpu-baseline", "--no-shapes", "--dump-outputs", str(d)] + extra, capture_output=True, text=True, timeout=280, cwd=root)
+        assert r.returncode == 0, r.stderr[-2000:]
+        line = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
+        assert line["steps"] == 3 and line["ms_per_step"] > 0 and line["config"]["gates_passed"] is True
+        dumps.append({f[:-4]: np.load(d / f) for f in os.listdir(d)})
+    a, b = dumps
+    assert sorted(a) == sorted(b) == ["base_id", "bwt_chunk_sums", "bwt_sample", "sa_chunk_sums", "sa_sample", "sample_index"]
+    assert sum(v.nbytes for v in a.values()) <= 64 << 20
+    for k in a:
+        assert a[k].dtype in (np.float32, np.float64) and np.array_equal(a[k], b[k]), k
+    x = S.gen_shape("random", n, block=0)
+    idx = a["sample_index"].astype(np.int64)
+    assert idx.size > 0 and (np.diff(idx) > 0).all() and idx[-1] < n
+    assert a["bwt_chunk_sums"].sum() == x.sum(dtype=np.int64) and a["sa_chunk_sums"].sum() == n * (n + 1) // 2
+    assert a["sa_sample"].min() >= 1 and a["sa_sample"].max() <= n and 0 <= a["base_id"][0] <= n
+
+
 def test_concurrent_host_threads(archon, oracle):
     """calls on one device from several host threads are serialised by the per-device mutex
     (ctypes releases the GIL during the call); every thread must get its own block's result."""

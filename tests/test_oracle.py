@@ -4,7 +4,8 @@
   * the brute-force statement of the definition (a7 sufCompare) on exhaustive small alphabets
   * tests/golden/golden.json -- outputs of the reference a7 binaries run in the development
     container (generator: tests/golden/make_golden.py)
-  * when oracle/_ref is present (development container), the live reference binaries
+  * tests/golden/live_reference.json -- the reference's answers on further seeds (make_live_reference.py), and,
+    when oracle/_ref is present (development container), the live reference binaries on the same inputs
 """
 import hashlib
 import itertools
@@ -18,6 +19,7 @@ import archon_synth as S
 import oracle_binding as OB
 
 GOLDEN = json.load(open(os.path.join(os.path.dirname(__file__), "golden", "golden.json")))
+LIVE = json.load(open(os.path.join(os.path.dirname(__file__), "golden", "live_reference.json")))
 
 
 def test_known_answers(oracle):
@@ -63,15 +65,17 @@ def test_golden_reference_outputs(oracle, case):
 
 
 def test_live_reference_lms(oracle):
-    """the reference's findLMS itself (when oracle/_ref/a7lms is present: development container and GPU box)"""
-    if not OB.ref_available("a7lms"):
-        pytest.skip("oracle/_ref/a7lms not built")
-    rng = np.random.default_rng(5)
-    for x in [rng.integers(0, 256, 5000).astype(np.uint8), rng.integers(0, 2, 777).astype(np.uint8), S.gen_text(30000),
-              np.arange(256, dtype=np.uint8).repeat(3), np.frombuffer(b"a" * 100, np.uint8), np.frombuffer(b"ba", np.uint8)]:
-        ref = OB.run_ref_lms(x)
+    """the reference's findLMS itself: its recorded answers (tests/golden/live_reference.json, make_live_reference.py) and,
+    when oracle/_ref/a7lms is present (development container and GPU box), the live binary on the same inputs"""
+    live = OB.ref_available("a7lms")
+    inputs = OB.live_lms_inputs()
+    assert len(inputs) == len(LIVE["lms"])
+    for x, rec in zip(inputs, LIVE["lms"]):
         count, items = oracle.lms_select(x)
-        assert ref is not None and (ref[0] == count).all() and ref[1].size == items.size and (ref[1] == items).all()
+        assert x.size == rec["n"] and items.size == rec["lms_n1"] and OB.lms_digest(count, items) == rec["sha256_lms"]
+        if live:
+            ref = OB.run_ref_lms(x)
+            assert ref is not None and (ref[0] == count).all() and ref[1].size == items.size and (ref[1] == items).all()
 
 
 def test_random_small_vs_definition(oracle):
@@ -110,12 +114,17 @@ def test_hist_and_scatter(oracle):
     assert (oracle.radix_scatter(x) == np.sort(x, kind="stable")).all()
 
 
-@pytest.mark.skipif(not OB.ref_available("a7ref_nt"), reason="oracle/_ref not built (no /root/reference here)")
 def test_live_reference(oracle):
-    """development container only: the oracle against the reference binary on fresh seeds"""
-    for shape, n, block in (("random", 300000, 5), ("dna", 200001, 6), ("text", 123457, 7), ("motif", 99999, 8)):
+    """the oracle against the reference's recorded answers on fresh seeds (tests/golden/live_reference.json) and, when oracle/_ref
+    is present (development container), against the reference binary itself"""
+    live = OB.ref_available("a7ref_nt")
+    assert len(OB.LIVE_SHAPES) == len(LIVE["shapes"])
+    for (shape, n, block), rec in zip(OB.LIVE_SHAPES, LIVE["shapes"]):
+        assert (shape, n, block) == (rec["shape"], rec["n"], rec["block"])
         x = S.gen_shape(shape, n, block=block)
-        r = OB.run_ref(x, "a7ref_nt")
-        assert r is not None and r["validate"] == 1
         P, bwt, base = oracle.forward(x)
-        assert (P == r["P"]).all() and (bwt == r["bwt"]).all() and base == r["base"]
+        assert OB.sha256_bytes(P, "<u4") == rec["sha256_P"] and OB.sha256_bytes(bwt) == rec["sha256_bwt"] and base == rec["base_id"]
+        if live:
+            r = OB.run_ref(x, "a7ref_nt")
+            assert r is not None and r["validate"] == 1
+            assert (P == r["P"]).all() and (bwt == r["bwt"]).all() and base == r["base"]
