@@ -69,7 +69,7 @@ unsigned Archon::countMemory() const
 bool Archon::validate()
 {
     // The reference walks P and str on the host (archon.cpp:862-874).  Here enCompute has left the block, its suffix array
-    // and its BWT on the device: the check runs on what is there -- no 5N-byte upload, no second gather of str[P[i]].
+    // and its BWT on the device: the check runs on what is there -- no 5N-byte upload; the resident BWT is compared with str[P[i]] row by row.
     // (An object that has not computed anything -- or has read another block since: the reference would then test the old P
     //  against the new str and fail, archon.cpp:862-874 -- has nothing resident: the host arrays are checked instead.)
     last_rc = (blk && resident) ? archon_hip_block_validate(blk) : ARCHON_E_ARG;

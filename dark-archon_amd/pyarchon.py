@@ -347,13 +347,16 @@ def hist256_dev(x_t, out_t):
 
 
 def validate_dev(x_t, sa_t):
+    """True if and only if sa_t is the a7 suffix array of x_t (include/archon_hip.h: archon_hip_validate)"""
     dev = x_t.device.index or 0
     return bool(_check(lib().archon_hip_validate_dev(ctypes.c_void_p(x_t.data_ptr()), x_t.numel(),
                                                      ctypes.c_void_p(sa_t.data_ptr()), dev, _stream_ptr())))
 
 
 def validate_resident_dev(x_t, sa_t, bwt_t, base_id):
-    """Archon::validate on the outputs of a forward pass that are still on the device (no second gather of x[sa[i]])"""
+    """Archon::validate on the outputs of a forward pass that are still on the device: True if and only if sa_t is the a7
+    suffix array of x_t, bwt_t its BWT (bwt_t[i] == x_t[sa_t[i]], x_t[0] where sa_t[i] == n, compared row by row) and
+    base_id its primary index"""
     dev = x_t.device.index or 0
     return bool(_check(lib().archon_hip_validate_resident_dev(ctypes.c_void_p(x_t.data_ptr()), x_t.numel(), ctypes.c_void_p(sa_t.data_ptr()),
                                                               ctypes.c_void_p(bwt_t.data_ptr()), int(base_id), dev, _stream_ptr())))

@@ -73,8 +73,8 @@ int archon_hip_forward(const uint8_t *x, uint32_t n, uint32_t *sa_or_null,
 /* ---- resident blocks: the device side of ONE block-coder object (class Archon, bwt/a7/src/archon.h:8-29) ----------
  * The reference's caller runs read -> enCompute -> validate -> enWrite on one object (main.cpp:39-46), and the host
  * must stay within 5N + O(1) bytes.  So enCompute leaves the block, its suffix array and its BWT resident in HBM, in
- * buffers that belong to the handle (6N device bytes): validate then checks what is there (no upload, no second
- * gather of x[sa[i]]), enWrite reads the BWT back in pieces through any O(1) bounce buffer.  Any number of handles,
+ * buffers that belong to the handle (6N device bytes): validate then checks what is there (no upload; the resident BWT
+ * is compared with its gather x[sa[i]] row by row), enWrite reads the BWT back in pieces through any O(1) bounce buffer.  Any number of handles,
  * on any threads; a handle is used by one thread at a time (as an Archon object is: a7 is re-entrant per object). */
 typedef struct archon_hip_block archon_hip_block;
 int  archon_hip_block_create(int dev, archon_hip_block **out);
@@ -83,9 +83,9 @@ void archon_hip_block_destroy(archon_hip_block *b);
 int  archon_hip_block_forward(archon_hip_block *b, const uint8_t *x, uint32_t n, uint32_t *sa_or_null, uint32_t *base_id);
 /* the gather loop of Archon::enWrite (archon.cpp:887-900), already done on the device: bytes [offset, offset+len) of the BWT */
 int  archon_hip_block_read_bwt(archon_hip_block *b, uint32_t offset, uint32_t len, uint8_t *dst);
-/* Archon::validate (archon.cpp:862-874) on the resident block: every sa[i] in 1..n, exactly one n and on the primary
- * row, the LF rule for every other row, the BWT a permutation of the block.  1 = consistent, 0 = not, <0 = error
- * (ARCHON_E_ARG when the last forward on the handle kept no suffix array). */
+/* Archon::validate (archon.cpp:862-874) on the resident block, by archon_hip_validate_resident_dev: 1 if and only if the
+ * resident SA is the a7 suffix array of the resident block, the resident BWT its BWT and the primary index its row of n;
+ * 0 = not, <0 = error (ARCHON_E_ARG when the last forward on the handle kept no suffix array). */
 int  archon_hip_block_validate(archon_hip_block *b);
 /* (archon_hip_stats is defined under "measurement" below) */
 struct archon_hip_stats;
@@ -109,7 +109,12 @@ int archon_hip_inverse(const uint8_t *bwt, uint32_t n, uint32_t base_id,
 /* 256-bin histogram of x[n] (host pointers). */
 int archon_hip_hist256(const uint8_t *x, size_t n, uint32_t out[256], int dev);
 
-/* LF-consistency of sa against x; returns 1 = consistent, 0 = not, <0 = error. */
+/* Archon::validate, stricter: returns 1 if and only if sa is the a7 suffix array of x, 0 = not, <0 = error.
+ * The check: every sa[i] in 1..n, exactly one row holds n (the primary row), and with bwt[i] = x[sa[i]] (x[0] on the
+ * primary row) the LF rule sa[T[i]] == sa[i] + 1 on every other row, T the LF table of (bwt, primary row).  Its buckets
+ * come from the byte counts in byte order with the primary row ranked last in its bucket, so it pins the order itself:
+ * the counts fix the first column, each LF step extends the sorted prefix by one byte, the end of the string sorts last.
+ * (a7's own Archon::validate takes its buckets from sa and accepts some permutations that are not the suffix array.) */
 int archon_hip_validate(const uint8_t *x, uint32_t n, const uint32_t *sa, int dev);
 
 /* SA -> BWT + primary index for a suffix array the caller already holds (Archon::enWrite, archon.cpp:887-900):
@@ -139,9 +144,11 @@ int archon_hip_inverse_dev(const uint8_t *d_bwt, uint32_t n, uint32_t base_id,
                            uint8_t *d_x_out, int dev, void *stream);
 int archon_hip_hist256_dev(const uint8_t *d_x, size_t n, uint32_t *d_out256, int dev, void *stream);
 int archon_hip_validate_dev(const uint8_t *d_x, uint32_t n, const uint32_t *d_sa, int dev, void *stream);
-/* Archon::validate for a caller that holds the forward pass's outputs on the device: like archon_hip_validate_dev, but the
- * rows' symbols are taken from d_bwt (checked to be a permutation of the block) instead of being gathered again, and
- * base_id must be the row that holds n.  This is what archon_hip_block_validate runs.  1 / 0 / <0. */
+/* Archon::validate for a caller that holds the forward pass's outputs on the device: returns 1 if and only if d_sa is the
+ * a7 suffix array of d_x, d_bwt its BWT and base_id its primary index (the row that holds n); 0 = not, <0 = error.  The LF
+ * table is built from d_bwt, and one sweep checks archon_hip_validate_dev's rules together with d_bwt[i] == d_x[d_sa[i]]
+ * (d_x[0] on the primary row) -- the same rows as archon_hip_validate_dev on d_x, plus the BWT and the primary index.  This
+ * is what archon_hip_block_validate runs. */
 int archon_hip_validate_resident_dev(const uint8_t *d_x, uint32_t n, const uint32_t *d_sa, const uint8_t *d_bwt, uint32_t base_id,
                                      int dev, void *stream);
 int archon_hip_sa_to_bwt_dev(const uint8_t *d_x, uint32_t n, const uint32_t *d_sa, uint8_t *d_bwt, uint32_t *d_base_id,

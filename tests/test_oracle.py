@@ -99,6 +99,61 @@ def test_validate_detects_errors(oracle):
     assert not oracle.check_sorted(x, Q)
 
 
+def test_a7_validate_is_not_a_sortedness_check(oracle):
+    """Archon::validate (archon.cpp:862-874, oracle.validate) takes each bucket's first row from sa itself, so it accepts
+    some permutations that are not the suffix array: for x = "ab" it accepts {2, 1}, while the a7 suffix array is {1, 2}.
+    The device validate is stricter (1 if and only if sa IS the suffix array, test_device_validate_rule_is_exact), so the
+    GPU tests of the validators take oracle.sa, not oracle.validate, as their expected answer."""
+    x = np.frombuffer(b"ab", np.uint8)
+    assert list(oracle.sa(x)) == [1, 2]
+    assert oracle.validate(x, np.array([2, 1], np.uint32))
+    assert not oracle.check_sorted(x, np.array([2, 1], np.uint32))
+
+
+def device_validate_rule(x, P):
+    """The rule of archon_hip_validate / validate_dev (csrc/inverse.hiph: k_val_bwt, lf_build_launch, k_val_check) in numpy:
+    every value in 1..n, exactly one row (the primary row) holds n, bwt[i] = x[P[i]] (x[0] on the primary row), and with T
+    the LF table of (bwt, primary row) -- buckets from the byte counts in byte order, the primary row last in its bucket --
+    P[T[i]] == P[i] + 1 on every other row."""
+    x = np.asarray(x, np.uint8)
+    P = np.asarray(P, np.int64)
+    n = x.size
+    if ((P < 1) | (P > n)).any() or (P == n).sum() != 1:
+        return False
+    base = int(np.flatnonzero(P == n)[0])
+    bwt = x[np.where(P == n, 0, P)].astype(np.int64)
+    key = bwt * 2
+    key[base] += 1
+    T = np.empty(n, np.int64)
+    T[np.argsort(key, kind="stable")] = np.arange(n)
+    rows = np.arange(n) != base
+    return bool((P[T[rows]] == P[rows] + 1).all())
+
+
+def test_device_validate_rule_is_exact(oracle):
+    """the device rule accepts exactly the a7 suffix array: every string of length 1..5 over {0, 1, 255}, every permutation
+    of 1..n (31 287 cases), and for n <= 3 every array over 0..n+1 (repeats, values out of range).  Why it holds, by
+    induction on key length: the byte counts fix the first column, the stable LF map extends sortedness by one byte per
+    step, and the end of the string (the primary row, rolled last) sorts last."""
+    cases = accepted_a7 = 0
+    for n in range(1, 6):
+        perms = [np.array(p, np.uint32) + 1 for p in itertools.permutations(range(n))]
+        for t in itertools.product((0, 1, 255), repeat=n):
+            x = np.array(t, np.uint8)
+            sa = oracle.sa(x)
+            for P in perms:
+                want = bool((P == sa).all())
+                assert device_validate_rule(x, P) == want, (t, list(P))
+                accepted_a7 += oracle.validate(x, P) and not want
+                cases += 1
+            if n <= 3:
+                for P in itertools.product(range(n + 2), repeat=n):
+                    P = np.array(P, np.uint32)
+                    assert device_validate_rule(x, P) == bool((P == sa).all()), (t, list(P))
+    assert cases == 31287
+    assert accepted_a7 > 0          # the a7 rule accepts wrong permutations on the same set
+
+
 def test_lf_build_base_last(oracle):
     """row baseId ranks last in its bucket (archon.cpp:931-933)"""
     bwt = np.frombuffer(b"aaaa", np.uint8)

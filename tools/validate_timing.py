@@ -1,5 +1,5 @@
 """Archon::validate (bwt/a7/src/archon.cpp:862-874) behind a forward pass: on what the pass left resident
-(archon_hip_block_validate: no upload, no second gather) against the host-buffer form (archon_hip_validate: 5N bytes up,
+(archon_hip_block_validate: no upload; the resident BWT compared with x[sa[i]]) against the host-buffer form (archon_hip_validate: 5N bytes up,
 x[sa[i]] gathered again) -- wall clock of both, same block, same process."""
 import ctypes, json, os, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
