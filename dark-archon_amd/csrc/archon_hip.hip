@@ -107,10 +107,10 @@ int ctx_get(int dev, Ctx **out)
         c->dev = dev;
         memset(&c->stats, 0, sizeof c->stats);
         ARCHON_HIP_TRY(hipStreamCreateWithFlags(&c->own_stream, hipStreamNonBlocking));
-        ARCHON_HIP_TRY(hipHostMalloc((void **)&c->h_mail, Ctx::kMailWords * sizeof(uint32_t), hipHostMallocDefault));
-        memset(c->h_mail, 0, Ctx::kMailWords * sizeof(uint32_t));
+        ARCHON_HIP_TRY(hipHostMalloc((void **)&c->h_mail, mail::kWords * sizeof(uint32_t), hipHostMallocDefault));
+        memset(c->h_mail, 0, mail::kWords * sizeof(uint32_t));
         ARCHON_HIP_TRY(hipHostGetDevicePointer((void **)&c->h_mail_dev, c->h_mail, 0));      // (coherent: bs::k_mail writes the block's summary there)
-        ARCHON_HIP_TRY(hipMalloc((void **)&c->d_mail, Ctx::kMailWords * sizeof(uint32_t)));
+        ARCHON_HIP_TRY(hipMalloc((void **)&c->d_mail, mail::kDevWords * sizeof(uint32_t)));
         g_ctx[dev][slot] = c;
     }
     *out = g_ctx[dev][slot];
@@ -178,7 +178,7 @@ int ctx_io(Ctx *c, int slot, size_t bytes, void **out)
 }
 
 // ------------------------------------------------------------------ forward driver
-// Device arena of one forward call (one hipMalloc per device, bump-allocated).  Lifetimes decide what shares memory:
+// Device arena of one forward call (one hipMalloc per context, carved by fwd_tier1 / fwd_tier2 below).  Lifetimes decide what shares memory:
 //   keyA / keyB (8N each), the value block (8N)   first stage (pass records, or the (key, item) pairs of the 7-pass sort);
 //        then the B rounds' (group | key, item) pairs, k_b_finish's rank log in the key buffer the sort left free, and --
 //        between rounds, when all of that is dead -- the rank writer's two record regions and the pair chains' sort buffers
@@ -196,53 +196,28 @@ static uint32_t h16_parts(int dev) { return eff_pass_ranges(dev) > 256u ? (uint3
 // groups the B list / a mid directory can hold: a group of the B list is longer than the S list's limit or straddles a
 // tile of the sweep that made it (at most one per tile)
 static size_t mid_dir_cap(uint32_t n) { return (size_t)n / 512 + 64; }
-// The last bytes of the first-tier arena are never bump-allocated: the closed form of a clean periodic block (periodic.hiph)
-// keeps the nested transform's results there -- suffix array, BWT and row offsets of the 2p-byte block, p <= 65 536 --
-// while the nested call uses the arena from its bottom.
+// The last kClosedTail bytes of the first-tier arena lie outside every forward call's cursor: the closed form of a clean periodic
+// block (periodic.hiph) keeps the nested transform's results there -- suffix array, BWT and row offsets of the 2p-byte block,
+// p <= 65 536 -- while the nested call carves the arena from its bottom.
 static constexpr size_t kClosedTail = 2u << 20;
-// Tier 1: what every block needs (the first stage and its tables).  Tier 2: what only the general stage needs.
-static size_t forward_stage1_bytes(uint32_t n, int dev, bool own_sa)
-{
-    const size_t N = n;
-    size_t b = 0;
-    auto add = [&](size_t bytes) { b += (bytes + 255) & ~size_t(255); };
-    add(N + 64);                    // aligned copy of x (when needed)
-    add(N + 64);                    // packed key text y (compacted alphabets)
-    add(8 * key_words(n)); add(8 * key_words(n));       // keyA keyB
-    add(8 * key_words(n));          // valA | valB
-    if (own_sa) add(4 * N);         // sa (when the caller wants none)
-    add(4 * rs::status_words(n));
-    add(4 * 8 * 256); add(4 * 8 * 256);       // ghist, gstart
-    add(4 * 65536);                           // hist16
-    add(4 * (size_t)bs::kMaxRanges * 256);    // range table of the passes
-    add(sizeof(bs::Prep));
-    add(sizeof(uint2) * kTieListCap);
-    add(sizeof(uint4) * (size_t)bs::kMaxRanges * bs::kTrashWords);
-    add(4 * (size_t)h16_parts(dev) * 32768u);        // partial two-byte counts, one table per workgroup of the count
-    add(4 * 1024);                            // counts, starts, ticket, err, base, totals, TieCtl
-    add(kClosedTail);
-    return b + (1u << 16);
+
+// The forward call's 1024 scratch words (FwdBuf::small), cleared by bs::k_prep, which sets the period probe's result word to "none".
+namespace fwd_small {
+constexpr uint32_t kCounts = 0;     // [256] byte counts of a small block (launch_hist256)
+constexpr uint32_t kTotal = 600;    // scan totals; the entries of the first B list (k_first_groups)
+constexpr uint32_t kTicket = 601;   // look-back ticket of the sorts and the list kernels (rs::Scratch)
+constexpr uint32_t kErr = 602;      // consistency flag (rs::Scratch)
+constexpr uint32_t kBase = 603;     // the primary index
+constexpr uint32_t kSettled = 604;  // rows the run shortcut settled
+constexpr uint32_t kLastBrk = 606;  // [2] the period's last real break, how many breaks
+constexpr uint32_t kProbe = 610;    // [pf::kCleanWords] the period probe: period, votes, breaks, whole text compared
+constexpr uint32_t kCtl = 640;      // bs::TieCtl
+constexpr uint32_t kFu = 700;       // [6] counters of the rounds (general_stage)
+constexpr uint32_t kLut = 900;      // [64] the packed keys' recode table (256 bytes)
+constexpr uint32_t kWords = 1024;
+static_assert(kCounts + 256 <= kTotal && kLastBrk + 2 <= kProbe && kProbe + pf::kCleanWords <= kCtl &&
+              kCtl + sizeof(bs::TieCtl) / 4 <= kFu && kFu + 6 <= kLut && kLut + 64 <= kWords, "forward scratch words overlap");
 }
-static size_t forward_stage2_bytes(uint32_t n)
-{
-    const size_t N = n;
-    size_t b = 0;
-    auto add = [&](size_t bytes) { b += (bytes + 255) & ~size_t(255); };
-    add(4 * (N + 1));               // rank
-    add(4 * N);                     // brk: the run shortcut's break table, kept for the break-distance round
-    add(4 * N); add(4 * N);         // v / gstart, keep
-    for (int i = 0; i < 6; ++i) add(4 * N);   // upos, ug, uitem (double-buffered): the B list
-    add(4 * (N / 2 + 8));           // the pair list's {row, flag} words
-    add(4 * scan_temp_words(N));
-    add(8 * N + 64); add(8 * N + 64); add(8 * N + 64);      // the S lists of the refinement rounds (double-buffered) and the rank log
-    add(4 * (rw::kMaxCoarse + rw::fine_buckets(n) + 64));
-    add(4 * 4 * (mid_dir_cap(n) + 8));                          // directory of the B list: first entry, first row, place in the big list, number among the big groups
-    for (int i = 0; i < 4; ++i) add(16 * (mid_dir_cap(n) + 8)); // directories of the two mid classes, double-buffered
-    add(4 * fwd::kMcWords);
-    add(4 * ((size_t)n / fwd::kBfTile + 8)); add(4 * ((size_t)n / fwd::kBfTile / 32 + 8));       // per tile of the B list: groups before it, "holds big entries"
-    return b + (1u << 16);
-}
-static size_t forward_arena_bytes(uint32_t n, int dev) { return forward_stage1_bytes(n, dev, true); }
 
 struct FwdBuf {
     uint8_t *xa;
@@ -263,10 +238,73 @@ struct FwdBuf {
     uint4 *dirS[2], *dirL[2];
 };
 
+// Tier 1: what every block needs (the first stage and its tables).  Returns the bytes to ask for: these, the closed-form tail
+// and slack.
+static size_t fwd_tier1(Carve &a, FwdBuf &B, uint32_t n, int dev, bool own_sa)
+{
+    B.xa = a.take<uint8_t>((size_t)n + 64);                     // aligned copy of x (when needed)
+    B.y = a.take<uint8_t>((size_t)n + 64);                      // packed key text y (compacted alphabets)
+    B.keyA = a.take<uint64_t>(key_words(n));
+    B.keyB = a.take<uint64_t>(key_words(n));
+    B.valA = reinterpret_cast<uint32_t *>(a.take<uint64_t>(key_words(n)));      // valA | valB
+    B.valB = B.valA ? B.valA + ((size_t)n + 16) : nullptr;
+    B.sa_own = own_sa ? a.take<uint32_t>(n) : nullptr;          // sa (when the caller wants none)
+    B.sc.d_status = a.take<uint32_t>(rs::status_words(n));
+    B.sc.d_ghist = a.take<uint32_t>(8 * 256);
+    B.sc.d_gstart = a.take<uint32_t>(8 * 256);
+    B.hist16 = a.take<uint32_t>(65536);                         // } contiguous: zeroed by ONE memset per count
+    B.rhist = a.take<uint32_t>((size_t)bs::kMaxRanges * 256);   // } (hist16, range table of the passes, the counters that
+    B.prep = a.take<bs::Prep>(1);                               // }  open Prep)
+    B.tie_list = a.take<uint2>(kTieListCap);
+    B.trash = a.take<uint4>((size_t)bs::kMaxRanges * bs::kTrashWords);
+    B.h16part = a.take<uint32_t>((size_t)h16_parts(dev) * 32768u);   // partial two-byte counts, one table per workgroup of the count
+    B.small = a.take<uint32_t>(fwd_small::kWords);
+    return a.off + kClosedTail + (1u << 16);
+}
+
+// Tier 2: what only the general stage needs.  Returns the bytes to ask for.
+static size_t fwd_tier2(Carve &a, FwdBuf &B, uint32_t n)
+{
+    const size_t dir = mid_dir_cap(n) + 8;
+    B.rank = a.take<uint32_t>((size_t)n + 1);
+    B.brk = a.take<uint32_t>(n);                                // the run shortcut's break table, kept for the break-distance round
+    B.v = a.take<uint32_t>(n);                                  // first row of the group of every row
+    B.keep = a.take<uint32_t>(n);
+    for (int i = 0; i < 2; ++i) {                               // the B list (double-buffered)
+        B.upos[i] = a.take<uint32_t>(n);
+        B.ug[i] = a.take<uint32_t>(n);
+        B.uitem[i] = a.take<uint32_t>(n);
+    }
+    B.pairw = a.take<uint32_t>((size_t)n / 2 + 8);              // the pair list's {row, flag} words
+    B.scan_tmp = a.take<uint32_t>(scan_temp_words(n));
+    B.slist[0] = a.take<uint2>((size_t)n + 8);                  // the S lists of the refinement rounds (double-buffered)
+    B.slist[1] = a.take<uint2>((size_t)n + 8);
+    B.rlog = a.take<uint2>((size_t)n + 8);                      // the rank log
+    B.dst = reinterpret_cast<uint32_t *>(B.rlog);               // (scratch of the run shortcut / the scans before the rounds)
+    B.rwb.cnt1 = a.take<uint32_t>(rw::kMaxCoarse + rw::fine_buckets(n) + 64);
+    B.rwb.cnt2 = B.rwb.cnt1 ? B.rwb.cnt1 + rw::kMaxCoarse : nullptr;
+    B.gdir_off = a.take<uint32_t>(dir);                         // directory of the B list: first entry, first row, place in the
+    B.gdir_row = a.take<uint32_t>(dir);                         // big list, number among the big groups
+    B.gcls = a.take<uint32_t>(dir);
+    B.gbig = a.take<uint32_t>(dir);
+    for (int i = 0; i < 2; ++i) {                               // directories of the two mid classes, double-buffered
+        B.dirS[i] = a.take<uint4>(dir);
+        B.dirL[i] = a.take<uint4>(dir);
+    }
+    B.mc = a.take<uint32_t>(fwd::kMcWords);
+    B.tile_g0 = a.take<uint32_t>((size_t)n / fwd::kBfTile + 8);         // per tile of the B list: groups before it,
+    B.tile_big = a.take<uint32_t>((size_t)n / fwd::kBfTile / 32 + 8);   // "holds big entries"
+    return a.off + (1u << 16);
+}
+
+static_assert(fwd::kMcWords <= mail::kRounds.len && fwd::kMcWords <= mail::kRoundsInit.len, "the mid lists' counters in the mailbox");
+static_assert(2 * fwd::kGapSlots <= mail::kGapTable.len, "the gap table in the mailbox");
+static_assert(pf::kCleanWords <= mail::kProbe.len, "the period probe in the mailbox");
+
 // A5 + A7 for whatever the first stage left tied.  On entry (k_first_groups): sa[] holds the items in first-stage order,
 // B.v[i] = first row of the group of row i, and -- ws_ready -- the two lists of the refinement rounds (rounds.hiph): S =
-// entries of groups of at most fwd::kFuMax rows in B.slist[0] (small + 700 counts them), B = the longer groups as
-// (row, group start, item) triples in buffer 0 (small + 600 counts them, small + 703 their groups).  Runs the run
+// entries of groups of at most fwd::kFuMax rows in B.slist[0] (fwd_small::kFu counts them), B = the longer groups as
+// (row, group start, item) triples in buffer 0 (fwd_small::kTotal counts them, fwd_small::kFu + 3 their groups).  Runs the run
 // shortcut for periodic blocks, text rounds, the rank table, doubling rounds with the pair chains.  Rows take their
 // BWT symbol when they become final.
 static int general_stage(Ctx *c, hipStream_t s, FwdBuf &B, const uint8_t *d_x, uint32_t n, uint32_t *sa, uint32_t h0,
@@ -288,12 +326,14 @@ static int general_stage(Ctx *c, hipStream_t s, FwdBuf &B, const uint8_t *d_x, u
     auto trace = [](const char *) {};
 #endif
     trace("enter");
-    uint32_t *d_total = B.small + 600;
-    uint32_t *d_fu = B.small + 700;              // [0] entries appended to the next S list, [1] rank log entries, [2] the next B list, [3] its groups, [4] pairs listed, [5] pairs seen
-    ARCHON_HIP_TRY(hipMemcpyAsync(c->h_mail, d_total, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
-    ARCHON_HIP_TRY(hipMemcpyAsync(c->h_mail + 4, d_fu, 4 * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+    uint32_t *rd = c->h_mail + mail::kRead.at;   // readback words
+    const uint32_t *h_mc = c->h_mail + mail::kRounds.at;     // the mid lists' counters (fwd::kMc*) after a round
+    uint32_t *d_total = B.small + fwd_small::kTotal;
+    uint32_t *d_fu = B.small + fwd_small::kFu;              // [0] entries appended to the next S list, [1] rank log entries, [2] the next B list, [3] its groups, [4] pairs listed, [5] pairs seen
+    ARCHON_HIP_TRY(hipMemcpyAsync(rd, d_total, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+    ARCHON_HIP_TRY(hipMemcpyAsync(rd + 4, d_fu, 4 * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
     ARCHON_SYNC(s);
-    const uint32_t ms_first = ws_ready ? c->h_mail[4] : 0u, mb_first = c->h_mail[0], groups_first = c->h_mail[7];
+    const uint32_t ms_first = ws_ready ? rd[4] : 0u, mb_first = rd[0], groups_first = rd[7];
     uint32_t m = ms_first + mb_first;
     st.unresolved_initial = m;
     uint32_t z_period = 0;                       // period of the break table in B.brk while its rounds (do_round modes 2, 3) can still settle something
@@ -320,22 +360,23 @@ static int general_stage(Ctx *c, hipStream_t s, FwdBuf &B, const uint8_t *d_x, u
                                                             // a list buffer of a small block is shorter than the table)
             ARCHON_HIP_TRY(hipMemsetAsync(tab, 0, 2 * fwd::kGapSlots * sizeof(uint32_t), s));
             hipLaunchKernelGGL(fwd::k_gap_sample, dim3(div_up(div_up(n, fwd::kGapStride), 256)), dim3(256), 0, s, sa, B.v, n, tab);
-            ARCHON_HIP_TRY(hipMemcpyAsync(c->h_mail, tab, 2 * fwd::kGapSlots * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+            const uint32_t *h_tab = c->h_mail + mail::kGapTable.at;
+            ARCHON_HIP_TRY(hipMemcpyAsync(c->h_mail + mail::kGapTable.at, tab, 2 * fwd::kGapSlots * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
             ARCHON_SYNC(s);
             c->launches += 1;
             uint64_t total = 0;
             uint32_t best = 0;
             for (uint32_t i = 0; i < fwd::kGapSlots; ++i) {
-                total += c->h_mail[i];
-                if (c->h_mail[i] > c->h_mail[best]) best = i;
+                total += h_tab[i];
+                if (h_tab[i] > h_tab[best]) best = i;
             }
-            p = c->h_mail[fwd::kGapSlots + best];
-            dominant = (uint64_t)c->h_mail[best] * 4 >= total;
+            p = h_tab[fwd::kGapSlots + best];
+            dominant = (uint64_t)h_tab[best] * 4 >= total;
         }
         if (p >= 1 && p < n && dominant) {
-            uint32_t *brk = B.brk, *ginfo = B.dst, *gend = B.keep, *settled = B.small + 601;
+            uint32_t *brk = B.brk, *ginfo = B.dst, *gend = B.keep, *settled = B.small + fwd_small::kSettled;
             uint32_t *gmin = B.ug[1], *gmax = B.uitem[1];       // the second triple buffers are idle
-            uint32_t *d_lastbrk = B.small + 606;
+            uint32_t *d_lastbrk = B.small + fwd_small::kLastBrk;
             if (!(brk_ready && p == p_hint)) {
                 ARCHON_HIP_TRY(hipMemsetAsync(d_lastbrk, 0, 2 * sizeof(uint32_t), s));  // [0] last real break, [1] how many
                 hipLaunchKernelGGL(fwd::k_period_breaks, dim3(div_up(div_up(n, 4), 256)), dim3(256), 0, s, d_x, n, p, brk, d_lastbrk);
@@ -350,27 +391,27 @@ static int general_stage(Ctx *c, hipStream_t s, FwdBuf &B, const uint8_t *d_x, u
             trace("chain_probe");
             hipLaunchKernelGGL(fwd::k_chain_apply, dim3(div_up(n, fwd::kChainRows)), dim3(256), 0, s, sa, B.v, ginfo, gend, gmin, gmax, brk, d_lastbrk, d_x, n, p, d_bwt, d_base, settled);
             trace("chain_apply");
-            ARCHON_HIP_TRY(hipMemcpyAsync(c->h_mail + 1, settled, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
-            ARCHON_HIP_TRY(hipMemcpyAsync(c->h_mail + 2, d_lastbrk + 1, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+            ARCHON_HIP_TRY(hipMemcpyAsync(rd + 1, settled, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+            ARCHON_HIP_TRY(hipMemcpyAsync(rd + 2, d_lastbrk + 1, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
             ARCHON_SYNC(s);
-            z_breaks = c->h_mail[2];
+            z_breaks = rd[2];
             c->launches += 8;
-            if (c->h_mail[1] >= m) {
+            if (rd[1] >= m) {
                 m = 0;                          // every tied row was settled: nothing to count or compact
-            } else if (c->h_mail[1] != 0 || !lists_ready) {
+            } else if (rd[1] != 0 || !lists_ready) {
                 lists_ready = false;
                 keep_ready = true;
                 // the tied set again, without the settled groups
                 hipLaunchKernelGGL(fwd::k_keep_flags, dim3(g256), dim3(256), 0, s, B.v, n, B.keep);
                 ARCHON_TRY(launch_scan<0>(s, B.keep, B.dst, n, B.scan_tmp, d_total));
-                ARCHON_HIP_TRY(hipMemcpyAsync(c->h_mail, d_total, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+                ARCHON_HIP_TRY(hipMemcpyAsync(rd, d_total, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
                 ARCHON_SYNC(s);
                 c->launches += 3;
-                m = c->h_mail[0];
+                m = rd[0];
             }
             trace("keep + scan again");
             st.period = p;
-            st.chain_items = c->h_mail[1];
+            st.chain_items = rd[1];
             if (m) z_period = p;                // what is left straddles defects of the period: one break-distance round once h >= p
         }
     }
@@ -384,8 +425,8 @@ static int general_stage(Ctx *c, hipStream_t s, FwdBuf &B, const uint8_t *d_x, u
     {
         uint32_t init[fwd::kMcWords] = {};
         init[fwd::kMcTop] = init[fwd::kMcTop + 1] = n;
-        memcpy(c->h_mail + 4400, init, sizeof init);                 // (words of their own: 4200.. take the rounds' counters)
-        ARCHON_HIP_TRY(hipMemcpyAsync(B.mc, c->h_mail + 4400, sizeof init, hipMemcpyHostToDevice, s));
+        memcpy(c->h_mail + mail::kRoundsInit.at, init, sizeof init);     // (words of their own: mail::kRounds takes the rounds' counters)
+        ARCHON_HIP_TRY(hipMemcpyAsync(B.mc, c->h_mail + mail::kRoundsInit.at, sizeof init, hipMemcpyHostToDevice, s));
     }
     int cs = 0;
     unsigned long long *fg_status = reinterpret_cast<unsigned long long *>(B.sc.d_status);
@@ -410,10 +451,10 @@ static int general_stage(Ctx *c, hipStream_t s, FwdBuf &B, const uint8_t *d_x, u
                            B.upos[1], B.ug[1], B.uitem[1], d_fu + 2, fg_status, B.sc.d_ticket, B.sc.d_err);
         ARCHON_HIP_TRY(hipGetLastError());
         c->launches += 2;
-        ARCHON_HIP_TRY(hipMemcpyAsync(c->h_mail, d_fu, 3 * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+        ARCHON_HIP_TRY(hipMemcpyAsync(rd, d_fu, 3 * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
         ARCHON_SYNC(s);
-        ms = c->h_mail[0];
-        mb = c->h_mail[2];
+        ms = rd[0];
+        mb = rd[2];
         bgroups = mb / (fwd::kFuMax + 1u) + 2u;          // every group left in B is longer than kFuMax
         cur = 1;
         if (ms + mb != m) { set_error("classification lost entries (%u + %u of %u)", ms, mb, m); return ARCHON_E_INTERNAL; }
@@ -455,7 +496,7 @@ static int general_stage(Ctx *c, hipStream_t s, FwdBuf &B, const uint8_t *d_x, u
         const int nxt = cur ^ 1;
         if (mid) {
             // the next list starts empty: no groups, its items from the top of the buffer downwards
-            // (fills, not copies out of the mailbox: the mailbox words 4200.. receive this round's counters further down)
+            // (fills, not copies out of the mailbox: mail::kRounds receives this round's counters further down)
             ARCHON_HIP_TRY(hipMemsetD32Async((hipDeviceptr_t)(B.mc + fwd::kMcSmall + nxt), 0, 1, s));
             ARCHON_HIP_TRY(hipMemsetD32Async((hipDeviceptr_t)(B.mc + fwd::kMcLarge + nxt), 0, 1, s));
             ARCHON_HIP_TRY(hipMemsetD32Async((hipDeviceptr_t)(B.mc + fwd::kMcTop + nxt), (int)n, 1, s));
@@ -470,15 +511,15 @@ static int general_stage(Ctx *c, hipStream_t s, FwdBuf &B, const uint8_t *d_x, u
                 hipLaunchKernelGGL(fwd::k_b_plan, dim3(1), dim3(1024), 0, s, B.gdir_off, B.gdir_row, mb, B.gcls, B.gbig, B.dirS[cur], B.dirL[cur], B.mc, (uint32_t)cur,
                                    (uint32_t)fwd::kMidSmallCap, (uint32_t)fwd::kMidLargeCap, (uint32_t)mid_dir_cap(n), B.sc.d_err, B.tile_big);
                 ARCHON_HIP_TRY(hipGetLastError());
-                ARCHON_HIP_TRY(hipMemcpyAsync(c->h_mail + 4200, B.mc, fwd::kMcWords * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+                ARCHON_HIP_TRY(hipMemcpyAsync(c->h_mail + mail::kRounds.at, B.mc, fwd::kMcWords * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
                 ARCHON_SYNC(s);
                 c->launches += 2;
-                if (c->h_mail[4200 + fwd::kMcGroups] > mid_dir_cap(n)) { set_error("B list of %u entries holds %u groups (directory: %zu)", mb, c->h_mail[4200], mid_dir_cap(n)); return ARCHON_E_INTERNAL; }
-                nS = c->h_mail[4200 + fwd::kMcSmall + cur];
-                nL = c->h_mail[4200 + fwd::kMcLarge + cur];
-                nbig = c->h_mail[4200 + fwd::kMcBigEntries];
-                nbig_groups = c->h_mail[4200 + fwd::kMcBigGroups];
-                mid_from_b = c->h_mail[4200 + fwd::kMcMidEntries];
+                if (h_mc[fwd::kMcGroups] > mid_dir_cap(n)) { set_error("B list of %u entries holds %u groups (directory: %zu)", mb, h_mc[fwd::kMcGroups], mid_dir_cap(n)); return ARCHON_E_INTERNAL; }
+                nS = h_mc[fwd::kMcSmall + cur];
+                nL = h_mc[fwd::kMcLarge + cur];
+                nbig = h_mc[fwd::kMcBigEntries];
+                nbig_groups = h_mc[fwd::kMcBigGroups];
+                mid_from_b = h_mc[fwd::kMcMidEntries];
                 if (nbig + mid_from_b != mb) { set_error("plan of the B list lost entries (%u + %u of %u)", nbig, mid_from_b, mb); return ARCHON_E_INTERNAL; }
             }
         }
@@ -573,10 +614,10 @@ static int general_stage(Ctx *c, hipStream_t s, FwdBuf &B, const uint8_t *d_x, u
         const bool flip = mid || mb != 0;           // (short groups that straddle a tile of k_b_finish's sweep stay in B for another round)
         // The round's counters come to the host BEFORE its rank updates are applied: how the S and mid lists' updates (the log) are
         // written depends on how many there are, and the host has to wait for these counters anyway.
-        if (mid) ARCHON_HIP_TRY(hipMemcpyAsync(c->h_mail + 4200, B.mc, fwd::kMcWords * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
-        ARCHON_HIP_TRY(hipMemcpyAsync(c->h_mail, d_fu, 6 * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+        if (mid) ARCHON_HIP_TRY(hipMemcpyAsync(c->h_mail + mail::kRounds.at, B.mc, fwd::kMcWords * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+        ARCHON_HIP_TRY(hipMemcpyAsync(rd, d_fu, 6 * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
         ARCHON_SYNC(s);
-        const uint32_t nlog = mode != 1 ? c->h_mail[1] : 0u;
+        const uint32_t nlog = mode != 1 ? rd[1] : 0u;
         // Rank updates, now that every key of the round has been read.  Dealt by item into windows of the table (rank_writer.hiph:
         // two partition sweeps + one window write, 0.6 ms whatever the number + 11 ps per update) they beat one random store each
         // (32 ps) from about 28 M updates on; the B list's updates are logged by position whenever that list is long (b_log).
@@ -592,19 +633,19 @@ static int general_stage(Ctx *c, hipStream_t s, FwdBuf &B, const uint8_t *d_x, u
             hipLaunchKernelGGL(fwd::k_rank_apply, dim3(div_up(nlog, 256)), dim3(256), 0, s, B.rlog, d_fu + 1, B.rank);
             ++c->launches;
         }
-        ms = c->h_mail[0];
-        mb = mb_round ? c->h_mail[2] : 0u;
-        bgroups = c->h_mail[3];
+        ms = rd[0];
+        mb = mb_round ? rd[2] : 0u;
+        bgroups = rd[3];
         if (mid) {
-            mdS = c->h_mail[4200 + fwd::kMcSmall + nxt];
-            mdL = c->h_mail[4200 + fwd::kMcLarge + nxt];
-            mm = n - c->h_mail[4200 + fwd::kMcTop + nxt];
+            mdS = h_mc[fwd::kMcSmall + nxt];
+            mdL = h_mc[fwd::kMcLarge + nxt];
+            mm = n - h_mc[fwd::kMcTop + nxt];
             if (mdS > mid_dir_cap(n) || mdL > mid_dir_cap(n)) { set_error("mid directory overflow (%u / %u groups)", mdS, mdL); return ARCHON_E_INTERNAL; }
         }
         if (flip) cur ^= 1;
         if (!b_only) cs ^= 1;
-        uint32_t np = chain ? c->h_mail[4] : 0u;
-        const uint32_t pairs_seen = chain ? np : c->h_mail[5];
+        uint32_t np = chain ? rd[4] : 0u;
+        const uint32_t pairs_seen = chain ? np : rd[5];
         if (np) {
             // the round's pairs by passage: sort the records by their smaller item, one look-up per run, spread, apply
             bool in2 = false;
@@ -618,10 +659,10 @@ static int general_stage(Ctx *c, hipStream_t s, FwdBuf &B, const uint8_t *d_x, u
                                B.slist[cs], d_fu);
             ARCHON_HIP_TRY(hipGetLastError());
             c->launches += 4;
-            ARCHON_HIP_TRY(hipMemcpyAsync(c->h_mail, d_fu, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+            ARCHON_HIP_TRY(hipMemcpyAsync(rd, d_fu, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
             ARCHON_SYNC(s);
-            const uint32_t back = c->h_mail[0] - ms;         // entries the pass could not settle (two per pair)
-            ms = c->h_mail[0];
+            const uint32_t back = rd[0] - ms;         // entries the pass could not settle (two per pair)
+            ms = rd[0];
             st.chain_pairs += np - back / 2u;
             if ((uint64_t)back > np) chain_cool = 3;         // fewer than half of the pairs settled: give the rounds some time
         }
@@ -769,86 +810,46 @@ static int forward_run(Ctx *c, hipStream_t s, const uint8_t *d_x_in, uint32_t n,
 #define ARCHON_HOST_STAMP(i) do { } while (0)
 #endif
     ARCHON_HOST_STAMP(0);
-    ARCHON_TRY(ctx_ensure_arena(c, forward_stage1_bytes(n, c->dev, d_sa_user == nullptr)));
-    c->arena_reset();
+    FwdBuf B;
+    memset(&B, 0, sizeof B);
+    { Carve count; ARCHON_TRY(ctx_ensure_arena(c, fwd_tier1(count, B, n, c->dev, d_sa_user == nullptr))); }
     c->launches = 0;
     if (depth == 0) t_sync_count = 0;
     archon_hip_stats &st = c->stats;
     memset(&st, 0, sizeof st);
     st.n = n;
 
-    FwdBuf B;
-    memset(&B, 0, sizeof B);
-    B.xa = c->alloc<uint8_t>((size_t)n + 64);
-    B.y = c->alloc<uint8_t>((size_t)n + 64);
-    B.keyA = c->alloc<uint64_t>(key_words(n));
-    B.keyB = c->alloc<uint64_t>(key_words(n));
-    B.valA = reinterpret_cast<uint32_t *>(c->alloc<uint64_t>(key_words(n)));
-    B.valB = B.valA ? B.valA + ((size_t)n + 16) : nullptr;
-    B.sa_own = d_sa_user ? nullptr : c->alloc<uint32_t>(n);
-    B.sc.d_status = c->alloc<uint32_t>(rs::status_words(n));
-    B.sc.d_ghist = c->alloc<uint32_t>(8 * 256);
-    B.sc.d_gstart = c->alloc<uint32_t>(8 * 256);
-    B.hist16 = c->alloc<uint32_t>(65536);                       // } contiguous: zeroed by ONE memset per count
-    B.rhist = c->alloc<uint32_t>((size_t)bs::kMaxRanges * 256);  // } (hist16, range table, the counters that
-    B.prep = c->alloc<bs::Prep>(1);                             // }  open Prep)
-    B.tie_list = c->alloc<uint2>(kTieListCap);
-    B.trash = c->alloc<uint4>((size_t)bs::kMaxRanges * bs::kTrashWords);
-    B.h16part = c->alloc<uint32_t>((size_t)h16_parts(c->dev) * 32768u);
-    B.small = c->alloc<uint32_t>(1024);
-    if (!B.small || (!d_sa_user && !B.sa_own)) {
-        set_error("arena exhausted");
+    // tier 1 from the arena's bottom up to the closed-form tail, which lies at a fixed distance from the arena's end
+    const size_t tail_at = (c->arena_bytes - kClosedTail) & ~size_t(255);
+    Carve a1{c->arena, 0, tail_at};
+    fwd_tier1(a1, B, n, c->dev, d_sa_user == nullptr);
+    if (!a1.ok()) {
+        set_error("arena exhausted (tier 1 of a %u-byte block reaches the closed-form tail)", n);
         return ARCHON_E_NOMEM;
     }
-    st.arena_bytes = c->arena_off;
+    st.arena_bytes = a1.off;
     // Tier 2, when the block first needs it (a periodic block's break table, the entry sweep of the general stage): rank table,
     // lists, logs, directories -- 70 N that a block the streaming stage settles never touches.
     auto general_buffers = [&]() -> int {
         if (B.rank) return ARCHON_OK;
-        ARCHON_TRY(ctx_ensure_arena2(c, forward_stage2_bytes(n)));
-        B.rank = c->alloc2<uint32_t>((size_t)n + 1);
-        B.brk = c->alloc2<uint32_t>(n);
-        B.v = c->alloc2<uint32_t>(n);
-        B.keep = c->alloc2<uint32_t>(n);
-        for (int i = 0; i < 2; ++i) {
-            B.upos[i] = c->alloc2<uint32_t>(n);
-            B.ug[i] = c->alloc2<uint32_t>(n);
-            B.uitem[i] = c->alloc2<uint32_t>(n);
-        }
-        B.pairw = c->alloc2<uint32_t>((size_t)n / 2 + 8);
-        B.scan_tmp = c->alloc2<uint32_t>(scan_temp_words(n));
-        B.slist[0] = c->alloc2<uint2>((size_t)n + 8);
-        B.slist[1] = c->alloc2<uint2>((size_t)n + 8);
-        B.rlog = c->alloc2<uint2>((size_t)n + 8);
-        B.dst = reinterpret_cast<uint32_t *>(B.rlog);               // (scratch of the run shortcut / the scans before the rounds)
+        { Carve count; ARCHON_TRY(ctx_ensure_arena2(c, fwd_tier2(count, B, n))); }
+        Carve a2{c->arena2, 0, c->arena2_bytes};
+        fwd_tier2(a2, B, n);
+        if (!a2.ok()) { set_error("arena exhausted (general stage)"); return ARCHON_E_NOMEM; }
         B.rwb.r1 = B.rwb.r2 = nullptr;
-        B.rwb.cnt1 = c->alloc2<uint32_t>(rw::kMaxCoarse + rw::fine_buckets(n) + 64);
-        B.rwb.cnt2 = B.rwb.cnt1 ? B.rwb.cnt1 + rw::kMaxCoarse : nullptr;
-        B.gdir_off = c->alloc2<uint32_t>(mid_dir_cap(n) + 8);
-        B.gdir_row = c->alloc2<uint32_t>(mid_dir_cap(n) + 8);
-        B.gcls = c->alloc2<uint32_t>(mid_dir_cap(n) + 8);
-        B.gbig = c->alloc2<uint32_t>(mid_dir_cap(n) + 8);
-        for (int i = 0; i < 2; ++i) {
-            B.dirS[i] = c->alloc2<uint4>(mid_dir_cap(n) + 8);
-            B.dirL[i] = c->alloc2<uint4>(mid_dir_cap(n) + 8);
-        }
-        B.mc = c->alloc2<uint32_t>(fwd::kMcWords);
-        B.tile_g0 = c->alloc2<uint32_t>((size_t)n / fwd::kBfTile + 8);
-        B.tile_big = c->alloc2<uint32_t>((size_t)n / fwd::kBfTile / 32 + 8);
-        if (!B.rank || !B.rlog || !B.rwb.cnt1 || !B.mc || !B.tile_big) { set_error("arena exhausted (general stage)"); return ARCHON_E_NOMEM; }
-        st.arena_bytes = c->arena_off + c->arena2_off;
+        st.arena_bytes = a1.off + a2.off;
         return ARCHON_OK;
     };
     uint32_t *small = B.small;
-    uint32_t *d_counts = small, *d_starts = small + 256;
-    B.sc.d_ticket = small + 601;
-    B.sc.d_err = small + 602;
-    uint32_t *d_base = small + 603;
-    bs::TieCtl *d_ctl = reinterpret_cast<bs::TieCtl *>(small + 640);
+    uint32_t *d_counts = small + fwd_small::kCounts;
+    B.sc.d_ticket = small + fwd_small::kTicket;
+    B.sc.d_err = small + fwd_small::kErr;
+    uint32_t *d_base = small + fwd_small::kBase;
+    bs::TieCtl *d_ctl = reinterpret_cast<bs::TieCtl *>(small + fwd_small::kCtl);
     B.sc.h_mail = c->h_mail;
     // (one launch clears the scratch words, arms the period probe's result word and clears the two-byte count's tables)
     const size_t count_zero_bytes = (size_t)(reinterpret_cast<char *>(&B.prep->rowtot[0]) - reinterpret_cast<char *>(B.hist16));
-    hipLaunchKernelGGL(bs::k_prep, dim3(256), dim3(256), 0, s, small, 1024u, 610u, reinterpret_cast<uint4 *>(B.hist16), (uint32_t)(count_zero_bytes / 16));
+    hipLaunchKernelGGL(bs::k_prep, dim3(256), dim3(256), 0, s, small, fwd_small::kWords, fwd_small::kProbe, reinterpret_cast<uint4 *>(B.hist16), (uint32_t)(count_zero_bytes / 16));
     static_assert(offsetof(bs::Prep, rowtot) % 16 == 0, "the count's tables end on a 16-byte boundary");
     bool count_tables_clear = true;
     ARCHON_HOST_STAMP(1);
@@ -909,7 +910,7 @@ static int forward_run(Ctx *c, hipStream_t s, const uint8_t *d_x_in, uint32_t n,
     // verdict comes to the host with the block's first round trip; k_rows_scan reads it too and lets the streaming kernels return.
     const int forced = g_route.force_path;       // (tests): 0 = 7-pass route, 1 = streaming stage, -1 = the block decides
     const bool closed_ok = depth == 0 && forced < 0 && n >= (1u << 16) && !route_off(kRtNoPeriodProbe) && !route_off(kRtNoChains) && !route_off(kRtNoClosedForm);
-    uint32_t *pres = small + 610;                // [0] period, [1] votes, [2] the text breaks it, [3] the whole text was compared
+    uint32_t *pres = small + fwd_small::kProbe;  // [0] period, [1] votes, [2] the text breaks it, [3] the whole text was compared
     bool probe_queued = false, probe_fetched = false;
     auto queue_probe = [&]() -> int {
         // (the result word was set to "none" and the votes and flags behind it cleared by k_prep)
@@ -924,7 +925,7 @@ static int forward_run(Ctx *c, hipStream_t s, const uint8_t *d_x_in, uint32_t n,
         return ARCHON_OK;
     };
     auto fetch_probe = [&]() -> int {            // (with the round trip that follows)
-        if (probe_queued) ARCHON_HIP_TRY(hipMemcpyAsync(c->h_mail + 530, pres, pf::kCleanWords * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+        if (probe_queued) ARCHON_HIP_TRY(hipMemcpyAsync(c->h_mail + mail::kProbe.at, pres, pf::kCleanWords * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
         probe_fetched = probe_queued;
         return ARCHON_OK;
     };
@@ -959,12 +960,13 @@ static int forward_run(Ctx *c, hipStream_t s, const uint8_t *d_x_in, uint32_t n,
     const uint32_t *d_skip = &B.prep->skip;
     // The byte histogram of the block comes with the two-byte count: its second-byte column sums are the bytes
     // x[0..n-2] plus the 0xFF in front of x[0]; the host adds x[n-1] and removes the pad (alphabet detection below).
-    bool have_byte_counts = false;               // h_mail[128..383] + h_mail[512] hold the count's byte histogram of THIS block
+    uint32_t *h_counts = c->h_mail + mail::kByteCounts.at, *h_last = c->h_mail + mail::kLastByte.at;
+    bool have_byte_counts = false;               // h_counts and h_last hold the count's byte histogram of THIS block
     auto fetch_byte_counts = [&]() -> int {
         have_byte_counts = true;
-        c->h_mail[512] = 0;
-        ARCHON_HIP_TRY(hipMemcpyAsync(c->h_mail + 128, B.prep->cntA, 256 * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
-        ARCHON_HIP_TRY(hipMemcpyAsync(c->h_mail + 512, d_x + (n - 1), 1, hipMemcpyDeviceToHost, s));
+        *h_last = 0;
+        ARCHON_HIP_TRY(hipMemcpyAsync(h_counts, B.prep->cntA, 256 * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+        ARCHON_HIP_TRY(hipMemcpyAsync(h_last, d_x + (n - 1), 1, hipMemcpyDeviceToHost, s));
         return ARCHON_OK;
     };
     // ---- streaming first stage: two LSB passes + in-LDS bucket sorts; ends with the block's host round trip ----
@@ -1027,7 +1029,6 @@ static int forward_run(Ctx *c, hipStream_t s, const uint8_t *d_x_in, uint32_t n,
         //  consistency flag to the host with the same round trip: the call then ends without a second one.  Everything the host
         //  reads -- summary, flag, byte counts for skewed blocks, the period probe -- is written into the pinned mailbox by k_mail.)
         e3 = tm.mark();
-        static_assert(sizeof(bs::TieCtl) <= 20 * sizeof(uint32_t), "the summary in front of the flag's mailbox word");
         hipLaunchKernelGGL(bs::k_mail, dim3(1), dim3(256), 0, s, d_ctl, B.sc.d_err, Q == 1 ? B.prep->cntA : nullptr, d_x + (n - 1),
                            probe_queued ? pres : nullptr, c->h_mail_dev, d_base_out, ++c->mail_seq);
         ARCHON_HIP_TRY(hipGetLastError());
@@ -1039,8 +1040,7 @@ static int forward_run(Ctx *c, hipStream_t s, const uint8_t *d_x_in, uint32_t n,
         // turn up within 50 ms the ordinary wait takes over (and reports whatever went wrong on the stream)
         {
             ++t_sync_count;
-            static_assert(bs::kMailSeq >= 4600 && bs::kMailSeq < Ctx::kMailWords, "the sequence word lies clear of every other use of the mailbox");
-            volatile uint32_t *seqw = c->h_mail + bs::kMailSeq;
+            volatile uint32_t *seqw = c->h_mail + bs::kMailSeq;         // (clear of every region of the mailbox: common.hiph)
             const uint32_t want = c->mail_seq;
             const auto t_spin = std::chrono::steady_clock::now();
             for (uint32_t spins = 0; *seqw != want; ++spins) {
@@ -1053,17 +1053,17 @@ static int forward_run(Ctx *c, hipStream_t s, const uint8_t *d_x_in, uint32_t n,
             std::atomic_thread_fence(std::memory_order_acquire);
         }
         ARCHON_HOST_STAMP(3);
-        memcpy(&h_ctl, c->h_mail, sizeof h_ctl);
+        memcpy(&h_ctl, c->h_mail + mail::kSummary.at, sizeof h_ctl);
         big_items = h_ctl.big_items;
         if (h_ctl.fault) { set_error("tie list names rows outside the block (device flag 0x%x)", h_ctl.fault); return ARCHON_E_INTERNAL; }
         return ARCHON_OK;
     };
     auto count_wait = [&]() -> int {             // routes that need the count on the host before going on
-        ARCHON_HIP_TRY(hipMemcpyAsync(c->h_mail + 64, &B.prep->big_items, 2 * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+        ARCHON_HIP_TRY(hipMemcpyAsync(c->h_mail + mail::kBigItems.at, &B.prep->big_items, 2 * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
         ARCHON_TRY(fetch_byte_counts());
         ARCHON_TRY(fetch_probe());
         ARCHON_SYNC(s);
-        big_items = c->h_mail[64];
+        big_items = c->h_mail[mail::kBigItems.at];
         return ARCHON_OK;
     };
     // entry of the general stage (k_first_groups): clean SA, group starts and the compacted working set in one sweep
@@ -1073,14 +1073,14 @@ static int forward_run(Ctx *c, hipStream_t s, const uint8_t *d_x_in, uint32_t n,
         const uint32_t tiles = div_up(n, fwd::kFgTile);
         ARCHON_HIP_TRY(hipMemsetAsync(fg_status, 0, (size_t)tiles * sizeof(unsigned long long), s));
         ARCHON_HIP_TRY(hipMemsetAsync(B.sc.d_ticket, 0, sizeof(uint32_t), s));
-        ARCHON_HIP_TRY(hipMemsetAsync(small + 700, 0, 4 * sizeof(uint32_t), s));
+        ARCHON_HIP_TRY(hipMemsetAsync(small + fwd_small::kFu, 0, 4 * sizeof(uint32_t), s));
         const uint32_t ws_mode = write_ws ? 2u : 0u;      // 2: the S / B lists of rounds.hiph
         if (mode == 0)
             hipLaunchKernelGGL(HIP_KERNEL_NAME(fwd::k_first_groups<0>), dim3(tiles), dim3(256), 0, s, keys, items, shift, n, sa, d_bwt, d_base, B.v,
-                               B.upos[0], B.ug[0], B.uitem[0], small + 600, fg_status, B.sc.d_ticket, B.sc.d_err, ws_mode, B.slist[0], small + 700, (uint32_t)fwd::kFuMax);
+                               B.upos[0], B.ug[0], B.uitem[0], small + fwd_small::kTotal, fg_status, B.sc.d_ticket, B.sc.d_err, ws_mode, B.slist[0], small + fwd_small::kFu, (uint32_t)fwd::kFuMax);
         else
             hipLaunchKernelGGL(HIP_KERNEL_NAME(fwd::k_first_groups<1>), dim3(tiles), dim3(256), 0, s, keys, items, shift, n, sa, d_bwt, d_base, B.v,
-                               B.upos[0], B.ug[0], B.uitem[0], small + 600, fg_status, B.sc.d_ticket, B.sc.d_err, ws_mode, B.slist[0], small + 700, (uint32_t)fwd::kFuMax);
+                               B.upos[0], B.ug[0], B.uitem[0], small + fwd_small::kTotal, fg_status, B.sc.d_ticket, B.sc.d_err, ws_mode, B.slist[0], small + fwd_small::kFu, (uint32_t)fwd::kFuMax);
         ARCHON_HIP_TRY(hipGetLastError());
         ++c->launches;
         return ARCHON_OK;
@@ -1110,11 +1110,11 @@ static int forward_run(Ctx *c, hipStream_t s, const uint8_t *d_x_in, uint32_t n,
         ARCHON_TRY(launch_hist256(s, d_x, n, d_counts, n));
         ++c->launches;
         e1 = tm.mark();
-        ARCHON_HIP_TRY(hipMemcpyAsync(c->h_mail + 128, d_counts, 256 * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
-        ARCHON_HIP_TRY(hipMemcpyAsync(c->h_mail + 512, d_x + (n - 1), 1, hipMemcpyDeviceToHost, s));
+        ARCHON_HIP_TRY(hipMemcpyAsync(h_counts, d_counts, 256 * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+        ARCHON_HIP_TRY(hipMemcpyAsync(h_last, d_x + (n - 1), 1, hipMemcpyDeviceToHost, s));
         // (a small block's time is its host round trips: the period probe and the block's last bytes -- what the LSB passes' digit
         //  counts need -- travel with the byte count instead of taking one each further down)
-        ARCHON_HIP_TRY(hipMemcpyAsync(c->h_mail + 520, d_x + (n - 8), 8, hipMemcpyDeviceToHost, s));
+        ARCHON_HIP_TRY(hipMemcpyAsync(c->h_mail + mail::kTail.at, d_x + (n - 8), 8, hipMemcpyDeviceToHost, s));
         tail_fetched = true;
         if (n >= (1u << 16) && !route_off(kRtNoPeriodProbe)) {
             ARCHON_TRY(queue_probe());
@@ -1124,8 +1124,8 @@ static int forward_run(Ctx *c, hipStream_t s, const uint8_t *d_x_in, uint32_t n,
         ARCHON_SYNC(s);
         // (in the form the two-byte count leaves its column sums in -- the bytes x[0 .. n-2] and the 0xFF in front of x[0] --
         //  which is what the code below undoes)
-        c->h_mail[128 + (c->h_mail[512] & 0xFFu)] -= 1u;
-        c->h_mail[128 + 0xFFu] += 1u;
+        h_counts[*h_last & 0xFFu] -= 1u;
+        h_counts[0xFFu] += 1u;
         have_byte_counts = true;
         path = 0;
     } else {
@@ -1138,45 +1138,59 @@ static int forward_run(Ctx *c, hipStream_t s, const uint8_t *d_x_in, uint32_t n,
     }
     // returns ARCHON_OK when the block was written down in closed form, 1 when it is not a clean periodic block, < 0 on error
     auto closed_form = [&]() -> int {
-        if (!(closed_ok && period_probed && probe_fetched && c->h_mail[530] != 0xFFFFFFFFu && c->h_mail[533] == 1u && c->h_mail[532] == 0u)) return 1;
+        const uint32_t *h_probe = c->h_mail + mail::kProbe.at;     // [0] period, [1] votes, [2] the text breaks it, [3] the whole text was compared
+        if (!(closed_ok && period_probed && probe_fetched && h_probe[0] != 0xFFFFFFFFu && h_probe[3] == 1u && h_probe[2] == 0u)) return 1;
         // ---- a clean periodic block (periodic.hiph): x[i] == x[i-p] for every i >= p (k_period_clean compared all of it), p minimal
         // (the smallest distance at which the block's middle window recurs: a smaller period would recur there too), n >= 16 p.
         // Sort the block's first 2p bytes -- the ordinary transform, nested -- and expand its suffix array.
-        const uint32_t p = c->h_mail[530], m2 = 2u * p;
-        char *tail = c->arena + ((c->arena_bytes - kClosedTail) & ~size_t(255));
-        uint32_t *sa2 = reinterpret_cast<uint32_t *>(tail);
-        uint32_t *off = sa2 + ((m2 + 63u) & ~63u);
-        uint8_t *bwt2 = reinterpret_cast<uint8_t *>(off + ((m2 + 1u + 63u) & ~63u));
-        uint32_t *base2 = reinterpret_cast<uint32_t *>(bwt2 + ((m2 + 255u) & ~255u));
-        if ((size_t)(reinterpret_cast<char *>(base2 + 64) - tail) > kClosedTail || (uint64_t)p * pf::kMinPeriods + 64u > n) {
+        const uint32_t p = h_probe[0], m2 = 2u * p;
+        Carve t{c->arena + tail_at, 0, kClosedTail};
+        uint32_t *sa2 = t.take<uint32_t>(m2);
+        uint32_t *off = t.take<uint32_t>(m2 + 1);
+        uint8_t *bwt2 = t.take<uint8_t>(m2);
+        uint32_t *base2 = t.take<uint32_t>(64);
+        if (!base2 || (uint64_t)p * pf::kMinPeriods + 64u > n) {
             set_error("closed form: period %u of a block of %u bytes does not fit its scratch", p, n);
             return ARCHON_E_INTERNAL;
         }
+        // the nested call asks for no more than the arena holds: it neither grows nor frees it, and its tier 1 ends below the tail
+        {
+            FwdBuf nb{};
+            Carve count;
+            if (fwd_tier1(count, nb, m2, c->dev, false) > c->arena_bytes) {
+                set_error("closed form: tier 1 of the %u-byte block of period %u does not fit below the tail", m2, p);
+                return ARCHON_E_INTERNAL;
+            }
+        }
         const uint32_t launches0 = c->launches;
         const bool x_in_arena = d_x == B.xa;
-        ARCHON_TRY(forward_run(c, s, d_x, m2, sa2, bwt2, base2, depth + 1));      // (c->stats, c->launches, the arena: the nested call's from here on)
+        ARCHON_TRY(forward_run(c, s, d_x, m2, sa2, bwt2, base2, depth + 1));      // (c->stats, c->launches, tier 1: the nested call's from here on)
         const uint32_t launches1 = c->stats.kernel_launches;
         const uint64_t arena1 = c->stats.arena_bytes;
-        c->arena_reset();
-        if (x_in_arena) (void)c->alloc<uint8_t>((size_t)n + 64);                  // the aligned copy of the text stays where it is
+        // Tier 1 again, for the expansion.  The nested call carved it from the bottom: of the aligned copy of the text (B.xa) only
+        // the slot is kept, so that tile_lo lands behind it -- its first 2p + 64 bytes are still the text (the nested block read them
+        // in place), the rest was overwritten, and k_expand reads nothing of x but x[0].
+        Carve a{c->arena, 0, tail_at};
+        if (x_in_arena) (void)a.take<uint8_t>((size_t)n + 64);
         const uint32_t ntiles = div_up(n, pf::kTile);
-        uint32_t *tile_lo = c->alloc<uint32_t>((size_t)ntiles + 2);
+        uint32_t *tile_lo = a.take<uint32_t>((size_t)ntiles + 2);
         if (!tile_lo) { set_error("arena exhausted (closed form)"); return ARCHON_E_NOMEM; }
         hipLaunchKernelGGL(pf::k_offsets, dim3(1), dim3(1024), 0, s, sa2, m2, p, n, off);
         hipLaunchKernelGGL(pf::k_tiles, dim3(div_up(ntiles + 1, 256)), dim3(256), 0, s, off, m2, ntiles, tile_lo);
         hipLaunchKernelGGL(pf::k_expand, dim3(ntiles), dim3(256), 0, s, off, sa2, bwt2, tile_lo, m2, p, n, d_x, d_sa_user, d_bwt, d_base_out);
         ARCHON_HIP_TRY(hipGetLastError());
         const int e_end = tm.mark();
-        ARCHON_HIP_TRY(hipMemcpyAsync(c->h_mail, off + m2, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+        uint32_t *rd = c->h_mail + mail::kRead.at;
+        ARCHON_HIP_TRY(hipMemcpyAsync(rd, off + m2, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
         ARCHON_SYNC(s);
-        if (c->h_mail[0] != n) { set_error("closed form: the classes of period %u hold %u rows of %u", p, c->h_mail[0], n); return ARCHON_E_INTERNAL; }
+        if (rd[0] != n) { set_error("closed form: the classes of period %u hold %u rows of %u", p, rd[0], n); return ARCHON_E_INTERNAL; }
         memset(&st, 0, sizeof st);
         st.n = n;
         st.path = 2;
         st.period = p;
         st.chain_items = n;
         st.kernel_launches = c->launches = launches0 + launches1 + 3;
-        st.arena_bytes = arena1 > c->arena_off ? arena1 : c->arena_off;
+        st.arena_bytes = arena1 > a.off ? arena1 : a.off;
         st.ms_hist = tm.ms(e0, e1);
         st.ms_sort = tm.ms(e1, e_end);
         st.ms_total = tm.ms(e0, e_end);
@@ -1187,20 +1201,21 @@ static int forward_run(Ctx *c, hipStream_t s, const uint8_t *d_x_in, uint32_t n,
     if (!hinted) { const int r = closed_form(); if (r <= 0) return r; }
     constexpr uint32_t kPackSigma = 32;          // alphabets up to this many distinct bytes sort on packed keys
     uint32_t sigma = 0, bits = 8;
-    uint8_t *d_lut = reinterpret_cast<uint8_t *>(small + 900);
+    uint8_t *d_lut = reinterpret_cast<uint8_t *>(small + fwd_small::kLut);
     uint8_t h_lut[256];
     bool have_lut = false;
     bool presence_done = false;
     auto presence = [&]() -> int {               // the exact alphabet: 256 presence bits -> sigma, h_lut (the order-preserving recode)
         hipLaunchKernelGGL(bs::k_presence, dim3(kNumCU * 8), dim3(256), 0, s, d_x, n, B.prep->present);
-        ARCHON_HIP_TRY(hipMemcpyAsync(c->h_mail + 520, B.prep->present, 8 * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+        const uint32_t *h_present = c->h_mail + mail::kPresence.at;
+        ARCHON_HIP_TRY(hipMemcpyAsync(c->h_mail + mail::kPresence.at, B.prep->present, 8 * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
         if (!probe_fetched) ARCHON_TRY(fetch_probe());         // (hinted: the period probe's verdict has not travelled yet)
         ARCHON_SYNC(s);
         ++c->launches;
         sigma = 0;
         for (uint32_t v = 0; v < 256; ++v) {
             h_lut[v] = (uint8_t)sigma;
-            if ((c->h_mail[520 + (v >> 5)] >> (v & 31u)) & 1u) ++sigma;
+            if ((h_present[v >> 5] >> (v & 31u)) & 1u) ++sigma;
         }
         presence_done = true;
         return ARCHON_OK;
@@ -1244,24 +1259,25 @@ static int forward_run(Ctx *c, hipStream_t s, const uint8_t *d_x_in, uint32_t n,
     // or, with that route switched off, three key bytes of the 7-pass sort.
     uint32_t key_bytes = fwd::kKeyBytes, period_hint = 0;
     if (path == 0 && n >= (1u << 16) && !route_off(kRtNoPeriodProbe)) {
-        uint32_t *pres = small + 610;
+        uint32_t *pres = small + fwd_small::kProbe;
+        uint32_t *rd = c->h_mail + mail::kRead.at;     // [0] period, [1] votes
         if (period_probed) {                         // (a small block: the probe went out with the byte count)
-            c->h_mail[0] = c->h_mail[530]; c->h_mail[1] = c->h_mail[531];
+            rd[0] = c->h_mail[mail::kProbe.at]; rd[1] = c->h_mail[mail::kProbe.at + 1];
         } else {
-            c->h_mail[0] = 0xFFFFFFFFu; c->h_mail[1] = 0;
-            ARCHON_HIP_TRY(hipMemcpyAsync(pres, c->h_mail, 2 * sizeof(uint32_t), hipMemcpyHostToDevice, s));
+            rd[0] = 0xFFFFFFFFu; rd[1] = 0;
+            ARCHON_HIP_TRY(hipMemcpyAsync(pres, rd, 2 * sizeof(uint32_t), hipMemcpyHostToDevice, s));
             hipLaunchKernelGGL(fwd::k_period_find, dim3(fwd::kPeriodSearch / 256), dim3(256), 0, s, d_x, n, pres);
             hipLaunchKernelGGL(fwd::k_period_vote, dim3(fwd::kPeriodVotes / 256), dim3(256), 0, s, d_x, n, pres);
-            ARCHON_HIP_TRY(hipMemcpyAsync(c->h_mail, pres, 2 * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+            ARCHON_HIP_TRY(hipMemcpyAsync(rd, pres, 2 * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
             ARCHON_SYNC(s);
             c->launches += 2;
         }
-        if (c->h_mail[0] != 0xFFFFFFFFu && c->h_mail[1] * 10 >= fwd::kPeriodVotes * 9) {
+        if (rd[0] != 0xFFFFFFFFu && rd[1] * 10 >= fwd::kPeriodVotes * 9) {
             key_bytes = 3;
             // ... provided every two-byte bucket is ONE run of the period: a bucket that joins two phases of the period (the same
             // two bytes at two places of the motif) is no run, and sorting it out at depth 2 costs more than a third key
             // byte.  The two-byte count tells: a single run holds n / p items.  (Periods 1 and 2 cannot collide.)
-            const uint32_t pp = c->h_mail[0];
+            const uint32_t pp = rd[0];
             if (!route_off(kRtNoPeriodHint)) period_hint = pp;     // the run shortcut need not sample neighbour gaps for it
             const bool count_ok = forced < 0 && !h_ctl.suspect;
             const bool single_runs = pp <= 2 || (count_ok && (uint64_t)h_ctl.max_bucket * 2 * pp <= (uint64_t)n * 3);
@@ -1282,24 +1298,25 @@ static int forward_run(Ctx *c, hipStream_t s, const uint8_t *d_x_in, uint32_t n,
     uint32_t period_breaks = 0;
     if (period_hint && !route_off(kRtNoChains)) {
         ARCHON_TRY(general_buffers());
-        uint32_t *d_lastbrk = small + 606;
+        uint32_t *d_lastbrk = small + fwd_small::kLastBrk;
         ARCHON_HIP_TRY(hipMemsetAsync(d_lastbrk, 0, 2 * sizeof(uint32_t), s));          // [0] last real break, [1] how many
         hipLaunchKernelGGL(fwd::k_period_breaks, dim3(div_up(div_up(n, 4), 256)), dim3(256), 0, s, d_x, n, period_hint, B.brk, d_lastbrk);
         ARCHON_TRY(launch_scan<1>(s, B.brk, B.brk, n, B.scan_tmp, nullptr));
-        ARCHON_HIP_TRY(hipMemcpyAsync(c->h_mail + 2, d_lastbrk + 1, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+        uint32_t *rd = c->h_mail + mail::kRead.at;
+        ARCHON_HIP_TRY(hipMemcpyAsync(rd + 2, d_lastbrk + 1, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
         ARCHON_SYNC(s);
         c->launches += 4;
         brk_ready = true;
-        period_breaks = route_off(kRtNoBreakRound) ? 0u : c->h_mail[2];
+        period_breaks = route_off(kRtNoBreakRound) ? 0u : rd[2];
     }
     if (path == 0) {
         // heavily skewed at two bytes.  Alphabet compaction: with <= 16 distinct bytes a key
         // byte holds 2, 4 or 8 symbols; if the two-byte buckets of THAT text are small enough the block still
         // takes the streaming stage (DNA: 8 symbols deep after two passes), else the 7-pass sort on packed keys.
         if (!have_lut) {
-            const uint32_t last_byte = c->h_mail[512] & 0xFFu;
+            const uint32_t last_byte = *h_last & 0xFFu;
             for (uint32_t v = 0; v < 256; ++v) {
-                const uint32_t cnt = c->h_mail[128 + v] - (v == 0xFFu ? 1u : 0u) + (v == last_byte ? 1u : 0u);
+                const uint32_t cnt = h_counts[v] - (v == 0xFFu ? 1u : 0u) + (v == last_byte ? 1u : 0u);
                 h_lut[v] = (uint8_t)sigma;
                 if (cnt) ++sigma;
             }
@@ -1309,8 +1326,9 @@ static int forward_run(Ctx *c, hipStream_t s, const uint8_t *d_x_in, uint32_t n,
         // (17 ... 32 distinct bytes -- lower-case prose -- still pack: five bits per symbol, eleven symbols in the seven key bytes instead of
         //  seven; the streaming stage's key text holds whole symbols per byte and stops at 16)
         if (sigma <= kPackSigma && !route_off(kRtNoPack)) {
-            memcpy(c->h_mail + 1024, h_lut, 256);
-            ARCHON_HIP_TRY(hipMemcpyAsync(d_lut, c->h_mail + 1024, 256, hipMemcpyHostToDevice, s));
+            static_assert(mail::kLut.len * 4 == sizeof h_lut, "the recode table's staging");
+            memcpy(c->h_mail + mail::kLut.at, h_lut, 256);
+            ARCHON_HIP_TRY(hipMemcpyAsync(d_lut, c->h_mail + mail::kLut.at, 256, hipMemcpyHostToDevice, s));
             if (sigma >= 2 && sigma <= 16 && forced < 0 && !small_block && !route_off(kRtNoPackStream)) {
                 const int q = bits == 1 ? 8 : bits == 2 ? 4 : 2;
                 const dim3 grid(div_up(div_up(n, 16), 256)), block(256);
@@ -1326,7 +1344,7 @@ static int forward_run(Ctx *c, hipStream_t s, const uint8_t *d_x_in, uint32_t n,
                     st.alphabet_bits = 8 / q;
                 }
             }
-            ARCHON_SYNC(s);          // the table upload has left h_mail
+            ARCHON_SYNC(s);          // the table upload has left mail::kLut, which the sorts below overwrite
         }
     }
     st.path = (uint32_t)path;
@@ -1376,8 +1394,8 @@ static int forward_run(Ctx *c, hipStream_t s, const uint8_t *d_x_in, uint32_t n,
             // of x came with the two-byte count (fetch_byte_counts); the last bytes of x are fetched here.
             if (have_byte_counts && n >= 8) {
                 uint32_t H[256];
-                const uint32_t last_byte = c->h_mail[512] & 0xFFu;
-                for (uint32_t v = 0; v < 256; ++v) H[v] = c->h_mail[128 + v] - (v == 0xFFu ? 1u : 0u) + (v == last_byte ? 1u : 0u);
+                const uint32_t last_byte = *h_last & 0xFFu;
+                for (uint32_t v = 0; v < 256; ++v) H[v] = h_counts[v] - (v == 0xFFu ? 1u : 0u) + (v == last_byte ? 1u : 0u);
                 // How many key bytes?  Were the bytes independent, an item would share its first d bytes with n * (sum p^2)^d others: a
                 // block whose byte counts say "fewer than one in 32" at d < 7 (incompressible data: 4 bytes for 4 MiB) sorts on d bytes --
                 // 38 us per pass saved on a 4 MiB block -- and what stays tied goes to the rounds at depth d like any other tie.  Text
@@ -1399,10 +1417,10 @@ static int forward_run(Ctx *c, hipStream_t s, const uint8_t *d_x_in, uint32_t n,
                     h0 = key_bytes;
                 }
                 if (!tail_fetched) {
-                    ARCHON_HIP_TRY(hipMemcpyAsync(c->h_mail + 520, d_x + (n - 8), 8, hipMemcpyDeviceToHost, s));
+                    ARCHON_HIP_TRY(hipMemcpyAsync(c->h_mail + mail::kTail.at, d_x + (n - 8), 8, hipMemcpyDeviceToHost, s));
                     ARCHON_SYNC(s);
                 }
-                const uint8_t *tail = reinterpret_cast<const uint8_t *>(c->h_mail + 520);      // x[n-8 .. n-1]
+                const uint8_t *tail = reinterpret_cast<const uint8_t *>(c->h_mail + mail::kTail.at);      // x[n-8 .. n-1]
                 for (uint32_t q = 1; q <= 7; ++q) {
                     uint32_t *hq = hist_given + (8 - q) * 256;                               // pass p = 8 - q sorts on key byte q
                     memcpy(hq, H, sizeof H);
@@ -1446,12 +1464,12 @@ static int forward_run(Ctx *c, hipStream_t s, const uint8_t *d_x_in, uint32_t n,
     int e5 = e3;
     uint32_t dev_err;
     if (stream_done) {
-        dev_err = c->h_mail[20];
+        dev_err = c->h_mail[mail::kFlag.at];
     } else {
         e5 = tm.mark();
-        ARCHON_HIP_TRY(hipMemcpyAsync(c->h_mail, B.sc.d_err, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+        ARCHON_HIP_TRY(hipMemcpyAsync(c->h_mail + mail::kRead.at, B.sc.d_err, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
         ARCHON_SYNC(s);
-        dev_err = c->h_mail[0];
+        dev_err = c->h_mail[mail::kRead.at];
     }
     if (dev_err) {
         set_error("device consistency flag 0x%x (look-back spin bound)", dev_err);
@@ -1474,7 +1492,6 @@ static int forward_run(Ctx *c, hipStream_t s, const uint8_t *d_x_in, uint32_t n,
         st.ms_radix_pass_sum = st.ms_pass_text + st.ms_pass_rec;
         st.radix_pass_timed = 2;
     }
-    (void)d_counts; (void)d_starts;
     ARCHON_HOST_STAMP(4);
 #ifdef ARCHON_EXPERIMENTS
     if (trace_host) {
@@ -1535,7 +1552,7 @@ int archon_hip_forward(const uint8_t *x, uint32_t n, uint32_t *sa_or_null, uint8
     ARCHON_TRY(ctx_io(c, 0, (size_t)n + 64, (void **)&d_x));
     ARCHON_TRY(ctx_io(c, 1, (size_t)n + 64, (void **)&d_bwt));
     if (sa_or_null) ARCHON_TRY(ctx_io(c, 2, (size_t)n * 4, (void **)&d_sa));
-    uint32_t *d_base = c->d_mail + 620;
+    uint32_t *d_base = c->d_mail + mail::kDevBase.at;
     ARCHON_HIP_TRY(hipMemcpyAsync(d_x, x, n, hipMemcpyHostToDevice, s));
     ARCHON_TRY(keep_stats(c, forward_run(c, s, d_x, n, d_sa, d_bwt, d_base)));
     // BWT first (the block coder's enWrite can start on it), then the 4N bytes of the suffix array
@@ -1631,7 +1648,7 @@ int archon_hip_block_forward(archon_hip_block *b, const uint8_t *x, uint32_t n, 
     ARCHON_TRY(block_reserve(b, n, sa_or_null != nullptr));
     hipStream_t s = c->own_stream;
     uint32_t *d_sa = sa_or_null ? b->d_sa : nullptr;
-    uint32_t *d_base = c->d_mail + 620;
+    uint32_t *d_base = c->d_mail + mail::kDevBase.at;
     ARCHON_HIP_TRY(hipMemcpyAsync(b->d_x, x, n, hipMemcpyHostToDevice, s));
     ARCHON_TRY(forward_run(c, s, b->d_x, n, d_sa, b->d_bwt, d_base));
     ARCHON_HIP_TRY(hipMemcpyAsync(base_id, d_base, 4, hipMemcpyDeviceToHost, s));
@@ -1822,8 +1839,9 @@ int archon_hip_hist256(const uint8_t *x, size_t n, uint32_t out[256], int dev)
     ARCHON_HIP_TRY(hipMalloc((void **)&d_x, n + 64));
     hipError_t e = hipMemcpyAsync(d_x, x, n, hipMemcpyHostToDevice, s);
     int rc = ARCHON_OK;
-    if (e == hipSuccess) rc = launch_hist256(s, d_x, n, c->d_mail, n);
-    if (e == hipSuccess && rc == ARCHON_OK) e = hipMemcpyAsync(out, c->d_mail, 256 * 4, hipMemcpyDeviceToHost, s);
+    uint32_t *d_counts = c->d_mail + mail::kDevCounts.at;
+    if (e == hipSuccess) rc = launch_hist256(s, d_x, n, d_counts, n);
+    if (e == hipSuccess && rc == ARCHON_OK) e = hipMemcpyAsync(out, d_counts, 256 * 4, hipMemcpyDeviceToHost, s);
     if (e == hipSuccess) e = hipStreamSynchronize(s);
     (void)hipFree(d_x);
     if (e != hipSuccess) { set_error("HIP call failed: %s", hipGetErrorString(e)); return ARCHON_E_HIP; }
@@ -1875,14 +1893,15 @@ int archon_hip_validate(const uint8_t *x, uint32_t n, const uint32_t *sa, int de
 static int sa_to_bwt_run(Ctx *c, hipStream_t s, const uint8_t *d_x, uint32_t n, const uint32_t *d_sa, uint8_t *d_bwt,
                          uint32_t *d_base_out)
 {
-    uint32_t *res = c->d_mail + 600;            // [0] bad value seen, [1] rows holding n, [2] the primary index
+    uint32_t *res = c->d_mail + mail::kDevSaRes.at;      // [0] bad value seen, [1] rows holding n, [2] the primary index
+    uint32_t *rd = c->h_mail + mail::kRead.at;
     ARCHON_HIP_TRY(hipMemsetAsync(res, 0, 3 * sizeof(uint32_t), s));
     hipLaunchKernelGGL(fwd::k_sa_to_bwt, dim3(div_up(div_up(n, 4), 256)), dim3(256), 0, s, d_x, d_sa, n, d_bwt, res + 2, res);
     ARCHON_HIP_TRY(hipGetLastError());
-    ARCHON_HIP_TRY(hipMemcpyAsync(c->h_mail, res, 3 * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+    ARCHON_HIP_TRY(hipMemcpyAsync(rd, res, 3 * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
     ARCHON_SYNC(s);
-    if (c->h_mail[0] || c->h_mail[1] != 1) {
-        set_error("not a suffix array in a7 order: %s", c->h_mail[0] ? "values outside 1..n" : "no single row holds n");
+    if (rd[0] || rd[1] != 1) {
+        set_error("not a suffix array in a7 order: %s", rd[0] ? "values outside 1..n" : "no single row holds n");
         return ARCHON_E_CORRUPT;
     }
     ARCHON_HIP_TRY(hipMemcpyAsync(d_base_out, res + 2, sizeof(uint32_t), hipMemcpyDeviceToDevice, s));
@@ -1919,9 +1938,9 @@ int archon_hip_sa_to_bwt(const uint8_t *x, uint32_t n, const uint32_t *sa, uint8
     ARCHON_TRY(ctx_io(c, 2, (size_t)n * 4 + 64, (void **)&d_sa));
     ARCHON_HIP_TRY(hipMemcpyAsync(d_x, x, n, hipMemcpyHostToDevice, s));
     ARCHON_HIP_TRY(hipMemcpyAsync(d_sa, sa, (size_t)n * 4, hipMemcpyHostToDevice, s));
-    ARCHON_TRY(sa_to_bwt_run(c, s, d_x, n, d_sa, d_bwt, c->d_mail + 610));
+    ARCHON_TRY(sa_to_bwt_run(c, s, d_x, n, d_sa, d_bwt, c->d_mail + mail::kDevSaBase.at));
     ARCHON_HIP_TRY(hipMemcpyAsync(bwt, d_bwt, n, hipMemcpyDeviceToHost, s));
-    ARCHON_HIP_TRY(hipMemcpyAsync(base_id, c->d_mail + 610, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+    ARCHON_HIP_TRY(hipMemcpyAsync(base_id, c->d_mail + mail::kDevSaBase.at, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
     ARCHON_SYNC(s);
     return ARCHON_OK;
 }
@@ -1936,19 +1955,21 @@ static int post_run(Ctx *c, hipStream_t s, const uint8_t *d_bwt, uint32_t n, uin
         *out_bytes = 4;
         return ARCHON_OK;
     }
-    ARCHON_TRY(ctx_ensure_arena(c, (size_t)np * post::kSlotBytes + 4 * (size_t)np + 4096));
-    c->arena_reset();
-    uint8_t *slots = c->alloc<uint8_t>((size_t)np * post::kSlotBytes);
-    uint32_t *sizes = c->alloc<uint32_t>(np);
-    unsigned long long *d_total = reinterpret_cast<unsigned long long *>(c->d_mail + 630);
-    if (!slots || !sizes) { set_error("arena exhausted"); return ARCHON_E_NOMEM; }
+    uint8_t *slots;
+    uint32_t *sizes;
+    ARCHON_TRY(ctx_carve(c, [&](Carve &a) {
+        slots = a.take<uint8_t>((size_t)np * post::kSlotBytes);
+        sizes = a.take<uint32_t>(np);
+        return a.off;
+    }));
+    unsigned long long *d_total = reinterpret_cast<unsigned long long *>(c->d_mail + mail::kDevPostTotal.at);
     hipLaunchKernelGGL(post::k_post_piece, dim3(np), dim3(post::kLanes), 0, s, d_bwt, n, slots, sizes);
     hipLaunchKernelGGL(post::k_post_gather, dim3(np), dim3(256), 0, s, slots, sizes, np, d_out, d_total);
     ARCHON_HIP_TRY(hipGetLastError());
-    ARCHON_HIP_TRY(hipMemcpyAsync(c->h_mail + 630, d_total, sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
+    ARCHON_HIP_TRY(hipMemcpyAsync(c->h_mail + mail::kPostTotal.at, d_total, sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
     ARCHON_SYNC(s);
     unsigned long long total;
-    memcpy(&total, c->h_mail + 630, sizeof total);
+    memcpy(&total, c->h_mail + mail::kPostTotal.at, sizeof total);
     if (total < 4 + 4ull * np || total > post::block_bound(n)) { set_error("post stage: stream length %llu out of bounds", total); return ARCHON_E_INTERNAL; }
     *out_bytes = (size_t)total;
     c->launches += 2;
@@ -1959,20 +1980,19 @@ static int post_run(Ctx *c, hipStream_t s, const uint8_t *d_bwt, uint32_t n, uin
 static int post_decode_run(Ctx *c, hipStream_t s, const uint8_t *d_in, size_t in_bytes, uint8_t *d_bwt, uint32_t cap, uint32_t *n_out)
 {
     const size_t np_max = (size_t)cap / post::kPiece + 2;
-    ARCHON_TRY(ctx_ensure_arena(c, 8 * (np_max + 2) + 4096));
-    c->arena_reset();
-    unsigned long long *off = c->alloc<unsigned long long>(np_max + 2);
-    uint32_t *meta = c->d_mail + 640;            // [0] n, [1] pieces, [2] bad
-    if (!off) { set_error("arena exhausted"); return ARCHON_E_NOMEM; }
+    unsigned long long *off;
+    ARCHON_TRY(ctx_carve(c, [&](Carve &a) { off = a.take<unsigned long long>(np_max + 2); return a.off; }));
+    uint32_t *meta = c->d_mail + mail::kDevPostMeta.at;      // [0] n, [1] pieces, [2] bad
     ARCHON_HIP_TRY(hipMemsetAsync(meta, 0, 3 * sizeof(uint32_t), s));
     hipLaunchKernelGGL(post::k_post_offsets, dim3(1), dim3(1024), 0, s, d_in, (unsigned long long)in_bytes, cap, off, meta, meta + 2);
     hipLaunchKernelGGL(post::k_post_decode, dim3(div_up(np_max, post::kDecWaves)), dim3(64 * post::kDecWaves), 0, s, d_in, off, meta, d_bwt, meta + 2);
     ARCHON_HIP_TRY(hipGetLastError());
-    ARCHON_HIP_TRY(hipMemcpyAsync(c->h_mail + 640, meta, 3 * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+    const uint32_t *h_meta = c->h_mail + mail::kPostMeta.at;
+    ARCHON_HIP_TRY(hipMemcpyAsync(c->h_mail + mail::kPostMeta.at, meta, 3 * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
     ARCHON_SYNC(s);
     c->launches += 2;
-    if (c->h_mail[642]) { set_error("post stage: malformed stream (flag 0x%x)", c->h_mail[642]); return ARCHON_E_CORRUPT; }
-    *n_out = c->h_mail[640];
+    if (h_meta[2]) { set_error("post stage: malformed stream (flag 0x%x)", h_meta[2]); return ARCHON_E_CORRUPT; }
+    *n_out = h_meta[0];
     return ARCHON_OK;
 }
 
@@ -2042,7 +2062,7 @@ int archon_hip_forward_post(const uint8_t *x, uint32_t n, uint8_t *out, size_t c
     ARCHON_TRY(ctx_io(c, 0, (size_t)n + 64, (void **)&d_x));
     ARCHON_TRY(ctx_io(c, 1, (size_t)n + 64, (void **)&d_bwt));
     ARCHON_TRY(ctx_io(c, 2, post::block_bound(n) + 64, (void **)&d_pk));
-    uint32_t *d_base = c->d_mail + 620;
+    uint32_t *d_base = c->d_mail + mail::kDevBase.at;
     ARCHON_HIP_TRY(hipMemcpyAsync(d_x, x, n, hipMemcpyHostToDevice, s));
     ARCHON_TRY(keep_stats(c, forward_run(c, s, d_x, n, nullptr, d_bwt, d_base)));
     ARCHON_TRY(post_run(c, s, d_bwt, n, d_pk, out_bytes));
@@ -2057,29 +2077,32 @@ int archon_hip_forward_post(const uint8_t *x, uint32_t n, uint8_t *out, size_t c
 static int lms_select_run(Ctx *c, hipStream_t s, const uint8_t *d_x, uint32_t n, uint32_t *d_count, uint32_t *d_items, uint32_t *n1_out)
 {
     // three word arrays over the items, two (key, value) pair buffers over the LMS half, scan and status words
-    ARCHON_TRY(ctx_ensure_arena(c, (size_t)n * 26 + 4 * scan_temp_words(n) + 4 * rs::status_words(n) + (1u << 20)));
-    c->arena_reset();
-    c->launches = 0;
-    uint32_t *v = c->alloc<uint32_t>(n), *flag = c->alloc<uint32_t>(n), *dst = c->alloc<uint32_t>(n);
-    uint64_t *kA = c->alloc<uint64_t>((size_t)n / 2 + 8), *kB = c->alloc<uint64_t>((size_t)n / 2 + 8);
-    uint32_t *vA = c->alloc<uint32_t>((size_t)n / 2 + 8), *vB = c->alloc<uint32_t>((size_t)n / 2 + 8);
-    uint32_t *scan_tmp = c->alloc<uint32_t>(scan_temp_words(n));
+    uint32_t *v, *flag, *dst, *vA, *vB, *scan_tmp, *small;
+    uint64_t *kA, *kB;
     rs::Scratch sc;
-    sc.d_status = c->alloc<uint32_t>(rs::status_words(n));
-    sc.d_ghist = c->alloc<uint32_t>(8 * 256);
-    sc.d_gstart = c->alloc<uint32_t>(8 * 256);
-    uint32_t *small = c->alloc<uint32_t>(1024);
-    if (!small) { set_error("arena exhausted"); return ARCHON_E_NOMEM; }
-    sc.d_ticket = small + 601; sc.d_err = small + 602; sc.h_mail = c->h_mail;
-    ARCHON_HIP_TRY(hipMemsetAsync(small, 0, 1024 * sizeof(uint32_t), s));
+    ARCHON_TRY(ctx_carve(c, [&](Carve &a) {
+        v = a.take<uint32_t>(n); flag = a.take<uint32_t>(n); dst = a.take<uint32_t>(n);
+        kA = a.take<uint64_t>((size_t)n / 2 + 8); kB = a.take<uint64_t>((size_t)n / 2 + 8);
+        vA = a.take<uint32_t>((size_t)n / 2 + 8); vB = a.take<uint32_t>((size_t)n / 2 + 8);
+        scan_tmp = a.take<uint32_t>(scan_temp_words(n));
+        sc.d_status = a.take<uint32_t>(rs::status_words(n));
+        sc.d_ghist = a.take<uint32_t>(8 * 256);
+        sc.d_gstart = a.take<uint32_t>(8 * 256);
+        small = a.take<uint32_t>(inv_small::kWords);
+        return a.off;
+    }));
+    c->launches = 0;
+    sc.d_ticket = small + inv_small::kTicket; sc.d_err = small + inv_small::kErr; sc.h_mail = c->h_mail;
+    uint32_t *d_total = small + inv_small::kTotal, *d_starts = small + inv_small::kStarts;
+    ARCHON_HIP_TRY(hipMemsetAsync(small, 0, inv_small::kWords * sizeof(uint32_t), s));
     const uint32_t g256 = div_up(n, 256);
     hipLaunchKernelGGL(fwd::k_lms_pairs, dim3(g256), dim3(256), 0, s, d_x, n, v);
     ARCHON_TRY(launch_scan<1>(s, v, v, n, scan_tmp, nullptr));
     hipLaunchKernelGGL(fwd::k_lms_flag, dim3(g256), dim3(256), 0, s, d_x, n, v, flag);
-    ARCHON_TRY(launch_scan<0>(s, flag, dst, n, scan_tmp, small + 600));
-    ARCHON_HIP_TRY(hipMemcpyAsync(c->h_mail, small + 600, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+    ARCHON_TRY(launch_scan<0>(s, flag, dst, n, scan_tmp, d_total));
+    ARCHON_HIP_TRY(hipMemcpyAsync(c->h_mail + mail::kRead.at, d_total, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
     ARCHON_SYNC(s);
-    const uint32_t n1 = c->h_mail[0];
+    const uint32_t n1 = c->h_mail[mail::kRead.at];
     *n1_out = n1;
     ARCHON_HIP_TRY(hipMemsetAsync(d_count, 0, 256 * sizeof(uint32_t), s));
     if (n1 == 1) {
@@ -2092,8 +2115,8 @@ static int lms_select_run(Ctx *c, hipStream_t s, const uint8_t *d_x, uint32_t n,
         ARCHON_TRY(rs::sort_pairs(s, sc, kA, vA, kB, vB, n1, 0x01u, &in_b, &passes, &c->launches));
         // (sort_pairs has left the digit histogram of byte 0 = the per-bucket counts in d_ghist[0..255])
         ARCHON_HIP_TRY(hipMemcpyAsync(d_count, sc.d_ghist, 256 * sizeof(uint32_t), hipMemcpyDeviceToDevice, s));
-        hipLaunchKernelGGL(k_scan257, dim3(1), dim3(64), 0, s, d_count, small);
-        hipLaunchKernelGGL(fwd::k_lms_place, dim3(div_up(n1, 256)), dim3(256), 0, s, in_b ? kB : kA, in_b ? vB : vA, n1, small, d_items);
+        hipLaunchKernelGGL(k_scan257, dim3(1), dim3(64), 0, s, d_count, d_starts);
+        hipLaunchKernelGGL(fwd::k_lms_place, dim3(div_up(n1, 256)), dim3(256), 0, s, in_b ? kB : kA, in_b ? vB : vA, n1, d_starts, d_items);
         ARCHON_HIP_TRY(hipGetLastError());
     }
     ARCHON_SYNC(s);
@@ -2126,8 +2149,8 @@ int archon_hip_lms_select(const uint8_t *x, uint32_t n, uint32_t count[256], uin
     ARCHON_TRY(ctx_io(c, 0, (size_t)n + 64, (void **)&d_x));
     ARCHON_TRY(ctx_io(c, 2, ((size_t)n / 2 + 8) * 4, (void **)&d_items));
     ARCHON_HIP_TRY(hipMemcpyAsync(d_x, x, n, hipMemcpyHostToDevice, s));
-    ARCHON_TRY(lms_select_run(c, s, d_x, n, c->d_mail + 1024, d_items, n1));
-    ARCHON_HIP_TRY(hipMemcpyAsync(count, c->d_mail + 1024, 256 * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+    ARCHON_TRY(lms_select_run(c, s, d_x, n, c->d_mail + mail::kDevLmsCount.at, d_items, n1));
+    ARCHON_HIP_TRY(hipMemcpyAsync(count, c->d_mail + mail::kDevLmsCount.at, 256 * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
     if (*n1) ARCHON_HIP_TRY(hipMemcpyAsync(items, d_items, (size_t)*n1 * 4, hipMemcpyDeviceToHost, s));
     ARCHON_SYNC(s);
     return ARCHON_OK;
@@ -2141,7 +2164,7 @@ int archon_hip_radix_scatter_dev(const uint8_t *d_src, size_t n, uint8_t *d_dst,
     std::lock_guard<std::mutex> lk(c->mu);
     ARCHON_HIP_TRY(hipSetDevice(dev));
     hipStream_t s = stream ? (hipStream_t)stream : c->own_stream;
-    uint32_t *d_counts = c->d_mail, *d_starts = c->d_mail + 256;
+    uint32_t *d_counts = c->d_mail + mail::kDevCounts.at, *d_starts = c->d_mail + mail::kDevStarts.at;
     ARCHON_TRY(launch_hist256(s, d_src, n, d_counts, n));
     hipLaunchKernelGGL(k_scan257, dim3(1), dim3(64), 0, s, d_counts, d_starts);
     uint32_t grid = div_up(n, 256 * 16);
@@ -2256,11 +2279,15 @@ int archon_hip_reserve(uint32_t n, int dev, size_t *bytes_or_null)
     ARCHON_TRY(ctx_get(dev, &c));
     std::lock_guard<std::mutex> lk(c->mu);
     ARCHON_HIP_TRY(hipSetDevice(dev));
-    size_t need = forward_arena_bytes(n, dev);
-    const size_t inv = inverse_arena_bytes(n);
+    // (reserving means: no allocation inside a later call, whatever the block) -- the layouts counted, not carved
+    FwdBuf B{};
+    InvArena L;
+    Carve f1, f2, i1;
+    size_t need = fwd_tier1(f1, B, n, dev, true);
+    const size_t inv = inv_layout(i1, L, n);
     if (inv > need) need = inv;
     ARCHON_TRY(ctx_ensure_arena(c, need));
-    ARCHON_TRY(ctx_ensure_arena2(c, forward_stage2_bytes(n)));       // (reserving means: no allocation inside a later call, whatever the block)
+    ARCHON_TRY(ctx_ensure_arena2(c, fwd_tier2(f2, B, n)));
     if (bytes_or_null) *bytes_or_null = c->arena_bytes + c->arena2_bytes;
     return ARCHON_OK;
 }
