@@ -11,6 +11,7 @@
 #include "mid_rounds.hiph"
 #include "inverse.hiph"
 #include "post.hiph"
+#include "lcp.hiph"
 
 #include <stdarg.h>
 #include <atomic>
@@ -57,6 +58,9 @@ static thread_local signed char t_slot[kMaxDev];      // 0: not bound yet; else 
 // other thread's call on the same context can replace them
 static thread_local archon_hip_stats t_stats[kMaxDev];
 static thread_local bool t_stats_set[kMaxDev];
+// the same for the thread's last LCP call (archon_hip_get_lcp_stats): LCP calls leave archon_hip_stats alone
+static thread_local archon_hip_lcp_stats t_lcp_stats[kMaxDev];
+static thread_local bool t_lcp_stats_set[kMaxDev];
 
 static inline int keep_stats(Ctx *c, int rc)
 {
@@ -1563,6 +1567,50 @@ int archon_hip_forward(const uint8_t *x, uint32_t n, uint32_t *sa_or_null, uint8
     return ARCHON_OK;
 }
 
+// ---- the LCP array (lcp.hiph)
+static int lcp_call(int dev, hipStream_t stream, const uint8_t *d_x, uint32_t n, const uint32_t *d_sa, const uint8_t *d_bwt, uint32_t *d_lcp,
+                    const uint32_t *sa_host, uint32_t *lcp_host, const uint8_t *x_host)
+{
+    Ctx *c;
+    ARCHON_TRY(ctx_get(dev, &c));
+    std::lock_guard<std::mutex> lk(c->mu);
+    ARCHON_HIP_TRY(hipSetDevice(dev));
+    hipStream_t s = stream ? stream : c->own_stream;
+    if (x_host) {                       // host buffers: block, suffix array and result through the context's staging buffers
+        ARCHON_TRY(ctx_io(c, 0, (size_t)n + 64, (void **)&d_x));
+        ARCHON_TRY(ctx_io(c, 1, (size_t)n * 4 + 64, (void **)&d_lcp));
+        ARCHON_TRY(ctx_io(c, 2, (size_t)n * 4 + 64, (void **)&d_sa));
+        ARCHON_HIP_TRY(hipMemcpyAsync((void *)d_x, x_host, n, hipMemcpyHostToDevice, s));
+    } else if (lcp_host) {              // a resident block: the result through a staging buffer
+        ARCHON_TRY(ctx_io(c, 1, (size_t)n * 4 + 64, (void **)&d_lcp));
+    }
+    if (sa_host) ARCHON_HIP_TRY(hipMemcpyAsync((void *)d_sa, sa_host, (size_t)n * 4, hipMemcpyHostToDevice, s));
+    archon_hip_lcp_stats st = {};
+    const int rc = lcp_run(c, s, d_x, n, d_sa, d_bwt, d_lcp, &st);
+    t_lcp_stats[dev] = st;
+    t_lcp_stats_set[dev] = true;
+    ARCHON_TRY(rc);
+    if (lcp_host) {
+        ARCHON_HIP_TRY(hipMemcpyAsync(lcp_host, d_lcp, (size_t)n * 4, hipMemcpyDeviceToHost, s));
+        ARCHON_SYNC(s);
+    }
+    return ARCHON_OK;
+}
+
+int archon_hip_lcp_dev(const uint8_t *d_x, uint32_t n, const uint32_t *d_sa, uint32_t *d_lcp, int dev, void *stream)
+{
+    if (!d_x || !d_sa || !d_lcp) { set_error("null pointer"); return ARCHON_E_ARG; }
+    ARCHON_TRY(check_n(n));
+    return lcp_call(dev, (hipStream_t)stream, d_x, n, d_sa, nullptr, d_lcp, nullptr, nullptr, nullptr);
+}
+
+int archon_hip_lcp(const uint8_t *x, uint32_t n, const uint32_t *sa, uint32_t *lcp, int dev)
+{
+    if (!x || !sa || !lcp) { set_error("null pointer"); return ARCHON_E_ARG; }
+    ARCHON_TRY(check_n(n));
+    return lcp_call(dev, nullptr, nullptr, n, nullptr, nullptr, nullptr, sa, lcp, x);
+}
+
 // ---- resident blocks ---------------------------------------------------------------------------------------------------
 // What a block-coder object keeps on the device between enCompute, validate and enWrite (bwt/a7/src/main.cpp:39-46): the
 // block, its suffix array and its BWT, in buffers of its own.  The state belongs to the HANDLE -- any number of objects on
@@ -1686,6 +1734,14 @@ int archon_hip_block_validate(archon_hip_block *b)
     return validate_resident_run(c, c->own_stream, b->d_x, b->n, b->d_sa, b->d_bwt, b->base);
 }
 
+int archon_hip_block_lcp(archon_hip_block *b, uint32_t *lcp)
+{
+    if (!b || !lcp) { set_error("null pointer"); return ARCHON_E_ARG; }
+    std::lock_guard<std::mutex> lkb(b->mu);
+    if (!b->valid || !b->has_sa) { set_error("no resident block with its suffix array"); return ARCHON_E_ARG; }
+    return lcp_call(b->dev, nullptr, b->d_x, b->n, b->d_sa, b->d_bwt, nullptr, nullptr, lcp, nullptr);
+}
+
 int archon_hip_block_stats(archon_hip_block *b, archon_hip_stats *out)
 {
     if (!b || !out) { set_error("null pointer"); return ARCHON_E_ARG; }
@@ -1729,6 +1785,14 @@ int archon_hip_validate_keep(int dev)
     archon_hip_block *b;
     ARCHON_TRY(default_block(dev, &b));
     return archon_hip_block_validate(b);
+}
+
+int archon_hip_lcp_keep(int dev, uint32_t *lcp)
+{
+    if (!lcp) { set_error("null pointer"); return ARCHON_E_ARG; }
+    archon_hip_block *b;
+    ARCHON_TRY(default_block(dev, &b));
+    return archon_hip_block_lcp(b, lcp);
 }
 
 int archon_hip_bind_context(int dev, int slot)
@@ -2374,6 +2438,16 @@ int archon_hip_test_route(const char *name, long value)
     if (!strcmp(name, "KEY_BYTES")) { g_route.key_bytes = (int)value; return ARCHON_OK; }
     if (!strcmp(name, "INV_SBITS")) { g_route.inv_sbits = (int)value; return ARCHON_OK; }
     if (!strcmp(name, "INV_WALK_WGS")) { g_route.inv_walk_wgs = (int)value; return ARCHON_OK; }
+    if (!strcmp(name, "LCP_CAP")) {
+        if (value > 4096) { set_error("LCP_CAP=%ld out of range [1, 4096]", value); return ARCHON_E_ARG; }
+        g_route.lcp_cap = value > 0 ? (int)value : 0;
+        return ARCHON_OK;
+    }
+    if (!strcmp(name, "LCP_WINDOW")) {
+        if (value > (1l << 30)) { set_error("LCP_WINDOW=%ld out of range [1, 2^30]", value); return ARCHON_E_ARG; }
+        g_route.lcp_window = value > 0 ? value : 0;
+        return ARCHON_OK;
+    }
     for (const auto &f : kFlags)
         if (!strcmp(name, f.name)) {
             if (value) g_route.flags |= f.bit; else g_route.flags &= ~f.bit;
@@ -2381,6 +2455,14 @@ int archon_hip_test_route(const char *name, long value)
         }
     set_error("unknown route '%s'", name);
     return ARCHON_E_ARG;
+}
+
+int archon_hip_get_lcp_stats(int dev, archon_hip_lcp_stats *out)
+{
+    if (!out) { set_error("null pointer"); return ARCHON_E_ARG; }
+    if (dev < 0 || dev >= kMaxDev || !t_lcp_stats_set[dev]) { set_error("the calling thread has run no LCP call on device %d", dev); return ARCHON_E_ARG; }
+    *out = t_lcp_stats[dev];
+    return ARCHON_OK;
 }
 
 int archon_hip_get_stats(int dev, archon_hip_stats *out)

@@ -32,6 +32,7 @@ SYMBOLS = [
     "archon_hip_post_bound", "archon_hip_post_encode_dev", "archon_hip_forward_post", "archon_hip_validate_resident_dev",
     "archon_hip_forward_batch", "archon_hip_inverse_batch", "archon_hip_forward_batch_dev", "archon_hip_inverse_batch_dev",
     "archon_hip_post_decode_dev", "archon_hip_inverse_post",
+    "archon_hip_lcp", "archon_hip_lcp_dev", "archon_hip_block_lcp", "archon_hip_lcp_keep", "archon_hip_get_lcp_stats",
 ]
 
 
@@ -56,6 +57,18 @@ class Stats(ctypes.Structure):
 
     def asdict(self):
         return {k: getattr(self, k) for k, _ in self._fields_ if not k.startswith("_")}
+
+
+class LcpStats(ctypes.Structure):
+    """archon_hip_lcp_stats: the calling thread's last LCP call on a device"""
+    _fields_ = [
+        ("n", ctypes.c_uint32), ("long_rounds", ctypes.c_uint32), ("max_lcp", ctypes.c_uint32), ("kernel_launches", ctypes.c_uint32),
+        ("irreducible", ctypes.c_uint64), ("long_items", ctypes.c_uint64), ("compared_bytes", ctypes.c_uint64),
+        ("host_syncs", ctypes.c_uint32), ("ms_total", ctypes.c_float),
+    ]
+
+    def asdict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
 
 
 class ArchonError(RuntimeError):
@@ -116,6 +129,11 @@ def load():
         "archon_hip_inverse_batch_dev": [vp, vp, vp, u32, vp, i32, i32],
         "archon_hip_post_encode_dev": [vp, u32, vp, sz, vp, i32, vp],
         "archon_hip_forward_post": [vp, u32, vp, sz, vp, vp, i32],
+        "archon_hip_lcp": [vp, u32, vp, vp, i32],
+        "archon_hip_lcp_dev": [vp, u32, vp, vp, i32, vp],
+        "archon_hip_block_lcp": [vp, vp],
+        "archon_hip_lcp_keep": [i32, vp],
+        "archon_hip_get_lcp_stats": [i32, ctypes.POINTER(LcpStats)],
     }.items():
         fn = getattr(lib, name)
         fn.argtypes = args
@@ -136,7 +154,8 @@ _routes_seen = None
 # before the next call into the library.
 _ROUTE_NAMES = ("FORCE_PATH", "SMALL_BLOCK", "PASS_RANGES", "INV_ROWS", "INV_SLAB", "INV_SBITS", "INV_WALK_WGS", "NO_ALIGNED", "NO_CHAINS", "NO_DEEP_HINT",
                 "NO_PACK", "NO_PACK_STREAM", "NO_PAIR_CHAINS", "NO_PERIOD_HINT", "NO_BREAK_ROUND", "NO_PERIOD_PROBE", "NO_PERIOD_STREAM", "NO_PROBE",
-                "NO_RANK_WRITER", "NO_TEXT_ROUNDS", "NO_MID", "NO_SHALLOW", "NO_CLOSED_FORM", "NO_REL_RECORDS", "ALIGNED_MIN", "REL_MIN_SEG", "KEY_BYTES")
+                "NO_RANK_WRITER", "NO_TEXT_ROUNDS", "NO_MID", "NO_SHALLOW", "NO_CLOSED_FORM", "NO_REL_RECORDS", "ALIGNED_MIN", "REL_MIN_SEG", "KEY_BYTES",
+                "LCP_CAP", "LCP_WINDOW")
 
 
 def _sync_routes(L):
@@ -233,6 +252,22 @@ def lms_select(x, dev=0):
     return count, items[:n1.value]
 
 
+def lcp(x, sa, dev=0):
+    """the LCP array of suffix array sa of x (include/archon_hip.h: archon_hip_lcp), uint32[n]"""
+    x = np.ascontiguousarray(x, dtype=np.uint8)
+    sa = np.ascontiguousarray(sa, dtype=np.uint32)
+    out = np.empty(x.size, np.uint32)
+    _check(lib().archon_hip_lcp(_p(x), x.size, _p(sa), _p(out), dev))
+    return out
+
+
+def lcp_stats(dev=0):
+    """LcpStats of the calling thread's last LCP call on dev"""
+    s = LcpStats()
+    _check(lib().archon_hip_get_lcp_stats(dev, ctypes.byref(s)))
+    return s
+
+
 def radix_scatter(src, dev=0):
     src = np.ascontiguousarray(src, dtype=np.uint8)
     dst = np.empty_like(src)
@@ -313,6 +348,12 @@ class Block:
     def validate(self):
         return bool(_check(lib().archon_hip_block_validate(self.h)))
 
+    def lcp(self):
+        """the LCP array of the resident block's suffix array (needs forward(want_sa=True))"""
+        out = np.empty(self.n, np.uint32)
+        _check(lib().archon_hip_block_lcp(self.h, _p(out)))
+        return out
+
     def stats(self):
         s = Stats()
         _check(lib().archon_hip_block_stats(self.h, ctypes.byref(s)))
@@ -351,6 +392,13 @@ def validate_dev(x_t, sa_t):
     dev = x_t.device.index or 0
     return bool(_check(lib().archon_hip_validate_dev(ctypes.c_void_p(x_t.data_ptr()), x_t.numel(),
                                                      ctypes.c_void_p(sa_t.data_ptr()), dev, _stream_ptr())))
+
+
+def lcp_dev(x_t, sa_t, lcp_t):
+    """torch CUDA tensors: x uint8[n], sa int32[n], lcp int32[n] (written; must not overlap x or sa), on the current stream"""
+    dev = x_t.device.index or 0
+    _check(lib().archon_hip_lcp_dev(ctypes.c_void_p(x_t.data_ptr()), x_t.numel(), ctypes.c_void_p(sa_t.data_ptr()),
+                                    ctypes.c_void_p(lcp_t.data_ptr()), dev, _stream_ptr()))
 
 
 def validate_resident_dev(x_t, sa_t, bwt_t, base_id):

@@ -13,6 +13,7 @@
  *   archon_hip_sa_to_bwt    the gather loop of Archon::enWrite alone (887-900), for a caller's own SA
  *   archon_hip_radix_scatter  the counting-sort scatter of tool/radix_dir/radix.c:40-44
  *   archon_hip_lms_select   Constructor::findLMS (160-172): the subset a7 sorts directly (a4 IT-2: bwt/a4/src/archon.c:163-169)
+ *   archon_hip_lcp          nothing: the LCP array of the suffix array, below
  *
  * Ordering convention ("a7 order"): item s in 1..N names the
  * reversed prefix x[s-1],x[s-2],...,x[0],INF with INF > 255; sa[0..N) lists the
@@ -215,6 +216,44 @@ int archon_hip_post_decode_dev(const uint8_t *d_in, size_t in_bytes, uint8_t *d_
 /* host stream + primary index -> the block (x_out holds cap bytes), host buffers: stream decoded and BWT inverted on the device, only the
  * packed stream goes up the link */
 int archon_hip_inverse_post(const uint8_t *in, size_t in_bytes, uint32_t base_id, uint8_t *x_out, uint32_t cap, uint32_t *n_out, int dev);
+
+/* ---- the LCP array of a suffix array (no counterpart in the reference: what its users compute next) -------------------
+ * lcp[0] = 0; for i >= 1, lcp[i] = the largest L such that the keys of items sa[i-1] and sa[i] agree in their first L
+ * symbols, keys in a7 order as above (item s: x[s-1], x[s-2], ..., x[0], INF).  INF matches nothing, so
+ * lcp[i] <= min(sa[i-1], sa[i]).  Orientation: for z[k] = 255 - x[n-1-k] (the block reversed, bytes complemented), item s
+ * is z's suffix at n - s and ascending a7 order is DESCENDING lexicographic order of z's suffixes, so with SA_z and LCP_z
+ * the textbook suffix and LCP arrays of z (LCP_z[k] = lcp of SA_z[k-1] and SA_z[k]): sa[i] = n - SA_z[n-1-i] and
+ * lcp[i] = LCP_z[n-i] for i >= 1.  A caller who wants the textbook arrays of a text z passes x[k] = 255 - z[n-1-k].
+ * Work: only rows where bwt[i] != bwt[i-1] (or that touch the item n, or row 0) compare key bytes; every other row follows
+ * from the row of item sa[i] + 1 by the LF rule.  Those comparisons sum to at most 2 n log2 n bytes (Kärkkäinen, Manzini
+ * and Puglisi, CPM 2009), and one row with a long lcp (a block of one repeated byte) runs over the whole device.
+ * Bad input: an sa that is not a permutation of 1..n (a value outside 1..n, or one value twice) is refused with
+ * ARCHON_E_CORRUPT before any key byte is compared.  A permutation that is not the a7 suffix array of x returns ARCHON_OK
+ * with unspecified contents: every access stays inside x, sa and lcp.  Check sa with archon_hip_validate first when it is
+ * not known to be right.  Workspace: about 8n bytes of the calling thread's context arena (grown on demand). */
+/* host buffers; lcp[n] */
+int archon_hip_lcp(const uint8_t *x, uint32_t n, const uint32_t *sa, uint32_t *lcp, int dev);
+/* device pointers; enqueued on `stream` (NULL = the context's own) like archon_hip_validate_dev, complete on return.
+ * d_lcp must not overlap d_x or d_sa (it is scratch of the call until its last kernel writes it). */
+int archon_hip_lcp_dev(const uint8_t *d_x, uint32_t n, const uint32_t *d_sa, uint32_t *d_lcp, int dev, void *stream);
+/* the resident block of the handle's last forward (x, SA and BWT on the device; the BWT stands in for x[sa[i]]); lcp[n]
+ * is a host buffer.  ARCHON_E_ARG when that forward kept no suffix array. */
+int archon_hip_block_lcp(archon_hip_block *b, uint32_t *lcp);
+/* the same on the calling thread's default block (archon_hip_forward_keep) */
+int archon_hip_lcp_keep(int dev, uint32_t *lcp);
+/* work counters and device time of the CALLING THREAD's last LCP call on `dev` (LCP calls leave archon_hip_stats alone) */
+typedef struct archon_hip_lcp_stats {
+    uint32_t n;                 /* block size of the call */
+    uint32_t long_rounds;       /* rounds of the long comparisons (one host wait each) */
+    uint32_t max_lcp;           /* the largest value of the array */
+    uint32_t kernel_launches;   /* launches issued by the call */
+    uint64_t irreducible;       /* rows whose value was found by comparing key bytes */
+    uint64_t long_items;        /* of them, rows that outgrew the per-lane cap K */
+    uint64_t compared_bytes;    /* key bytes compared, all stages */
+    uint32_t host_syncs;        /* times the host waited for the stream inside the call */
+    float ms_total;             /* device time of the call (HIP events on its stream) */
+} archon_hip_lcp_stats;
+int archon_hip_get_lcp_stats(int dev, archon_hip_lcp_stats *out);
 
 /* ---- measurement ------------------------------------------------------------- */
 
