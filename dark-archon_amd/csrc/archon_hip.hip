@@ -12,6 +12,7 @@
 #include "inverse.hiph"
 #include "post.hiph"
 #include "lcp.hiph"
+#include "fm.hiph"
 
 #include <stdarg.h>
 #include <atomic>
@@ -61,6 +62,9 @@ static thread_local bool t_stats_set[kMaxDev];
 // the same for the thread's last LCP call (archon_hip_get_lcp_stats): LCP calls leave archon_hip_stats alone
 static thread_local archon_hip_lcp_stats t_lcp_stats[kMaxDev];
 static thread_local bool t_lcp_stats_set[kMaxDev];
+// and for its last FM call (archon_hip_get_fm_stats): FM calls leave both of the others alone
+static thread_local archon_hip_fm_stats t_fm_stats[kMaxDev];
+static thread_local bool t_fm_stats_set[kMaxDev];
 
 static inline int keep_stats(Ctx *c, int rc)
 {
@@ -1611,6 +1615,285 @@ int archon_hip_lcp(const uint8_t *x, uint32_t n, const uint32_t *sa, uint32_t *l
     return lcp_call(dev, nullptr, nullptr, n, nullptr, nullptr, nullptr, sa, lcp, x);
 }
 
+// ---- the FM index (fm.hiph)
+// The handle owns one device allocation: [its copy of the BWT] | super | sub | R.  A resident block's handle reads the
+// block's own d_bwt (n + 64 bytes, so 16-byte loads that start below n stay inside it) and has no copy.
+struct archon_hip_fm {
+    int dev = 0;
+    uint32_t n = 0, base = 0, base_sym = 0, sbits = 0, bbits = 0;
+    char *mem = nullptr;
+    const uint8_t *bwt = nullptr;
+    uint32_t *super = nullptr, *R = nullptr;
+    uint16_t *sub = nullptr;
+    uint64_t table_bytes = 0;
+    fmk::FmTable table() const { return fmk::FmTable{bwt, super, sub, R, n, base, base_sym, sbits, bbits}; }
+};
+
+static void fm_release(archon_hip_fm *f)
+{
+    if (!f) return;
+    if (f->mem) {
+        (void)hipSetDevice(f->dev);
+        (void)hipFree(f->mem);
+    }
+    delete f;
+}
+
+static inline size_t round256(size_t b) { return (b + 255) & ~size_t(255); }
+
+static inline int log2_exact(uint32_t v)
+{
+    int b = 0;
+    while ((1u << b) < v) ++b;
+    return b;
+}
+
+// Builds a table over a BWT: h_bwt (host) or d_bwt (device) is copied into the handle's memory when `copy`; otherwise the
+// handle reads d_bwt where it is.  The stream holds the build until the one wait at its end (the primary row's byte).
+static int fm_build(Ctx *c, hipStream_t s, const uint8_t *h_bwt, const uint8_t *d_bwt, bool copy, uint32_t n, uint32_t base,
+                    archon_hip_fm **out, archon_hip_fm_stats *st)
+{
+    using namespace fmk;
+    const uint32_t sub_rows = g_route.fm_sub_rows > 0 ? (uint32_t)g_route.fm_sub_rows : 1u << kSubBits;
+    const uint32_t super_rows = g_route.fm_super_rows > 0 ? (uint32_t)g_route.fm_super_rows : 1u << kSuperBits;
+    if (super_rows < sub_rows) { set_error("FM_SUPER_ROWS=%u is not a multiple of FM_SUB_ROWS=%u", super_rows, sub_rows); return ARCHON_E_ARG; }
+    FmArena L;
+    ARCHON_TRY(ctx_carve(c, [&](Carve &a) { return fm_layout(a, L, 0, 0, 0); }));
+    const uint32_t syncs0 = t_sync_count;
+    archon_hip_fm *f = new archon_hip_fm();
+    f->dev = c->dev;
+    f->n = n;
+    f->base = base;
+    f->sbits = (uint32_t)log2_exact(super_rows);
+    f->bbits = (uint32_t)log2_exact(sub_rows);
+    const uint32_t nsuper = (n >> f->sbits) + 1, nsub = (n >> f->bbits) + 1;
+    const size_t own = copy ? round256((size_t)n + 64) : 0;
+    const size_t super_b = (size_t)nsuper * 256 * 4, sub_b = round256((size_t)nsub * 256 * 2), r_b = round256(257 * 4);
+    f->table_bytes = super_b + sub_b + r_b;
+    if (hipMalloc((void **)&f->mem, own + f->table_bytes) != hipSuccess) {
+        (void)hipGetLastError();
+        delete f;
+        set_error("FM index: device allocation of %zu bytes failed", own + (size_t)f->table_bytes);
+        return ARCHON_E_NOMEM;
+    }
+    f->bwt = copy ? reinterpret_cast<const uint8_t *>(f->mem) : d_bwt;
+    f->super = reinterpret_cast<uint32_t *>(f->mem + own);
+    f->sub = reinterpret_cast<uint16_t *>(f->mem + own + super_b);
+    f->R = reinterpret_cast<uint32_t *>(f->mem + own + super_b + sub_b);
+    auto fail = [&](int rc) { fm_release(f); return rc; };
+    if (copy && hipMemcpyAsync(f->mem, h_bwt ? (const void *)h_bwt : (const void *)d_bwt, n,
+                               h_bwt ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice, s) != hipSuccess) {
+        set_error("FM index: copy of the BWT failed: %s", hipGetErrorString(hipGetLastError()));
+        return fail(ARCHON_E_HIP);
+    }
+    StageTimer tm(c, 72, s);
+    const int e0 = tm.mark();
+    hipLaunchKernelGGL(inv::k_chunk_hist, dim3(nsuper), dim3(kHistBlock), 0, s, f->bwt, n, base, super_rows, f->super);
+    hipLaunchKernelGGL(inv::k_chunk_scan, dim3(1), dim3(1024), 0, s, f->super, nsuper, f->bwt, base, L.totals, f->R);
+    hipLaunchKernelGGL(k_fm_sub, dim3(nsuper), dim3(256), 0, s, f->bwt, n, base, f->sbits, f->bbits, nsub, f->sub);
+    const int e1 = tm.mark();
+    uint32_t *rd = c->h_mail + mail::kRead.at;
+    rd[0] = 0;
+    if (hipGetLastError() != hipSuccess || hipMemcpyAsync(rd, f->bwt + base, 1, hipMemcpyDeviceToHost, s) != hipSuccess ||
+        hipStreamSynchronize(s) != hipSuccess) {
+        set_error("FM index: table build failed: %s", hipGetErrorString(hipGetLastError()));
+        return fail(ARCHON_E_HIP);
+    }
+    ++t_sync_count;
+    f->base_sym = rd[0] & 0xFFu;
+    st->n = n;
+    st->built = 1;
+    st->table_bytes = f->table_bytes;
+    st->kernel_launches += 3;
+    st->host_syncs += t_sync_count - syncs0;
+    st->ms_build = tm.ms(e0, e1);
+    *out = f;
+    return ARCHON_OK;
+}
+
+// The count kernel over device patterns, offsets and ranges; the step counters and the bad-offsets flag into *st / the return.
+static int fm_count_run(Ctx *c, hipStream_t s, const archon_hip_fm *f, const uint8_t *d_pat, const uint32_t *d_off, uint32_t k,
+                        uint32_t *d_lo, uint32_t *d_hi, StageTimer &tm, archon_hip_fm_stats *st)
+{
+    using namespace fmk;
+    uint32_t *mail = c->d_mail + mail::kDevFm.at, *rd = c->h_mail + mail::kRead.at;
+    static_assert(kWords <= mail::kDevFm.len && kWords <= mail::kRead.len, "the FM words in the mailbox");
+    ARCHON_HIP_TRY(hipMemsetAsync(mail, 0, kWords * sizeof(uint32_t), s));
+    const uint32_t g = div_up(k, 4);
+    hipLaunchKernelGGL(k_fm_count, dim3(g < kCountGrid ? g : kCountGrid), dim3(256), 0, s, f->table(), d_pat, d_off, k, d_lo, d_hi, mail);
+    ARCHON_HIP_TRY(hipGetLastError());
+    tm.mark();
+    ARCHON_HIP_TRY(hipMemcpyAsync(rd, mail, kWords * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+    ARCHON_SYNC(s);
+    st->kernel_launches += 1;
+    memcpy(&st->steps, rd + kSteps, sizeof(uint64_t));
+    memcpy(&st->shared_steps, rd + kShared, sizeof(uint64_t));
+    if (rd[kBadOffsets]) { set_error("FM index: offsets decrease"); return ARCHON_E_ARG; }
+    return ARCHON_OK;
+}
+
+static int fm_check_offsets(const uint32_t *offsets, uint32_t k)
+{
+    for (uint32_t j = 0; j < k; ++j)
+        if (offsets[j + 1] < offsets[j]) { set_error("FM index: offsets[%u] < offsets[%u]", j + 1, j); return ARCHON_E_ARG; }
+    return ARCHON_OK;
+}
+
+static void fm_keep_stats(int dev, const archon_hip_fm_stats &st)
+{
+    t_fm_stats[dev] = st;
+    t_fm_stats_set[dev] = true;
+}
+
+// Host patterns and ranges through the context's arena.  When `locate` is given (a resident block's suffix array), the
+// ranges come back, the host sums them, and a gather writes the starts.
+struct FmLocate {
+    const uint32_t *d_sa;
+    uint32_t *pos;
+    uint64_t cap;
+    uint64_t *total;
+};
+static int fm_host_query(Ctx *c, hipStream_t s, const archon_hip_fm *f, const uint8_t *patterns, const uint32_t *offsets, uint32_t k,
+                         uint32_t *lo, uint32_t *hi, const FmLocate *loc, archon_hip_fm_stats *st)
+{
+    using namespace fmk;
+    const size_t pat_bytes = offsets[k];
+    st->n = f->n;
+    st->patterns = k;
+    st->pattern_bytes = (uint64_t)offsets[k] - offsets[0];
+    st->table_bytes = f->table_bytes;
+    FmArena L;
+    ARCHON_TRY(ctx_carve(c, [&](Carve &a) { return fm_layout(a, L, pat_bytes, k, 0); }));
+    const uint32_t syncs0 = t_sync_count;
+    if (pat_bytes) ARCHON_HIP_TRY(hipMemcpyAsync(L.pat, patterns, pat_bytes, hipMemcpyHostToDevice, s));
+    ARCHON_HIP_TRY(hipMemcpyAsync(L.off, offsets, ((size_t)k + 1) * 4, hipMemcpyHostToDevice, s));
+    StageTimer tm(c, 72, s);
+    const int e0 = tm.mark();
+    ARCHON_TRY(fm_count_run(c, s, f, L.pat, L.off, k, L.lo, L.hi, tm, st));
+    const int e1 = tm.n - 1;
+    ARCHON_HIP_TRY(hipMemcpyAsync(lo, L.lo, (size_t)k * 4, hipMemcpyDeviceToHost, s));
+    ARCHON_HIP_TRY(hipMemcpyAsync(hi, L.hi, (size_t)k * 4, hipMemcpyDeviceToHost, s));
+    ARCHON_SYNC(s);
+    st->ms_query = tm.ms(e0, e1);
+    if (loc) {
+        std::vector<uint64_t> first((size_t)k + 1);
+        uint64_t t = 0;
+        for (uint32_t j = 0; j < k; ++j) {
+            first[j] = t;
+            t += hi[j] > lo[j] ? hi[j] - lo[j] : 0;
+        }
+        first[k] = t;
+        *loc->total = t;
+        if (t > loc->cap) {
+            st->host_syncs += t_sync_count - syncs0;
+            set_error("FM locate: %llu starts, room for %llu", (unsigned long long)t, (unsigned long long)loc->cap);
+            return ARCHON_E_ARG;
+        }
+        // the arena may move for the positions: the offsets, lo and the sums go up again
+        ARCHON_TRY(ctx_carve(c, [&](Carve &a) { return fm_layout(a, L, 0, k, t); }));
+        ARCHON_HIP_TRY(hipMemcpyAsync(L.off, offsets, ((size_t)k + 1) * 4, hipMemcpyHostToDevice, s));
+        ARCHON_HIP_TRY(hipMemcpyAsync(L.lo, lo, (size_t)k * 4, hipMemcpyHostToDevice, s));
+        ARCHON_HIP_TRY(hipMemcpyAsync(L.first, first.data(), ((size_t)k + 1) * 8, hipMemcpyHostToDevice, s));
+        const int e2 = tm.mark();
+        if (t) {
+            const uint64_t g = (t + 255) / 256;
+            hipLaunchKernelGGL(k_fm_locate, dim3(g < kLocateGrid ? (uint32_t)g : kLocateGrid), dim3(256), 0, s, loc->d_sa, L.off, L.lo, L.first, k, L.pos);
+            ARCHON_HIP_TRY(hipGetLastError());
+            st->kernel_launches += 1;
+        }
+        const int e3 = tm.mark();
+        if (t) ARCHON_HIP_TRY(hipMemcpyAsync(loc->pos, L.pos, t * 4, hipMemcpyDeviceToHost, s));
+        ARCHON_SYNC(s);
+        st->ms_query += tm.ms(e2, e3);
+    }
+    st->host_syncs += t_sync_count - syncs0;
+    return ARCHON_OK;
+}
+
+int archon_hip_fm_create(const uint8_t *bwt, uint32_t n, uint32_t base_id, int dev, archon_hip_fm **out)
+{
+    if (!bwt || !out) { set_error("null pointer"); return ARCHON_E_ARG; }
+    ARCHON_TRY(check_n(n));
+    if (base_id >= n) { set_error("primary row %u out of range [0, %u)", base_id, n); return ARCHON_E_ARG; }
+    Ctx *c;
+    ARCHON_TRY(ctx_get(dev, &c));
+    std::lock_guard<std::mutex> lk(c->mu);
+    ARCHON_HIP_TRY(hipSetDevice(dev));
+    archon_hip_fm_stats st = {};
+    const int rc = fm_build(c, c->own_stream, bwt, nullptr, true, n, base_id, out, &st);
+    fm_keep_stats(dev, st);
+    return rc;
+}
+
+int archon_hip_fm_create_dev(const uint8_t *d_bwt, uint32_t n, uint32_t base_id, int dev, void *stream, archon_hip_fm **out)
+{
+    if (!d_bwt || !out) { set_error("null pointer"); return ARCHON_E_ARG; }
+    ARCHON_TRY(check_n(n));
+    if (base_id >= n) { set_error("primary row %u out of range [0, %u)", base_id, n); return ARCHON_E_ARG; }
+    Ctx *c;
+    ARCHON_TRY(ctx_get(dev, &c));
+    std::lock_guard<std::mutex> lk(c->mu);
+    ARCHON_HIP_TRY(hipSetDevice(dev));
+    archon_hip_fm_stats st = {};
+    const int rc = fm_build(c, stream ? (hipStream_t)stream : c->own_stream, nullptr, d_bwt, true, n, base_id, out, &st);
+    fm_keep_stats(dev, st);
+    return rc;
+}
+
+void archon_hip_fm_destroy(archon_hip_fm *f) { fm_release(f); }
+
+int archon_hip_fm_count(archon_hip_fm *f, const uint8_t *patterns, const uint32_t *offsets, uint32_t k, uint32_t *lo, uint32_t *hi)
+{
+    if (!f || !patterns || !offsets || !lo || !hi) { set_error("null pointer"); return ARCHON_E_ARG; }
+    if (!k) return ARCHON_OK;
+    ARCHON_TRY(fm_check_offsets(offsets, k));
+    Ctx *c;
+    ARCHON_TRY(ctx_get(f->dev, &c));
+    std::lock_guard<std::mutex> lk(c->mu);
+    ARCHON_HIP_TRY(hipSetDevice(f->dev));
+    archon_hip_fm_stats st = {};
+    const int rc = fm_host_query(c, c->own_stream, f, patterns, offsets, k, lo, hi, nullptr, &st);
+    fm_keep_stats(f->dev, st);
+    return rc;
+}
+
+int archon_hip_fm_count_dev(archon_hip_fm *f, const uint8_t *d_patterns, const uint32_t *d_offsets, uint32_t k, uint32_t *d_lo, uint32_t *d_hi,
+                            void *stream)
+{
+    if (!f || !d_patterns || !d_offsets || !d_lo || !d_hi) { set_error("null pointer"); return ARCHON_E_ARG; }
+    if (!k) return ARCHON_OK;
+    Ctx *c;
+    ARCHON_TRY(ctx_get(f->dev, &c));
+    std::lock_guard<std::mutex> lk(c->mu);
+    ARCHON_HIP_TRY(hipSetDevice(f->dev));
+    hipStream_t s = stream ? (hipStream_t)stream : c->own_stream;
+    archon_hip_fm_stats st = {};
+    st.n = f->n;
+    st.patterns = k;
+    st.table_bytes = f->table_bytes;
+    const uint32_t syncs0 = t_sync_count;
+    uint32_t *ends = c->h_mail + mail::kRead.at + fmk::kWords;     // offsets[0] and offsets[k], for the statistics
+    static_assert(fmk::kWords + 2 <= mail::kRead.len, "the FM words and the offsets' ends in the readback words");
+    ARCHON_HIP_TRY(hipMemcpyAsync(&ends[0], d_offsets, 4, hipMemcpyDeviceToHost, s));
+    ARCHON_HIP_TRY(hipMemcpyAsync(&ends[1], d_offsets + k, 4, hipMemcpyDeviceToHost, s));
+    StageTimer tm(c, 72, s);
+    const int e0 = tm.mark();
+    const int rc = fm_count_run(c, s, f, d_patterns, d_offsets, k, d_lo, d_hi, tm, &st);
+    st.ms_query = tm.ms(e0, tm.n - 1);
+    st.pattern_bytes = ends[1] >= ends[0] ? ends[1] - ends[0] : 0;
+    st.host_syncs = t_sync_count - syncs0;
+    fm_keep_stats(f->dev, st);
+    return rc;
+}
+
+int archon_hip_get_fm_stats(int dev, archon_hip_fm_stats *out)
+{
+    if (!out) { set_error("null pointer"); return ARCHON_E_ARG; }
+    if (dev < 0 || dev >= kMaxDev || !t_fm_stats_set[dev]) { set_error("the calling thread has run no FM call on device %d", dev); return ARCHON_E_ARG; }
+    *out = t_fm_stats[dev];
+    return ARCHON_OK;
+}
+
 // ---- resident blocks ---------------------------------------------------------------------------------------------------
 // What a block-coder object keeps on the device between enCompute, validate and enWrite (bwt/a7/src/main.cpp:39-46): the
 // block, its suffix array and its BWT, in buffers of its own.  The state belongs to the HANDLE -- any number of objects on
@@ -1624,6 +1907,7 @@ struct archon_hip_block {
     uint32_t n = 0, base = 0;
     bool valid = false, has_sa = false;
     archon_hip_stats stats;
+    archon_hip_fm *fm = nullptr;        // the FM index over d_bwt, built by the first FM call after a forward
 };
 
 static int block_reserve(archon_hip_block *b, uint32_t n, bool want_sa)
@@ -1673,6 +1957,7 @@ void archon_hip_block_destroy(archon_hip_block *b)
     if (!b) return;
     {
         std::lock_guard<std::mutex> lk(b->mu);
+        fm_release(b->fm);
         if (b->d_x || b->d_sa) {
             (void)hipSetDevice(b->dev);
             if (b->d_x) (void)hipFree(b->d_x);
@@ -1689,6 +1974,8 @@ int archon_hip_block_forward(archon_hip_block *b, const uint8_t *x, uint32_t n, 
     ARCHON_TRY(check_n(n));
     std::lock_guard<std::mutex> lkb(b->mu);
     b->valid = false;
+    fm_release(b->fm);
+    b->fm = nullptr;
     Ctx *c;
     ARCHON_TRY(ctx_get(b->dev, &c));
     std::lock_guard<std::mutex> lk(c->mu);
@@ -1740,6 +2027,51 @@ int archon_hip_block_lcp(archon_hip_block *b, uint32_t *lcp)
     std::lock_guard<std::mutex> lkb(b->mu);
     if (!b->valid || !b->has_sa) { set_error("no resident block with its suffix array"); return ARCHON_E_ARG; }
     return lcp_call(b->dev, nullptr, b->d_x, b->n, b->d_sa, b->d_bwt, nullptr, nullptr, lcp, nullptr);
+}
+
+// the block's FM handle over its own BWT: built on the first FM call after a forward (b->mu and the context held)
+static int block_fm(archon_hip_block *b, Ctx *c, archon_hip_fm_stats *st)
+{
+    if (b->fm) return ARCHON_OK;
+    return fm_build(c, c->own_stream, nullptr, b->d_bwt, false, b->n, b->base, &b->fm, st);
+}
+
+static int block_fm_query(archon_hip_block *b, const uint8_t *patterns, const uint32_t *offsets, uint32_t k, uint32_t *lo, uint32_t *hi,
+                          const FmLocate *loc)
+{
+    Ctx *c;
+    ARCHON_TRY(ctx_get(b->dev, &c));
+    std::lock_guard<std::mutex> lk(c->mu);
+    ARCHON_HIP_TRY(hipSetDevice(b->dev));
+    archon_hip_fm_stats st = {};
+    int rc = block_fm(b, c, &st);
+    if (rc == ARCHON_OK) rc = fm_host_query(c, c->own_stream, b->fm, patterns, offsets, k, lo, hi, loc, &st);
+    fm_keep_stats(b->dev, st);
+    return rc;
+}
+
+int archon_hip_block_fm_count(archon_hip_block *b, const uint8_t *patterns, const uint32_t *offsets, uint32_t k, uint32_t *lo, uint32_t *hi)
+{
+    if (!b || !patterns || !offsets || !lo || !hi) { set_error("null pointer"); return ARCHON_E_ARG; }
+    std::lock_guard<std::mutex> lkb(b->mu);
+    if (!b->valid) { set_error("no resident block"); return ARCHON_E_ARG; }
+    if (!k) return ARCHON_OK;
+    ARCHON_TRY(fm_check_offsets(offsets, k));
+    return block_fm_query(b, patterns, offsets, k, lo, hi, nullptr);
+}
+
+int archon_hip_block_fm_locate(archon_hip_block *b, const uint8_t *patterns, const uint32_t *offsets, uint32_t k, uint32_t *pos, uint64_t cap,
+                               uint64_t *total)
+{
+    if (!b || !patterns || !offsets || !pos || !total) { set_error("null pointer"); return ARCHON_E_ARG; }
+    std::lock_guard<std::mutex> lkb(b->mu);
+    if (!b->valid || !b->has_sa) { set_error("no resident block with its suffix array"); return ARCHON_E_ARG; }
+    *total = 0;
+    if (!k) return ARCHON_OK;
+    ARCHON_TRY(fm_check_offsets(offsets, k));
+    std::vector<uint32_t> lo(k), hi(k);
+    const FmLocate loc{b->d_sa, pos, cap, total};
+    return block_fm_query(b, patterns, offsets, k, lo.data(), hi.data(), &loc);
 }
 
 int archon_hip_block_stats(archon_hip_block *b, archon_hip_stats *out)
@@ -2446,6 +2778,22 @@ int archon_hip_test_route(const char *name, long value)
     if (!strcmp(name, "LCP_WINDOW")) {
         if (value > (1l << 30)) { set_error("LCP_WINDOW=%ld out of range [1, 2^30]", value); return ARCHON_E_ARG; }
         g_route.lcp_window = value > 0 ? value : 0;
+        return ARCHON_OK;
+    }
+    if (!strcmp(name, "FM_SUB_ROWS")) {
+        if (value && (value < 16 || value > 1024 || (value & (value - 1)))) {
+            set_error("FM_SUB_ROWS=%ld: not a power of two in [16, 1024]", value);
+            return ARCHON_E_ARG;
+        }
+        g_route.fm_sub_rows = (int)value;
+        return ARCHON_OK;
+    }
+    if (!strcmp(name, "FM_SUPER_ROWS")) {
+        if (value && (value < 16 || value > 65536 || (value & (value - 1)))) {
+            set_error("FM_SUPER_ROWS=%ld: not a power of two in [16, 65536]", value);
+            return ARCHON_E_ARG;
+        }
+        g_route.fm_super_rows = (int)value;
         return ARCHON_OK;
     }
     for (const auto &f : kFlags)

@@ -33,6 +33,8 @@ SYMBOLS = [
     "archon_hip_forward_batch", "archon_hip_inverse_batch", "archon_hip_forward_batch_dev", "archon_hip_inverse_batch_dev",
     "archon_hip_post_decode_dev", "archon_hip_inverse_post",
     "archon_hip_lcp", "archon_hip_lcp_dev", "archon_hip_block_lcp", "archon_hip_lcp_keep", "archon_hip_get_lcp_stats",
+    "archon_hip_fm_create", "archon_hip_fm_create_dev", "archon_hip_fm_destroy", "archon_hip_fm_count", "archon_hip_fm_count_dev",
+    "archon_hip_block_fm_count", "archon_hip_block_fm_locate", "archon_hip_get_fm_stats",
 ]
 
 
@@ -65,6 +67,18 @@ class LcpStats(ctypes.Structure):
         ("n", ctypes.c_uint32), ("long_rounds", ctypes.c_uint32), ("max_lcp", ctypes.c_uint32), ("kernel_launches", ctypes.c_uint32),
         ("irreducible", ctypes.c_uint64), ("long_items", ctypes.c_uint64), ("compared_bytes", ctypes.c_uint64),
         ("host_syncs", ctypes.c_uint32), ("ms_total", ctypes.c_float),
+    ]
+
+    def asdict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
+class FmStats(ctypes.Structure):
+    """archon_hip_fm_stats: the calling thread's last FM call on a device"""
+    _fields_ = [
+        ("n", ctypes.c_uint32), ("patterns", ctypes.c_uint32), ("pattern_bytes", ctypes.c_uint64), ("steps", ctypes.c_uint64),
+        ("shared_steps", ctypes.c_uint64), ("kernel_launches", ctypes.c_uint32), ("host_syncs", ctypes.c_uint32), ("built", ctypes.c_uint32),
+        ("table_bytes", ctypes.c_uint64), ("ms_build", ctypes.c_float), ("ms_query", ctypes.c_float),
     ]
 
     def asdict(self):
@@ -134,12 +148,21 @@ def load():
         "archon_hip_block_lcp": [vp, vp],
         "archon_hip_lcp_keep": [i32, vp],
         "archon_hip_get_lcp_stats": [i32, ctypes.POINTER(LcpStats)],
+        "archon_hip_fm_create": [vp, u32, u32, i32, vp],
+        "archon_hip_fm_create_dev": [vp, u32, u32, i32, vp, vp],
+        "archon_hip_fm_count": [vp, vp, vp, u32, vp, vp],
+        "archon_hip_fm_count_dev": [vp, vp, vp, u32, vp, vp, vp],
+        "archon_hip_block_fm_count": [vp, vp, vp, u32, vp, vp],
+        "archon_hip_block_fm_locate": [vp, vp, vp, u32, vp, ctypes.c_uint64, vp],
+        "archon_hip_get_fm_stats": [i32, ctypes.POINTER(FmStats)],
     }.items():
         fn = getattr(lib, name)
         fn.argtypes = args
         fn.restype = i32
     lib.archon_hip_block_destroy.argtypes = [vp]
     lib.archon_hip_block_destroy.restype = None
+    lib.archon_hip_fm_destroy.argtypes = [vp]
+    lib.archon_hip_fm_destroy.restype = None
     lib.archon_hip_post_bound.argtypes = [u32]
     lib.archon_hip_post_bound.restype = sz
     lib.archon_hip_test_route.argtypes = [ctypes.c_char_p, ctypes.c_long]      # include/archon_hip_test.h (tests only)
@@ -155,7 +178,7 @@ _routes_seen = None
 _ROUTE_NAMES = ("FORCE_PATH", "SMALL_BLOCK", "PASS_RANGES", "INV_ROWS", "INV_SLAB", "INV_SBITS", "INV_WALK_WGS", "NO_ALIGNED", "NO_CHAINS", "NO_DEEP_HINT",
                 "NO_PACK", "NO_PACK_STREAM", "NO_PAIR_CHAINS", "NO_PERIOD_HINT", "NO_BREAK_ROUND", "NO_PERIOD_PROBE", "NO_PERIOD_STREAM", "NO_PROBE",
                 "NO_RANK_WRITER", "NO_TEXT_ROUNDS", "NO_MID", "NO_SHALLOW", "NO_CLOSED_FORM", "NO_REL_RECORDS", "ALIGNED_MIN", "REL_MIN_SEG", "KEY_BYTES",
-                "LCP_CAP", "LCP_WINDOW")
+                "LCP_CAP", "LCP_WINDOW", "FM_SUB_ROWS", "FM_SUPER_ROWS")
 
 
 def _sync_routes(L):
@@ -268,6 +291,72 @@ def lcp_stats(dev=0):
     return s
 
 
+def fm_stats(dev=0):
+    """FmStats of the calling thread's last FM call on dev"""
+    s = FmStats()
+    _check(lib().archon_hip_get_fm_stats(dev, ctypes.byref(s)))
+    return s
+
+
+def _pack_patterns(patterns):
+    """a list of bytes / uint8 arrays -> (packed bytes, uint32 offsets[k + 1])"""
+    parts = [np.frombuffer(bytes(p), np.uint8) if isinstance(p, (bytes, bytearray)) else np.ascontiguousarray(p, dtype=np.uint8).ravel()
+             for p in patterns]
+    offsets = np.zeros(len(parts) + 1, np.uint64)
+    np.cumsum([q.size for q in parts], out=offsets[1:])
+    if offsets[-1] > 0xFFFFFFFF:
+        raise ValueError("patterns: more than 2^32 - 1 bytes in one call")
+    packed = np.concatenate(parts) if parts else np.zeros(0, np.uint8)
+    return np.concatenate([packed, np.zeros(1, np.uint8)]), offsets.astype(np.uint32)
+
+
+class FmIndex:
+    """archon_hip_fm: the rank table of a BWT on the device (include/archon_hip.h).  count(patterns) -> (lo, hi), the rows
+    [lo[j], hi[j]) of pattern j; hi - lo is its number of occurrences"""
+
+    def __init__(self, bwt=None, base_id=0, dev=0, _handle=None):
+        self.h = _handle
+        if self.h is None:
+            bwt = np.ascontiguousarray(bwt, dtype=np.uint8)
+            h = ctypes.c_void_p(None)
+            _check(lib().archon_hip_fm_create(_p(bwt), bwt.size, int(base_id), dev, ctypes.byref(h)))
+            self.h = h
+            self.n = bwt.size
+
+    @classmethod
+    def from_dev(cls, bwt_t, base_id):
+        """from a torch uint8 tensor on the device, on the current stream"""
+        dev = bwt_t.device.index or 0
+        h = ctypes.c_void_p(None)
+        _check(lib().archon_hip_fm_create_dev(ctypes.c_void_p(bwt_t.data_ptr()), bwt_t.numel(), int(base_id), dev, _stream_ptr(), ctypes.byref(h)))
+        f = cls(_handle=h)
+        f.n = bwt_t.numel()
+        return f
+
+    def count(self, patterns):
+        packed, offsets = _pack_patterns(patterns)
+        k = offsets.size - 1
+        lo, hi = np.zeros(k, np.uint32), np.zeros(k, np.uint32)
+        _check(lib().archon_hip_fm_count(self.h, _p(packed), _p(offsets), k, _p(lo), _p(hi)))
+        return lo, hi
+
+    def count_dev(self, patterns_t, offsets_t, lo_t, hi_t):
+        """torch tensors on the device: patterns uint8, offsets int32[k + 1], lo and hi int32[k] (written); current stream"""
+        _check(lib().archon_hip_fm_count_dev(self.h, ctypes.c_void_p(patterns_t.data_ptr()), ctypes.c_void_p(offsets_t.data_ptr()), lo_t.numel(),
+                                             ctypes.c_void_p(lo_t.data_ptr()), ctypes.c_void_p(hi_t.data_ptr()), _stream_ptr()))
+
+    def close(self):
+        if self.h:
+            lib().archon_hip_fm_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 def radix_scatter(src, dev=0):
     src = np.ascontiguousarray(src, dtype=np.uint8)
     dst = np.empty_like(src)
@@ -353,6 +442,27 @@ class Block:
         out = np.empty(self.n, np.uint32)
         _check(lib().archon_hip_block_lcp(self.h, _p(out)))
         return out
+
+    def fm_count(self, patterns):
+        """(lo, hi) of every pattern in the resident block's BWT (the FM index is built on the first call after a forward)"""
+        packed, offsets = _pack_patterns(patterns)
+        k = offsets.size - 1
+        lo, hi = np.zeros(k, np.uint32), np.zeros(k, np.uint32)
+        _check(lib().archon_hip_block_fm_count(self.h, _p(packed), _p(offsets), k, _p(lo), _p(hi)))
+        return lo, hi
+
+    def fm_locate(self, patterns):
+        """the starts of every pattern's occurrences: a list of uint32 arrays, each in row order (not sorted); needs
+        forward(want_sa=True)"""
+        lo, hi = self.fm_count(patterns)
+        cuts = np.zeros(lo.size + 1, np.int64)
+        np.cumsum(hi.astype(np.int64) - lo, out=cuts[1:])
+        packed, offsets = _pack_patterns(patterns)
+        pos = np.zeros(max(int(cuts[-1]), 1), np.uint32)
+        total = ctypes.c_uint64(0)
+        _check(lib().archon_hip_block_fm_locate(self.h, _p(packed), _p(offsets), lo.size, _p(pos), int(cuts[-1]),
+                                                ctypes.cast(ctypes.byref(total), ctypes.c_void_p)))
+        return [pos[cuts[j]:cuts[j + 1]] for j in range(lo.size)]
 
     def stats(self):
         s = Stats()

@@ -14,6 +14,7 @@
  *   archon_hip_radix_scatter  the counting-sort scatter of tool/radix_dir/radix.c:40-44
  *   archon_hip_lms_select   Constructor::findLMS (160-172): the subset a7 sorts directly (a4 IT-2: bwt/a4/src/archon.c:163-169)
  *   archon_hip_lcp          nothing: the LCP array of the suffix array, below
+ *   archon_hip_fm_*         nothing: counting and locating patterns by backward search on the BWT (an FM index), below
  *
  * Ordering convention ("a7 order"): item s in 1..N names the
  * reversed prefix x[s-1],x[s-2],...,x[0],INF with INF > 255; sa[0..N) lists the
@@ -254,6 +255,58 @@ typedef struct archon_hip_lcp_stats {
     float ms_total;             /* device time of the call (HIP events on its stream) */
 } archon_hip_lcp_stats;
 int archon_hip_get_lcp_stats(int dev, archon_hip_lcp_stats *out);
+
+/* ---- patterns in a block's BWT: an FM index (no counterpart in the reference) ------------------------------------------
+ * The search rule in a7 order.  An LF step prepends bwt[i] to a key, so a pattern P of length m is consumed in TEXT
+ * order, P[0] first (not last, as in the textbook backward search):
+ *   P[0] = c            [lo, hi) = [R[c], R[c+1]), R the starts of the 256 buckets counted over the BWT, primary row included
+ *   each later P[t] = c [lo, hi) = [R[c] + occ'(c, lo), R[c] + occ'(c, hi)), occ'(c, i) = the rows j < i with bwt[j] == c,
+ *                       the primary row EXCLUDED (it holds x[0] only as a stand-in: its item n has no item n + 1)
+ *   stop as soon as lo >= hi.  Each later symbol is one rank step.
+ * The occurrences are the rows r in [lo, hi), and P starts at offset sa[r] - m of x (every p with x[p .. p+m) == P and
+ * 1 <= p + m <= n).  m = 0 gives [0, n) (starts 1 .. n); a pattern that does not occur gives lo == hi; a pattern longer than
+ * the block gives lo == hi == 0 with no rank step.  Example: "banana" (BWT nnbaaa, primary row 2, sa = 2 4 6 1 3 5): "an"
+ * gives [0, 3) then [4, 6), starts 1 and 3; "ab" is empty at its second step.
+ * Table: superblocks of 65 536 rows hold R[c] + occ'(c, start) (u32), sub-chunks of 1024 rows hold counts relative to
+ * their superblock (u16): 0.5 n + n / 64 bytes plus one entry for i = n, beside the BWT as it is.  A rank step reads the
+ * two table entries of lo and of hi and counts the rest in the 1024 BWT bytes of their sub-chunk (one load when lo and hi
+ * share it).  Ranges stay inside [0, n] for any bytes: a BWT that is not a BWT returns ARCHON_OK with unspecified ranges.
+ * Patterns: pattern j is patterns[offsets[j] .. offsets[j+1]), offsets[0 .. k] nondecreasing (else ARCHON_E_ARG); k = 0
+ * returns ARCHON_OK and writes nothing.  Results lo[k], hi[k]. */
+typedef struct archon_hip_fm archon_hip_fm;    /* rank table + the handle's own copy of the BWT; one thread at a time */
+/* host BWT of n bytes with primary row base_id (< n): builds the table on device `dev`; ARCHON_E_ARG for n = 0 or
+ * base_id >= n.  The handle owns its device memory until archon_hip_fm_destroy. */
+int  archon_hip_fm_create(const uint8_t *bwt, uint32_t n, uint32_t base_id, int dev, archon_hip_fm **out);
+/* the same from a device BWT (any address), enqueued on `stream` (NULL = the context's own), complete on return */
+int  archon_hip_fm_create_dev(const uint8_t *d_bwt, uint32_t n, uint32_t base_id, int dev, void *stream, archon_hip_fm **out);
+void archon_hip_fm_destroy(archon_hip_fm *f);
+/* host patterns, offsets[k+1] and ranges lo[k], hi[k] */
+int  archon_hip_fm_count(archon_hip_fm *f, const uint8_t *patterns, const uint32_t *offsets, uint32_t k, uint32_t *lo, uint32_t *hi);
+/* device pointers, on `stream` (NULL = the context's own), complete on return; decreasing offsets are found on the device */
+int  archon_hip_fm_count_dev(archon_hip_fm *f, const uint8_t *d_patterns, const uint32_t *d_offsets, uint32_t k,
+                             uint32_t *d_lo, uint32_t *d_hi, void *stream);
+/* the resident block of the handle's last forward: the table is built over the block's own BWT on the first call after a
+ * forward and kept with the handle (a forward drops it).  Needs no suffix array.  ARCHON_E_ARG before any forward. */
+int  archon_hip_block_fm_count(archon_hip_block *b, const uint8_t *patterns, const uint32_t *offsets, uint32_t k, uint32_t *lo, uint32_t *hi);
+/* starts of every occurrence, pattern by pattern, each in row order (not sorted); *total = their number.  ARCHON_E_ARG
+ * (nothing written, *total set) when cap < total; ARCHON_E_ARG when the last forward kept no suffix array */
+int  archon_hip_block_fm_locate(archon_hip_block *b, const uint8_t *patterns, const uint32_t *offsets, uint32_t k,
+                                uint32_t *pos, uint64_t cap, uint64_t *total);
+/* work counters and device time of the CALLING THREAD's last FM call on `dev` (FM calls leave the other stats alone) */
+typedef struct archon_hip_fm_stats {
+    uint32_t n;                 /* block size of the index */
+    uint32_t patterns;          /* patterns of the call (0 for a create) */
+    uint64_t pattern_bytes;     /* their bytes */
+    uint64_t steps;             /* rank steps executed */
+    uint64_t shared_steps;      /* of them, steps whose lo and hi shared one sub-chunk load */
+    uint32_t kernel_launches;   /* launches issued by the call */
+    uint32_t host_syncs;        /* times the host waited for the stream inside the call */
+    uint32_t built;             /* 1 when the call built a table */
+    uint64_t table_bytes;       /* bytes of the rank table (without the BWT) */
+    float ms_build;             /* device time of the table build (HIP events), 0 without one */
+    float ms_query;             /* device time of the count and locate kernels (HIP events) */
+} archon_hip_fm_stats;
+int  archon_hip_get_fm_stats(int dev, archon_hip_fm_stats *out);
 
 /* ---- measurement ------------------------------------------------------------- */
 

@@ -18,6 +18,9 @@
  *                                       128- / 64-byte rows of LDS, -1 = the product's rule (rows above 128 MiB)
  *   LCP_CAP      1..4096 / 0  LCP: key bytes a lane of stage A compares before a row goes to the long list (0: 32)
  *   LCP_WINDOW   bytes / 0    LCP: the first window of the long comparisons, doubled every round (0: 256; at most 2^30)
+ *   FM_SUB_ROWS    16..1024 / 0   FM index: rows of a sub-chunk of the rank table, a power of two (0: 1024)
+ *   FM_SUPER_ROWS  ..65536 / 0    FM index: rows of a superblock, a power of two, a multiple of the sub-chunk (0: 65536; checked
+ *                                 when a table is built).  Neither changes a result: tiny blocks cross many table boundaries
  *   NO_ALIGNED NO_BREAK_ROUND NO_CHAINS NO_DEEP_HINT NO_PACK NO_PACK_STREAM NO_PAIR_CHAINS NO_PERIOD_HINT NO_PERIOD_PROBE
  *   NO_PERIOD_STREAM NO_PROBE NO_RANK_WRITER NO_TEXT_ROUNDS NO_MID NO_SHALLOW NO_CLOSED_FORM NO_REL_RECORDS      nonzero switches the named step off
  * Returns 0, or ARCHON_E_ARG for an unknown name / a value out of range.  Process-wide; not thread-safe against
