@@ -19,6 +19,7 @@
 #include <chrono>
 #include <stdlib.h>
 #include <thread>
+#include <type_traits>
 #include <vector>
 
 namespace archon {
@@ -309,16 +310,69 @@ static_assert(fwd::kMcWords <= mail::kRounds.len && fwd::kMcWords <= mail::kRoun
 static_assert(2 * fwd::kGapSlots <= mail::kGapTable.len, "the gap table in the mailbox");
 static_assert(pf::kCleanWords <= mail::kProbe.len, "the period probe in the mailbox");
 
+// ---- one forward call (forward_run): its buffers, and what each step of the driver decides and leaves for the next
+
+// The route a block takes; the values are those of archon_hip_stats::path.
+enum class Path : uint32_t { kSevenPass = 0, kStream = 1, kClosed = 2 };
+
+struct Fwd {
+    Ctx *c;
+    hipStream_t s;
+    uint32_t n;
+    int depth;                   // 0 = a caller's block, 1 = the 2p-byte block of a clean periodic block's closed form
+    const uint8_t *d_x;          // the text, 16-byte aligned: the caller's, or its copy in B.xa
+    uint32_t *d_sa_user;         // the caller's suffix array, or null
+    uint8_t *d_bwt;
+    uint32_t *d_base_out;        // the caller's primary index
+    uint32_t *sa = nullptr, *d_base = nullptr;      // where the suffix array goes; the call's own primary index (fwd_small::kBase)
+    bs::TieCtl *d_ctl = nullptr;
+    uint32_t *pres = nullptr;    // [pf::kCleanWords] the period probe: [0] period, [1] votes, [2] the text breaks it, [3] the whole text was compared
+    FwdBuf B{};
+    size_t tail_at = 0, tier1_bytes = 0, arena_bytes = 0, count_zero_bytes = 0;     // the closed-form tail; the arena's tiers; the count's tables
+    bool count_tables_clear = true;
+    uint32_t R = 0, tpr = 0, allow_aligned = 0;     // the passes' ranges and tiles per range; pass B may deal whole buckets
+    bool rel_ok = false;         // ... and take range-relative records
+    int forced = -1;             // (tests): 0 = 7-pass route, 1 = streaming stage, -1 = the block decides
+    bool closed_ok = false, probe = false, small_block = false;
+    bool probe_queued = false, probe_clean = false, probe_fetched = false;      // the period probe: queued, with the whole-text comparison, on its way up
+    bool closed = false;         // the probe's verdict: a clean periodic block, written down in closed form
+    bs::TieCtl ctl{};            // the streaming stage's tie summary (big_items: its count of items in oversized buckets)
+    uint32_t big_items = 0;
+    uint32_t hist[256] = {};     // the exact byte histogram x[0 .. n-1], when have_hist
+    bool have_hist = false, tail_fetched = false;
+    uint32_t sigma = 0, bits = 8;
+    uint8_t lut[256];            // the order-preserving recode of the alphabet (have_lut: taken from the presence map)
+    bool have_lut = false, presence_done = false;
+    Path path = Path::kSevenPass;
+    int Q = 1;                   // symbols per key byte on the streaming path
+    uint32_t key_bytes = fwd::kKeyBytes, period_hint = 0, period_breaks = 0, closed_period = 0;
+    bool brk_ready = false;      // B.brk holds the break table of period_hint, which has period_breaks breaks
+    uint32_t h0 = fwd::kKeyBytes, alphabet_bits = 0, radix_passes = 0;      // symbols the first stage sorted on
+    bool ws_ready = true, deep_ties = false, stream_done = false;
+    // the stages; the 7-pass route's passes (rs::sort_pairs); the streaming stage's passes A and B (their own event banks)
+    StageTimer tm{c, 72 * depth, s}, pt{c, 72 * depth + 24, s}, ps{c, 72 * depth + 48, s};
+    int e_start = -1, e_count = -1, e_sorted = -1, e_local = -1, e_first = -1, e_general = -1, e_end = -1;
+    int iA0 = -1, iA1 = -1, iB0 = -1, iB1 = -1;
+    bool trace_host = false;     // (experiments library, ARCHON_TRACE_HOST)
+
+    // the steps of forward_run, in its order, and what they share
+    int setup(), first_look(), closed_form(), alphabet(), period(), recode(), first_stage(), tied_rows(), general_stage(), finish();
+    int general_buffers(), fetch_probe(uint32_t words = pf::kCleanWords), fetch_byte_counts(const uint32_t *d_counts), presence();
+    int count16(int form, const uint8_t *src, bool force_stream, bool alpha_probe), streaming(int form, const uint8_t *key_text);
+    int seven_pass(), first_groups(int mode, const uint64_t *keys, const uint32_t *items, uint32_t shift);
+    void queue_probe(bool clean), probe_arrived(), take_byte_hist(bool exact), stamp(int i);
+};
+
 // A5 + A7 for whatever the first stage left tied.  On entry (k_first_groups): sa[] holds the items in first-stage order,
 // B.v[i] = first row of the group of row i, and -- ws_ready -- the two lists of the refinement rounds (rounds.hiph): S =
 // entries of groups of at most fwd::kFuMax rows in B.slist[0] (fwd_small::kFu counts them), B = the longer groups as
 // (row, group start, item) triples in buffer 0 (fwd_small::kTotal counts them, fwd_small::kFu + 3 their groups).  Runs the run
 // shortcut for periodic blocks, text rounds, the rank table, doubling rounds with the pair chains.  Rows take their
 // BWT symbol when they become final.
-static int general_stage(Ctx *c, hipStream_t s, FwdBuf &B, const uint8_t *d_x, uint32_t n, uint32_t *sa, uint32_t h0,
-                         uint8_t *d_bwt, uint32_t *d_base, archon_hip_stats &st, uint32_t p_hint, bool ws_ready, bool deep_ties,
-                         bool brk_ready /*B.brk holds the break table of period p_hint*/, uint32_t p_breaks /*... which has that many breaks*/)
+int Fwd::general_stage()
 {
+    archon_hip_stats &st = c->stats;
+    const uint32_t p_hint = period_hint, p_breaks = period_breaks;
     const uint32_t g256 = div_up(n, 256);
 #ifdef ARCHON_EXPERIMENTS
     const bool tracing = getenv("ARCHON_TRACE_ROUNDS") != nullptr;
@@ -804,708 +858,739 @@ static int general_stage(Ctx *c, hipStream_t s, FwdBuf &B, const uint8_t *d_x, u
     return ARCHON_OK;
 }
 
-// depth: 0 = a caller's block, 1 = the 2p-byte block of a clean periodic block's closed form (periodic.hiph): its own event
-// banks, no closed form of its own
-static int forward_run(Ctx *c, hipStream_t s, const uint8_t *d_x_in, uint32_t n, uint32_t *d_sa_user,
-                       uint8_t *d_bwt, uint32_t *d_base_out, int depth = 0)
+// ---- the forward driver: its steps (Fwd), then forward_run, which takes them in order
+
+#ifdef ARCHON_EXPERIMENTS
+// host-side phases of a call (experiments library, ARCHON_TRACE_HOST): entry, first launch issued, everything queued, wait over, statistics read
+static thread_local std::chrono::steady_clock::time_point t_host[5];
+void Fwd::stamp(int i) { if (trace_host) t_host[i] = std::chrono::steady_clock::now(); }
+#else
+void Fwd::stamp(int) {}
+#endif
+
+// Calls fn(std::integral_constant<int, V>{}) for the first V of the list that equals v, for the last one when none does: the
+// driver's runtime choices (symbols per key byte, a mode, a flag) as the template arguments of the kernel that matches.
+template <int V, int... Vs, class Fn>
+static void with_const(int v, Fn &&fn)
+{
+    if constexpr (sizeof...(Vs) == 0) fn(std::integral_constant<int, V>{});
+    else if (v == V) fn(std::integral_constant<int, V>{});
+    else with_const<Vs...>(v, fn);
+}
+// The key forms of the streaming stage: Q symbols per key byte (1 = plain bytes; 2 / 4 / 8 = a compacted alphabet), or
+// kHotForm -- plain bytes, ranked wave-aggregated for periodic blocks (measured on a^N: passes 0.98 + 1.12 ms against 1.48 + 1.46).
+constexpr int kHotForm = 0;
+static constexpr int key_q(int form) { return form == kHotForm ? 1 : form; }
+// Pass geometry: 1024 lanes x 12 items = tiles of 12 288 items, one workgroup per CU (passes.hiph).
+constexpr uint32_t kTileItems = bs::kPassTile;
+constexpr uint32_t kPackSigma = 32;          // alphabets up to this many distinct bytes sort on packed keys
+
+// Tier 2, when the block first needs it (a periodic block's break table, the entry sweep of the general stage): rank table,
+// lists, logs, directories -- 70 N that a block the streaming stage settles never touches.
+int Fwd::general_buffers()
+{
+    if (B.rank) return ARCHON_OK;
+    { Carve count; ARCHON_TRY(ctx_ensure_arena2(c, fwd_tier2(count, B, n))); }
+    Carve a2{c->arena2, 0, c->arena2_bytes};
+    fwd_tier2(a2, B, n);
+    if (!a2.ok()) { set_error("arena exhausted (general stage)"); return ARCHON_E_NOMEM; }
+    B.rwb.r1 = B.rwb.r2 = nullptr;
+    arena_bytes = tier1_bytes + a2.off;
+    return ARCHON_OK;
+}
+
+// 1. Arena tier 1, the block's prologue (k_prep), the aligned copy of the text, the pass geometry and what the block may try.
+int Fwd::setup()
 {
 #ifdef ARCHON_EXPERIMENTS
-    // host-side phases of a call (experiments library, ARCHON_TRACE_HOST): entry, first launch issued, everything queued, wait over, statistics read
-    static thread_local std::chrono::steady_clock::time_point t_host[5];
-    const bool trace_host = depth == 0 && getenv("ARCHON_TRACE_HOST") != nullptr;
-#define ARCHON_HOST_STAMP(i) do { if (trace_host) t_host[i] = std::chrono::steady_clock::now(); } while (0)
-#else
-#define ARCHON_HOST_STAMP(i) do { } while (0)
+    trace_host = depth == 0 && getenv("ARCHON_TRACE_HOST") != nullptr;
 #endif
-    ARCHON_HOST_STAMP(0);
-    FwdBuf B;
-    memset(&B, 0, sizeof B);
+    stamp(0);
     { Carve count; ARCHON_TRY(ctx_ensure_arena(c, fwd_tier1(count, B, n, c->dev, d_sa_user == nullptr))); }
     c->launches = 0;
     if (depth == 0) t_sync_count = 0;
-    archon_hip_stats &st = c->stats;
-    memset(&st, 0, sizeof st);
-    st.n = n;
+    memset(&c->stats, 0, sizeof c->stats);
+    c->stats.n = n;
 
     // tier 1 from the arena's bottom up to the closed-form tail, which lies at a fixed distance from the arena's end
-    const size_t tail_at = (c->arena_bytes - kClosedTail) & ~size_t(255);
+    tail_at = (c->arena_bytes - kClosedTail) & ~size_t(255);
     Carve a1{c->arena, 0, tail_at};
     fwd_tier1(a1, B, n, c->dev, d_sa_user == nullptr);
-    if (!a1.ok()) {
-        set_error("arena exhausted (tier 1 of a %u-byte block reaches the closed-form tail)", n);
-        return ARCHON_E_NOMEM;
-    }
-    st.arena_bytes = a1.off;
-    // Tier 2, when the block first needs it (a periodic block's break table, the entry sweep of the general stage): rank table,
-    // lists, logs, directories -- 70 N that a block the streaming stage settles never touches.
-    auto general_buffers = [&]() -> int {
-        if (B.rank) return ARCHON_OK;
-        { Carve count; ARCHON_TRY(ctx_ensure_arena2(c, fwd_tier2(count, B, n))); }
-        Carve a2{c->arena2, 0, c->arena2_bytes};
-        fwd_tier2(a2, B, n);
-        if (!a2.ok()) { set_error("arena exhausted (general stage)"); return ARCHON_E_NOMEM; }
-        B.rwb.r1 = B.rwb.r2 = nullptr;
-        st.arena_bytes = a1.off + a2.off;
-        return ARCHON_OK;
-    };
-    uint32_t *small = B.small;
-    uint32_t *d_counts = small + fwd_small::kCounts;
-    B.sc.d_ticket = small + fwd_small::kTicket;
-    B.sc.d_err = small + fwd_small::kErr;
-    uint32_t *d_base = small + fwd_small::kBase;
-    bs::TieCtl *d_ctl = reinterpret_cast<bs::TieCtl *>(small + fwd_small::kCtl);
+    if (!a1.ok()) { set_error("arena exhausted (tier 1 of a %u-byte block reaches the closed-form tail)", n); return ARCHON_E_NOMEM; }
+    tier1_bytes = arena_bytes = a1.off;
+    B.sc.d_ticket = B.small + fwd_small::kTicket;
+    B.sc.d_err = B.small + fwd_small::kErr;
     B.sc.h_mail = c->h_mail;
+    d_base = B.small + fwd_small::kBase;
+    d_ctl = reinterpret_cast<bs::TieCtl *>(B.small + fwd_small::kCtl);
+    pres = B.small + fwd_small::kProbe;
     // (one launch clears the scratch words, arms the period probe's result word and clears the two-byte count's tables)
-    const size_t count_zero_bytes = (size_t)(reinterpret_cast<char *>(&B.prep->rowtot[0]) - reinterpret_cast<char *>(B.hist16));
-    hipLaunchKernelGGL(bs::k_prep, dim3(256), dim3(256), 0, s, small, fwd_small::kWords, fwd_small::kProbe, reinterpret_cast<uint4 *>(B.hist16), (uint32_t)(count_zero_bytes / 16));
+    count_zero_bytes = (size_t)(reinterpret_cast<char *>(&B.prep->rowtot[0]) - reinterpret_cast<char *>(B.hist16));
+    hipLaunchKernelGGL(bs::k_prep, dim3(256), dim3(256), 0, s, B.small, fwd_small::kWords, fwd_small::kProbe, reinterpret_cast<uint4 *>(B.hist16), (uint32_t)(count_zero_bytes / 16));
     static_assert(offsetof(bs::Prep, rowtot) % 16 == 0, "the count's tables end on a 16-byte boundary");
-    bool count_tables_clear = true;
-    ARCHON_HOST_STAMP(1);
+    stamp(1);
 
-    const uint8_t *d_x = d_x_in;
-    if ((uintptr_t)d_x_in & 15) {   // kernels want 16-byte aligned text
-        ARCHON_HIP_TRY(hipMemcpyAsync(B.xa, d_x_in, n, hipMemcpyDeviceToDevice, s));
+    if ((uintptr_t)d_x & 15) {   // kernels want 16-byte aligned text
+        ARCHON_HIP_TRY(hipMemcpyAsync(B.xa, d_x, n, hipMemcpyDeviceToDevice, s));
         d_x = B.xa;
     }
-    uint32_t *sa = d_sa_user ? d_sa_user : B.sa_own;
-
-    StageTimer tm(c, 72 * depth, s);
-    StageTimer pt(c, 72 * depth + 24, s);
-    const int e0 = tm.mark();
+    sa = d_sa_user ? d_sa_user : B.sa_own;
+    e_start = tm.mark();
 
     // A2 / bucket setup: the two-byte count (a4 compute(), archon.c:146-161) and its scans.  The count
     // runs over the tile ranges of LSB pass A (R contiguous ranges, one persistent workgroup each), so
     // the same sweep also delivers that pass's per-range digit table.
-    // Pass geometry: 1024 lanes x 12 items = tiles of 12 288 items, one workgroup per CU (passes.hiph).
-    constexpr uint32_t kTileItems = bs::kPassTile;
     const uint32_t ntiles = div_up(n, kTileItems);
     // option "pass_ranges" (archon_hip_set_option): ranges the passes are cut into (default: one per CU).  bench.py asks for 1024 at N > 1
     // (shorter tails while RCCL's kernels hold CUs); tests use odd counts.  Whatever is asked for, a range never
     // exceeds 2^24 items (pass A stages positions relative to its range start in 24 bits).
-    uint32_t R = (uint32_t)kNumCU;
+    R = (uint32_t)kNumCU;
     if (const uint32_t asked = eff_pass_ranges(c->dev)) {
         if (asked > (uint32_t)bs::kMaxRanges) { set_error("pass ranges %u out of range [1, %d]", asked, bs::kMaxRanges); return ARCHON_E_ARG; }
         R = asked;
     }
     if (R > ntiles) R = ntiles;
-    uint32_t tpr = div_up(ntiles, R);
+    tpr = div_up(ntiles, R);
     const uint32_t tpr_max = bs::kRangeMaxItems / kTileItems;
     if (tpr > tpr_max) tpr = tpr_max;
     R = div_up(ntiles, tpr);
     if (R > (uint32_t)bs::kMaxRanges) { set_error("block of %u bytes needs %u pass ranges (max %d)", n, R, bs::kMaxRanges); return ARCHON_E_INTERNAL; }
-    uint32_t *rhist = B.rhist;                  // [R][256], reused by both passes
-    // Q = symbols per key byte of the streaming stage: 1 = plain bytes; 2/4/8 = compacted alphabet (below)
-    StageTimer ps(c, 72 * depth + 48, s);               // streaming stage: pass A, pass B (their own HIP events)
-    int iA0 = -1, iA1 = -1, iB0 = -1, iB1 = -1;
-    uint2 *A_R = reinterpret_cast<uint2 *>(B.keyA);     // pass A out: {K, I} records + the first-key-byte stream
-    uint8_t *A_B1 = reinterpret_cast<uint8_t *>(B.valA);
-    uint2 *B_R = reinterpret_cast<uint2 *>(B.keyB);     // pass B out
     // The two-byte count decides the route.  The host does not wait for it: the count leaves a `skip` flag on the
     // device, the whole streaming stage is queued behind it, and its kernels return at once when the flag says
     // "skewed".  One host round trip per block (after k_resolve_ties) instead of two.
     // bucket-per-workgroup pass B (Prep::aligned) needs 256 workgroups and enough tiles per bucket to matter
     const uint32_t aligned_min = g_route.aligned_min >= 0 ? (uint32_t)g_route.aligned_min : (1u << 24);      // (tests lower it to run bucket mode on small blocks)
-    const uint32_t allow_aligned = (n >= aligned_min && !route_off(kRtNoAligned) && g_opt[c->dev].pass_b_buckets.load()) ? 1u : 0u;
+    allow_aligned = (n >= aligned_min && !route_off(kRtNoAligned) && g_opt[c->dev].pass_b_buckets.load()) ? 1u : 0u;
     // bucket mode moves range-relative records between the passes (passes.hiph: no byte stream beside them)
     // -- where a bucket's segments (one per pass-A range: n / (256 R) places on average) are long enough that a wave's 1024 places
     // nearly always lie inside one: from 4096 places on, i.e. 256 MiB with one range per CU.  Shorter segments make pass B look its
     // records' ranges up one by one: 16 / 64 / 128 MiB blocks measured 0.36 / 0.46 / 0.62 ms in pass B against 0.08 / 0.25 / 0.52.
     const uint32_t rel_min_seg = g_route.rel_min_seg >= 0 ? (uint32_t)g_route.rel_min_seg : 4096u;
-    const bool rel_ok = allow_aligned && !route_off(kRtNoRelRecords) && (uint64_t)n >= (uint64_t)R * 256u * rel_min_seg;
-    int e1 = -1;
+    rel_ok = allow_aligned && !route_off(kRtNoRelRecords) && (uint64_t)n >= (uint64_t)R * 256u * rel_min_seg;
     // Clean periodic blocks (periodic.hiph): the period probe and the comparison of the whole text with itself p further down are
     // queued in FRONT of the count -- device-conditional, a block without a voted period pays three empty launches -- and their
     // verdict comes to the host with the block's first round trip; k_rows_scan reads it too and lets the streaming kernels return.
-    const int forced = g_route.force_path;       // (tests): 0 = 7-pass route, 1 = streaming stage, -1 = the block decides
-    const bool closed_ok = depth == 0 && forced < 0 && n >= (1u << 16) && !route_off(kRtNoPeriodProbe) && !route_off(kRtNoChains) && !route_off(kRtNoClosedForm);
-    uint32_t *pres = small + fwd_small::kProbe;  // [0] period, [1] votes, [2] the text breaks it, [3] the whole text was compared
-    bool probe_queued = false, probe_fetched = false;
-    auto queue_probe = [&]() -> int {
-        // (the result word was set to "none" and the votes and flags behind it cleared by k_prep)
-        hipLaunchKernelGGL(fwd::k_period_find, dim3(fwd::kPeriodSearch / 256), dim3(256), 0, s, d_x, n, pres);
-        hipLaunchKernelGGL(fwd::k_period_vote, dim3(fwd::kPeriodVotes / 256), dim3(256), 0, s, d_x, n, pres);
-        c->launches += 2;
-        if (closed_ok) {
-            hipLaunchKernelGGL(pf::k_period_clean, dim3(kNumCU * 8), dim3(256), 0, s, d_x, n, pres);
-            ++c->launches;
-        }
-        probe_queued = true;
-        return ARCHON_OK;
-    };
-    auto fetch_probe = [&]() -> int {            // (with the round trip that follows)
-        if (probe_queued) ARCHON_HIP_TRY(hipMemcpyAsync(c->h_mail + mail::kProbe.at, pres, pf::kCleanWords * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
-        probe_fetched = probe_queued;
-        return ARCHON_OK;
-    };
-    auto count16 = [&](int Q, const uint8_t *src, bool force_stream, bool probe = false, bool hot = false) -> int {
-        uint32_t *d_suspect = probe ? &B.prep->suspect : nullptr;
-        if (!count_tables_clear) ARCHON_HIP_TRY(hipMemsetAsync(B.hist16, 0, count_zero_bytes, s));      // (the block's first count finds them cleared by k_prep)
-        count_tables_clear = false;
-        // the count runs with at most 256 workgroups per half: with more pass ranges each workgroup covers several of
-        // them and reads the column sums off between two (more workgroups would only flush their 32 768 bins more often)
-        const uint32_t sub = (R > 256u && R % 256u == 0u) ? R / 256u : 1u;
-        const uint32_t nparts = div_up(R, sub);
-        const dim3 grid(nparts), block(bs::kH16Block);
-        // B.hist16 (zeroed above) first serves as the spill table of the count, then receives the totals (k_rows_total)
-        if (Q == 1 && hot) hipLaunchKernelGGL(HIP_KERNEL_NAME(bs::k_hist16<1, true>), grid, block, 0, s, src, n, B.h16part, B.hist16, tpr * kTileItems, rhist, d_suspect, sub);
-        else if (Q == 1) hipLaunchKernelGGL(HIP_KERNEL_NAME(bs::k_hist16<1>), grid, block, 0, s, src, n, B.h16part, B.hist16, tpr * kTileItems, rhist, d_suspect, sub);
-        else if (Q == 2) hipLaunchKernelGGL(HIP_KERNEL_NAME(bs::k_hist16<2>), grid, block, 0, s, src, n, B.h16part, B.hist16, tpr * kTileItems, rhist, d_suspect, sub);
-        else if (Q == 4) hipLaunchKernelGGL(HIP_KERNEL_NAME(bs::k_hist16<4>), grid, block, 0, s, src, n, B.h16part, B.hist16, tpr * kTileItems, rhist, d_suspect, sub);
-        else hipLaunchKernelGGL(HIP_KERNEL_NAME(bs::k_hist16<8>), grid, block, 0, s, src, n, B.h16part, B.hist16, tpr * kTileItems, rhist, d_suspect, sub);
-        static_assert(bs::kMaxRanges <= 1024, "four ranges per lane in the column half of k_rows_sum_total");
-        hipLaunchKernelGGL(bs::k_rows_sum_total, dim3(512), dim3(256), 0, s, B.hist16, B.h16part, nparts, B.prep, (uint32_t)bs::kLsCap, rhist, R);
-        hipLaunchKernelGGL(bs::k_rows_scan, dim3(256), dim3(256), 0, s, B.hist16, B.prep, force_stream ? 1u : 0u, allow_aligned, d_ctl, (uint32_t)kTieListCap, n,
-                           probe_queued ? pres : nullptr);
-        ARCHON_HIP_TRY(hipGetLastError());
-        c->launches += 3;
-        e1 = tm.mark();
-        return ARCHON_OK;
-    };
-    int e2 = -1, e2b = -1, e3 = -1, e4 = -1;
-    bs::TieCtl h_ctl;
-    memset(&h_ctl, 0, sizeof h_ctl);
-    uint32_t big_items = 0;
-    const uint32_t *d_skip = &B.prep->skip;
-    // The byte histogram of the block comes with the two-byte count: its second-byte column sums are the bytes
-    // x[0..n-2] plus the 0xFF in front of x[0]; the host adds x[n-1] and removes the pad (alphabet detection below).
-    uint32_t *h_counts = c->h_mail + mail::kByteCounts.at, *h_last = c->h_mail + mail::kLastByte.at;
-    bool have_byte_counts = false;               // h_counts and h_last hold the count's byte histogram of THIS block
-    auto fetch_byte_counts = [&]() -> int {
-        have_byte_counts = true;
-        *h_last = 0;
-        ARCHON_HIP_TRY(hipMemcpyAsync(h_counts, B.prep->cntA, 256 * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
-        ARCHON_HIP_TRY(hipMemcpyAsync(h_last, d_x + (n - 1), 1, hipMemcpyDeviceToHost, s));
-        return ARCHON_OK;
-    };
-    // ---- streaming first stage: two LSB passes + in-LDS bucket sorts; ends with the block's host round trip ----
-    constexpr bool kHotRank = true;    // periodic blocks: wave-aggregated ranking (measured on a^N: passes 0.98 + 1.12 ms against 1.48 + 1.46)
-    auto streaming = [&](int Q, const uint8_t *key_text, bool defer_big = false) -> int {
-        // (the tie summary was initialised on the device by k_rows_scan, which also left the count summary in it)
-        constexpr int PB = bs::kPassBlock, PI = bs::kPassIPT;
-        iA0 = ps.mark();
-        // Both record formats of the passes are queued (passes.hiph): the plain one and -- where bucket mode is possible at all -- the
-        // range-relative one; which of the two a block takes is the count's choice of pass-B mode (Prep::aligned), known on the device
-        // only, and the instantiation that does not match returns at once.
-        const uint32_t twin = rel_ok ? 1u : 0u;
-#define ARCHON_PASS_A(QQ, HOTF, KT) do { \
-            hipLaunchKernelGGL(HIP_KERNEL_NAME(bs::k_pass_text<PB, PI, QQ, HOTF, false>), dim3(R), dim3(PB), 0, s, d_x, n, tpr, A_R, A_B1, B.prep->startA, rhist, KT, d_skip, B.trash, &d_ctl->base_bucket, twin); \
-            if (rel_ok) { \
-                hipLaunchKernelGGL(HIP_KERNEL_NAME(bs::k_pass_text<PB, PI, QQ, HOTF, true>), dim3(R), dim3(PB), 0, s, d_x, n, tpr, A_R, A_B1, B.prep->startA, rhist, KT, d_skip, B.trash, &d_ctl->base_bucket, twin); \
-                ++c->launches; \
-            } } while (0)
-        if (Q == 2) ARCHON_PASS_A(2, false, key_text);
-        else if (Q == 4) ARCHON_PASS_A(4, false, key_text);
-        else if (Q == 8) ARCHON_PASS_A(8, false, key_text);
-        else if (defer_big) ARCHON_PASS_A(1, kHotRank, d_x);      // periodic block: a few digits per tile
-        else ARCHON_PASS_A(1, false, d_x);
-#undef ARCHON_PASS_A
-        iA1 = ps.mark();
-        // pass B walks the same tile grid in the same ranges; in bucket mode (Prep::aligned) workgroup c takes bucket c
-        const uint32_t gridB = (allow_aligned && R < 256u) ? 256u : R;      // bucket mode needs 256; surplus workgroups return at once
-        hipLaunchKernelGGL(bs::k_range_hist_text, dim3(R), dim3(bs::kRhBlock), 0, s, A_B1, n, tpr, rhist, 0u, kTileItems, d_skip);
-        hipLaunchKernelGGL(bs::k_col_prefix, dim3(256), dim3(1024), 0, s, rhist, R, d_skip, twin);    // (bucket mode with range-relative records: pass A's table stays)
-        iB0 = ps.mark();
-#define ARCHON_PASS_B(HOTF, RELF) hipLaunchKernelGGL(HIP_KERNEL_NAME(bs::k_pass_rec<bs::kPassBBlock, bs::kPassBIPT, HOTF, RELF>), dim3(gridB), dim3(bs::kPassBBlock), 0, s, A_R, A_B1, n, tpr, B_R, \
-                                                     B.prep->startB, rhist, B.prep->startA, d_skip, B.prep->start16, B.trash, twin, rhist, R, tpr * kTileItems)
-        if (defer_big) { ARCHON_PASS_B(kHotRank, false); if (rel_ok) ARCHON_PASS_B(kHotRank, true); }
-        else { ARCHON_PASS_B(false, false); if (rel_ok) ARCHON_PASS_B(false, true); }
-        if (rel_ok) ++c->launches;
-#undef ARCHON_PASS_B
-        iB1 = ps.mark();
-        e2 = tm.mark();
-        // (a block of few rows per bucket: the short instance of the bucket sort in front of the general one -- whichever matches the
-        //  count's largest bucket runs, the other returns at once)
-        const uint32_t avg_rows = n >> 16;
-        const uint32_t short_rounds = defer_big ? 0u : avg_rows <= 400u ? 1u : avg_rows <= 1350u ? 3u : 0u;
-        if (short_rounds == 1u)
-            hipLaunchKernelGGL(HIP_KERNEL_NAME(bs::k_local_sort<1>), dim3(65536), dim3(bs::kLsBlock), 0, s, B_R, B.prep->start16, n, sa, d_bwt, d_ctl, B.tie_list, d_skip, 0u, 0u);
-        else if (short_rounds == 3u)
-            hipLaunchKernelGGL(HIP_KERNEL_NAME(bs::k_local_sort<3>), dim3(65536), dim3(bs::kLsBlock), 0, s, B_R, B.prep->start16, n, sa, d_bwt, d_ctl, B.tie_list, d_skip, 0u, 0u);
-        if (short_rounds) ++c->launches;
-        hipLaunchKernelGGL(HIP_KERNEL_NAME(bs::k_local_sort<bs::kLsIPT>), dim3(65536), dim3(bs::kLsBlock), 0, s, B_R, B.prep->start16, n, sa,
-                           d_bwt, d_ctl, B.tie_list, d_skip, defer_big ? 1u : 0u, short_rounds * (uint32_t)bs::kLsBlock);
-        if (defer_big) {
-            hipLaunchKernelGGL(bs::k_unpack_big, dim3(div_up(n, bs::kUnpackChunk)), dim3(256), 0, s, B_R, B.prep->start16, n, sa, d_bwt, d_ctl, d_skip);
-            ++c->launches;
-        }
-        e2b = tm.mark();
-        hipLaunchKernelGGL(bs::k_resolve_ties, dim3(div_up(kTieListCap, 256)), dim3(256), 0, s, d_x, n, B.tie_list, d_ctl,
-                           sa, d_bwt, 5u * (uint32_t)Q, 64u * (uint32_t)Q, d_skip);
-        ARCHON_HIP_TRY(hipGetLastError());
-        c->launches += 7;
-        // (on the chance that this is all the block needs -- the graded case -- the primary index goes to the caller and the
-        //  consistency flag to the host with the same round trip: the call then ends without a second one.  Everything the host
-        //  reads -- summary, flag, byte counts for skewed blocks, the period probe -- is written into the pinned mailbox by k_mail.)
-        e3 = tm.mark();
-        hipLaunchKernelGGL(bs::k_mail, dim3(1), dim3(256), 0, s, d_ctl, B.sc.d_err, Q == 1 ? B.prep->cntA : nullptr, d_x + (n - 1),
-                           probe_queued ? pres : nullptr, c->h_mail_dev, d_base_out, ++c->mail_seq);
-        ARCHON_HIP_TRY(hipGetLastError());
-        ++c->launches;
-        if (Q == 1) have_byte_counts = true;                     // (used only by skewed blocks)
-        probe_fetched = probe_queued;
-        ARCHON_HOST_STAMP(2);
-        // the host's one wait of the block: spin on the sequence word k_mail writes last (pinned, coherent memory); should it not
-        // turn up within 50 ms the ordinary wait takes over (and reports whatever went wrong on the stream)
-        {
-            ++t_sync_count;
-            volatile uint32_t *seqw = c->h_mail + bs::kMailSeq;         // (clear of every region of the mailbox: common.hiph)
-            const uint32_t want = c->mail_seq;
-            const auto t_spin = std::chrono::steady_clock::now();
-            for (uint32_t spins = 0; *seqw != want; ++spins) {
-                __builtin_ia32_pause();
-                if ((spins & 0xFFFu) == 0xFFFu && std::chrono::steady_clock::now() - t_spin > std::chrono::milliseconds(50)) {
-                    ARCHON_HIP_TRY(hipStreamSynchronize(s));
-                    break;
-                }
-            }
-            std::atomic_thread_fence(std::memory_order_acquire);
-        }
-        ARCHON_HOST_STAMP(3);
-        memcpy(&h_ctl, c->h_mail + mail::kSummary.at, sizeof h_ctl);
-        big_items = h_ctl.big_items;
-        if (h_ctl.fault) { set_error("tie list names rows outside the block (device flag 0x%x)", h_ctl.fault); return ARCHON_E_INTERNAL; }
-        return ARCHON_OK;
-    };
-    auto count_wait = [&]() -> int {             // routes that need the count on the host before going on
-        ARCHON_HIP_TRY(hipMemcpyAsync(c->h_mail + mail::kBigItems.at, &B.prep->big_items, 2 * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
-        ARCHON_TRY(fetch_byte_counts());
-        ARCHON_TRY(fetch_probe());
-        ARCHON_SYNC(s);
-        big_items = c->h_mail[mail::kBigItems.at];
-        return ARCHON_OK;
-    };
-    // entry of the general stage (k_first_groups): clean SA, group starts and the compacted working set in one sweep
-    auto first_groups = [&](int mode, const uint64_t *keys, const uint32_t *items, uint32_t shift, bool write_ws) -> int {
-        ARCHON_TRY(general_buffers());
-        unsigned long long *fg_status = reinterpret_cast<unsigned long long *>(B.sc.d_status);
-        const uint32_t tiles = div_up(n, fwd::kFgTile);
-        ARCHON_HIP_TRY(hipMemsetAsync(fg_status, 0, (size_t)tiles * sizeof(unsigned long long), s));
-        ARCHON_HIP_TRY(hipMemsetAsync(B.sc.d_ticket, 0, sizeof(uint32_t), s));
-        ARCHON_HIP_TRY(hipMemsetAsync(small + fwd_small::kFu, 0, 4 * sizeof(uint32_t), s));
-        const uint32_t ws_mode = write_ws ? 2u : 0u;      // 2: the S / B lists of rounds.hiph
-        if (mode == 0)
-            hipLaunchKernelGGL(HIP_KERNEL_NAME(fwd::k_first_groups<0>), dim3(tiles), dim3(256), 0, s, keys, items, shift, n, sa, d_bwt, d_base, B.v,
-                               B.upos[0], B.ug[0], B.uitem[0], small + fwd_small::kTotal, fg_status, B.sc.d_ticket, B.sc.d_err, ws_mode, B.slist[0], small + fwd_small::kFu, (uint32_t)fwd::kFuMax);
-        else
-            hipLaunchKernelGGL(HIP_KERNEL_NAME(fwd::k_first_groups<1>), dim3(tiles), dim3(256), 0, s, keys, items, shift, n, sa, d_bwt, d_base, B.v,
-                               B.upos[0], B.ug[0], B.uitem[0], small + fwd_small::kTotal, fg_status, B.sc.d_ticket, B.sc.d_err, ws_mode, B.slist[0], small + fwd_small::kFu, (uint32_t)fwd::kFuMax);
-        ARCHON_HIP_TRY(hipGetLastError());
-        ++c->launches;
-        return ARCHON_OK;
-    };
-    int path;
-    int Q = 1;                                   // symbols per key byte on the streaming path
-    const bool probe = forced < 0 && !route_off(kRtNoProbe);
+    forced = g_route.force_path;
+    closed_ok = depth == 0 && forced < 0 && n >= (1u << 16) && !route_off(kRtNoPeriodProbe) && !route_off(kRtNoChains) && !route_off(kRtNoClosedForm);
+    probe = forced < 0 && !route_off(kRtNoProbe);
     // Small blocks (the container's default is 4 MiB, bwt/final/x3/archon.c:100): the streaming stage is built for blocks that fill
     // the chip -- its two-byte count keeps 128 KiB of counters per workgroup on all 256 CUs, its bucket sort launches 65 536
     // workgroups -- and costs 0.7 ms whatever the block holds.  Below kSmallBlock a block takes a plain byte count and the LSB
     // passes, whose cost follows its size.
-    bool tail_fetched = false, period_probed = false, hinted = false;
-    auto first_attempt = [&]() -> int {          // a big block: two-byte count (with the alphabet probe) and the streaming stage behind it
-        ARCHON_TRY(count16(1, d_x, forced == 1, probe));
-        if (forced == 0) {
-            ARCHON_TRY(count_wait());
-            path = 0;
-        } else {
-            ARCHON_TRY(streaming(1, d_x));
-            path = (forced == 1 || (uint64_t)big_items * 2 <= n) ? 1 : 0;
-        }
-        return ARCHON_OK;
-    };
     const uint32_t small_limit = g_route.small_block >= 0 ? (uint32_t)g_route.small_block : kSmallBlock;
-    const bool small_block = forced < 0 && n >= 8 && n < small_limit;
+    small_block = forced < 0 && n >= 8 && n < small_limit;
+    return ARCHON_OK;
+}
+
+// The period probe (k_period_find, k_period_vote) and -- `clean` -- the comparison of the whole text with itself p further down
+// (pf::k_period_clean).  The result word was set to "none" and the votes and flags behind it cleared by k_prep.
+void Fwd::queue_probe(bool clean)
+{
+    hipLaunchKernelGGL(fwd::k_period_find, dim3(fwd::kPeriodSearch / 256), dim3(256), 0, s, d_x, n, pres);
+    hipLaunchKernelGGL(fwd::k_period_vote, dim3(fwd::kPeriodVotes / 256), dim3(256), 0, s, d_x, n, pres);
+    c->launches += 2;
+    if (clean) {
+        hipLaunchKernelGGL(pf::k_period_clean, dim3(kNumCU * 8), dim3(256), 0, s, d_x, n, pres);
+        ++c->launches;
+    }
+    probe_queued = true;
+    probe_clean = clean;
+}
+
+// the probe's verdict into the mailbox (mail::kProbe), with the round trip that follows
+int Fwd::fetch_probe(uint32_t words)
+{
+    if (probe_queued) ARCHON_HIP_TRY(hipMemcpyAsync(c->h_mail + mail::kProbe.at, pres, words * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+    probe_fetched = probe_queued;
+    return ARCHON_OK;
+}
+
+// The verdict has arrived (the wait behind fetch_probe or k_mail is over).  A clean periodic block (periodic.hiph): x[i] == x[i-p]
+// for every i >= p (k_period_clean compared all of it), p minimal (the smallest distance at which the block's middle window
+// recurs: a smaller period would recur there too), n >= 16 p -- it is written down in closed form.
+void Fwd::probe_arrived()
+{
+    const uint32_t *h_probe = c->h_mail + mail::kProbe.at;
+    if (closed_ok && probe_fetched && h_probe[0] != 0xFFFFFFFFu && h_probe[3] == 1u && h_probe[2] == 0u) closed = true;
+}
+
+// The block's byte counts (a small block's exact ones, or the two-byte count's column sums) and x[n-1] into the mailbox
+int Fwd::fetch_byte_counts(const uint32_t *d_counts)
+{
+    uint32_t *h_last = c->h_mail + mail::kLastByte.at;
+    *h_last = 0;
+    ARCHON_HIP_TRY(hipMemcpyAsync(c->h_mail + mail::kByteCounts.at, d_counts, 256 * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+    ARCHON_HIP_TRY(hipMemcpyAsync(h_last, d_x + (n - 1), 1, hipMemcpyDeviceToHost, s));
+    return ARCHON_OK;
+}
+
+// The block's byte histogram x[0 .. n-1] out of the mailbox, right after the wait that brought it (mail::kByteCounts lies inside
+// the staging rs::sort_pairs overwrites).  The two-byte count's second-byte column sums are the bytes x[0 .. n-2] plus the 0xFF
+// in front of x[0]: x[n-1] is added and the pad removed.
+void Fwd::take_byte_hist(bool exact)
+{
+    const uint32_t *h_counts = c->h_mail + mail::kByteCounts.at, last_byte = c->h_mail[mail::kLastByte.at] & 0xFFu;
+    for (uint32_t v = 0; v < 256; ++v) hist[v] = exact ? h_counts[v] : h_counts[v] - (v == 0xFFu ? 1u : 0u) + (v == last_byte ? 1u : 0u);
+    have_hist = true;
+}
+
+// the exact alphabet: 256 presence bits -> sigma, lut (the order-preserving recode)
+int Fwd::presence()
+{
+    hipLaunchKernelGGL(bs::k_presence, dim3(kNumCU * 8), dim3(256), 0, s, d_x, n, B.prep->present);
+    const uint32_t *h_present = c->h_mail + mail::kPresence.at;
+    ARCHON_HIP_TRY(hipMemcpyAsync(c->h_mail + mail::kPresence.at, B.prep->present, 8 * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+    if (!probe_fetched) ARCHON_TRY(fetch_probe());         // (hinted: the period probe's verdict has not travelled yet)
+    ARCHON_SYNC(s);
+    ++c->launches;
+    probe_arrived();
+    sigma = 0;
+    for (uint32_t v = 0; v < 256; ++v) {
+        lut[v] = (uint8_t)sigma;
+        if ((h_present[v >> 5] >> (v & 31u)) & 1u) ++sigma;
+    }
+    presence_done = true;
+    return ARCHON_OK;
+}
+
+// The two-byte count of src in key form `form` and its scans; k_rows_scan leaves the route's verdict on the device.
+// alpha_probe: a workgroup that sees at most 4 distinct bytes gives the count up (Prep::suspect).
+int Fwd::count16(int form, const uint8_t *src, bool force_stream, bool alpha_probe)
+{
+    uint32_t *d_suspect = alpha_probe ? &B.prep->suspect : nullptr;
+    if (!count_tables_clear) ARCHON_HIP_TRY(hipMemsetAsync(B.hist16, 0, count_zero_bytes, s));      // (the block's first count finds them cleared by k_prep)
+    count_tables_clear = false;
+    // the count runs with at most 256 workgroups per half: with more pass ranges each workgroup covers several of
+    // them and reads the column sums off between two (more workgroups would only flush their 32 768 bins more often)
+    const uint32_t sub = (R > 256u && R % 256u == 0u) ? R / 256u : 1u;
+    const uint32_t nparts = div_up(R, sub);
+    // B.hist16 (zeroed above) first serves as the spill table of the count, then receives the totals (k_rows_total)
+    with_const<kHotForm, 1, 2, 4, 8>(form, [&](auto k) {
+        constexpr int F = decltype(k)::value;
+        hipLaunchKernelGGL(HIP_KERNEL_NAME(bs::k_hist16<key_q(F), F == kHotForm>), dim3(nparts), dim3(bs::kH16Block), 0, s, src, n, B.h16part, B.hist16,
+                           tpr * kTileItems, B.rhist, d_suspect, sub);
+    });
+    static_assert(bs::kMaxRanges <= 1024, "four ranges per lane in the column half of k_rows_sum_total");
+    hipLaunchKernelGGL(bs::k_rows_sum_total, dim3(512), dim3(256), 0, s, B.hist16, B.h16part, nparts, B.prep, (uint32_t)bs::kLsCap, B.rhist, R);
+    hipLaunchKernelGGL(bs::k_rows_scan, dim3(256), dim3(256), 0, s, B.hist16, B.prep, force_stream ? 1u : 0u, allow_aligned, d_ctl, (uint32_t)kTieListCap, n,
+                       probe_clean ? pres : nullptr);
+    ARCHON_HIP_TRY(hipGetLastError());
+    c->launches += 3;
+    e_count = tm.mark();
+    return ARCHON_OK;
+}
+
+// ---- streaming first stage: two LSB passes + in-LDS bucket sorts; ends with the block's host round trip ----
+// (the tie summary was initialised on the device by k_rows_scan, which also left the count summary in it)
+int Fwd::streaming(int form, const uint8_t *key_text)
+{
+    const int q = key_q(form);
+    const bool hot = form == kHotForm;      // a periodic block: a few digits per tile, its oversized buckets deferred (k_unpack_big)
+    const uint32_t *d_skip = &B.prep->skip;
+    uint2 *A_R = reinterpret_cast<uint2 *>(B.keyA);     // pass A out: {K, I} records + the first-key-byte stream
+    uint8_t *A_B1 = reinterpret_cast<uint8_t *>(B.valA);
+    uint2 *B_R = reinterpret_cast<uint2 *>(B.keyB);     // pass B out
+    iA0 = ps.mark();
+    // Both record formats of the passes are queued (passes.hiph): the plain one and -- where bucket mode is possible at all -- the
+    // range-relative one; which of the two a block takes is the count's choice of pass-B mode (Prep::aligned), known on the device
+    // only, and the instantiation that does not match returns at once.
+    const uint32_t twin = rel_ok ? 1u : 0u;
+    with_const<kHotForm, 1, 2, 4, 8>(form, [&](auto k) {
+        constexpr int F = decltype(k)::value;
+        auto pass_a = [&](auto rel) {
+            hipLaunchKernelGGL(HIP_KERNEL_NAME(bs::k_pass_text<bs::kPassBlock, bs::kPassIPT, key_q(F), F == kHotForm, decltype(rel)::value>), dim3(R), dim3(bs::kPassBlock),
+                               0, s, d_x, n, tpr, A_R, A_B1, B.prep->startA, B.rhist, key_text, d_skip, B.trash, &d_ctl->base_bucket, twin);
+        };
+        pass_a(std::false_type{});
+        if (rel_ok) pass_a(std::true_type{});
+    });
+    if (rel_ok) ++c->launches;
+    iA1 = ps.mark();
+    // pass B walks the same tile grid in the same ranges; in bucket mode (Prep::aligned) workgroup c takes bucket c
+    const uint32_t gridB = (allow_aligned && R < 256u) ? 256u : R;      // bucket mode needs 256; surplus workgroups return at once
+    hipLaunchKernelGGL(bs::k_range_hist_text, dim3(R), dim3(bs::kRhBlock), 0, s, A_B1, n, tpr, B.rhist, 0u, kTileItems, d_skip);
+    hipLaunchKernelGGL(bs::k_col_prefix, dim3(256), dim3(1024), 0, s, B.rhist, R, d_skip, twin);    // (bucket mode with range-relative records: pass A's table stays)
+    iB0 = ps.mark();
+    with_const<0, 1>(hot, [&](auto h) {
+        auto pass_b = [&](auto rel) {
+            hipLaunchKernelGGL(HIP_KERNEL_NAME(bs::k_pass_rec<bs::kPassBBlock, bs::kPassBIPT, decltype(h)::value != 0, decltype(rel)::value>), dim3(gridB), dim3(bs::kPassBBlock),
+                               0, s, A_R, A_B1, n, tpr, B_R, B.prep->startB, B.rhist, B.prep->startA, d_skip, B.prep->start16, B.trash, twin, B.rhist, R, tpr * kTileItems);
+        };
+        pass_b(std::false_type{});
+        if (rel_ok) pass_b(std::true_type{});
+    });
+    if (rel_ok) ++c->launches;
+    iB1 = ps.mark();
+    e_sorted = tm.mark();
+    // (a block of few rows per bucket: the short instance of the bucket sort in front of the general one -- whichever matches the
+    //  count's largest bucket runs, the other returns at once)
+    const uint32_t avg_rows = n >> 16;
+    const uint32_t short_rounds = hot ? 0u : avg_rows <= 400u ? 1u : avg_rows <= 1350u ? 3u : 0u;
+    if (short_rounds) {
+        with_const<1, 3>((int)short_rounds, [&](auto r) {
+            hipLaunchKernelGGL(HIP_KERNEL_NAME(bs::k_local_sort<decltype(r)::value>), dim3(65536), dim3(bs::kLsBlock), 0, s, B_R, B.prep->start16, n, sa, d_bwt, d_ctl,
+                               B.tie_list, d_skip, 0u, 0u);
+        });
+        ++c->launches;
+    }
+    hipLaunchKernelGGL(HIP_KERNEL_NAME(bs::k_local_sort<bs::kLsIPT>), dim3(65536), dim3(bs::kLsBlock), 0, s, B_R, B.prep->start16, n, sa,
+                       d_bwt, d_ctl, B.tie_list, d_skip, hot ? 1u : 0u, short_rounds * (uint32_t)bs::kLsBlock);
+    if (hot) {
+        hipLaunchKernelGGL(bs::k_unpack_big, dim3(div_up(n, bs::kUnpackChunk)), dim3(256), 0, s, B_R, B.prep->start16, n, sa, d_bwt, d_ctl, d_skip);
+        ++c->launches;
+    }
+    e_local = tm.mark();
+    hipLaunchKernelGGL(bs::k_resolve_ties, dim3(div_up(kTieListCap, 256)), dim3(256), 0, s, d_x, n, B.tie_list, d_ctl,
+                       sa, d_bwt, 5u * (uint32_t)q, 64u * (uint32_t)q, d_skip);
+    ARCHON_HIP_TRY(hipGetLastError());
+    c->launches += 7;
+    // (on the chance that this is all the block needs -- the graded case -- the primary index goes to the caller and the
+    //  consistency flag to the host with the same round trip: the call then ends without a second one.  Everything the host
+    //  reads -- summary, flag, byte counts for skewed blocks, the period probe -- is written into the pinned mailbox by k_mail.)
+    e_first = tm.mark();
+    hipLaunchKernelGGL(bs::k_mail, dim3(1), dim3(256), 0, s, d_ctl, B.sc.d_err, q == 1 ? B.prep->cntA : nullptr, d_x + (n - 1),
+                       probe_clean ? pres : nullptr, c->h_mail_dev, d_base_out, ++c->mail_seq);
+    ARCHON_HIP_TRY(hipGetLastError());
+    ++c->launches;
+    probe_fetched = probe_clean;
+    stamp(2);
+    // the host's one wait of the block: spin on the sequence word k_mail writes last (pinned, coherent memory); should it not
+    // turn up within 50 ms the ordinary wait takes over (and reports whatever went wrong on the stream)
+    {
+        ++t_sync_count;
+        volatile uint32_t *seqw = c->h_mail + bs::kMailSeq;         // (clear of every region of the mailbox: common.hiph)
+        const uint32_t want = c->mail_seq;
+        const auto t_spin = std::chrono::steady_clock::now();
+        for (uint32_t spins = 0; *seqw != want; ++spins) {
+            __builtin_ia32_pause();
+            if ((spins & 0xFFFu) == 0xFFFu && std::chrono::steady_clock::now() - t_spin > std::chrono::milliseconds(50)) {
+                ARCHON_HIP_TRY(hipStreamSynchronize(s));
+                break;
+            }
+        }
+        std::atomic_thread_fence(std::memory_order_acquire);
+    }
+    stamp(3);
+    memcpy(&ctl, c->h_mail + mail::kSummary.at, sizeof ctl);
+    big_items = ctl.big_items;
+    if (ctl.fault) { set_error("tie list names rows outside the block (device flag 0x%x)", ctl.fault); return ARCHON_E_INTERNAL; }
+    if (q == 1) take_byte_hist(false);          // (used only by skewed blocks)
+    probe_arrived();
+    return ARCHON_OK;
+}
+
+// 2. The first look at the block: a small block's byte count; a big block's probe, two-byte count and streaming stage -- or
+// its alphabet first, when the context's last block suggests it.
+int Fwd::first_look()
+{
     if (small_block) {
+        uint32_t *d_counts = B.small + fwd_small::kCounts;
         ARCHON_TRY(launch_hist256(s, d_x, n, d_counts, n));
         ++c->launches;
-        e1 = tm.mark();
-        ARCHON_HIP_TRY(hipMemcpyAsync(h_counts, d_counts, 256 * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
-        ARCHON_HIP_TRY(hipMemcpyAsync(h_last, d_x + (n - 1), 1, hipMemcpyDeviceToHost, s));
+        e_count = tm.mark();
+        ARCHON_TRY(fetch_byte_counts(d_counts));
         // (a small block's time is its host round trips: the period probe and the block's last bytes -- what the LSB passes' digit
         //  counts need -- travel with the byte count instead of taking one each further down)
         ARCHON_HIP_TRY(hipMemcpyAsync(c->h_mail + mail::kTail.at, d_x + (n - 8), 8, hipMemcpyDeviceToHost, s));
         tail_fetched = true;
         if (n >= (1u << 16) && !route_off(kRtNoPeriodProbe)) {
-            ARCHON_TRY(queue_probe());
+            queue_probe(closed_ok);
             ARCHON_TRY(fetch_probe());
-            period_probed = true;
         }
         ARCHON_SYNC(s);
-        // (in the form the two-byte count leaves its column sums in -- the bytes x[0 .. n-2] and the 0xFF in front of x[0] --
-        //  which is what the code below undoes)
-        h_counts[*h_last & 0xFFu] -= 1u;
-        h_counts[0xFFu] += 1u;
-        have_byte_counts = true;
-        path = 0;
-    } else {
-    if (closed_ok) {
-        ARCHON_TRY(queue_probe());
-        period_probed = true;
-    }
-    hinted = probe && c->hint_poor_alphabet;
-    if (!hinted) ARCHON_TRY(first_attempt());
-    }
-    // returns ARCHON_OK when the block was written down in closed form, 1 when it is not a clean periodic block, < 0 on error
-    auto closed_form = [&]() -> int {
-        const uint32_t *h_probe = c->h_mail + mail::kProbe.at;     // [0] period, [1] votes, [2] the text breaks it, [3] the whole text was compared
-        if (!(closed_ok && period_probed && probe_fetched && h_probe[0] != 0xFFFFFFFFu && h_probe[3] == 1u && h_probe[2] == 0u)) return 1;
-        // ---- a clean periodic block (periodic.hiph): x[i] == x[i-p] for every i >= p (k_period_clean compared all of it), p minimal
-        // (the smallest distance at which the block's middle window recurs: a smaller period would recur there too), n >= 16 p.
-        // Sort the block's first 2p bytes -- the ordinary transform, nested -- and expand its suffix array.
-        const uint32_t p = h_probe[0], m2 = 2u * p;
-        Carve t{c->arena + tail_at, 0, kClosedTail};
-        uint32_t *sa2 = t.take<uint32_t>(m2);
-        uint32_t *off = t.take<uint32_t>(m2 + 1);
-        uint8_t *bwt2 = t.take<uint8_t>(m2);
-        uint32_t *base2 = t.take<uint32_t>(64);
-        if (!base2 || (uint64_t)p * pf::kMinPeriods + 64u > n) {
-            set_error("closed form: period %u of a block of %u bytes does not fit its scratch", p, n);
-            return ARCHON_E_INTERNAL;
-        }
-        // the nested call asks for no more than the arena holds: it neither grows nor frees it, and its tier 1 ends below the tail
-        {
-            FwdBuf nb{};
-            Carve count;
-            if (fwd_tier1(count, nb, m2, c->dev, false) > c->arena_bytes) {
-                set_error("closed form: tier 1 of the %u-byte block of period %u does not fit below the tail", m2, p);
-                return ARCHON_E_INTERNAL;
-            }
-        }
-        const uint32_t launches0 = c->launches;
-        const bool x_in_arena = d_x == B.xa;
-        ARCHON_TRY(forward_run(c, s, d_x, m2, sa2, bwt2, base2, depth + 1));      // (c->stats, c->launches, tier 1: the nested call's from here on)
-        const uint32_t launches1 = c->stats.kernel_launches;
-        const uint64_t arena1 = c->stats.arena_bytes;
-        // Tier 1 again, for the expansion.  The nested call carved it from the bottom: of the aligned copy of the text (B.xa) only
-        // the slot is kept, so that tile_lo lands behind it -- its first 2p + 64 bytes are still the text (the nested block read them
-        // in place), the rest was overwritten, and k_expand reads nothing of x but x[0].
-        Carve a{c->arena, 0, tail_at};
-        if (x_in_arena) (void)a.take<uint8_t>((size_t)n + 64);
-        const uint32_t ntiles = div_up(n, pf::kTile);
-        uint32_t *tile_lo = a.take<uint32_t>((size_t)ntiles + 2);
-        if (!tile_lo) { set_error("arena exhausted (closed form)"); return ARCHON_E_NOMEM; }
-        hipLaunchKernelGGL(pf::k_offsets, dim3(1), dim3(1024), 0, s, sa2, m2, p, n, off);
-        hipLaunchKernelGGL(pf::k_tiles, dim3(div_up(ntiles + 1, 256)), dim3(256), 0, s, off, m2, ntiles, tile_lo);
-        hipLaunchKernelGGL(pf::k_expand, dim3(ntiles), dim3(256), 0, s, off, sa2, bwt2, tile_lo, m2, p, n, d_x, d_sa_user, d_bwt, d_base_out);
-        ARCHON_HIP_TRY(hipGetLastError());
-        const int e_end = tm.mark();
-        uint32_t *rd = c->h_mail + mail::kRead.at;
-        ARCHON_HIP_TRY(hipMemcpyAsync(rd, off + m2, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
-        ARCHON_SYNC(s);
-        if (rd[0] != n) { set_error("closed form: the classes of period %u hold %u rows of %u", p, rd[0], n); return ARCHON_E_INTERNAL; }
-        memset(&st, 0, sizeof st);
-        st.n = n;
-        st.path = 2;
-        st.period = p;
-        st.chain_items = n;
-        st.kernel_launches = c->launches = launches0 + launches1 + 3;
-        st.arena_bytes = arena1 > a.off ? arena1 : a.off;
-        st.ms_hist = tm.ms(e0, e1);
-        st.ms_sort = tm.ms(e1, e_end);
-        st.ms_total = tm.ms(e0, e_end);
-        st.host_syncs = t_sync_count;
-        if (depth == 0) c->hint_poor_alphabet = true;      // (periodic after periodic: the probe's verdict before any count)
+        take_byte_hist(true);
+        probe_arrived();
         return ARCHON_OK;
-    };
-    if (!hinted) { const int r = closed_form(); if (r <= 0) return r; }
-    constexpr uint32_t kPackSigma = 32;          // alphabets up to this many distinct bytes sort on packed keys
-    uint32_t sigma = 0, bits = 8;
-    uint8_t *d_lut = reinterpret_cast<uint8_t *>(small + fwd_small::kLut);
-    uint8_t h_lut[256];
-    bool have_lut = false;
-    bool presence_done = false;
-    auto presence = [&]() -> int {               // the exact alphabet: 256 presence bits -> sigma, h_lut (the order-preserving recode)
-        hipLaunchKernelGGL(bs::k_presence, dim3(kNumCU * 8), dim3(256), 0, s, d_x, n, B.prep->present);
-        const uint32_t *h_present = c->h_mail + mail::kPresence.at;
-        ARCHON_HIP_TRY(hipMemcpyAsync(c->h_mail + mail::kPresence.at, B.prep->present, 8 * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
-        if (!probe_fetched) ARCHON_TRY(fetch_probe());         // (hinted: the period probe's verdict has not travelled yet)
-        ARCHON_SYNC(s);
-        ++c->launches;
-        sigma = 0;
-        for (uint32_t v = 0; v < 256; ++v) {
-            h_lut[v] = (uint8_t)sigma;
-            if ((h_present[v >> 5] >> (v & 31u)) & 1u) ++sigma;
-        }
-        presence_done = true;
-        return ARCHON_OK;
-    };
-    if (hinted) {
+    }
+    if (closed_ok) queue_probe(true);
+    if (probe && c->hint_poor_alphabet) {
         // The last block of this context had at most 4 distinct bytes (DNA after DNA: BASELINE.json configs[3]), and its first
         // attempt -- a count that gives up at once, the streaming stage queued behind it returning kernel by kernel, a round
         // trip -- cost 160 us for nothing.  This one shows its alphabet first; with more than 4 distinct bytes it takes the
         // ordinary first attempt after all, with 4 or fewer it goes where the count's probe would have sent it.
         ARCHON_TRY(presence());
-        { const int r = closed_form(); if (r <= 0) return r; }
+        if (closed) return ARCHON_OK;
         if (sigma <= 4) {
-            h_ctl.suspect = 1;
-            path = 0;
-        } else {
-            ARCHON_TRY(first_attempt());
-            { const int r = closed_form(); if (r <= 0) return r; }
+            ctl.suspect = 1;
+            return ARCHON_OK;
         }
     }
-    if (probe && h_ctl.suspect) {
-        // a workgroup of the count saw at most 4 distinct bytes and the count was abandoned (k_hist16): get the exact
-        // alphabet from a presence map; a block that only LOOKED poor is counted again without the probe
+    // a big block's first attempt: two-byte count (with the alphabet probe) and the streaming stage behind it
+    ARCHON_TRY(count16(1, d_x, forced == 1, probe));
+    if (forced == 0) {          // (tests: the 7-pass route needs the count on the host before going on)
+        ARCHON_HIP_TRY(hipMemcpyAsync(c->h_mail + mail::kBigItems.at, &B.prep->big_items, 2 * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+        ARCHON_TRY(fetch_byte_counts(B.prep->cntA));
+        ARCHON_SYNC(s);
+        big_items = c->h_mail[mail::kBigItems.at];
+        take_byte_hist(false);
+        return ARCHON_OK;
+    }
+    ARCHON_TRY(streaming(1, d_x));
+    path = (forced == 1 || (uint64_t)big_items * 2 <= n) ? Path::kStream : Path::kSevenPass;
+    return ARCHON_OK;
+}
+
+static int forward_run(Ctx *c, hipStream_t s, const uint8_t *d_x_in, uint32_t n, uint32_t *d_sa_user, uint8_t *d_bwt, uint32_t *d_base_out, int depth);
+
+// 3. A clean periodic block: sort its first 2p bytes -- the ordinary transform, nested -- and expand their suffix array.
+int Fwd::closed_form()
+{
+    const uint32_t p = c->h_mail[mail::kProbe.at], m2 = 2u * p;
+    Carve t{c->arena + tail_at, 0, kClosedTail};
+    uint32_t *sa2 = t.take<uint32_t>(m2);
+    uint32_t *off = t.take<uint32_t>(m2 + 1);
+    uint8_t *bwt2 = t.take<uint8_t>(m2);
+    uint32_t *base2 = t.take<uint32_t>(64);
+    if (!base2 || (uint64_t)p * pf::kMinPeriods + 64u > n) {
+        set_error("closed form: period %u of a block of %u bytes does not fit its scratch", p, n);
+        return ARCHON_E_INTERNAL;
+    }
+    // the nested call asks for no more than the arena holds: it neither grows nor frees it, and its tier 1 ends below the tail
+    FwdBuf nb{};
+    Carve count;
+    if (fwd_tier1(count, nb, m2, c->dev, false) > c->arena_bytes) {
+        set_error("closed form: tier 1 of the %u-byte block of period %u does not fit below the tail", m2, p);
+        return ARCHON_E_INTERNAL;
+    }
+    const uint32_t launches0 = c->launches;
+    const bool x_in_arena = d_x == B.xa;
+    ARCHON_TRY(forward_run(c, s, d_x, m2, sa2, bwt2, base2, depth + 1));      // (c->stats, c->launches, tier 1: the nested call's from here on)
+    const uint32_t launches1 = c->stats.kernel_launches;
+    const uint64_t arena1 = c->stats.arena_bytes;
+    // Tier 1 again, for the expansion.  The nested call carved it from the bottom: of the aligned copy of the text (B.xa) only
+    // the slot is kept, so that tile_lo lands behind it -- its first 2p + 64 bytes are still the text (the nested block read them
+    // in place), the rest was overwritten, and k_expand reads nothing of x but x[0].
+    Carve a{c->arena, 0, tail_at};
+    if (x_in_arena) (void)a.take<uint8_t>((size_t)n + 64);
+    const uint32_t ntiles = div_up(n, pf::kTile);
+    uint32_t *tile_lo = a.take<uint32_t>((size_t)ntiles + 2);
+    if (!tile_lo) { set_error("arena exhausted (closed form)"); return ARCHON_E_NOMEM; }
+    hipLaunchKernelGGL(pf::k_offsets, dim3(1), dim3(1024), 0, s, sa2, m2, p, n, off);
+    hipLaunchKernelGGL(pf::k_tiles, dim3(div_up(ntiles + 1, 256)), dim3(256), 0, s, off, m2, ntiles, tile_lo);
+    hipLaunchKernelGGL(pf::k_expand, dim3(ntiles), dim3(256), 0, s, off, sa2, bwt2, tile_lo, m2, p, n, d_x, d_sa_user, d_bwt, d_base_out);
+    ARCHON_HIP_TRY(hipGetLastError());
+    e_sorted = e_end = tm.mark();
+    uint32_t *rd = c->h_mail + mail::kRead.at;
+    ARCHON_HIP_TRY(hipMemcpyAsync(rd, off + m2, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+    ARCHON_SYNC(s);
+    if (rd[0] != n) { set_error("closed form: the classes of period %u hold %u rows of %u", p, rd[0], n); return ARCHON_E_INTERNAL; }
+    path = Path::kClosed;
+    closed_period = p;
+    c->launches = launches0 + launches1 + 3;
+    arena_bytes = arena1 > a.off ? arena1 : a.off;
+    if (depth == 0) c->hint_poor_alphabet = true;      // (periodic after periodic: the probe's verdict before any count)
+    return ARCHON_OK;
+}
+
+// 4. A workgroup of the count saw at most 4 distinct bytes and the count was abandoned (k_hist16): get the exact
+// alphabet from a presence map; a block that only LOOKED poor is counted again without the probe
+int Fwd::alphabet()
+{
+    if (probe && ctl.suspect) {
         if (!presence_done) ARCHON_TRY(presence());
         if (sigma <= 16 && !route_off(kRtNoPack)) {
             have_lut = true;
-            path = 0;
+            path = Path::kSevenPass;
         } else {
             sigma = 0;
-            h_ctl.suspect = 0;
+            ctl.suspect = 0;
             ARCHON_TRY(count16(1, d_x, false, false));
             ARCHON_TRY(streaming(1, d_x));
-            path = ((uint64_t)big_items * 2 <= n) ? 1 : 0;
+            path = ((uint64_t)big_items * 2 <= n) ? Path::kStream : Path::kSevenPass;
         }
     } else {
         sigma = 0;
     }
     if (probe && !small_block) c->hint_poor_alphabet = have_lut && sigma <= 4;      // (what the next block of this context looks at first)
-    // A periodic block (aaa..., abab..., a motif repeated: BASELINE.json configs[2]) needs no deep first stage: the run
-    // shortcut of general_stage settles its chains whatever depth the first stage reached.  So it takes the streaming
-    // passes after all -- two key bytes, its oversized buckets handed on as groups tied at depth 2 (k_unpack_big) --
-    // or, with that route switched off, three key bytes of the 7-pass sort.
-    uint32_t key_bytes = fwd::kKeyBytes, period_hint = 0;
-    if (path == 0 && n >= (1u << 16) && !route_off(kRtNoPeriodProbe)) {
-        uint32_t *pres = small + fwd_small::kProbe;
-        uint32_t *rd = c->h_mail + mail::kRead.at;     // [0] period, [1] votes
-        if (period_probed) {                         // (a small block: the probe went out with the byte count)
-            rd[0] = c->h_mail[mail::kProbe.at]; rd[1] = c->h_mail[mail::kProbe.at + 1];
-        } else {
-            rd[0] = 0xFFFFFFFFu; rd[1] = 0;
-            ARCHON_HIP_TRY(hipMemcpyAsync(pres, rd, 2 * sizeof(uint32_t), hipMemcpyHostToDevice, s));
-            hipLaunchKernelGGL(fwd::k_period_find, dim3(fwd::kPeriodSearch / 256), dim3(256), 0, s, d_x, n, pres);
-            hipLaunchKernelGGL(fwd::k_period_vote, dim3(fwd::kPeriodVotes / 256), dim3(256), 0, s, d_x, n, pres);
-            ARCHON_HIP_TRY(hipMemcpyAsync(rd, pres, 2 * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+    return ARCHON_OK;
+}
+
+// 4. A periodic block (aaa..., abab..., a motif repeated: BASELINE.json configs[2]) needs no deep first stage: the run
+// shortcut of general_stage settles its chains whatever depth the first stage reached.  So it takes the streaming
+// passes after all -- two key bytes, its oversized buckets handed on as groups tied at depth 2 (k_unpack_big) --
+// or, with that route switched off, three key bytes of the 7-pass sort.
+int Fwd::period()
+{
+    if (path == Path::kSevenPass && n >= (1u << 16) && !route_off(kRtNoPeriodProbe)) {
+        if (!probe_queued) {        // (k_prep armed the result word, and no kernel has been handed it since)
+            queue_probe(false);
+            ARCHON_TRY(fetch_probe(2));              // the period and its votes
             ARCHON_SYNC(s);
-            c->launches += 2;
         }
-        if (rd[0] != 0xFFFFFFFFu && rd[1] * 10 >= fwd::kPeriodVotes * 9) {
+        const uint32_t *h_probe = c->h_mail + mail::kProbe.at;
+        if (h_probe[0] != 0xFFFFFFFFu && h_probe[1] * 10 >= fwd::kPeriodVotes * 9) {
             key_bytes = 3;
             // ... provided every two-byte bucket is ONE run of the period: a bucket that joins two phases of the period (the same
             // two bytes at two places of the motif) is no run, and sorting it out at depth 2 costs more than a third key
             // byte.  The two-byte count tells: a single run holds n / p items.  (Periods 1 and 2 cannot collide.)
-            const uint32_t pp = rd[0];
+            const uint32_t pp = h_probe[0];
             if (!route_off(kRtNoPeriodHint)) period_hint = pp;     // the run shortcut need not sample neighbour gaps for it
-            const bool count_ok = forced < 0 && !h_ctl.suspect;
-            const bool single_runs = pp <= 2 || (count_ok && (uint64_t)h_ctl.max_bucket * 2 * pp <= (uint64_t)n * 3);
+            const bool count_ok = forced < 0 && !ctl.suspect;
+            const bool single_runs = pp <= 2 || (count_ok && (uint64_t)ctl.max_bucket * 2 * pp <= (uint64_t)n * 3);
             if (forced < 0 && single_runs && !small_block && !route_off(kRtNoPeriodStream)) {
                 period_hint = pp;               // (the streaming passes keep no order inside a bucket: gap sampling would not work)
-                ARCHON_TRY(count16(1, d_x, true, false, true));
-                ARCHON_TRY(streaming(1, d_x, true));
-                path = 1;
-                Q = 1;
-                st.alphabet_bits = 0;
+                ARCHON_TRY(count16(kHotForm, d_x, true, false));
+                ARCHON_TRY(streaming(kHotForm, d_x));
+                path = Path::kStream;
             }
         }
     }
     // A block with a period: where does the text break it?  (The table serves the run shortcut; a block WITH breaks skips the
     // shortcut -- its groups straddle the defects -- gets its tied rows listed by the entry sweep and goes to the
     // period-defect rounds.)
-    bool brk_ready = false;
-    uint32_t period_breaks = 0;
-    if (period_hint && !route_off(kRtNoChains)) {
-        ARCHON_TRY(general_buffers());
-        uint32_t *d_lastbrk = small + fwd_small::kLastBrk;
-        ARCHON_HIP_TRY(hipMemsetAsync(d_lastbrk, 0, 2 * sizeof(uint32_t), s));          // [0] last real break, [1] how many
-        hipLaunchKernelGGL(fwd::k_period_breaks, dim3(div_up(div_up(n, 4), 256)), dim3(256), 0, s, d_x, n, period_hint, B.brk, d_lastbrk);
-        ARCHON_TRY(launch_scan<1>(s, B.brk, B.brk, n, B.scan_tmp, nullptr));
-        uint32_t *rd = c->h_mail + mail::kRead.at;
-        ARCHON_HIP_TRY(hipMemcpyAsync(rd + 2, d_lastbrk + 1, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
-        ARCHON_SYNC(s);
-        c->launches += 4;
-        brk_ready = true;
-        period_breaks = route_off(kRtNoBreakRound) ? 0u : rd[2];
-    }
-    if (path == 0) {
-        // heavily skewed at two bytes.  Alphabet compaction: with <= 16 distinct bytes a key
-        // byte holds 2, 4 or 8 symbols; if the two-byte buckets of THAT text are small enough the block still
-        // takes the streaming stage (DNA: 8 symbols deep after two passes), else the 7-pass sort on packed keys.
-        if (!have_lut) {
-            const uint32_t last_byte = *h_last & 0xFFu;
-            for (uint32_t v = 0; v < 256; ++v) {
-                const uint32_t cnt = h_counts[v] - (v == 0xFFu ? 1u : 0u) + (v == last_byte ? 1u : 0u);
-                h_lut[v] = (uint8_t)sigma;
-                if (cnt) ++sigma;
-            }
-        }
-        bits = 1;
-        while ((1u << bits) < sigma) ++bits;
-        // (17 ... 32 distinct bytes -- lower-case prose -- still pack: five bits per symbol, eleven symbols in the seven key bytes instead of
-        //  seven; the streaming stage's key text holds whole symbols per byte and stops at 16)
-        if (sigma <= kPackSigma && !route_off(kRtNoPack)) {
-            static_assert(mail::kLut.len * 4 == sizeof h_lut, "the recode table's staging");
-            memcpy(c->h_mail + mail::kLut.at, h_lut, 256);
-            ARCHON_HIP_TRY(hipMemcpyAsync(d_lut, c->h_mail + mail::kLut.at, 256, hipMemcpyHostToDevice, s));
-            if (sigma >= 2 && sigma <= 16 && forced < 0 && !small_block && !route_off(kRtNoPackStream)) {
-                const int q = bits == 1 ? 8 : bits == 2 ? 4 : 2;
-                const dim3 grid(div_up(div_up(n, 16), 256)), block(256);
-                if (q == 8) hipLaunchKernelGGL(HIP_KERNEL_NAME(bs::k_build_y<8>), grid, block, 0, s, d_x, n, d_lut, B.y);
-                else if (q == 4) hipLaunchKernelGGL(HIP_KERNEL_NAME(bs::k_build_y<4>), grid, block, 0, s, d_x, n, d_lut, B.y);
-                else hipLaunchKernelGGL(HIP_KERNEL_NAME(bs::k_build_y<2>), grid, block, 0, s, d_x, n, d_lut, B.y);
-                ++c->launches;
-                ARCHON_TRY(count16(q, B.y, false));
-                ARCHON_TRY(streaming(q, B.y));
-                if ((uint64_t)big_items * 2 <= n) {
-                    path = 1;
-                    Q = q;
-                    st.alphabet_bits = 8 / q;
-                }
-            }
-            ARCHON_SYNC(s);          // the table upload has left mail::kLut, which the sorts below overwrite
-        }
-    }
-    st.path = (uint32_t)path;
+    if (!period_hint || route_off(kRtNoChains)) return ARCHON_OK;
+    ARCHON_TRY(general_buffers());
+    uint32_t *d_lastbrk = B.small + fwd_small::kLastBrk;
+    ARCHON_HIP_TRY(hipMemsetAsync(d_lastbrk, 0, 2 * sizeof(uint32_t), s));          // [0] last real break, [1] how many
+    hipLaunchKernelGGL(fwd::k_period_breaks, dim3(div_up(div_up(n, 4), 256)), dim3(256), 0, s, d_x, n, period_hint, B.brk, d_lastbrk);
+    ARCHON_TRY(launch_scan<1>(s, B.brk, B.brk, n, B.scan_tmp, nullptr));
+    uint32_t *rd = c->h_mail + mail::kRead.at;
+    ARCHON_HIP_TRY(hipMemcpyAsync(rd + 2, d_lastbrk + 1, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+    ARCHON_SYNC(s);
+    c->launches += 4;
+    brk_ready = true;
+    period_breaks = route_off(kRtNoBreakRound) ? 0u : rd[2];
+    return ARCHON_OK;
+}
 
-    if (e2 < 0) e2 = e1;
-    if (e3 < 0) e3 = e1;
-    e4 = e1;
-    bool need_general = true, ws_ready = true, stream_done = false;
-    uint32_t h0 = fwd::kKeyBytes;
-    if (path == 1) {
-        st.radix_passes = 2;
-        st.tie_groups = h_ctl.tie_groups;
-        st.tie_items = h_ctl.tie_items;
-        st.ms_local_sort = tm.ms(e2, e2b);
-        st.ms_resolve = tm.ms(e2b, e3);
-        if (h_ctl.unresolved == 0 && h_ctl.tie_groups <= kTieListCap) {
-            need_general = false;
-            if (h_ctl.base_id >= n) { set_error("primary index not found"); return ARCHON_E_INTERNAL; }
-            stream_done = true;                 // (the primary index and the consistency flag came with the summary)
-        } else {
-            h0 = (h_ctl.min_depth < 5 ? h_ctl.min_depth : 5) * (uint32_t)Q;     // key bytes -> symbols
-            ws_ready = period_hint == 0 || period_breaks != 0;
-            ARCHON_TRY(first_groups(1, nullptr, nullptr, 0, ws_ready));
-            ARCHON_HIP_TRY(hipMemcpyAsync(d_base, &d_ctl->base_id, sizeof(uint32_t), hipMemcpyDeviceToDevice, s));
+// 5. Heavily skewed at two bytes.  Alphabet compaction: with <= 16 distinct bytes a key
+// byte holds 2, 4 or 8 symbols; if the two-byte buckets of THAT text are small enough the block still
+// takes the streaming stage (DNA: 8 symbols deep after two passes), else the 7-pass sort on packed keys.
+int Fwd::recode()
+{
+    if (path != Path::kSevenPass) return ARCHON_OK;
+    if (!have_lut) {
+        for (uint32_t v = 0; v < 256; ++v) {
+            lut[v] = (uint8_t)sigma;
+            if (hist[v]) ++sigma;
         }
-        e4 = e3;
+    }
+    bits = 1;
+    while ((1u << bits) < sigma) ++bits;
+    // (17 ... 32 distinct bytes -- lower-case prose -- still pack: five bits per symbol, eleven symbols in the seven key bytes instead of
+    //  seven; the streaming stage's key text holds whole symbols per byte and stops at 16)
+    if (sigma > kPackSigma || route_off(kRtNoPack)) return ARCHON_OK;
+    uint8_t *d_lut = reinterpret_cast<uint8_t *>(B.small + fwd_small::kLut);
+    static_assert(mail::kLut.len * 4 == sizeof lut, "the recode table's staging");
+    memcpy(c->h_mail + mail::kLut.at, lut, 256);
+    ARCHON_HIP_TRY(hipMemcpyAsync(d_lut, c->h_mail + mail::kLut.at, 256, hipMemcpyHostToDevice, s));
+    if (sigma >= 2 && sigma <= 16 && forced < 0 && !small_block && !route_off(kRtNoPackStream)) {
+        const int q = bits == 1 ? 8 : bits == 2 ? 4 : 2;
+        with_const<8, 4, 2>(q, [&](auto k) {
+            hipLaunchKernelGGL(HIP_KERNEL_NAME(bs::k_build_y<decltype(k)::value>), dim3(div_up(div_up(n, 16), 256)), dim3(256), 0, s, d_x, n, d_lut, B.y);
+        });
+        ++c->launches;
+        ARCHON_TRY(count16(q, B.y, false, false));
+        ARCHON_TRY(streaming(q, B.y));
+        if ((uint64_t)big_items * 2 <= n) {
+            path = Path::kStream;
+            Q = q;
+            alphabet_bits = 8 / q;
+        }
+    }
+    ARCHON_SYNC(s);          // the table upload has left mail::kLut, which the sorts below overwrite
+    return ARCHON_OK;
+}
+
+// entry of the general stage (k_first_groups): clean SA, group starts and the compacted working set in one sweep
+int Fwd::first_groups(int mode, const uint64_t *keys, const uint32_t *items, uint32_t shift)
+{
+    ARCHON_TRY(general_buffers());
+    unsigned long long *fg_status = reinterpret_cast<unsigned long long *>(B.sc.d_status);
+    const uint32_t tiles = div_up(n, fwd::kFgTile);
+    ARCHON_HIP_TRY(hipMemsetAsync(fg_status, 0, (size_t)tiles * sizeof(unsigned long long), s));
+    ARCHON_HIP_TRY(hipMemsetAsync(B.sc.d_ticket, 0, sizeof(uint32_t), s));
+    ARCHON_HIP_TRY(hipMemsetAsync(B.small + fwd_small::kFu, 0, 4 * sizeof(uint32_t), s));
+    const uint32_t ws_mode = ws_ready ? 2u : 0u;      // 2: the S / B lists of rounds.hiph
+    with_const<0, 1>(mode, [&](auto m) {
+        hipLaunchKernelGGL(HIP_KERNEL_NAME(fwd::k_first_groups<decltype(m)::value>), dim3(tiles), dim3(256), 0, s, keys, items, shift, n, sa, d_bwt, d_base, B.v,
+                           B.upos[0], B.ug[0], B.uitem[0], B.small + fwd_small::kTotal, fg_status, B.sc.d_ticket, B.sc.d_err, ws_mode, B.slist[0],
+                           B.small + fwd_small::kFu, (uint32_t)fwd::kFuMax);
+    });
+    ARCHON_HIP_TRY(hipGetLastError());
+    ++c->launches;
+    return ARCHON_OK;
+}
+
+// ---- first stage for heavily skewed blocks: LSB passes on packed 7-byte keys ----
+// alphabet compaction: with <= 16 distinct bytes the key holds 56/bits symbols
+int Fwd::seven_pass()
+{
+    const bool packed = sigma <= kPackSigma && !route_off(kRtNoPack);
+    static thread_local uint32_t hist_given[8 * 256];
+    bool use_given = false, shallow = false;
+    if (packed) {
+        h0 = 56 / bits;
+        ARCHON_HIP_TRY(hipMemsetAsync(B.sc.d_ghist, 0, 8 * 256 * sizeof(uint32_t), s));
+        const uint32_t want = div_up(div_up(n, 4), 256), cap = (uint32_t)kNumCU * 8;
+        hipLaunchKernelGGL(fwd::k_init_keys_packed, dim3(want < cap ? want : cap), dim3(256), 0, s, d_x, n, reinterpret_cast<const uint8_t *>(B.small + fwd_small::kLut),
+                           bits, h0, B.keyA, B.valA, B.sc.d_ghist);        // (... and the digit counts of the passes)
+        alphabet_bits = bits;
+        h0 = (8 * key_bytes) / bits;            // symbols the sorted key bytes hold
     } else {
-        // ---- first stage for heavily skewed blocks: LSB passes on packed 7-byte keys ----
-        // alphabet compaction: with <= 16 distinct bytes the key holds 56/bits symbols
-        const bool packed = sigma <= kPackSigma && !route_off(kRtNoPack);
-        static thread_local uint32_t hist_given[8 * 256];
-        bool use_given = false, shallow = false;
-        if (packed) {
-            h0 = 56 / bits;
-            ARCHON_HIP_TRY(hipMemsetAsync(B.sc.d_ghist, 0, 8 * 256 * sizeof(uint32_t), s));
-            {
-                const uint32_t want = div_up(div_up(n, 4), 256), cap = (uint32_t)kNumCU * 8;
-                hipLaunchKernelGGL(fwd::k_init_keys_packed, dim3(want < cap ? want : cap), dim3(256), 0, s, d_x, n, d_lut, bits, h0,
-                                   B.keyA, B.valA, B.sc.d_ghist);        // (... and the digit counts of the passes)
-            }
-            st.alphabet_bits = bits;
-            h0 = (8 * key_bytes) / bits;            // symbols the sorted key bytes hold
-        } else {
-            h0 = key_bytes;
+        h0 = key_bytes;
+        if (have_hist && n >= 8) {
             // Digit histograms without a sweep over the keys: key byte q (q = 1 is the top byte) of item s is x[s-q], or
             // 0xFF where s < q; over s = 1..n that is the byte histogram of x[0 .. n-q] plus q-1 pads.  The byte histogram
-            // of x came with the two-byte count (fetch_byte_counts); the last bytes of x are fetched here.
-            if (have_byte_counts && n >= 8) {
-                uint32_t H[256];
-                const uint32_t last_byte = *h_last & 0xFFu;
-                for (uint32_t v = 0; v < 256; ++v) H[v] = h_counts[v] - (v == 0xFFu ? 1u : 0u) + (v == last_byte ? 1u : 0u);
-                // How many key bytes?  Were the bytes independent, an item would share its first d bytes with n * (sum p^2)^d others: a
-                // block whose byte counts say "fewer than one in 32" at d < 7 (incompressible data: 4 bytes for 4 MiB) sorts on d bytes --
-                // 38 us per pass saved on a 4 MiB block -- and what stays tied goes to the rounds at depth d like any other tie.  Text
-                // (sum p^2 about 1/15) keeps its seven bytes -- its bytes are far from independent, so anything above 1/128 does.  An
-                // estimate only: the order never depends on it.
-                if (key_bytes == fwd::kKeyBytes && period_hint == 0 && !route_off(kRtNoShallow)) {
-                    double s2 = 0.0;
-                    for (uint32_t v = 0; v < 256; ++v) s2 += ((double)H[v] / n) * ((double)H[v] / n);
-                    double e = (double)n;
-                    for (uint32_t d = 1; d < fwd::kKeyBytes && s2 * 128.0 <= 1.0; ++d) {     // (nearly flat counts only: text is far from independent)
-                        e *= s2;
-                        if (d >= 3 && e * 32.0 <= 1.0) { key_bytes = d; shallow = true; break; }
-                    }
-                    h0 = key_bytes;
+            // of x came with the first look (take_byte_hist); the last bytes of x are fetched here.
+            // How many key bytes?  Were the bytes independent, an item would share its first d bytes with n * (sum p^2)^d others: a
+            // block whose byte counts say "fewer than one in 32" at d < 7 (incompressible data: 4 bytes for 4 MiB) sorts on d bytes --
+            // 38 us per pass saved on a 4 MiB block -- and what stays tied goes to the rounds at depth d like any other tie.  Text
+            // (sum p^2 about 1/15) keeps its seven bytes -- its bytes are far from independent, so anything above 1/128 does.  An
+            // estimate only: the order never depends on it.
+            if (key_bytes == fwd::kKeyBytes && period_hint == 0 && !route_off(kRtNoShallow)) {
+                double s2 = 0.0;
+                for (uint32_t v = 0; v < 256; ++v) s2 += ((double)hist[v] / n) * ((double)hist[v] / n);
+                double e = (double)n;
+                for (uint32_t d = 1; d < fwd::kKeyBytes && s2 * 128.0 <= 1.0; ++d) {     // (nearly flat counts only: text is far from independent)
+                    e *= s2;
+                    if (d >= 3 && e * 32.0 <= 1.0) { key_bytes = d; shallow = true; break; }
                 }
-                if (g_route.key_bytes >= 3 && g_route.key_bytes < (int)fwd::kKeyBytes && key_bytes == fwd::kKeyBytes && period_hint == 0) {
-                    key_bytes = (uint32_t)g_route.key_bytes;       // (tests / experiments: the order never depends on the depth)
-                    shallow = true;
-                    h0 = key_bytes;
-                }
-                if (!tail_fetched) {
-                    ARCHON_HIP_TRY(hipMemcpyAsync(c->h_mail + mail::kTail.at, d_x + (n - 8), 8, hipMemcpyDeviceToHost, s));
-                    ARCHON_SYNC(s);
-                }
-                const uint8_t *tail = reinterpret_cast<const uint8_t *>(c->h_mail + mail::kTail.at);      // x[n-8 .. n-1]
-                for (uint32_t q = 1; q <= 7; ++q) {
-                    uint32_t *hq = hist_given + (8 - q) * 256;                               // pass p = 8 - q sorts on key byte q
-                    memcpy(hq, H, sizeof H);
-                    for (uint32_t j = n - q + 1; j < n; ++j) --hq[tail[j - (n - 8)]];        // bytes past x[n-q] are no digit of depth q
-                    hq[0xFF] += q - 1;
-                }
-                use_given = true;
+                h0 = key_bytes;
             }
+            if (g_route.key_bytes >= 3 && g_route.key_bytes < (int)fwd::kKeyBytes && key_bytes == fwd::kKeyBytes && period_hint == 0) {
+                key_bytes = (uint32_t)g_route.key_bytes;       // (tests / experiments: the order never depends on the depth)
+                shallow = true;
+                h0 = key_bytes;
+            }
+            if (!tail_fetched) {
+                ARCHON_HIP_TRY(hipMemcpyAsync(c->h_mail + mail::kTail.at, d_x + (n - 8), 8, hipMemcpyDeviceToHost, s));
+                ARCHON_SYNC(s);
+            }
+            const uint8_t *tail = reinterpret_cast<const uint8_t *>(c->h_mail + mail::kTail.at);      // x[n-8 .. n-1]
+            for (uint32_t q = 1; q <= 7; ++q) {
+                uint32_t *hq = hist_given + (8 - q) * 256;                               // pass p = 8 - q sorts on key byte q
+                memcpy(hq, hist, sizeof hist);
+                for (uint32_t j = n - q + 1; j < n; ++j) --hq[tail[j - (n - 8)]];        // bytes past x[n-q] are no digit of depth q
+                hq[0xFF] += q - 1;
+            }
+            use_given = true;
         }
-        ARCHON_HIP_TRY(hipGetLastError());
-        c->launches += 2;
-        bool in_b = false;
-        const uint32_t pass_mask = (0xFFu << (8 - key_bytes)) & 0xFEu;          // the top key_bytes bytes; byte 0 is payload
-        // (plain bytes with the histograms in hand: the first pass that runs makes the pairs from the text itself)
-        const bool from_text = !packed && use_given;
-        if (!packed && !from_text)
-            hipLaunchKernelGGL(fwd::k_init_keys, dim3(div_up(div_up(n, 4), 256)), dim3(256), 0, s, d_x, n, B.keyA, B.valA);
-        ARCHON_TRY(rs::sort_pairs(s, B.sc, B.keyA, B.valA, B.keyB, B.valB, n, pass_mask, &in_b, &st.radix_passes, &c->launches, &pt,
-                                  use_given ? hist_given : nullptr, from_text ? d_x : nullptr, packed));
-        if (from_text && st.radix_passes == 0)          // every digit constant: no pass ran, the pairs still have to exist
-            hipLaunchKernelGGL(fwd::k_init_keys, dim3(div_up(div_up(n, 4), 256)), dim3(256), 0, s, d_x, n, B.keyA, B.valA);
-        uint64_t *kS = in_b ? B.keyB : B.keyA;
-        uint32_t *vS = in_b ? B.valB : B.valA;
-        e2 = tm.mark();
-        ws_ready = key_bytes == fwd::kKeyBytes || period_breaks != 0 || shallow;     // a clean periodic block: the run shortcut will empty the working set
-        ARCHON_TRY(first_groups(0, kS, vS, 8u * (8u - key_bytes), ws_ready));
-        e3 = e2;
     }
+    ARCHON_HIP_TRY(hipGetLastError());
+    c->launches += 2;
+    bool in_b = false;
+    const uint32_t pass_mask = (0xFFu << (8 - key_bytes)) & 0xFEu;          // the top key_bytes bytes; byte 0 is payload
+    // (plain bytes with the histograms in hand: the first pass that runs makes the pairs from the text itself)
+    const bool from_text = !packed && use_given;
+    if (!packed && !from_text)
+        hipLaunchKernelGGL(fwd::k_init_keys, dim3(div_up(div_up(n, 4), 256)), dim3(256), 0, s, d_x, n, B.keyA, B.valA);
+    ARCHON_TRY(rs::sort_pairs(s, B.sc, B.keyA, B.valA, B.keyB, B.valB, n, pass_mask, &in_b, &radix_passes, &c->launches, &pt,
+                              use_given ? hist_given : nullptr, from_text ? d_x : nullptr, packed));
+    if (from_text && radix_passes == 0)          // every digit constant: no pass ran, the pairs still have to exist
+        hipLaunchKernelGGL(fwd::k_init_keys, dim3(div_up(div_up(n, 4), 256)), dim3(256), 0, s, d_x, n, B.keyA, B.valA);
+    e_sorted = e_first = tm.mark();
+    ws_ready = key_bytes == fwd::kKeyBytes || period_breaks != 0 || shallow;     // a clean periodic block: the run shortcut will empty the working set
+    return first_groups(0, in_b ? B.keyB : B.keyA, in_b ? B.valB : B.valA, 8u * (8u - key_bytes));
+}
 
-    if (need_general) {
-        // deep ties: the streaming stage compared the tied groups 64 symbols deep and a good part of the block still agrees
-        // (when the tie list overflowed only a sample of it was compared -- bs::kTieSample groups: they stand for the rest)
-        const bool listed_all = h_ctl.tie_groups <= kTieListCap;
-        const bool deep_ties = path == 1 && big_items == 0 && h_ctl.min_depth >= 5 && !route_off(kRtNoDeepHint) &&
-                               (listed_all ? (uint64_t)h_ctl.unresolved * 64 >= n
-                                           : (uint64_t)h_ctl.unresolved * 2 >= bs::kTieSample && (uint64_t)h_ctl.tie_items * 64 >= n);
-        ARCHON_TRY(general_stage(c, s, B, d_x, n, sa, h0, d_bwt, d_base, st, period_hint, ws_ready, deep_ties, brk_ready, period_breaks));
-        e4 = tm.mark();
-        ARCHON_HIP_TRY(hipMemcpyAsync(d_base_out, d_base, sizeof(uint32_t), hipMemcpyDeviceToDevice, s));
+// 6. The first stage: the 7-pass sort, or what the streaming stage left -- nothing, or tied rows for the general stage
+int Fwd::first_stage()
+{
+    if (path == Path::kSevenPass) return seven_pass();
+    if (ctl.unresolved == 0 && ctl.tie_groups <= kTieListCap) {
+        if (ctl.base_id >= n) { set_error("primary index not found"); return ARCHON_E_INTERNAL; }
+        stream_done = true;                 // (the primary index and the consistency flag came with the summary)
+        return ARCHON_OK;
     }
-    int e5 = e3;
-    uint32_t dev_err;
-    if (stream_done) {
-        dev_err = c->h_mail[mail::kFlag.at];
+    h0 = (ctl.min_depth < 5 ? ctl.min_depth : 5) * (uint32_t)Q;     // key bytes -> symbols
+    ws_ready = period_hint == 0 || period_breaks != 0;
+    ARCHON_TRY(first_groups(1, nullptr, nullptr, 0));
+    ARCHON_HIP_TRY(hipMemcpyAsync(d_base, &d_ctl->base_id, sizeof(uint32_t), hipMemcpyDeviceToDevice, s));
+    return ARCHON_OK;
+}
+
+// 7. The general stage, for whatever the first stage left tied
+int Fwd::tied_rows()
+{
+    if (stream_done) return ARCHON_OK;
+    // deep ties: the streaming stage compared the tied groups 64 symbols deep and a good part of the block still agrees
+    // (when the tie list overflowed only a sample of it was compared -- bs::kTieSample groups: they stand for the rest)
+    const bool listed_all = ctl.tie_groups <= kTieListCap;
+    deep_ties = path == Path::kStream && big_items == 0 && ctl.min_depth >= 5 && !route_off(kRtNoDeepHint) &&
+                (listed_all ? (uint64_t)ctl.unresolved * 64 >= n
+                            : (uint64_t)ctl.unresolved * 2 >= bs::kTieSample && (uint64_t)ctl.tie_items * 64 >= n);
+    ARCHON_TRY(general_stage());
+    e_general = tm.mark();
+    ARCHON_HIP_TRY(hipMemcpyAsync(d_base_out, d_base, sizeof(uint32_t), hipMemcpyDeviceToDevice, s));
+    return ARCHON_OK;
+}
+
+// 8. The device's consistency flag -- it came with the streaming stage's summary, or it is read now -- and the statistics of
+// every route (the general stage and the 7-pass sort count theirs as they go).  A stage that did not run left its marks at
+// -1, which StageTimer::ms reads as 0.
+int Fwd::finish()
+{
+    archon_hip_stats &st = c->stats;
+    if (path == Path::kClosed) {          // (the nested transform of the 2p-byte block left its own statistics here, and read its own flag)
+        memset(&st, 0, sizeof st);
+        st.n = n;
+        st.period = closed_period;
+        st.chain_items = n;
     } else {
-        e5 = tm.mark();
-        ARCHON_HIP_TRY(hipMemcpyAsync(c->h_mail + mail::kRead.at, B.sc.d_err, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
-        ARCHON_SYNC(s);
-        dev_err = c->h_mail[mail::kRead.at];
+        uint32_t dev_err;
+        if (stream_done) {
+            e_end = e_first;
+            dev_err = c->h_mail[mail::kFlag.at];
+        } else {
+            e_end = tm.mark();
+            ARCHON_HIP_TRY(hipMemcpyAsync(c->h_mail + mail::kRead.at, B.sc.d_err, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+            ARCHON_SYNC(s);
+            dev_err = c->h_mail[mail::kRead.at];
+        }
+        if (dev_err) { set_error("device consistency flag 0x%x (look-back spin bound)", dev_err); return ARCHON_E_INTERNAL; }
     }
-    if (dev_err) {
-        set_error("device consistency flag 0x%x (look-back spin bound)", dev_err);
-        return ARCHON_E_INTERNAL;
-    }
-    st.ms_hist = tm.ms(e0, e1);
-    st.ms_sort = tm.ms(e1, e2);
-    st.ms_doubling = need_general ? tm.ms(e3, e4) : 0.f;
-    st.ms_bwt = need_general ? tm.ms(e4, e5) : 0.f;
-    st.ms_total = tm.ms(e0, e5);
+    st.path = (uint32_t)path;
+    st.arena_bytes = arena_bytes;
+    st.alphabet_bits = alphabet_bits;
+    st.radix_passes = path == Path::kStream ? 2u : radix_passes;
     st.kernel_launches = c->launches;
     st.host_syncs = t_sync_count;
+    st.ms_hist = tm.ms(e_start, e_count);
+    st.ms_sort = tm.ms(e_count, e_sorted);
+    st.ms_doubling = tm.ms(e_first, e_general);
+    st.ms_bwt = tm.ms(e_general, e_end);
+    st.ms_total = tm.ms(e_start, e_end);
     for (int i = 0; i + 1 < pt.n; i += 2) {      // 7-pass route: rs::sort_pairs brackets each pass
         st.ms_radix_pass_sum += pt.ms(i, i + 1);
         ++st.radix_pass_timed;
     }
-    if (path == 1) {
+    if (path == Path::kStream) {
+        st.tie_groups = ctl.tie_groups;
+        st.tie_items = ctl.tie_items;
+        st.ms_local_sort = tm.ms(e_sorted, e_local);
+        st.ms_resolve = tm.ms(e_local, e_first);
         st.ms_pass_text = ps.ms(iA0, iA1);
         st.ms_pass_rec = ps.ms(iB0, iB1);
         st.ms_radix_pass_sum = st.ms_pass_text + st.ms_pass_rec;
         st.radix_pass_timed = 2;
     }
-    ARCHON_HOST_STAMP(4);
+    return ARCHON_OK;
+}
+
+// One forward transform.  depth: 0 = a caller's block, 1 = the 2p-byte block of a clean periodic block's closed form
+// (periodic.hiph): its own event banks, no closed form of its own
+static int forward_run(Ctx *c, hipStream_t s, const uint8_t *d_x_in, uint32_t n, uint32_t *d_sa_user, uint8_t *d_bwt, uint32_t *d_base_out, int depth = 0)
+{
+    Fwd f{c, s, n, depth, d_x_in, d_sa_user, d_bwt, d_base_out};
+    ARCHON_TRY(f.setup());
+    ARCHON_TRY(f.first_look());
+    if (f.closed) {
+        ARCHON_TRY(f.closed_form());
+    } else {
+        ARCHON_TRY(f.alphabet());
+        ARCHON_TRY(f.period());
+        ARCHON_TRY(f.recode());
+        ARCHON_TRY(f.first_stage());
+        ARCHON_TRY(f.tied_rows());
+    }
+    ARCHON_TRY(f.finish());
+    f.stamp(4);
 #ifdef ARCHON_EXPERIMENTS
-    if (trace_host) {
+    if (f.trace_host) {
         auto us = [&](int a, int b) { return std::chrono::duration<double, std::micro>(t_host[b] - t_host[a]).count(); };
         fprintf(stderr, "host phases: entry->first launch %.1f us, queue the rest %.1f us, wait %.1f us, statistics %.1f us (device %.1f us)\n",
-                us(0, 1), us(1, 2), us(2, 3), us(3, 4), st.ms_total * 1e3);
+                us(0, 1), us(1, 2), us(2, 3), us(3, 4), c->stats.ms_total * 1e3);
     }
 #endif
     return ARCHON_OK;
