@@ -21,12 +21,18 @@ config.blocks_in_flight): two feeder threads, each bound to its own compute cont
 (include/archon_hip.h: "two threads feeding one GPU"), take the K steps in turn -- every step is
 still one whole forward pass over one block, and the timed region is still exactly K of them; for
 N>1 a feeder hands its step to the gather pipe only when every earlier step has been handed over
-(the collectives leave every rank in step order).  The same K steps then run once more one block
-at a time ("one_block_at_a_time"), and the per-kernel times of `roofline` are taken there (a
-kernel's elapsed time beside another block's kernels is not its own).  --in-flight 1 is the run
-of the earlier rounds.
+(the collectives leave every rank in step order).  --in-flight 1 is the run of the earlier rounds.
 
-Rank 0 prints ONE JSON line with the contract fields plus
+A plain run does only what the headline needs: it sets up, warms up, times the K steps, writes
+--dump-outputs if asked, and rank 0 prints ONE JSON line with the contract fields and `config`.
+Everything else the benchmark measures or checks runs with --full, behind the timed region:
+  one_block_at_a_time  the same K steps once more one block at a time; the per-kernel times of
+                `roofline` and `pipeline` are taken there (a kernel's elapsed time beside another
+                block's kernels is not its own)
+  gates         config.sa_sha256_matches_reference (every rank's SA and BWT||baseId against the
+                reference's digests), config.sa_lf_consistent (LF consistency on the device),
+                config.gathered_block_round_trip (N>1: the block gathered from the last rank
+                decoded again), config.gates_passed; exit code 1 on a miss
   roofline      the dominant kernel = whichever of the three streaming kernels (LSB pass A, LSB
                 pass B, in-LDS bucket sort) ran longest: algorithmic bytes per launch (5 / 9 / 13 B
                 x N, SURVEY.md 8(d) and DESIGN.md 4) / its mean launch time, taken live from HIP
@@ -35,7 +41,8 @@ Rank 0 prints ONE JSON line with the contract fields plus
                 "traffic" = HBM bytes per launch from the committed rocprofv3 PMC passes
                 (the newest profiles/rNN_final/pmc_traffic.json, named in "traffic_source"),
                 null when no matching measurement is committed
-  cpu_baseline  the reference a7 (oracle/_ref/a7ref, built from /root/reference by
+  pipeline      device time per block and per stage, arena use, the host side of a step
+  cpu_baseline  the reference a7 (oracle/_ref/a7ref, built from the reference's sources by
                 oracle/Makefile; kind "reference") or, when that binary is absent, the
                 repo's CPU oracle (kind "port"): single thread, taskset-pinned to one core,
                 the WHOLE block of the metric (one stated run, about half a minute;
@@ -157,6 +164,74 @@ def pmc_traffic(path, n, shape, kname):
         except Exception:
             continue
     return None, None
+
+
+def stage_figures(stage, pass_ms, pass_cnt, host_trace, n, shape, steps, in_flight):
+    """`roofline` and `pipeline` of the --full line, from the per-step statistics of the steps that ran one block at a time."""
+    last = stage[-1]
+    kernels = None
+    if last["path"] == 1:
+        # streaming first stage: three kernels carry the step; the dominant one is whichever ran longest (measured
+        # live, HIP events around each launch).  Algorithmic bytes per item (DESIGN.md 4): pass A 5 and pass B 9 are
+        # SURVEY.md 8(d)'s LSB-pass figures; the in-LDS bucket sort must read one 8-byte record and write 4 (SA) + 1
+        # (BWT) bytes per item = 13 (in 8(d)'s pass-by-pass model it stands for passes 3..6 and sa_to_bwt, 42 B --
+        # NOT used here: the fraction below prices only bytes the kernel itself has to move).
+        spec = [("bs::k_pass_text (LSB pass A: text -> 8-byte records, 256-way by x[s-2])", "ms_pass_text", B_FIRST_PASS),
+                ("bs::k_pass_rec (LSB pass B: records 256-way by x[s-1])", "ms_pass_rec", B_RADIX_PASS),
+                ("bs::k_local_sort (in-LDS sort of a 16-bit bucket, SA + BWT out)", "ms_local_sort", B_LOCAL_SORT)]
+        kernels = []
+        for nm, key, bpi in spec:
+            t = float(np.mean([s[key] for s in stage]))
+            gbs = bpi * n / (t * 1e-3) / 1e9 if t > 0 else 0.0
+            kernels.append({"kernel": nm, "launch_ms": round(t, 4), "algorithmic_bytes_per_item": bpi,
+                            "achieved_GBps": round(gbs, 1), "frac": round(gbs / HBM_PEAK_GBS, 4)})
+        dom = max(kernels, key=lambda k: k["launch_ms"])
+        t_pass_ms, kname, bpi_dom, per_step = dom["launch_ms"], dom["kernel"], dom["algorithmic_bytes_per_item"], 1
+    else:
+        npass = max(1, sum(pass_cnt))
+        t_pass_ms = sum(pass_ms) / npass
+        kname = "rs::k_scatter (one LSB radix pass over %d (key,index) pairs)" % n
+        per_step = last["radix_pass_timed"]
+        bpi_dom = B_RADIX_PASS
+    achieved = bpi_dom * n / (t_pass_ms * 1e-3) / 1e9 if t_pass_ms > 0 else 0.0
+    traffic, traffic_src = pmc_traffic(last["path"], n, shape, kname)
+    dev_ms = float(np.mean([s["ms_total"] for s in stage]))
+    return {
+        "roofline": {
+            "bound": "hbm",
+            "kernel": kname,
+            "achieved": round(achieved, 1),
+            "peak": HBM_PEAK_GBS,
+            "unit": "GB/s",
+            "frac": round(achieved / HBM_PEAK_GBS, 4),
+            "traffic": traffic,
+            "traffic_source": traffic_src,
+            "launch_ms": round(t_pass_ms, 4),
+            "launches_per_step": per_step,
+            "algorithmic_bytes_per_launch": bpi_dom * n,
+            "kernels": kernels,
+            "measured_over": ("the %d steps run one block at a time behind the timed region (HIP events around each launch); with %d blocks "
+                              "in flight a kernel's elapsed time includes the other block's kernels" % (steps, in_flight)) if in_flight > 1
+                             else "the timed region (HIP events around each launch)",
+        },
+        "pipeline": {
+            "device_ms_per_block": round(dev_ms, 3),           # one block alone on the chip
+            "algorithmic_bytes_per_input_byte": B_FWD_CFG2,
+            "frac_of_hbm_roofline": round(B_FWD_CFG2 * n / (dev_ms * 1e-3) / 1e9 / HBM_PEAK_GBS, 4) if dev_ms > 0 else None,
+            "path": PATH_NAMES.get(last["path"], str(last["path"])),
+            "ms_hist": round(last["ms_hist"], 3), "ms_sort": round(last["ms_sort"], 3),
+            "ms_pass_text": round(last["ms_pass_text"], 3), "ms_pass_rec": round(last["ms_pass_rec"], 3),
+            "ms_local_sort": round(last["ms_local_sort"], 3), "ms_resolve": round(last["ms_resolve"], 3),
+            "ms_doubling": round(last["ms_doubling"], 3), "ms_bwt": round(last["ms_bwt"], 3),
+            # host side of a step, mean microseconds: waiting for the payload buffer's previous gather, the forward call
+            # (device pipeline + its one host round trip), statistics + handing the gather to the helper thread
+            "host_us_buffer_forward_submit": [round(1e6 * float(np.mean([h[i] for h in host_trace])), 1) for i in range(3)],
+            "arena_bytes_per_input_byte": round(last["arena_bytes"] / n, 2),
+            "tie_groups_after_5_bytes": last["tie_groups"],
+            "radix_passes": last["radix_passes"], "doubling_rounds": last["doubling_rounds"],
+            "unresolved_initial": last["unresolved_initial"], "kernel_launches": last["kernel_launches"],
+        },
+    }
 
 
 DUMP_SAMPLE = 1 << 20          # --dump-outputs: positions drawn for the fixed sample of SA and BWT
@@ -320,9 +395,12 @@ def main():
     ap.add_argument("--warmup", type=int, default=3)       # (the first steps behind a cold start run 4 % slower: clocks, first touch of the arena)
     ap.add_argument("--block-mib", type=int, default=256, help="block size per GPU (BASELINE config: 256)")
     ap.add_argument("--shape", default="random", help="random|dna|text|a|ab|motif (graded config: random)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true", help="behind the timed region, also run what the headline does not need: the steps "
+                    "one block at a time, roofline and pipeline figures, the correctness gates and, at N=1, the inverse, the other "
+                    "shapes and the CPU baseline (a plain run prints the contract fields and config alone)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
     ap.add_argument("--cpu-sample-mib", type=int, default=1 << 20, help="bound the CPU baseline to the first so many MiB of the block (default: the whole block)")
-    ap.add_argument("--no-shapes", action="store_true", help="skip the other named shapes and the inverse behind the timed region (N=1 runs them by default)")
+    ap.add_argument("--no-shapes", action="store_true", help="with --full: skip the other named shapes and the inverse behind the timed region (N=1 runs them by default)")
     ap.add_argument("--no-sa", action="store_true", help="emit BWT only (the metric is quoted WITH the SA)")
     ap.add_argument("--in-flight", type=int, default=0, help="blocks in flight per GPU: F host threads, each bound to its own compute context "
                     "of the library (include/archon_hip.h: 'two threads feeding one GPU'), take the steps in turn (step k -> thread k mod F). "
@@ -465,27 +543,28 @@ def main():
             dumped = last_step_outputs(sa_f[(args.steps - 1) % in_flight], pipe.last()[0], n)
         stage_flight = [s.asdict() for lst in stage_f for s in lst]
         feeders.close()
-        # every feeder's last block against the reference's digests (the one-at-a-time region's goes through the ordinary gate below)
         flight_ok = True
-        ref_f = reference_digest(args.shape, my_block, n)
-        pipe.drain()
-        for back in range(min(in_flight, args.steps)):
-            if ref_f is not None:
-                flight_ok = flight_ok and sha256_of(pipe.outs[(pipe.step_no - 1 - back) % pipe.nbuf].cpu().numpy()) == ref_f["sha256_bwt_base"]
-        for t in range(1, in_flight):
-            if ref_f is not None and sa_f[t] is not None and stage_f[t]:
-                flight_ok = flight_ok and sha256_of(sa_f[t].cpu().numpy()) == ref_f["sha256_P"]
-        # ... and the same K steps one block at a time (the calling thread: context 0 again), for the kernels' own times
-        for _ in range(2):
-            step()
-        del stage[:], host_trace[:]
-        fence()
-        t1 = time.perf_counter()
-        for _ in range(args.steps):
-            step()
-        fence()
-        dt_alone = time.perf_counter() - t1
-        alone = {"ms_per_step": round(dt_alone * 1e3 / args.steps, 3), "MB_s": round(float(n) * args.steps / 1e6 / dt_alone, 1), "steps": args.steps}
+        if args.full:
+            # every feeder's last block against the reference's digests (the one-at-a-time region's goes through the ordinary gate below)
+            ref_f = reference_digest(args.shape, my_block, n)
+            pipe.drain()
+            for back in range(min(in_flight, args.steps)):
+                if ref_f is not None:
+                    flight_ok = flight_ok and sha256_of(pipe.outs[(pipe.step_no - 1 - back) % pipe.nbuf].cpu().numpy()) == ref_f["sha256_bwt_base"]
+            for t in range(1, in_flight):
+                if ref_f is not None and sa_f[t] is not None and stage_f[t]:
+                    flight_ok = flight_ok and sha256_of(sa_f[t].cpu().numpy()) == ref_f["sha256_P"]
+            # ... and the same K steps one block at a time (the calling thread: context 0 again), for the kernels' own times
+            for _ in range(2):
+                step()
+            del stage[:], host_trace[:]
+            fence()
+            t1 = time.perf_counter()
+            for _ in range(args.steps):
+                step()
+            fence()
+            dt_alone = time.perf_counter() - t1
+            alone = {"ms_per_step": round(dt_alone * 1e3 / args.steps, 3), "MB_s": round(float(n) * args.steps / 1e6 / dt_alone, 1), "steps": args.steps}
     else:
         flight_ok = True
         for _ in range(args.warmup):
@@ -507,76 +586,47 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = float(t.item())
 
-    # correctness gates on the timed output (after the timed region):
-    #  (1) the rank's SA and BWT||baseId hashed against what THE REFERENCE produced for the same block
-    #      (golden_full.json; every rank checks its own block), (2) LF-consistency of the SA on the device
     ok = flight_ok
-    sha_ok = None
-    ref = reference_digest(args.shape, my_block, n)
+    sha_ok = lf_ok = gathered_ok = None
     own_last, gathered_last = pipe.last()
-    if ref is not None:
-        sha_ok = sha256_of(own_last.cpu().numpy()) == ref["sha256_bwt_base"]
+    if args.full:
+        # correctness gates on the timed output (after the timed region):
+        #  (1) the rank's SA and BWT||baseId hashed against what THE REFERENCE produced for the same block
+        #      (golden_full.json; every rank checks its own block), (2) LF-consistency of the SA on the device
+        ref = reference_digest(args.shape, my_block, n)
+        if ref is not None:
+            sha_ok = sha256_of(own_last.cpu().numpy()) == ref["sha256_bwt_base"]
+            if sa_t is not None:
+                sha_ok = sha_ok and sha256_of(sa_t.cpu().numpy()) == ref["sha256_P"]
+            ok = ok and sha_ok
         if sa_t is not None:
-            sha_ok = sha_ok and sha256_of(sa_t.cpu().numpy()) == ref["sha256_P"]
-        ok = ok and sha_ok
-    lf_ok = None
-    if sa_t is not None:
-        lf_ok = pyarchon.validate_dev(x_t, sa_t)
-        ok = lf_ok and ok
-    # the exchange step: rank 0 decodes the block it received from the LAST rank (inverse BWT on its own GPU)
-    # and compares with that rank's input, regenerated from the seed -- after the timed region
-    gathered_ok = None
-    last_root = pipe.last_root()
-    if dist is not None and rank == last_root:
-        got = gathered_last[world - 1].to(dev)
-        base_r = int(got[n:].view(torch.int32).item())
-        back = torch.empty(n, dtype=torch.uint8, device=dev)
-        pyarchon.inverse_dev(got[:n], base_r, back)
-        want = torch.from_numpy(archon_synth.gen_shape(args.shape, n, block=archon_shard.blocks_of(world - 1, world, world)[0])).to(dev)
-        gathered_ok = bool(torch.equal(back, want))
-        ok = ok and gathered_ok
-    if dist is not None:
-        # (the gathered block is decoded on the rank that was the root of the LAST step: its verdict travels with the flags)
-        flag = torch.tensor([1 if ok else 0, 0 if sha_ok is False else 1, 0 if sha_ok is None else 1, 0 if lf_ok is False else 1,
-                             0 if gathered_ok is False else 1], device=gdev)
-        dist.all_reduce(flag, op=dist.ReduceOp.MIN)
-        ok = bool(flag[0].item())
-        lf_ok = None if lf_ok is None else bool(flag[3].item())
-        gathered_ok = bool(flag[4].item())
-        sha_ok = bool(flag[1].item()) if flag[2].item() else None      # true only if EVERY rank had a digest and matched it
+            lf_ok = pyarchon.validate_dev(x_t, sa_t)
+            ok = lf_ok and ok
+        # the exchange step: rank 0 decodes the block it received from the LAST rank (inverse BWT on its own GPU)
+        # and compares with that rank's input, regenerated from the seed -- after the timed region
+        last_root = pipe.last_root()
+        if dist is not None and rank == last_root:
+            got = gathered_last[world - 1].to(dev)
+            base_r = int(got[n:].view(torch.int32).item())
+            back = torch.empty(n, dtype=torch.uint8, device=dev)
+            pyarchon.inverse_dev(got[:n], base_r, back)
+            want = torch.from_numpy(archon_synth.gen_shape(args.shape, n, block=archon_shard.blocks_of(world - 1, world, world)[0])).to(dev)
+            gathered_ok = bool(torch.equal(back, want))
+            ok = ok and gathered_ok
+        if dist is not None:
+            # (the gathered block is decoded on the rank that was the root of the LAST step: its verdict travels with the flags)
+            flag = torch.tensor([1 if ok else 0, 0 if sha_ok is False else 1, 0 if sha_ok is None else 1, 0 if lf_ok is False else 1,
+                                 0 if gathered_ok is False else 1], device=gdev)
+            dist.all_reduce(flag, op=dist.ReduceOp.MIN)
+            ok = bool(flag[0].item())
+            lf_ok = None if lf_ok is None else bool(flag[3].item())
+            gathered_ok = bool(flag[4].item())
+            sha_ok = bool(flag[1].item()) if flag[2].item() else None      # true only if EVERY rank had a digest and matched it
 
     if rank == 0:
         ms_per_step = dt * 1e3 / args.steps
         total_bytes = float(n) * world * args.steps
         value = total_bytes / 1e6 / dt
-        last = stage[-1]
-        kernels = None
-        if last["path"] == 1:
-            # streaming first stage: three kernels carry the step; the dominant one is whichever ran longest (measured
-            # live, HIP events around each launch).  Algorithmic bytes per item: pass A 5 and pass B 9 are
-            # SURVEY.md 8(d)'s LSB-pass figures; the in-LDS bucket sort must read one 8-byte record and write 4 (SA) + 1
-            # (BWT) bytes per item = 13 (in 8(d)'s pass-by-pass model it stands for passes 3..6 and sa_to_bwt, 42 B --
-            # NOT used here: the fraction below prices only bytes the kernel itself has to move).
-            spec = [("bs::k_pass_text (LSB pass A: text -> 8-byte records, 256-way by x[s-2])", "ms_pass_text", B_FIRST_PASS),
-                    ("bs::k_pass_rec (LSB pass B: records 256-way by x[s-1])", "ms_pass_rec", B_RADIX_PASS),
-                    ("bs::k_local_sort (in-LDS sort of a 16-bit bucket, SA + BWT out)", "ms_local_sort", B_LOCAL_SORT)]
-            kernels = []
-            for nm, key, bpi in spec:
-                t = float(np.mean([s[key] for s in stage]))
-                gbs = bpi * n / (t * 1e-3) / 1e9 if t > 0 else 0.0
-                kernels.append({"kernel": nm, "launch_ms": round(t, 4), "algorithmic_bytes_per_item": bpi,
-                                "achieved_GBps": round(gbs, 1), "frac": round(gbs / HBM_PEAK_GBS, 4)})
-            dom = max(kernels, key=lambda k: k["launch_ms"])
-            t_pass_ms, kname, bpi_dom, per_step = dom["launch_ms"], dom["kernel"], dom["algorithmic_bytes_per_item"], 1
-        else:
-            npass = max(1, sum(pass_cnt))
-            t_pass_ms = sum(pass_ms) / npass
-            kname = "rs::k_scatter (one LSB radix pass over %d (key,index) pairs)" % n
-            per_step = last["radix_pass_timed"]
-            bpi_dom = B_RADIX_PASS
-        achieved = bpi_dom * n / (t_pass_ms * 1e-3) / 1e9 if t_pass_ms > 0 else 0.0
-        traffic, traffic_src = pmc_traffic(last["path"], n, args.shape, kname)
-        dev_ms = float(np.mean([s["ms_total"] for s in stage]))
         line = {
             "metric": "forward-BWT MB/s on 256 MB block (SA bit-exact vs a7 order)",
             "value": round(value, 1),
@@ -597,10 +647,6 @@ def main():
                 "blocks_per_step": world,
                 "parallelism": "block-sharded x%d, one RCCL gather of BWT||baseId per step (async, overlapped with the next steps)" % world if world > 1 else "single GPU",
                 "sa_emitted": sa_t is not None,
-                "sa_lf_consistent": lf_ok,
-                "sa_sha256_matches_reference": sha_ok,     # null: no reference digest committed for this shape / size
-                "gates_passed": ok,                        # reference digests + LF-consistency (+ gathered round trip)
-                "gathered_block_round_trip": gathered_ok,
                 "pass_ranges": pass_ranges or 256,
                 "blocks_in_flight": in_flight,     # F feeder threads, one compute context each; a step is still one whole block
                 "backend": (dist.get_backend() if dist is not None else None),
@@ -610,63 +656,37 @@ def main():
                               "collective; %d bytes per rank and step" % (world, world, n + 4)) if pipe.batched else
                              ("torch.distributed.gather (RCCL grouped send/recv) of %d bytes per rank per step, root %s" % (n + 4, "k mod N at step k" if args.gather_root == "rotate" else "0"))) if dist is not None else None,
             },
-            "roofline": {
-                "bound": "hbm",
-                "kernel": kname,
-                "achieved": round(achieved, 1),
-                "peak": HBM_PEAK_GBS,
-                "unit": "GB/s",
-                "frac": round(achieved / HBM_PEAK_GBS, 4),
-                "traffic": traffic,
-                "traffic_source": traffic_src,
-                "launch_ms": round(t_pass_ms, 4),
-                "launches_per_step": per_step,
-                "algorithmic_bytes_per_launch": bpi_dom * n,
-                "kernels": kernels,
-                "measured_over": ("the %d steps run one block at a time behind the timed region (HIP events around each launch); with %d blocks "
-                                  "in flight a kernel's elapsed time includes the other block's kernels" % (args.steps, in_flight)) if in_flight > 1
-                                 else "the timed region (HIP events around each launch)",
-            },
-            "pipeline": {
-                "device_ms_per_block": round(dev_ms, 3),           # one block alone on the chip
-                "algorithmic_bytes_per_input_byte": B_FWD_CFG2,
-                "frac_of_hbm_roofline": round(B_FWD_CFG2 * n / (dev_ms * 1e-3) / 1e9 / HBM_PEAK_GBS, 4) if dev_ms > 0 else None,
-                "path": PATH_NAMES.get(last["path"], str(last["path"])),
-                "ms_hist": round(last["ms_hist"], 3), "ms_sort": round(last["ms_sort"], 3),
-                "ms_pass_text": round(last["ms_pass_text"], 3), "ms_pass_rec": round(last["ms_pass_rec"], 3),
-                "ms_local_sort": round(last["ms_local_sort"], 3), "ms_resolve": round(last["ms_resolve"], 3),
-                "ms_doubling": round(last["ms_doubling"], 3), "ms_bwt": round(last["ms_bwt"], 3),
-                # host side of a step, mean microseconds: waiting for the payload buffer's previous gather, the forward call
-                # (device pipeline + its one host round trip), statistics + handing the gather to the helper thread
-                "host_us_buffer_forward_submit": [round(1e6 * float(np.mean([h[i] for h in host_trace])), 1) for i in range(3)],
-                "arena_bytes_per_input_byte": round(last["arena_bytes"] / n, 2),
-                "tie_groups_after_5_bytes": last["tie_groups"],
-                "radix_passes": last["radix_passes"], "doubling_rounds": last["doubling_rounds"],
-                "unresolved_initial": last["unresolved_initial"], "kernel_launches": last["kernel_launches"],
-            },
         }
-        if alone is not None:
-            # the timed region's own fraction: 57 B x N / (wall time per block) / 8 TB/s; and the one-block-at-a-time region
-            line["pipeline"]["frac_of_hbm_roofline_in_flight"] = round(B_FWD_CFG2 * n / (ms_per_step * 1e-3) / 1e9 / HBM_PEAK_GBS, 4)
-            line["pipeline"]["device_ms_per_block_in_flight"] = round(float(np.mean([s["ms_total"] for s in stage_flight])), 3)
-            line["one_block_at_a_time"] = alone
-        if world == 1 and dist is None and not args.no_shapes:
-            # behind the timed region: the other named shapes at this block size and the inverse of the graded block, each gated
-            inv, inv_ok = inverse_leg(own_last[:n], int(own_last[n:].view(torch.int32).item()), x_t)
-            line["inverse"] = inv
-            shapes, shapes_ok = extra_shapes(n, dev, [sh for sh in EXTRA_SHAPES if sh != args.shape])
-            line["shapes"] = shapes
-            ok = ok and inv_ok and shapes_ok
-            line["config"]["gates_passed"] = ok
-        if world == 1 and not args.no_cpu_baseline:
-            line["cpu_baseline"] = cpu_baseline(n, args.cpu_sample_mib)
-            # informational, NOT measured on this host and never part of cpu_baseline / vs_baseline: a7 slows down with the block
-            # size; what it took on the WHOLE block of the metric when the reference digests were made (development container)
-            full = reference_digest("random", 0, n)
-            if full is not None and full.get("reference_sa_time_s"):
-                line["reference_elsewhere"] = {"what": "reference a7 on the whole %d MiB block, 1 core" % (n >> 20), "unit": "MB/s",
-                                               "value": round(n / 1e6 / full["reference_sa_time_s"], 3), "seconds": round(full["reference_sa_time_s"], 1),
-                                               "host": "development container, recorded in tests/golden/golden_full.json -- not this machine"}
+        if args.full:
+            line["config"].update({
+                "sa_lf_consistent": lf_ok,
+                "sa_sha256_matches_reference": sha_ok,     # null: no reference digest committed for this shape / size
+                "gates_passed": ok,                        # reference digests + LF-consistency (+ gathered round trip)
+                "gathered_block_round_trip": gathered_ok,
+            })
+            line.update(stage_figures(stage, pass_ms, pass_cnt, host_trace, n, args.shape, args.steps, in_flight))
+            if alone is not None:
+                # the timed region's own fraction: 57 B x N / (wall time per block) / 8 TB/s; and the one-block-at-a-time region
+                line["pipeline"]["frac_of_hbm_roofline_in_flight"] = round(B_FWD_CFG2 * n / (ms_per_step * 1e-3) / 1e9 / HBM_PEAK_GBS, 4)
+                line["pipeline"]["device_ms_per_block_in_flight"] = round(float(np.mean([s["ms_total"] for s in stage_flight])), 3)
+                line["one_block_at_a_time"] = alone
+            if world == 1 and dist is None and not args.no_shapes:
+                # behind the timed region: the other named shapes at this block size and the inverse of the graded block, each gated
+                inv, inv_ok = inverse_leg(own_last[:n], int(own_last[n:].view(torch.int32).item()), x_t)
+                line["inverse"] = inv
+                shapes, shapes_ok = extra_shapes(n, dev, [sh for sh in EXTRA_SHAPES if sh != args.shape])
+                line["shapes"] = shapes
+                ok = ok and inv_ok and shapes_ok
+                line["config"]["gates_passed"] = ok
+            if world == 1 and not args.no_cpu_baseline:
+                line["cpu_baseline"] = cpu_baseline(n, args.cpu_sample_mib)
+                # informational, NOT measured on this host and never part of cpu_baseline / vs_baseline: a7 slows down with the block
+                # size; what it took on the WHOLE block of the metric when the reference digests were made (development container)
+                whole = reference_digest("random", 0, n)
+                if whole is not None and whole.get("reference_sa_time_s"):
+                    line["reference_elsewhere"] = {"what": "reference a7 on the whole %d MiB block, 1 core" % (n >> 20), "unit": "MB/s",
+                                                   "value": round(n / 1e6 / whole["reference_sa_time_s"], 3), "seconds": round(whole["reference_sa_time_s"], 1),
+                                                   "host": "development container, recorded in tests/golden/golden_full.json -- not this machine"}
         if args.dump_outputs:
             dump_outputs(args.dump_outputs, dumped)
         print(json.dumps(line), flush=True)

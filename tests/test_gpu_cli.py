@@ -131,11 +131,12 @@ def test_container_rejects_plain_file(archon, tmp_path):
     assert r.returncode != 0
 
 
-@pytest.mark.parametrize("ranks,steps,extra", [(2, 2, []), (2, 5, ["--gather-batch", "1"]), (3, 7, []), (2, 5, ["--in-flight", "1"])])
+@pytest.mark.parametrize("ranks,steps,extra", [(2, 2, ["--full"]), (2, 5, ["--full", "--gather-batch", "1"]), (3, 7, ["--full"]),
+                                               (2, 5, ["--full", "--in-flight", "1"]), (2, 3, [])])
 def test_bench_two_rank_rehearsal(ranks, steps, extra):
     """bench.py's N>1 control flow (the rotated gathers of N steps as one exchange -- full batches and the part of one a fence finds --,
-    or one gather per step; barriers, max-over-ranks clock, decode of the block gathered from the last rank) with 2 or 3 ranks
-    sharing this one GPU over gloo.  Not a measurement."""
+    or one gather per step; barriers, max-over-ranks clock, with --full the decode of the block gathered from the last rank) with 2
+    or 3 ranks sharing this one GPU over gloo; without --full the line holds the headline and config alone.  Not a measurement."""
     import json
     import subprocess
     import sys
@@ -149,14 +150,19 @@ def test_bench_two_rank_rehearsal(ranks, steps, extra):
     line = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
     flight = 1 if "--in-flight" in extra else 2
     assert line["n_gpus"] == ranks and line["config"]["blocks_per_step"] == ranks and line["config"]["blocks_in_flight"] == flight
-    assert ("one_block_at_a_time" in line) == (flight > 1)
     assert ("all_to_all_single" in line["config"]["exchange"]) == ("--gather-batch" not in extra)
-    assert line["config"]["sa_lf_consistent"] is True and line["config"]["gathered_block_round_trip"] is True
-    assert line["value"] > 0 and "roofline" in line and "cpu_baseline" not in line
+    assert line["value"] > 0 and line["ms_per_step"] > 0 and "cpu_baseline" not in line
+    if "--full" in extra:
+        assert ("one_block_at_a_time" in line) == (flight > 1)
+        assert line["config"]["sa_lf_consistent"] is True and line["config"]["gathered_block_round_trip"] is True
+        assert "roofline" in line
+    else:
+        assert not {"one_block_at_a_time", "roofline", "pipeline"} & set(line)
+        assert not {"gates_passed", "sa_lf_consistent", "gathered_block_round_trip"} & set(line["config"])
 
 
 def test_bench_default_run_keeps_two_blocks_in_flight():
-    """the driver's N = 1 command at a small block: two feeder threads with a compute context each take the steps in turn, the same
+    """the N = 1 command with --full at a small block: two feeder threads with a compute context each take the steps in turn, the same
     steps then run one block at a time for the kernels' own times; every gate (LF consistency, the inverse, the other shapes -- at
     sizes without a committed digest the digest gates report null) still passes.  Not a measurement."""
     import json
@@ -165,7 +171,7 @@ def test_bench_default_run_keeps_two_blocks_in_flight():
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     for extra, flight in (([], 2), (["--in-flight", "1"], 1), (["--in-flight", "3", "--no-sa"], 3)):
         r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "5", "--warmup", "1", "--block-mib", "16",
-                            "--no-cpu-baseline"] + extra, capture_output=True, text=True, timeout=280, cwd=root)
+                            "--full", "--no-cpu-baseline"] + extra, capture_output=True, text=True, timeout=280, cwd=root)
         assert r.returncode == 0, r.stderr[-2000:]
         line = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
         assert line["config"]["blocks_in_flight"] == flight and line["steps"] == 5 and line["n_gpus"] == 1
@@ -181,7 +187,8 @@ def test_bench_default_run_keeps_two_blocks_in_flight():
 
 def test_bench_dump_outputs(tmp_path):
     """bench.py --dump-outputs: the last timed step's SA and BWT || baseId as float .npy files -- the same arrays whether the steps ran
-    with two blocks in flight or one at a time, sums over the whole block that match its input, under 64 MB.  Not a measurement."""
+    with two blocks in flight or one at a time, in a plain run or with --full, sums over the whole block that match its input, under
+    64 MB.  A plain run's line holds the headline and config alone.  Not a measurement."""
     import json
     import subprocess
     import sys
@@ -189,19 +196,25 @@ def test_bench_dump_outputs(tmp_path):
     mib = 16
     n = mib << 20
     dumps = []
-    for extra in ([], ["--in-flight", "1"]):
+    for extra in (["--full"], ["--full", "--in-flight", "1"], []):
         d = tmp_path / ("out%d" % len(dumps))
         r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--block-mib", str(mib),
                             "--no-cpu-baseline", "--no-shapes", "--dump-outputs", str(d)] + extra, capture_output=True, text=True, timeout=280, cwd=root)
         assert r.returncode == 0, r.stderr[-2000:]
         line = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
-        assert line["steps"] == 3 and line["ms_per_step"] > 0 and line["config"]["gates_passed"] is True
+        assert line["steps"] == 3 and line["ms_per_step"] > 0
+        if "--full" in extra:
+            assert line["config"]["gates_passed"] is True
+        else:
+            assert {"metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"} <= set(line) and line["value"] > 0
+            assert not {"roofline", "pipeline", "one_block_at_a_time", "inverse", "shapes", "cpu_baseline"} & set(line)
+            assert "gates_passed" not in line["config"]
         dumps.append({f[:-4]: np.load(d / f) for f in os.listdir(d)})
-    a, b = dumps
-    assert sorted(a) == sorted(b) == ["base_id", "bwt_chunk_sums", "bwt_sample", "sa_chunk_sums", "sa_sample", "sample_index"]
+    a, b, c = dumps
+    assert sorted(a) == sorted(b) == sorted(c) == ["base_id", "bwt_chunk_sums", "bwt_sample", "sa_chunk_sums", "sa_sample", "sample_index"]
     assert sum(v.nbytes for v in a.values()) <= 64 << 20
     for k in a:
-        assert a[k].dtype in (np.float32, np.float64) and np.array_equal(a[k], b[k]), k
+        assert a[k].dtype in (np.float32, np.float64) and np.array_equal(a[k], b[k]) and np.array_equal(a[k], c[k]), k
     x = S.gen_shape("random", n, block=0)
     idx = a["sample_index"].astype(np.int64)
     assert idx.size > 0 and (np.diff(idx) > 0).all() and idx[-1] < n

@@ -3,7 +3,7 @@
 set -o pipefail
 export TMPDIR=/tmp
 out=gpurun_out/${1:-final_short}; mkdir -p $out
-timeout -k 10 300 python3 bench.py --gpus 1 --steps 20 --warmup 5 > $out/bench_line.json 2> $out/bench.err || { tail -20 $out/bench.err; exit 1; }
+timeout -k 10 300 python3 bench.py --full --gpus 1 --steps 20 --warmup 5 > $out/bench_line.json 2> $out/bench.err || { tail -20 $out/bench.err; exit 1; }
 python3 -c "
 import json
 d=json.load(open('$out/bench_line.json'))
