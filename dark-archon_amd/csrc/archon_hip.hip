@@ -13,6 +13,7 @@
 #include "post.hiph"
 #include "lcp.hiph"
 #include "fm.hiph"
+#include "fm_walk.hiph"
 
 #include <stdarg.h>
 #include <atomic>
@@ -66,6 +67,9 @@ static thread_local bool t_lcp_stats_set[kMaxDev];
 // and for its last FM call (archon_hip_get_fm_stats): FM calls leave both of the others alone
 static thread_local archon_hip_fm_stats t_fm_stats[kMaxDev];
 static thread_local bool t_fm_stats_set[kMaxDev];
+// and for its last sampled-index call (archon_hip_get_fm_walk_stats: sample, block_fm_index, locate, extract)
+static thread_local archon_hip_fm_walk_stats t_fmw_stats[kMaxDev];
+static thread_local bool t_fmw_stats_set[kMaxDev];
 
 static inline int keep_stats(Ctx *c, int rc)
 {
@@ -1702,7 +1706,8 @@ int archon_hip_lcp(const uint8_t *x, uint32_t n, const uint32_t *sa, uint32_t *l
 
 // ---- the FM index (fm.hiph)
 // The handle owns one device allocation: [its copy of the BWT] | super | sub | R.  A resident block's handle reads the
-// block's own d_bwt (n + 64 bytes, so 16-byte loads that start below n stay inside it) and has no copy.
+// block's own d_bwt (n + 64 bytes, so 16-byte loads that start below n stay inside it) and has no copy.  A sampled handle
+// (fm_walk.hiph) owns a second one: isa | sa | marks | dir, rate 0 without it.
 struct archon_hip_fm {
     int dev = 0;
     uint32_t n = 0, base = 0, base_sym = 0, sbits = 0, bbits = 0;
@@ -1711,15 +1716,21 @@ struct archon_hip_fm {
     uint32_t *super = nullptr, *R = nullptr;
     uint16_t *sub = nullptr;
     uint64_t table_bytes = 0;
+    uint32_t rate = 0, rbits = 0, ns = 0;
+    char *smem = nullptr;
+    uint32_t *isa = nullptr, *sa_s = nullptr, *marks = nullptr, *dir = nullptr;
+    uint64_t sample_bytes = 0;
     fmk::FmTable table() const { return fmk::FmTable{bwt, super, sub, R, n, base, base_sym, sbits, bbits}; }
+    fmw::FmSamples samples() const { return fmw::FmSamples{isa, sa_s, marks, dir, rbits, ns}; }
 };
 
 static void fm_release(archon_hip_fm *f)
 {
     if (!f) return;
-    if (f->mem) {
+    if (f->mem || f->smem) {
         (void)hipSetDevice(f->dev);
-        (void)hipFree(f->mem);
+        if (f->mem) (void)hipFree(f->mem);
+        if (f->smem) (void)hipFree(f->smem);
     }
     delete f;
 }
@@ -1830,13 +1841,15 @@ static void fm_keep_stats(int dev, const archon_hip_fm_stats &st)
     t_fm_stats_set[dev] = true;
 }
 
-// Host patterns and ranges through the context's arena.  When `locate` is given (a resident block's suffix array), the
-// ranges come back, the host sums them, and a gather writes the starts.
+// Host patterns and ranges through the context's arena.  When `locate` is given (a resident block's suffix array, or the
+// samples of a sampled handle: d_sa null), the ranges come back, the host sums them, and a gather or the LF walks write the
+// starts (the walks' counters into *wst).
 struct FmLocate {
     const uint32_t *d_sa;
     uint32_t *pos;
     uint64_t cap;
     uint64_t *total;
+    archon_hip_fm_walk_stats *wst;
 };
 static int fm_host_query(Ctx *c, hipStream_t s, const archon_hip_fm *f, const uint8_t *patterns, const uint32_t *offsets, uint32_t k,
                          uint32_t *lo, uint32_t *hi, const FmLocate *loc, archon_hip_fm_stats *st)
@@ -1879,17 +1892,34 @@ static int fm_host_query(Ctx *c, hipStream_t s, const archon_hip_fm *f, const ui
         ARCHON_HIP_TRY(hipMemcpyAsync(L.off, offsets, ((size_t)k + 1) * 4, hipMemcpyHostToDevice, s));
         ARCHON_HIP_TRY(hipMemcpyAsync(L.lo, lo, (size_t)k * 4, hipMemcpyHostToDevice, s));
         ARCHON_HIP_TRY(hipMemcpyAsync(L.first, first.data(), ((size_t)k + 1) * 8, hipMemcpyHostToDevice, s));
+        uint32_t *wmail = c->d_mail + mail::kDevFmWalk.at, *rd = c->h_mail + mail::kRead.at;
+        static_assert(fmw::kWords <= mail::kDevFmWalk.len && fmw::kWords <= mail::kRead.len, "the sampled FM words in the mailbox");
+        if (!loc->d_sa) ARCHON_HIP_TRY(hipMemsetAsync(wmail, 0, fmw::kWords * sizeof(uint32_t), s));
         const int e2 = tm.mark();
-        if (t) {
+        if (t && loc->d_sa) {
             const uint64_t g = (t + 255) / 256;
             hipLaunchKernelGGL(k_fm_locate, dim3(g < kLocateGrid ? (uint32_t)g : kLocateGrid), dim3(256), 0, s, loc->d_sa, L.off, L.lo, L.first, k, L.pos);
+            ARCHON_HIP_TRY(hipGetLastError());
+            st->kernel_launches += 1;
+        } else if (t) {
+            const uint64_t g = (t + 3) / 4;
+            hipLaunchKernelGGL(fmw::k_fm_walk_locate, dim3(g < fmw::kWalkGrid ? (uint32_t)g : fmw::kWalkGrid), dim3(256), 0, s, f->table(), f->samples(),
+                               L.off, L.lo, L.first, k, L.pos, wmail);
             ARCHON_HIP_TRY(hipGetLastError());
             st->kernel_launches += 1;
         }
         const int e3 = tm.mark();
         if (t) ARCHON_HIP_TRY(hipMemcpyAsync(loc->pos, L.pos, t * 4, hipMemcpyDeviceToHost, s));
+        if (!loc->d_sa) ARCHON_HIP_TRY(hipMemcpyAsync(rd, wmail, fmw::kWords * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
         ARCHON_SYNC(s);
         st->ms_query += tm.ms(e2, e3);
+        if (loc->wst) {
+            loc->wst->walks = t;
+            memcpy(&loc->wst->lf_steps, rd + fmw::kSteps, sizeof(uint64_t));
+            loc->wst->max_walk = rd[fmw::kMaxWalk];
+            loc->wst->kernel_launches = t ? 1 : 0;
+            loc->wst->ms_query = tm.ms(e2, e3);
+        }
     }
     st->host_syncs += t_sync_count - syncs0;
     return ARCHON_OK;
@@ -1976,6 +2006,297 @@ int archon_hip_get_fm_stats(int dev, archon_hip_fm_stats *out)
     if (!out) { set_error("null pointer"); return ARCHON_E_ARG; }
     if (dev < 0 || dev >= kMaxDev || !t_fm_stats_set[dev]) { set_error("the calling thread has run no FM call on device %d", dev); return ARCHON_E_ARG; }
     *out = t_fm_stats[dev];
+    return ARCHON_OK;
+}
+
+// ---- the sampled FM index (fm_walk.hiph)
+static void fmw_keep_stats(int dev, const archon_hip_fm_walk_stats &st)
+{
+    t_fmw_stats[dev] = st;
+    t_fmw_stats_set[dev] = true;
+}
+
+static int fmw_rate_bits(uint32_t rate, uint32_t *rbits)
+{
+    if (rate == 0 || (rate & (rate - 1)) || rate > (1u << fmw::kMaxRateBits)) {
+        set_error("sample rate %u: not a power of two in [1, 65536]", rate);
+        return ARCHON_E_ARG;
+    }
+    *rbits = (uint32_t)log2_exact(rate);
+    return ARCHON_OK;
+}
+
+// The ISA samples by the LF walk over the handle's own BWT: the inverse's LF table and cut, a measuring walk (the inverse's
+// first walk with no slab), the list ranking, then k_walk_sample.  One wait at the end tells whether the cut has to be made
+// again (as inverse_run) or the bytes are no BWT.
+static int fm_sample_walk(Ctx *c, hipStream_t s, const archon_hip_fm *f, uint32_t rbits, uint32_t *isa, const FmwArena &L, uint32_t *launches)
+{
+    const uint32_t n = f->n, base = f->base;
+    uint32_t *small = L.small, *rd = c->h_mail + mail::kRead.at;
+    ARCHON_HIP_TRY(hipMemsetAsync(small, 0, inv_small::kWords * sizeof(uint32_t), s));
+    ARCHON_TRY(lf_build_launch(c, s, f->bwt, n, base, L.T, L.status, small));
+    *launches += 3;
+    uint32_t lut_shift = 0;
+    while (((uint64_t)(n - 1) >> lut_shift) >= (1u << inv::kSymLutBits)) ++lut_shift;
+    const uint32_t sbits = inv_sbits(n), nreg = div_up(n, 1u << sbits), nchains = nreg + 1;
+    const uint32_t gc = div_up(nchains, 256);
+    const uint32_t max_steps = (4096u << sbits) < n ? (4096u << sbits) : n;
+    const uint32_t gq = (uint32_t)kNumCU * 3, gs = div_up(nchains, inv::kWalkLanes) < gq ? div_up(nchains, inv::kWalkLanes) : gq;
+    inv::Cut cut;
+    cut.n = n; cut.base = base; cut.sbits = sbits; cut.nreg = nreg;
+    uint2 *nd[2] = {L.nd[0], L.nd[1]};
+    for (uint32_t attempt = 0;; ++attempt) {
+        cut.salt = attempt * 0x85EBCA6Bu;
+        if (nchains >= (uint32_t)kNumCU * 64u)
+            hipLaunchKernelGGL(inv::k_walk_queue, dim3(gq), dim3(inv::kWalkLanes), 0, s, L.T, cut, nchains, max_steps, small + inv_small::kStarts, lut_shift,
+                               0u, (uint8_t *)nullptr, L.next, L.len, small + inv_small::kErr, 0u);
+        else
+            hipLaunchKernelGGL(inv::k_walk_store, dim3(gc), dim3(256), 0, s, L.T, cut, nchains, max_steps, small + inv_small::kStarts, lut_shift, 0u,
+                               (uint8_t *)nullptr, L.next, L.len, small + inv_small::kErr);
+        const uint32_t head = (inv::cut_row(cut, base >> sbits) == base) ? (base >> sbits) : nreg;
+        hipLaunchKernelGGL(inv::k_rank_init, dim3(gc), dim3(256), 0, s, L.next, L.len, nchains, head, nd[0]);
+        *launches += 2;
+        int cur = 0;
+        for (uint64_t span = 1; span < nchains; span *= (inv::kRankHops + 1)) {
+            hipLaunchKernelGGL(inv::k_rank_jump, dim3(gc), dim3(256), 0, s, nd[cur], nchains, nd[cur ^ 1]);
+            cur ^= 1;
+            ++*launches;
+        }
+        hipLaunchKernelGGL(fmw::k_walk_sample, dim3(gs), dim3(inv::kWalkLanes), 0, s, L.T, cut, nchains, L.len, nd[cur], rbits, isa,
+                           small + inv_small::kErr);
+        ++*launches;
+        ARCHON_HIP_TRY(hipGetLastError());
+        ARCHON_HIP_TRY(hipMemcpyAsync(rd, small + inv_small::kErr, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+        ARCHON_HIP_TRY(hipMemcpyAsync(rd + 1, &nd[cur][head].y, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+        ARCHON_SYNC(s);
+        if (rd[0] & 1u) { set_error("device consistency flag (look-back spin bound)"); return ARCHON_E_INTERNAL; }
+        if (!(rd[0] & 2u)) {
+            if (rd[1] != n) { set_error("LF walk closes after %u of %u rows: not a BWT in a7 format", rd[1], n); return ARCHON_E_CORRUPT; }
+            return ARCHON_OK;
+        }
+        if (attempt == 1) { set_error("LF walk does not reach a cut row: not a BWT in a7 format"); return ARCHON_E_CORRUPT; }
+        ARCHON_HIP_TRY(hipMemsetAsync(small + inv_small::kErr, 0, sizeof(uint32_t), s));
+    }
+}
+
+// Samples of rate 2^rbits for f: from d_sa (a suffix array of f's BWT) when given, else by the LF walk.  They replace f's
+// earlier samples only when the build succeeds.
+static int fm_sample_run(Ctx *c, hipStream_t s, archon_hip_fm *f, uint32_t rbits, const uint32_t *d_sa, archon_hip_fm_walk_stats *st)
+{
+    using namespace fmw;
+    const uint32_t n = f->n, rate = 1u << rbits;
+    const uint32_t ns = (uint32_t)(((uint64_t)n + rate - 1) >> rbits), nblk = (n >> kDirBits) + 1;
+    const bool walk = d_sa == nullptr;
+    st->n = n;
+    st->rate = rate;
+    st->route = walk ? 2 : 1;
+    FmwArena L;
+    ARCHON_TRY(ctx_carve(c, [&](Carve &a) { return fmw_layout(a, L, n, walk); }));
+    const size_t isa_b = round256((size_t)ns * 4), marks_b = round256((size_t)nblk * 32), dir_b = round256((size_t)nblk * 4);
+    const size_t bytes = 2 * isa_b + marks_b + dir_b;
+    struct Owned {
+        char *p = nullptr;
+        ~Owned() { if (p) (void)hipFree(p); }
+    } mem;
+    if (hipMalloc((void **)&mem.p, bytes) != hipSuccess) {
+        (void)hipGetLastError();
+        set_error("FM samples: device allocation of %zu bytes failed", bytes);
+        return ARCHON_E_NOMEM;
+    }
+    uint32_t *isa = reinterpret_cast<uint32_t *>(mem.p), *sa_s = reinterpret_cast<uint32_t *>(mem.p + isa_b);
+    uint32_t *marks = reinterpret_cast<uint32_t *>(mem.p + 2 * isa_b), *dir = reinterpret_cast<uint32_t *>(mem.p + 2 * isa_b + marks_b);
+    const uint32_t syncs0 = t_sync_count;
+    uint32_t launches = 0;
+    StageTimer tm(c, 72, s);
+    const int e0 = tm.mark();
+    if (walk) {
+        ARCHON_TRY(fm_sample_walk(c, s, f, rbits, isa, L, &launches));
+    } else {
+        const uint32_t g = div_up(n, 256);
+        hipLaunchKernelGGL(k_samp_from_sa, dim3(g < 8192u ? g : 8192u), dim3(256), 0, s, d_sa, n, f->base, rbits, ns, isa);
+        ++launches;
+    }
+    ARCHON_HIP_TRY(hipMemsetAsync(marks, 0, marks_b, s));
+    const uint32_t gk = div_up(ns, 256), gb = div_up(nblk, 256);
+    hipLaunchKernelGGL(k_samp_mark, dim3(gk < 8192u ? gk : 8192u), dim3(256), 0, s, isa, ns, n, marks);
+    hipLaunchKernelGGL(k_samp_dir, dim3(gb < 8192u ? gb : 8192u), dim3(256), 0, s, marks, nblk, dir);
+    ARCHON_TRY(launch_scan<0>(s, dir, dir, nblk, L.scan, nullptr));
+    hipLaunchKernelGGL(k_samp_sa, dim3(gk < 8192u ? gk : 8192u), dim3(256), 0, s, isa, ns, n, rbits, marks, dir, sa_s);
+    launches += 6;
+    const int e1 = tm.mark();
+    ARCHON_HIP_TRY(hipGetLastError());
+    ARCHON_SYNC(s);
+    if (f->smem) (void)hipFree(f->smem);
+    f->smem = mem.p;
+    mem.p = nullptr;
+    f->rate = rate;
+    f->rbits = rbits;
+    f->ns = ns;
+    f->isa = isa;
+    f->sa_s = sa_s;
+    f->marks = marks;
+    f->dir = dir;
+    f->sample_bytes = bytes;
+    st->samples = ns;
+    st->sample_bytes = bytes;
+    st->kernel_launches = launches;
+    st->host_syncs = t_sync_count - syncs0;
+    st->ms_build = tm.ms(e0, e1);
+    return ARCHON_OK;
+}
+
+static void fmw_handle_stats(const archon_hip_fm *f, archon_hip_fm_walk_stats *st)
+{
+    st->n = f->n;
+    st->rate = f->rate;
+    st->samples = f->ns;
+    st->sample_bytes = f->sample_bytes;
+}
+
+int archon_hip_fm_sample(archon_hip_fm *f, uint32_t rate)
+{
+    if (!f) { set_error("null pointer"); return ARCHON_E_ARG; }
+    uint32_t rbits;
+    ARCHON_TRY(fmw_rate_bits(rate, &rbits));
+    Ctx *c;
+    ARCHON_TRY(ctx_get(f->dev, &c));
+    std::lock_guard<std::mutex> lk(c->mu);
+    ARCHON_HIP_TRY(hipSetDevice(f->dev));
+    archon_hip_fm_walk_stats st = {};
+    const int rc = fm_sample_run(c, c->own_stream, f, rbits, nullptr, &st);
+    fmw_keep_stats(f->dev, st);
+    return rc;
+}
+
+int archon_hip_fm_read_samples(archon_hip_fm *f, uint32_t *isa, uint32_t cap, uint32_t *count)
+{
+    if (!f || !isa || !count) { set_error("null pointer"); return ARCHON_E_ARG; }
+    if (!f->rate) { set_error("FM index: the handle has no samples (archon_hip_fm_sample)"); return ARCHON_E_ARG; }
+    *count = f->ns;
+    if (cap < f->ns) { set_error("FM samples: %u ISA entries, room for %u", f->ns, cap); return ARCHON_E_ARG; }
+    ARCHON_HIP_TRY(hipSetDevice(f->dev));
+    ARCHON_HIP_TRY(hipMemcpy(isa, f->isa, (size_t)f->ns * 4, hipMemcpyDeviceToHost));
+    return ARCHON_OK;
+}
+
+int archon_hip_fm_locate(archon_hip_fm *f, const uint8_t *patterns, const uint32_t *offsets, uint32_t k, uint32_t *pos, uint64_t cap, uint64_t *total)
+{
+    if (!f || !patterns || !offsets || !pos || !total) { set_error("null pointer"); return ARCHON_E_ARG; }
+    if (!f->rate) { set_error("FM index: the handle has no samples (archon_hip_fm_sample)"); return ARCHON_E_ARG; }
+    *total = 0;
+    if (!k) return ARCHON_OK;
+    ARCHON_TRY(fm_check_offsets(offsets, k));
+    Ctx *c;
+    ARCHON_TRY(ctx_get(f->dev, &c));
+    std::lock_guard<std::mutex> lk(c->mu);
+    ARCHON_HIP_TRY(hipSetDevice(f->dev));
+    archon_hip_fm_stats st = {};
+    archon_hip_fm_walk_stats wst = {};
+    fmw_handle_stats(f, &wst);
+    std::vector<uint32_t> lo(k), hi(k);
+    const FmLocate loc{nullptr, pos, cap, total, &wst};
+    const uint32_t syncs0 = t_sync_count;
+    const int rc = fm_host_query(c, c->own_stream, f, patterns, offsets, k, lo.data(), hi.data(), &loc, &st);
+    wst.host_syncs = t_sync_count - syncs0;
+    fm_keep_stats(f->dev, st);
+    fmw_keep_stats(f->dev, wst);
+    return rc;
+}
+
+// Requests on the device (d_starts, d_off) into d_out[off[j] - shift ..): checks, segment counts and their sums, the walks.
+static int fm_extract_run(Ctx *c, hipStream_t s, const archon_hip_fm *f, const uint32_t *d_starts, const uint32_t *d_off, uint32_t k,
+                          uint8_t *d_out, uint32_t shift, const FmqArena &L, archon_hip_fm_walk_stats *st)
+{
+    using namespace fmw;
+    uint32_t *mail = c->d_mail + mail::kDevFmWalk.at, *rd = c->h_mail + mail::kRead.at;
+    static_assert(kWords + 1 <= mail::kRead.len, "the sampled FM words and the segment total in the readback words");
+    ARCHON_HIP_TRY(hipMemsetAsync(mail, 0, kWords * sizeof(uint32_t), s));
+    StageTimer tm(c, 72, s);
+    const int e0 = tm.mark();
+    const uint32_t g = div_up(k, 256);
+    hipLaunchKernelGGL(k_ext_prep, dim3(g < 4096u ? g : 4096u), dim3(256), 0, s, d_starts, d_off, k, f->n, f->rbits, L.seg, mail);
+    ARCHON_TRY(launch_scan<0>(s, L.seg, L.seg, k, L.scan, L.seg + k));
+    hipLaunchKernelGGL(k_fm_walk_extract, dim3(kWalkGrid), dim3(256), 0, s, f->table(), f->samples(), d_starts, d_off, L.seg, k, d_out, shift, mail);
+    ARCHON_HIP_TRY(hipGetLastError());
+    const int e1 = tm.mark();
+    ARCHON_HIP_TRY(hipMemcpyAsync(rd, mail, kWords * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+    ARCHON_HIP_TRY(hipMemcpyAsync(rd + kWords, L.seg + k, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+    ARCHON_SYNC(s);
+    st->kernel_launches = 5;
+    st->ms_query = tm.ms(e0, e1);
+    if (rd[kBad]) { set_error("FM extract: a request lies outside [0, %u] or the offsets decrease", f->n); return ARCHON_E_ARG; }
+    st->walks = rd[kWords];
+    memcpy(&st->lf_steps, rd + kSteps, sizeof(uint64_t));
+    st->max_walk = rd[kMaxWalk];
+    return ARCHON_OK;
+}
+
+int archon_hip_fm_extract(archon_hip_fm *f, const uint32_t *starts, const uint32_t *offsets, uint32_t k, uint8_t *out)
+{
+    if (!f || !starts || !offsets || !out) { set_error("null pointer"); return ARCHON_E_ARG; }
+    if (!f->rate) { set_error("FM index: the handle has no samples (archon_hip_fm_sample)"); return ARCHON_E_ARG; }
+    if (!k) return ARCHON_OK;
+    for (uint32_t j = 0; j < k; ++j) {
+        if (offsets[j + 1] < offsets[j]) { set_error("FM extract: offsets[%u] < offsets[%u]", j + 1, j); return ARCHON_E_ARG; }
+        if ((uint64_t)starts[j] + (offsets[j + 1] - offsets[j]) > f->n) {
+            set_error("FM extract: request %u [%u, %llu) outside [0, %u]", j, starts[j], (unsigned long long)starts[j] + (offsets[j + 1] - offsets[j]), f->n);
+            return ARCHON_E_ARG;
+        }
+    }
+    Ctx *c;
+    ARCHON_TRY(ctx_get(f->dev, &c));
+    std::lock_guard<std::mutex> lk(c->mu);
+    ARCHON_HIP_TRY(hipSetDevice(f->dev));
+    hipStream_t s = c->own_stream;
+    archon_hip_fm_walk_stats st = {};
+    fmw_handle_stats(f, &st);
+    const uint32_t syncs0 = t_sync_count;
+    const size_t bytes = (size_t)offsets[k] - offsets[0];
+    FmqArena L;
+    int rc = ctx_carve(c, [&](Carve &a) { return fmq_layout(a, L, k, bytes, true); });
+    if (rc == ARCHON_OK) {
+        auto up = [&]() -> int {
+            ARCHON_HIP_TRY(hipMemcpyAsync(L.starts, starts, (size_t)k * 4, hipMemcpyHostToDevice, s));
+            ARCHON_HIP_TRY(hipMemcpyAsync(L.off, offsets, ((size_t)k + 1) * 4, hipMemcpyHostToDevice, s));
+            ARCHON_TRY(fm_extract_run(c, s, f, L.starts, L.off, k, L.out, offsets[0], L, &st));
+            if (bytes) {
+                ARCHON_HIP_TRY(hipMemcpyAsync(out + offsets[0], L.out, bytes, hipMemcpyDeviceToHost, s));
+                ARCHON_SYNC(s);
+            }
+            return ARCHON_OK;
+        };
+        rc = up();
+    }
+    st.host_syncs = t_sync_count - syncs0;
+    fmw_keep_stats(f->dev, st);
+    return rc;
+}
+
+int archon_hip_fm_extract_dev(archon_hip_fm *f, const uint32_t *d_starts, const uint32_t *d_offsets, uint32_t k, uint8_t *d_out, void *stream)
+{
+    if (!f || !d_starts || !d_offsets || !d_out) { set_error("null pointer"); return ARCHON_E_ARG; }
+    if (!f->rate) { set_error("FM index: the handle has no samples (archon_hip_fm_sample)"); return ARCHON_E_ARG; }
+    if (!k) return ARCHON_OK;
+    Ctx *c;
+    ARCHON_TRY(ctx_get(f->dev, &c));
+    std::lock_guard<std::mutex> lk(c->mu);
+    ARCHON_HIP_TRY(hipSetDevice(f->dev));
+    archon_hip_fm_walk_stats st = {};
+    fmw_handle_stats(f, &st);
+    const uint32_t syncs0 = t_sync_count;
+    FmqArena L;
+    int rc = ctx_carve(c, [&](Carve &a) { return fmq_layout(a, L, k, 0, false); });
+    if (rc == ARCHON_OK) rc = fm_extract_run(c, stream ? (hipStream_t)stream : c->own_stream, f, d_starts, d_offsets, k, d_out, 0, L, &st);
+    st.host_syncs = t_sync_count - syncs0;
+    fmw_keep_stats(f->dev, st);
+    return rc;
+}
+
+int archon_hip_get_fm_walk_stats(int dev, archon_hip_fm_walk_stats *out)
+{
+    if (!out) { set_error("null pointer"); return ARCHON_E_ARG; }
+    if (dev < 0 || dev >= kMaxDev || !t_fmw_stats_set[dev]) { set_error("the calling thread has run no sampled FM call on device %d", dev); return ARCHON_E_ARG; }
+    *out = t_fmw_stats[dev];
     return ARCHON_OK;
 }
 
@@ -2155,8 +2476,34 @@ int archon_hip_block_fm_locate(archon_hip_block *b, const uint8_t *patterns, con
     if (!k) return ARCHON_OK;
     ARCHON_TRY(fm_check_offsets(offsets, k));
     std::vector<uint32_t> lo(k), hi(k);
-    const FmLocate loc{b->d_sa, pos, cap, total};
+    const FmLocate loc{b->d_sa, pos, cap, total, nullptr};
     return block_fm_query(b, patterns, offsets, k, lo.data(), hi.data(), &loc);
+}
+
+int archon_hip_block_fm_index(archon_hip_block *b, uint32_t rate, archon_hip_fm **out)
+{
+    if (!b || !out) { set_error("null pointer"); return ARCHON_E_ARG; }
+    uint32_t rbits;
+    ARCHON_TRY(fmw_rate_bits(rate, &rbits));
+    std::lock_guard<std::mutex> lkb(b->mu);
+    if (!b->valid) { set_error("no resident block"); return ARCHON_E_ARG; }
+    Ctx *c;
+    ARCHON_TRY(ctx_get(b->dev, &c));
+    std::lock_guard<std::mutex> lk(c->mu);
+    ARCHON_HIP_TRY(hipSetDevice(b->dev));
+    archon_hip_fm_stats st = {};
+    archon_hip_fm_walk_stats wst = {};
+    archon_hip_fm *f = nullptr;
+    int rc = fm_build(c, c->own_stream, nullptr, b->d_bwt, true, b->n, b->base, &f, &st);
+    fm_keep_stats(b->dev, st);
+    if (rc == ARCHON_OK) {
+        const bool from_sa = b->has_sa && !g_route.fm_sample_walk;
+        rc = fm_sample_run(c, c->own_stream, f, rbits, from_sa ? b->d_sa : nullptr, &wst);
+        fmw_keep_stats(b->dev, wst);
+        if (rc != ARCHON_OK) fm_release(f);
+        else *out = f;
+    }
+    return rc;
 }
 
 int archon_hip_block_stats(archon_hip_block *b, archon_hip_stats *out)
@@ -2873,6 +3220,7 @@ int archon_hip_test_route(const char *name, long value)
         g_route.fm_sub_rows = (int)value;
         return ARCHON_OK;
     }
+    if (!strcmp(name, "FM_SAMPLE_WALK")) { g_route.fm_sample_walk = value ? 1 : 0; return ARCHON_OK; }
     if (!strcmp(name, "FM_SUPER_ROWS")) {
         if (value && (value < 16 || value > 65536 || (value & (value - 1)))) {
             set_error("FM_SUPER_ROWS=%ld: not a power of two in [16, 65536]", value);

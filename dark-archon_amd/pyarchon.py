@@ -35,6 +35,8 @@ SYMBOLS = [
     "archon_hip_lcp", "archon_hip_lcp_dev", "archon_hip_block_lcp", "archon_hip_lcp_keep", "archon_hip_get_lcp_stats",
     "archon_hip_fm_create", "archon_hip_fm_create_dev", "archon_hip_fm_destroy", "archon_hip_fm_count", "archon_hip_fm_count_dev",
     "archon_hip_block_fm_count", "archon_hip_block_fm_locate", "archon_hip_get_fm_stats",
+    "archon_hip_fm_sample", "archon_hip_block_fm_index", "archon_hip_fm_read_samples", "archon_hip_fm_locate", "archon_hip_fm_extract",
+    "archon_hip_fm_extract_dev", "archon_hip_get_fm_walk_stats",
 ]
 
 
@@ -79,6 +81,19 @@ class FmStats(ctypes.Structure):
         ("n", ctypes.c_uint32), ("patterns", ctypes.c_uint32), ("pattern_bytes", ctypes.c_uint64), ("steps", ctypes.c_uint64),
         ("shared_steps", ctypes.c_uint64), ("kernel_launches", ctypes.c_uint32), ("host_syncs", ctypes.c_uint32), ("built", ctypes.c_uint32),
         ("table_bytes", ctypes.c_uint64), ("ms_build", ctypes.c_float), ("ms_query", ctypes.c_float),
+    ]
+
+    def asdict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
+class FmWalkStats(ctypes.Structure):
+    """archon_hip_fm_walk_stats: the calling thread's last sample / locate / extract call on a device"""
+    _fields_ = [
+        ("n", ctypes.c_uint32), ("rate", ctypes.c_uint32), ("route", ctypes.c_uint32), ("kernel_launches", ctypes.c_uint32),
+        ("host_syncs", ctypes.c_uint32), ("samples", ctypes.c_uint64), ("sample_bytes", ctypes.c_uint64), ("walks", ctypes.c_uint64),
+        ("lf_steps", ctypes.c_uint64), ("max_walk", ctypes.c_uint32), ("reserved0", ctypes.c_uint32), ("ms_build", ctypes.c_float),
+        ("ms_query", ctypes.c_float),
     ]
 
     def asdict(self):
@@ -155,6 +170,13 @@ def load():
         "archon_hip_block_fm_count": [vp, vp, vp, u32, vp, vp],
         "archon_hip_block_fm_locate": [vp, vp, vp, u32, vp, ctypes.c_uint64, vp],
         "archon_hip_get_fm_stats": [i32, ctypes.POINTER(FmStats)],
+        "archon_hip_fm_sample": [vp, u32],
+        "archon_hip_block_fm_index": [vp, u32, vp],
+        "archon_hip_fm_read_samples": [vp, vp, u32, vp],
+        "archon_hip_fm_locate": [vp, vp, vp, u32, vp, ctypes.c_uint64, vp],
+        "archon_hip_fm_extract": [vp, vp, vp, u32, vp],
+        "archon_hip_fm_extract_dev": [vp, vp, vp, u32, vp, vp],
+        "archon_hip_get_fm_walk_stats": [i32, ctypes.POINTER(FmWalkStats)],
     }.items():
         fn = getattr(lib, name)
         fn.argtypes = args
@@ -178,7 +200,7 @@ _routes_seen = None
 _ROUTE_NAMES = ("FORCE_PATH", "SMALL_BLOCK", "PASS_RANGES", "INV_ROWS", "INV_SLAB", "INV_SBITS", "INV_WALK_WGS", "NO_ALIGNED", "NO_CHAINS", "NO_DEEP_HINT",
                 "NO_PACK", "NO_PACK_STREAM", "NO_PAIR_CHAINS", "NO_PERIOD_HINT", "NO_BREAK_ROUND", "NO_PERIOD_PROBE", "NO_PERIOD_STREAM", "NO_PROBE",
                 "NO_RANK_WRITER", "NO_TEXT_ROUNDS", "NO_MID", "NO_SHALLOW", "NO_CLOSED_FORM", "NO_REL_RECORDS", "ALIGNED_MIN", "REL_MIN_SEG", "KEY_BYTES",
-                "LCP_CAP", "LCP_WINDOW", "FM_SUB_ROWS", "FM_SUPER_ROWS")
+                "LCP_CAP", "LCP_WINDOW", "FM_SUB_ROWS", "FM_SUPER_ROWS", "FM_SAMPLE_WALK")
 
 
 def _sync_routes(L):
@@ -298,6 +320,13 @@ def fm_stats(dev=0):
     return s
 
 
+def fm_walk_stats(dev=0):
+    """FmWalkStats of the calling thread's last sample / locate / extract call on dev"""
+    s = FmWalkStats()
+    _check(lib().archon_hip_get_fm_walk_stats(dev, ctypes.byref(s)))
+    return s
+
+
 def _pack_patterns(patterns):
     """a list of bytes / uint8 arrays -> (packed bytes, uint32 offsets[k + 1])"""
     parts = [np.frombuffer(bytes(p), np.uint8) if isinstance(p, (bytes, bytearray)) else np.ascontiguousarray(p, dtype=np.uint8).ravel()
@@ -344,6 +373,53 @@ class FmIndex:
         """torch tensors on the device: patterns uint8, offsets int32[k + 1], lo and hi int32[k] (written); current stream"""
         _check(lib().archon_hip_fm_count_dev(self.h, ctypes.c_void_p(patterns_t.data_ptr()), ctypes.c_void_p(offsets_t.data_ptr()), lo_t.numel(),
                                              ctypes.c_void_p(lo_t.data_ptr()), ctypes.c_void_p(hi_t.data_ptr()), _stream_ptr()))
+
+    def sample(self, rate):
+        """ISA / SA samples of rate `rate` (a power of two <= 65536) by the LF walk over the handle's BWT; returns self"""
+        _check(lib().archon_hip_fm_sample(self.h, int(rate)))
+        return self
+
+    def samples(self):
+        """the ISA samples: uint32 array, entry k the row of item k * rate"""
+        cnt = ctypes.c_uint32(0)
+        probe = np.zeros(1, np.uint32)
+        rc = lib().archon_hip_fm_read_samples(self.h, _p(probe), 0, ctypes.cast(ctypes.byref(cnt), ctypes.c_void_p))
+        if rc < 0 and cnt.value == 0:
+            _check(rc)
+        out = np.zeros(max(cnt.value, 1), np.uint32)
+        _check(lib().archon_hip_fm_read_samples(self.h, _p(out), cnt.value, ctypes.cast(ctypes.byref(cnt), ctypes.c_void_p)))
+        return out[:cnt.value]
+
+    def locate(self, patterns):
+        """the starts of every pattern's occurrences from the samples: a list of uint32 arrays, each in row order (the shape and
+        order of Block.fm_locate)"""
+        lo, hi = self.count(patterns)
+        cuts = np.zeros(lo.size + 1, np.int64)
+        np.cumsum(hi.astype(np.int64) - lo, out=cuts[1:])
+        packed, offsets = _pack_patterns(patterns)
+        pos = np.zeros(max(int(cuts[-1]), 1), np.uint32)
+        total = ctypes.c_uint64(0)
+        _check(lib().archon_hip_fm_locate(self.h, _p(packed), _p(offsets), lo.size, _p(pos), int(cuts[-1]),
+                                          ctypes.cast(ctypes.byref(total), ctypes.c_void_p)))
+        return [pos[cuts[j]:cuts[j + 1]] for j in range(lo.size)]
+
+    def extract(self, starts, lengths):
+        """x[starts[j] .. starts[j] + lengths[j]) for every j: a list of uint8 arrays"""
+        starts = np.ascontiguousarray(starts, dtype=np.uint32).ravel()
+        lengths = np.asarray(lengths, dtype=np.uint64).ravel()
+        offsets = np.zeros(starts.size + 1, np.uint64)
+        np.cumsum(lengths, out=offsets[1:])
+        if offsets[-1] > 0xFFFFFFFF:
+            raise ValueError("extract: more than 2^32 - 1 bytes in one call")
+        offsets = offsets.astype(np.uint32)
+        out = np.zeros(max(int(offsets[-1]), 1), np.uint8)
+        _check(lib().archon_hip_fm_extract(self.h, _p(starts), _p(offsets), starts.size, _p(out)))
+        return [out[offsets[j]:offsets[j + 1]] for j in range(starts.size)]
+
+    def extract_dev(self, starts_t, offsets_t, out_t):
+        """torch tensors on the device: starts int32[k], offsets int32[k + 1], out uint8 (written at offsets[j]); current stream"""
+        _check(lib().archon_hip_fm_extract_dev(self.h, ctypes.c_void_p(starts_t.data_ptr()), ctypes.c_void_p(offsets_t.data_ptr()), starts_t.numel(),
+                                               ctypes.c_void_p(out_t.data_ptr()), _stream_ptr()))
 
     def close(self):
         if self.h:
@@ -463,6 +539,15 @@ class Block:
         _check(lib().archon_hip_block_fm_locate(self.h, _p(packed), _p(offsets), lo.size, _p(pos), int(cuts[-1]),
                                                 ctypes.cast(ctypes.byref(total), ctypes.c_void_p)))
         return [pos[cuts[j]:cuts[j + 1]] for j in range(lo.size)]
+
+    def fm_index(self, rate):
+        """a standalone sampled FmIndex of the last forward's BWT (samples from the SA when that forward kept one, else by the
+        LF walk); it outlives later forwards and close()"""
+        h = ctypes.c_void_p(None)
+        _check(lib().archon_hip_block_fm_index(self.h, int(rate), ctypes.byref(h)))
+        f = FmIndex(_handle=h)
+        f.n = self.n
+        return f
 
     def stats(self):
         s = Stats()

@@ -14,7 +14,8 @@
  *   archon_hip_radix_scatter  the counting-sort scatter of tool/radix_dir/radix.c:40-44
  *   archon_hip_lms_select   Constructor::findLMS (160-172): the subset a7 sorts directly (a4 IT-2: bwt/a4/src/archon.c:163-169)
  *   archon_hip_lcp          nothing: the LCP array of the suffix array, below
- *   archon_hip_fm_*         nothing: counting and locating patterns by backward search on the BWT (an FM index), below
+ *   archon_hip_fm_*         nothing: counting and locating patterns by backward search on the BWT (an FM index), below;
+ *                           with a sampled SA and ISA it locates and extracts without the block's suffix array
  *
  * Ordering convention ("a7 order"): item s in 1..N names the
  * reversed prefix x[s-1],x[s-2],...,x[0],INF with INF > 255; sa[0..N) lists the
@@ -307,6 +308,62 @@ typedef struct archon_hip_fm_stats {
     float ms_query;             /* device time of the count and locate kernels (HIP events) */
 } archon_hip_fm_stats;
 int  archon_hip_get_fm_stats(int dev, archon_hip_fm_stats *out);
+
+/* ---- locate and extract without the suffix array: a sampled FM index --------------------------------------------------
+ * The rule in a7 order.  Item s is the key x[s-1], x[s-2], ..., x[0], INF (s = 1 .. n); bwt[r] = x[sa[r]], except at the
+ * primary row `base`, which holds item n and stores x[0] as a stand-in.  R and occ' are those of the search rule above.
+ * LF moves from item s to item s + 1:
+ *   LF(r)    = R[bwt[r]] + occ'(bwt[r], r)     r != base
+ *   LF(base) = R[bwt[base] + 1] - 1            the row of item 1 (x[0], INF is the last key of its bucket)
+ * Walking LF from the row of item s visits items s+1, s+2, ...; bwt at the row of item p is x[p].  Item 0 means the
+ * primary row (x[0] = bwt[base]).
+ * Sample rate S: a power of two, 1 <= S <= 65 536 (else ARCHON_E_ARG).  Sampled items are p = 0, S, 2S, ... < n.
+ *   ISA samples   isa_s[k] = the row of item kS, k = 0 .. ceil(n/S) - 1; isa_s[0] = base
+ *   SA samples    one value per sampled row, in row order: sa[r], and n for the primary row; a marks bitvector over the
+ *                 rows with a rank directory (one u32 per 256 rows) maps a sampled row to its slot
+ *   locate        row r of item s = sa[r]: LF steps until the row is sampled; after t steps sa[r] = sample - t, t the least
+ *                 t >= 0 with (s + t) mod S == 0 or s + t == n.  The starts of pattern j are sa[r] - m_j for r in
+ *                 [lo_j, hi_j), pattern by pattern, each in row order: exactly the order and values of
+ *                 archon_hip_block_fm_locate
+ *   extract       x[a .. a+L): from isa_s[a / S], (a mod S) steps, then emit bwt[row] and step, L times.  Requests are cut at
+ *                 the sample points into independent walks of at most S - 1 steps; a request of length 0 reads nothing
+ *                 (also at a = n)
+ * Example: "banana" (BWT nnbaaa, base 2, sa = 2 4 6 1 3 5), S = 2: isa_s = [2, 0, 1], sampled rows 0, 1, 2.  "an" has rows
+ * [4, 6): row 4 takes one step to row 1 (sa 4), giving 3 - 2 = 1; row 5 one step to the primary row (sa 6), giving
+ * 5 - 2 = 3.  Extracting x[3 .. 5) starts at isa_s[1] = row 0, takes one step to row 4, then emits 'a' and 'n' (cut at item 4,
+ * the 'n' comes from its own walk: isa_s[2] = row 1, no step).
+ * Memory: the samples of a handle take at most 8 ceil(n/S) + n/8 + n/64 + 4096 device bytes, beside the BWT and the rank
+ * table (at S = 32: about 0.38 n).  Handles without samples count exactly as before and refuse locate and extract
+ * (ARCHON_E_ARG).  archon_hip_fm_destroy frees the samples with the rest. */
+/* samples from the handle's own BWT (the walk route); replaces earlier samples of the handle.  ARCHON_E_CORRUPT when the
+ * handle's bytes are no BWT in a7 format (the LF cycle does not close) */
+int  archon_hip_fm_sample(archon_hip_fm *f, uint32_t rate);
+/* a standalone handle (own BWT copy + rank table + samples) from the resident block's last forward: samples from its SA when
+ * that forward kept one, else by the walk route.  The handle outlives later forwards and archon_hip_block_destroy. */
+int  archon_hip_block_fm_index(archon_hip_block *b, uint32_t rate, archon_hip_fm **out);
+/* the ISA samples (row of item kS, k = 0 .. ceil(n/S)-1) to a host buffer; *count set even when cap is short (ARCHON_E_ARG) */
+int  archon_hip_fm_read_samples(archon_hip_fm *f, uint32_t *isa, uint32_t cap, uint32_t *count);
+/* like archon_hip_block_fm_locate, same output order and cap rule; ARCHON_E_ARG on a handle without samples */
+int  archon_hip_fm_locate(archon_hip_fm *f, const uint8_t *patterns, const uint32_t *offsets, uint32_t k,
+                          uint32_t *pos, uint64_t cap, uint64_t *total);
+/* request j: x[starts[j] .. starts[j] + offsets[j+1] - offsets[j]) into out[offsets[j] ..); offsets nondecreasing,
+ * every range inside [0, n] (else ARCHON_E_ARG, nothing written); k = 0 writes nothing */
+int  archon_hip_fm_extract(archon_hip_fm *f, const uint32_t *starts, const uint32_t *offsets, uint32_t k, uint8_t *out);
+int  archon_hip_fm_extract_dev(archon_hip_fm *f, const uint32_t *d_starts, const uint32_t *d_offsets, uint32_t k,
+                               uint8_t *d_out, void *stream);   /* bad ranges found on the device -> ARCHON_E_ARG */
+typedef struct archon_hip_fm_walk_stats {
+    uint32_t n, rate;            /* of the handle */
+    uint32_t route;              /* sample builds: 1 = from an SA, 2 = by the LF walk; 0 for queries */
+    uint32_t kernel_launches, host_syncs;
+    uint64_t samples;            /* ISA entries of the handle */
+    uint64_t sample_bytes;       /* device bytes of ISA + SA samples + marks + rank directory */
+    uint64_t walks;              /* locate: occurrences; extract: segments */
+    uint64_t lf_steps;           /* LF steps of all walks */
+    uint32_t max_walk;           /* the longest walk's steps */
+    uint32_t reserved0;
+    float ms_build, ms_query;    /* HIP events on the call's stream */
+} archon_hip_fm_walk_stats;
+int  archon_hip_get_fm_walk_stats(int dev, archon_hip_fm_walk_stats *out);   /* calling thread's last sample/locate/extract call */
 
 /* ---- measurement ------------------------------------------------------------- */
 
