@@ -57,24 +57,32 @@ static std::mutex g_ctx_mu;
 // or the context it asked for by name (archon_hip_bind_context: the container's worker w of GPU d asks for context w / G).
 static std::atomic<unsigned> g_next_slot[kMaxDev];
 static thread_local signed char t_slot[kMaxDev];      // 0: not bound yet; else slot + 1
-// the statistics of the calling thread's last transform on a device (archon_hip_get_stats): kept per thread, so that no
-// other thread's call on the same context can replace them
-static thread_local archon_hip_stats t_stats[kMaxDev];
-static thread_local bool t_stats_set[kMaxDev];
-// the same for the thread's last LCP call (archon_hip_get_lcp_stats): LCP calls leave archon_hip_stats alone
-static thread_local archon_hip_lcp_stats t_lcp_stats[kMaxDev];
-static thread_local bool t_lcp_stats_set[kMaxDev];
-// and for its last FM call (archon_hip_get_fm_stats): FM calls leave both of the others alone
-static thread_local archon_hip_fm_stats t_fm_stats[kMaxDev];
-static thread_local bool t_fm_stats_set[kMaxDev];
-// and for its last sampled-index call (archon_hip_get_fm_walk_stats: sample, block_fm_index, locate, extract)
-static thread_local archon_hip_fm_walk_stats t_fmw_stats[kMaxDev];
-static thread_local bool t_fmw_stats_set[kMaxDev];
+// The statistics of the calling thread's last call of one kind on a device: kept per thread, so that no other thread's
+// call on the same context can replace them.
+template <class T>
+struct LastStats {
+    T v[kMaxDev];
+    bool set[kMaxDev];
+    void keep(int dev, const T &st)
+    {
+        v[dev] = st;
+        set[dev] = true;
+    }
+    int get(int dev, T *out, const char *what) const
+    {
+        if (dev < 0 || dev >= kMaxDev || !set[dev]) { set_error("the calling thread has run no %s on device %d", what, dev); return ARCHON_E_ARG; }
+        *out = v[dev];
+        return ARCHON_OK;
+    }
+};
+static thread_local LastStats<archon_hip_stats> t_stats;                // transforms (archon_hip_get_stats)
+static thread_local LastStats<archon_hip_lcp_stats> t_lcp_stats;        // LCP calls: they leave archon_hip_stats alone
+static thread_local LastStats<archon_hip_fm_stats> t_fm_stats;          // FM calls: they leave both of the others alone
+static thread_local LastStats<archon_hip_fm_walk_stats> t_fmw_stats;    // sampled-index calls: sample, block_fm_index, locate, extract
 
 static inline int keep_stats(Ctx *c, int rc)
 {
-    t_stats[c->dev] = c->stats;
-    t_stats_set[c->dev] = true;
+    t_stats.keep(c->dev, c->stats);
     return rc;
 }
 
@@ -101,7 +109,7 @@ static int device_count()
     return n;
 }
 
-int ctx_get(int dev, Ctx **out)
+static int check_device(int dev)
 {
     const int ndev = device_count();
     if (ndev <= 0) {
@@ -112,6 +120,12 @@ int ctx_get(int dev, Ctx **out)
         set_error("device %d out of range (have %d)", dev, ndev);
         return ARCHON_E_NODEVICE;
     }
+    return ARCHON_OK;
+}
+
+int ctx_get(int dev, Ctx **out)
+{
+    ARCHON_TRY(check_device(dev));
     const int slot = thread_slot(dev);
     std::lock_guard<std::mutex> lk(g_ctx_mu);
     ARCHON_HIP_TRY(hipSetDevice(dev));
@@ -130,64 +144,54 @@ int ctx_get(int dev, Ctx **out)
     return ARCHON_OK;
 }
 
-int ctx_ensure_arena(Ctx *c, size_t bytes)
+// Grows a buffer of a context (*p, *have bytes) to `want` bytes when it holds fewer than `need`: the device is idle before
+// the old buffer goes.  `fail` is the message of a failed allocation, given the bytes asked for.
+static int regrow(char **p, size_t *have, size_t need, size_t want, const char *fail)
 {
-    if (bytes <= c->arena_bytes) return ARCHON_OK;
+    if (need <= *have) return ARCHON_OK;
     ARCHON_HIP_TRY(hipDeviceSynchronize());
-    if (c->arena) {
-        ARCHON_HIP_TRY(hipFree(c->arena));
-        c->arena = nullptr;
-        c->arena_bytes = 0;
+    if (*p) {
+        ARCHON_HIP_TRY(hipFree(*p));
+        *p = nullptr;
+        *have = 0;
     }
-    const size_t want = bytes + (bytes >> 4) + (1u << 20);
-    if (hipMalloc((void **)&c->arena, want) != hipSuccess) {
+    if (hipMalloc((void **)p, want) != hipSuccess) {
         (void)hipGetLastError();
-        set_error("device arena allocation of %zu bytes failed", want);
+        set_error(fail, want);
         return ARCHON_E_NOMEM;
     }
-    c->arena_bytes = want;
+    *have = want;
     return ARCHON_OK;
+}
+
+int ctx_ensure_arena(Ctx *c, size_t bytes)
+{
+    return regrow(&c->arena, &c->arena_bytes, bytes, bytes + (bytes >> 4) + (1u << 20), "device arena allocation of %zu bytes failed");
 }
 
 // the second tier grows like the first; growing it never touches the first (a forward call asks for it in mid-flight)
 static int ctx_ensure_arena2(Ctx *c, size_t bytes)
 {
-    if (bytes <= c->arena2_bytes) return ARCHON_OK;
-    ARCHON_HIP_TRY(hipDeviceSynchronize());
-    if (c->arena2) {
-        ARCHON_HIP_TRY(hipFree(c->arena2));
-        c->arena2 = nullptr;
-        c->arena2_bytes = 0;
-    }
-    const size_t want = bytes + (bytes >> 4) + (1u << 20);
-    if (hipMalloc((void **)&c->arena2, want) != hipSuccess) {
-        (void)hipGetLastError();
-        set_error("device arena allocation of %zu bytes (general stage) failed", want);
-        return ARCHON_E_NOMEM;
-    }
-    c->arena2_bytes = want;
-    return ARCHON_OK;
+    return regrow(&c->arena2, &c->arena2_bytes, bytes, bytes + (bytes >> 4) + (1u << 20), "device arena allocation of %zu bytes (general stage) failed");
 }
 
 int ctx_io(Ctx *c, int slot, size_t bytes, void **out)
 {
-    if (bytes > c->io_bytes[slot]) {
-        ARCHON_HIP_TRY(hipDeviceSynchronize());
-        if (c->io[slot]) {
-            ARCHON_HIP_TRY(hipFree(c->io[slot]));
-            c->io[slot] = nullptr;
-            c->io_bytes[slot] = 0;
-        }
-        const size_t want = bytes + 256;
-        if (hipMalloc((void **)&c->io[slot], want) != hipSuccess) {
-            (void)hipGetLastError();
-            set_error("device staging allocation of %zu bytes failed", want);
-            return ARCHON_E_NOMEM;
-        }
-        c->io_bytes[slot] = want;
-    }
+    ARCHON_TRY(regrow(&c->io[slot], &c->io_bytes[slot], bytes, bytes + 256, "device staging allocation of %zu bytes failed"));
     *out = c->io[slot];
     return ARCHON_OK;
+}
+
+// Every entry point that computes runs `body` on the calling thread's context of `dev`, under the context's lock, with the
+// device set, on the caller's stream when it gave one and on the context's own otherwise.
+template <class Body>
+static int with_ctx(int dev, void *stream, Body &&body)
+{
+    Ctx *c;
+    ARCHON_TRY(ctx_get(dev, &c));
+    std::lock_guard<std::mutex> lk(c->mu);
+    ARCHON_HIP_TRY(hipSetDevice(dev));
+    return body(c, stream ? (hipStream_t)stream : c->own_stream);
 }
 
 // ------------------------------------------------------------------ forward driver
@@ -1627,81 +1631,65 @@ int archon_hip_forward_dev(const uint8_t *d_x, uint32_t n, uint32_t *d_sa_or_nul
 {
     if (!d_x || !d_bwt || !d_base_id) { set_error("null pointer"); return ARCHON_E_ARG; }
     ARCHON_TRY(check_n(n));
-    Ctx *c;
-    ARCHON_TRY(ctx_get(dev, &c));
-    std::lock_guard<std::mutex> lk(c->mu);
-    ARCHON_HIP_TRY(hipSetDevice(dev));
-    hipStream_t s = stream ? (hipStream_t)stream : c->own_stream;
-    return keep_stats(c, forward_run(c, s, d_x, n, d_sa_or_null, d_bwt, d_base_id));
+    return with_ctx(dev, stream, [&](Ctx *c, hipStream_t s) -> int { return keep_stats(c, forward_run(c, s, d_x, n, d_sa_or_null, d_bwt, d_base_id)); });
 }
 
 int archon_hip_forward(const uint8_t *x, uint32_t n, uint32_t *sa_or_null, uint8_t *bwt, uint32_t *base_id, int dev)
 {
     if (!x || !bwt || !base_id) { set_error("null pointer"); return ARCHON_E_ARG; }
     ARCHON_TRY(check_n(n));
-    Ctx *c;
-    ARCHON_TRY(ctx_get(dev, &c));
-    std::lock_guard<std::mutex> lk(c->mu);
-    ARCHON_HIP_TRY(hipSetDevice(dev));
-    hipStream_t s = c->own_stream;
-    uint8_t *d_x = nullptr, *d_bwt = nullptr;
-    uint32_t *d_sa = nullptr;
-    ARCHON_TRY(ctx_io(c, 0, (size_t)n + 64, (void **)&d_x));
-    ARCHON_TRY(ctx_io(c, 1, (size_t)n + 64, (void **)&d_bwt));
-    if (sa_or_null) ARCHON_TRY(ctx_io(c, 2, (size_t)n * 4, (void **)&d_sa));
-    uint32_t *d_base = c->d_mail + mail::kDevBase.at;
-    ARCHON_HIP_TRY(hipMemcpyAsync(d_x, x, n, hipMemcpyHostToDevice, s));
-    ARCHON_TRY(keep_stats(c, forward_run(c, s, d_x, n, d_sa, d_bwt, d_base)));
-    // BWT first (the block coder's enWrite can start on it), then the 4N bytes of the suffix array
-    ARCHON_HIP_TRY(hipMemcpyAsync(bwt, d_bwt, n, hipMemcpyDeviceToHost, s));
-    ARCHON_HIP_TRY(hipMemcpyAsync(base_id, d_base, 4, hipMemcpyDeviceToHost, s));
-    if (sa_or_null) ARCHON_HIP_TRY(hipMemcpyAsync(sa_or_null, d_sa, (size_t)n * 4, hipMemcpyDeviceToHost, s));
-    ARCHON_SYNC(s);
-    return ARCHON_OK;
+    return with_ctx(dev, nullptr, [&](Ctx *c, hipStream_t s) -> int {
+        uint8_t *d_x = nullptr, *d_bwt = nullptr;
+        uint32_t *d_sa = nullptr;
+        ARCHON_TRY(ctx_io(c, 0, (size_t)n + 64, (void **)&d_x));
+        ARCHON_TRY(ctx_io(c, 1, (size_t)n + 64, (void **)&d_bwt));
+        if (sa_or_null) ARCHON_TRY(ctx_io(c, 2, (size_t)n * 4, (void **)&d_sa));
+        uint32_t *d_base = c->d_mail + mail::kDevBase.at;
+        ARCHON_HIP_TRY(hipMemcpyAsync(d_x, x, n, hipMemcpyHostToDevice, s));
+        ARCHON_TRY(keep_stats(c, forward_run(c, s, d_x, n, d_sa, d_bwt, d_base)));
+        // BWT first (the block coder's enWrite can start on it), then the 4N bytes of the suffix array
+        ARCHON_HIP_TRY(hipMemcpyAsync(bwt, d_bwt, n, hipMemcpyDeviceToHost, s));
+        ARCHON_HIP_TRY(hipMemcpyAsync(base_id, d_base, 4, hipMemcpyDeviceToHost, s));
+        if (sa_or_null) ARCHON_HIP_TRY(hipMemcpyAsync(sa_or_null, d_sa, (size_t)n * 4, hipMemcpyDeviceToHost, s));
+        ARCHON_SYNC(s);
+        return ARCHON_OK;
+    });
 }
 
 // ---- the LCP array (lcp.hiph)
-static int lcp_call(int dev, hipStream_t stream, const uint8_t *d_x, uint32_t n, const uint32_t *d_sa, const uint8_t *d_bwt, uint32_t *d_lcp,
-                    const uint32_t *sa_host, uint32_t *lcp_host, const uint8_t *x_host)
-{
-    Ctx *c;
-    ARCHON_TRY(ctx_get(dev, &c));
-    std::lock_guard<std::mutex> lk(c->mu);
-    ARCHON_HIP_TRY(hipSetDevice(dev));
-    hipStream_t s = stream ? stream : c->own_stream;
-    if (x_host) {                       // host buffers: block, suffix array and result through the context's staging buffers
-        ARCHON_TRY(ctx_io(c, 0, (size_t)n + 64, (void **)&d_x));
-        ARCHON_TRY(ctx_io(c, 1, (size_t)n * 4 + 64, (void **)&d_lcp));
-        ARCHON_TRY(ctx_io(c, 2, (size_t)n * 4 + 64, (void **)&d_sa));
-        ARCHON_HIP_TRY(hipMemcpyAsync((void *)d_x, x_host, n, hipMemcpyHostToDevice, s));
-    } else if (lcp_host) {              // a resident block: the result through a staging buffer
-        ARCHON_TRY(ctx_io(c, 1, (size_t)n * 4 + 64, (void **)&d_lcp));
-    }
-    if (sa_host) ARCHON_HIP_TRY(hipMemcpyAsync((void *)d_sa, sa_host, (size_t)n * 4, hipMemcpyHostToDevice, s));
-    archon_hip_lcp_stats st = {};
-    const int rc = lcp_run(c, s, d_x, n, d_sa, d_bwt, d_lcp, &st);
-    t_lcp_stats[dev] = st;
-    t_lcp_stats_set[dev] = true;
-    ARCHON_TRY(rc);
-    if (lcp_host) {
-        ARCHON_HIP_TRY(hipMemcpyAsync(lcp_host, d_lcp, (size_t)n * 4, hipMemcpyDeviceToHost, s));
-        ARCHON_SYNC(s);
-    }
-    return ARCHON_OK;
-}
-
 int archon_hip_lcp_dev(const uint8_t *d_x, uint32_t n, const uint32_t *d_sa, uint32_t *d_lcp, int dev, void *stream)
 {
     if (!d_x || !d_sa || !d_lcp) { set_error("null pointer"); return ARCHON_E_ARG; }
     ARCHON_TRY(check_n(n));
-    return lcp_call(dev, (hipStream_t)stream, d_x, n, d_sa, nullptr, d_lcp, nullptr, nullptr, nullptr);
+    return with_ctx(dev, stream, [&](Ctx *c, hipStream_t s) -> int {
+        archon_hip_lcp_stats st = {};
+        const int rc = lcp_run(c, s, d_x, n, d_sa, nullptr, d_lcp, &st);
+        t_lcp_stats.keep(dev, st);
+        return rc;
+    });
 }
 
+// host buffers: block, suffix array and result through the context's staging buffers
 int archon_hip_lcp(const uint8_t *x, uint32_t n, const uint32_t *sa, uint32_t *lcp, int dev)
 {
     if (!x || !sa || !lcp) { set_error("null pointer"); return ARCHON_E_ARG; }
     ARCHON_TRY(check_n(n));
-    return lcp_call(dev, nullptr, nullptr, n, nullptr, nullptr, nullptr, sa, lcp, x);
+    return with_ctx(dev, nullptr, [&](Ctx *c, hipStream_t s) -> int {
+        uint8_t *d_x = nullptr;
+        uint32_t *d_lcp = nullptr, *d_sa = nullptr;
+        ARCHON_TRY(ctx_io(c, 0, (size_t)n + 64, (void **)&d_x));
+        ARCHON_TRY(ctx_io(c, 1, (size_t)n * 4 + 64, (void **)&d_lcp));
+        ARCHON_TRY(ctx_io(c, 2, (size_t)n * 4 + 64, (void **)&d_sa));
+        ARCHON_HIP_TRY(hipMemcpyAsync(d_x, x, n, hipMemcpyHostToDevice, s));
+        ARCHON_HIP_TRY(hipMemcpyAsync(d_sa, sa, (size_t)n * 4, hipMemcpyHostToDevice, s));
+        archon_hip_lcp_stats st = {};
+        const int rc = lcp_run(c, s, d_x, n, d_sa, nullptr, d_lcp, &st);
+        t_lcp_stats.keep(dev, st);
+        ARCHON_TRY(rc);
+        ARCHON_HIP_TRY(hipMemcpyAsync(lcp, d_lcp, (size_t)n * 4, hipMemcpyDeviceToHost, s));
+        ARCHON_SYNC(s);
+        return ARCHON_OK;
+    });
 }
 
 // ---- the FM index (fm.hiph)
@@ -1835,12 +1823,6 @@ static int fm_check_offsets(const uint32_t *offsets, uint32_t k)
     return ARCHON_OK;
 }
 
-static void fm_keep_stats(int dev, const archon_hip_fm_stats &st)
-{
-    t_fm_stats[dev] = st;
-    t_fm_stats_set[dev] = true;
-}
-
 // Host patterns and ranges through the context's arena.  When `locate` is given (a resident block's suffix array, or the
 // samples of a sampled handle: d_sa null), the ranges come back, the host sums them, and a gather or the LF walks write the
 // starts (the walks' counters into *wst).
@@ -1930,14 +1912,12 @@ int archon_hip_fm_create(const uint8_t *bwt, uint32_t n, uint32_t base_id, int d
     if (!bwt || !out) { set_error("null pointer"); return ARCHON_E_ARG; }
     ARCHON_TRY(check_n(n));
     if (base_id >= n) { set_error("primary row %u out of range [0, %u)", base_id, n); return ARCHON_E_ARG; }
-    Ctx *c;
-    ARCHON_TRY(ctx_get(dev, &c));
-    std::lock_guard<std::mutex> lk(c->mu);
-    ARCHON_HIP_TRY(hipSetDevice(dev));
-    archon_hip_fm_stats st = {};
-    const int rc = fm_build(c, c->own_stream, bwt, nullptr, true, n, base_id, out, &st);
-    fm_keep_stats(dev, st);
-    return rc;
+    return with_ctx(dev, nullptr, [&](Ctx *c, hipStream_t s) -> int {
+        archon_hip_fm_stats st = {};
+        const int rc = fm_build(c, s, bwt, nullptr, true, n, base_id, out, &st);
+        t_fm_stats.keep(dev, st);
+        return rc;
+    });
 }
 
 int archon_hip_fm_create_dev(const uint8_t *d_bwt, uint32_t n, uint32_t base_id, int dev, void *stream, archon_hip_fm **out)
@@ -1945,14 +1925,12 @@ int archon_hip_fm_create_dev(const uint8_t *d_bwt, uint32_t n, uint32_t base_id,
     if (!d_bwt || !out) { set_error("null pointer"); return ARCHON_E_ARG; }
     ARCHON_TRY(check_n(n));
     if (base_id >= n) { set_error("primary row %u out of range [0, %u)", base_id, n); return ARCHON_E_ARG; }
-    Ctx *c;
-    ARCHON_TRY(ctx_get(dev, &c));
-    std::lock_guard<std::mutex> lk(c->mu);
-    ARCHON_HIP_TRY(hipSetDevice(dev));
-    archon_hip_fm_stats st = {};
-    const int rc = fm_build(c, stream ? (hipStream_t)stream : c->own_stream, nullptr, d_bwt, true, n, base_id, out, &st);
-    fm_keep_stats(dev, st);
-    return rc;
+    return with_ctx(dev, stream, [&](Ctx *c, hipStream_t s) -> int {
+        archon_hip_fm_stats st = {};
+        const int rc = fm_build(c, s, nullptr, d_bwt, true, n, base_id, out, &st);
+        t_fm_stats.keep(dev, st);
+        return rc;
+    });
 }
 
 void archon_hip_fm_destroy(archon_hip_fm *f) { fm_release(f); }
@@ -1962,14 +1940,12 @@ int archon_hip_fm_count(archon_hip_fm *f, const uint8_t *patterns, const uint32_
     if (!f || !patterns || !offsets || !lo || !hi) { set_error("null pointer"); return ARCHON_E_ARG; }
     if (!k) return ARCHON_OK;
     ARCHON_TRY(fm_check_offsets(offsets, k));
-    Ctx *c;
-    ARCHON_TRY(ctx_get(f->dev, &c));
-    std::lock_guard<std::mutex> lk(c->mu);
-    ARCHON_HIP_TRY(hipSetDevice(f->dev));
-    archon_hip_fm_stats st = {};
-    const int rc = fm_host_query(c, c->own_stream, f, patterns, offsets, k, lo, hi, nullptr, &st);
-    fm_keep_stats(f->dev, st);
-    return rc;
+    return with_ctx(f->dev, nullptr, [&](Ctx *c, hipStream_t s) -> int {
+        archon_hip_fm_stats st = {};
+        const int rc = fm_host_query(c, s, f, patterns, offsets, k, lo, hi, nullptr, &st);
+        t_fm_stats.keep(f->dev, st);
+        return rc;
+    });
 }
 
 int archon_hip_fm_count_dev(archon_hip_fm *f, const uint8_t *d_patterns, const uint32_t *d_offsets, uint32_t k, uint32_t *d_lo, uint32_t *d_hi,
@@ -1977,44 +1953,34 @@ int archon_hip_fm_count_dev(archon_hip_fm *f, const uint8_t *d_patterns, const u
 {
     if (!f || !d_patterns || !d_offsets || !d_lo || !d_hi) { set_error("null pointer"); return ARCHON_E_ARG; }
     if (!k) return ARCHON_OK;
-    Ctx *c;
-    ARCHON_TRY(ctx_get(f->dev, &c));
-    std::lock_guard<std::mutex> lk(c->mu);
-    ARCHON_HIP_TRY(hipSetDevice(f->dev));
-    hipStream_t s = stream ? (hipStream_t)stream : c->own_stream;
-    archon_hip_fm_stats st = {};
-    st.n = f->n;
-    st.patterns = k;
-    st.table_bytes = f->table_bytes;
-    const uint32_t syncs0 = t_sync_count;
-    uint32_t *ends = c->h_mail + mail::kRead.at + fmk::kWords;     // offsets[0] and offsets[k], for the statistics
-    static_assert(fmk::kWords + 2 <= mail::kRead.len, "the FM words and the offsets' ends in the readback words");
-    ARCHON_HIP_TRY(hipMemcpyAsync(&ends[0], d_offsets, 4, hipMemcpyDeviceToHost, s));
-    ARCHON_HIP_TRY(hipMemcpyAsync(&ends[1], d_offsets + k, 4, hipMemcpyDeviceToHost, s));
-    StageTimer tm(c, 72, s);
-    const int e0 = tm.mark();
-    const int rc = fm_count_run(c, s, f, d_patterns, d_offsets, k, d_lo, d_hi, tm, &st);
-    st.ms_query = tm.ms(e0, tm.n - 1);
-    st.pattern_bytes = ends[1] >= ends[0] ? ends[1] - ends[0] : 0;
-    st.host_syncs = t_sync_count - syncs0;
-    fm_keep_stats(f->dev, st);
-    return rc;
+    return with_ctx(f->dev, stream, [&](Ctx *c, hipStream_t s) -> int {
+        archon_hip_fm_stats st = {};
+        st.n = f->n;
+        st.patterns = k;
+        st.table_bytes = f->table_bytes;
+        const uint32_t syncs0 = t_sync_count;
+        uint32_t *ends = c->h_mail + mail::kRead.at + fmk::kWords;     // offsets[0] and offsets[k], for the statistics
+        static_assert(fmk::kWords + 2 <= mail::kRead.len, "the FM words and the offsets' ends in the readback words");
+        ARCHON_HIP_TRY(hipMemcpyAsync(&ends[0], d_offsets, 4, hipMemcpyDeviceToHost, s));
+        ARCHON_HIP_TRY(hipMemcpyAsync(&ends[1], d_offsets + k, 4, hipMemcpyDeviceToHost, s));
+        StageTimer tm(c, 72, s);
+        const int e0 = tm.mark();
+        const int rc = fm_count_run(c, s, f, d_patterns, d_offsets, k, d_lo, d_hi, tm, &st);
+        st.ms_query = tm.ms(e0, tm.n - 1);
+        st.pattern_bytes = ends[1] >= ends[0] ? ends[1] - ends[0] : 0;
+        st.host_syncs = t_sync_count - syncs0;
+        t_fm_stats.keep(f->dev, st);
+        return rc;
+    });
 }
 
 int archon_hip_get_fm_stats(int dev, archon_hip_fm_stats *out)
 {
     if (!out) { set_error("null pointer"); return ARCHON_E_ARG; }
-    if (dev < 0 || dev >= kMaxDev || !t_fm_stats_set[dev]) { set_error("the calling thread has run no FM call on device %d", dev); return ARCHON_E_ARG; }
-    *out = t_fm_stats[dev];
-    return ARCHON_OK;
+    return t_fm_stats.get(dev, out, "FM call");
 }
 
 // ---- the sampled FM index (fm_walk.hiph)
-static void fmw_keep_stats(int dev, const archon_hip_fm_walk_stats &st)
-{
-    t_fmw_stats[dev] = st;
-    t_fmw_stats_set[dev] = true;
-}
 
 static int fmw_rate_bits(uint32_t rate, uint32_t *rbits)
 {
@@ -2158,14 +2124,12 @@ int archon_hip_fm_sample(archon_hip_fm *f, uint32_t rate)
     if (!f) { set_error("null pointer"); return ARCHON_E_ARG; }
     uint32_t rbits;
     ARCHON_TRY(fmw_rate_bits(rate, &rbits));
-    Ctx *c;
-    ARCHON_TRY(ctx_get(f->dev, &c));
-    std::lock_guard<std::mutex> lk(c->mu);
-    ARCHON_HIP_TRY(hipSetDevice(f->dev));
-    archon_hip_fm_walk_stats st = {};
-    const int rc = fm_sample_run(c, c->own_stream, f, rbits, nullptr, &st);
-    fmw_keep_stats(f->dev, st);
-    return rc;
+    return with_ctx(f->dev, nullptr, [&](Ctx *c, hipStream_t s) -> int {
+        archon_hip_fm_walk_stats st = {};
+        const int rc = fm_sample_run(c, s, f, rbits, nullptr, &st);
+        t_fmw_stats.keep(f->dev, st);
+        return rc;
+    });
 }
 
 int archon_hip_fm_read_samples(archon_hip_fm *f, uint32_t *isa, uint32_t cap, uint32_t *count)
@@ -2186,21 +2150,19 @@ int archon_hip_fm_locate(archon_hip_fm *f, const uint8_t *patterns, const uint32
     *total = 0;
     if (!k) return ARCHON_OK;
     ARCHON_TRY(fm_check_offsets(offsets, k));
-    Ctx *c;
-    ARCHON_TRY(ctx_get(f->dev, &c));
-    std::lock_guard<std::mutex> lk(c->mu);
-    ARCHON_HIP_TRY(hipSetDevice(f->dev));
-    archon_hip_fm_stats st = {};
-    archon_hip_fm_walk_stats wst = {};
-    fmw_handle_stats(f, &wst);
-    std::vector<uint32_t> lo(k), hi(k);
-    const FmLocate loc{nullptr, pos, cap, total, &wst};
-    const uint32_t syncs0 = t_sync_count;
-    const int rc = fm_host_query(c, c->own_stream, f, patterns, offsets, k, lo.data(), hi.data(), &loc, &st);
-    wst.host_syncs = t_sync_count - syncs0;
-    fm_keep_stats(f->dev, st);
-    fmw_keep_stats(f->dev, wst);
-    return rc;
+    return with_ctx(f->dev, nullptr, [&](Ctx *c, hipStream_t s) -> int {
+        archon_hip_fm_stats st = {};
+        archon_hip_fm_walk_stats wst = {};
+        fmw_handle_stats(f, &wst);
+        std::vector<uint32_t> lo(k), hi(k);
+        const FmLocate loc{nullptr, pos, cap, total, &wst};
+        const uint32_t syncs0 = t_sync_count;
+        const int rc = fm_host_query(c, s, f, patterns, offsets, k, lo.data(), hi.data(), &loc, &st);
+        wst.host_syncs = t_sync_count - syncs0;
+        t_fm_stats.keep(f->dev, st);
+        t_fmw_stats.keep(f->dev, wst);
+        return rc;
+    });
 }
 
 // Requests on the device (d_starts, d_off) into d_out[off[j] - shift ..): checks, segment counts and their sums, the walks.
@@ -2243,33 +2205,30 @@ int archon_hip_fm_extract(archon_hip_fm *f, const uint32_t *starts, const uint32
             return ARCHON_E_ARG;
         }
     }
-    Ctx *c;
-    ARCHON_TRY(ctx_get(f->dev, &c));
-    std::lock_guard<std::mutex> lk(c->mu);
-    ARCHON_HIP_TRY(hipSetDevice(f->dev));
-    hipStream_t s = c->own_stream;
-    archon_hip_fm_walk_stats st = {};
-    fmw_handle_stats(f, &st);
-    const uint32_t syncs0 = t_sync_count;
-    const size_t bytes = (size_t)offsets[k] - offsets[0];
-    FmqArena L;
-    int rc = ctx_carve(c, [&](Carve &a) { return fmq_layout(a, L, k, bytes, true); });
-    if (rc == ARCHON_OK) {
-        auto up = [&]() -> int {
-            ARCHON_HIP_TRY(hipMemcpyAsync(L.starts, starts, (size_t)k * 4, hipMemcpyHostToDevice, s));
-            ARCHON_HIP_TRY(hipMemcpyAsync(L.off, offsets, ((size_t)k + 1) * 4, hipMemcpyHostToDevice, s));
-            ARCHON_TRY(fm_extract_run(c, s, f, L.starts, L.off, k, L.out, offsets[0], L, &st));
-            if (bytes) {
-                ARCHON_HIP_TRY(hipMemcpyAsync(out + offsets[0], L.out, bytes, hipMemcpyDeviceToHost, s));
-                ARCHON_SYNC(s);
-            }
-            return ARCHON_OK;
-        };
-        rc = up();
-    }
-    st.host_syncs = t_sync_count - syncs0;
-    fmw_keep_stats(f->dev, st);
-    return rc;
+    return with_ctx(f->dev, nullptr, [&](Ctx *c, hipStream_t s) -> int {
+        archon_hip_fm_walk_stats st = {};
+        fmw_handle_stats(f, &st);
+        const uint32_t syncs0 = t_sync_count;
+        const size_t bytes = (size_t)offsets[k] - offsets[0];
+        FmqArena L;
+        int rc = ctx_carve(c, [&](Carve &a) { return fmq_layout(a, L, k, bytes, true); });
+        if (rc == ARCHON_OK) {
+            auto up = [&]() -> int {
+                ARCHON_HIP_TRY(hipMemcpyAsync(L.starts, starts, (size_t)k * 4, hipMemcpyHostToDevice, s));
+                ARCHON_HIP_TRY(hipMemcpyAsync(L.off, offsets, ((size_t)k + 1) * 4, hipMemcpyHostToDevice, s));
+                ARCHON_TRY(fm_extract_run(c, s, f, L.starts, L.off, k, L.out, offsets[0], L, &st));
+                if (bytes) {
+                    ARCHON_HIP_TRY(hipMemcpyAsync(out + offsets[0], L.out, bytes, hipMemcpyDeviceToHost, s));
+                    ARCHON_SYNC(s);
+                }
+                return ARCHON_OK;
+            };
+            rc = up();
+        }
+        st.host_syncs = t_sync_count - syncs0;
+        t_fmw_stats.keep(f->dev, st);
+        return rc;
+    });
 }
 
 int archon_hip_fm_extract_dev(archon_hip_fm *f, const uint32_t *d_starts, const uint32_t *d_offsets, uint32_t k, uint8_t *d_out, void *stream)
@@ -2277,27 +2236,23 @@ int archon_hip_fm_extract_dev(archon_hip_fm *f, const uint32_t *d_starts, const 
     if (!f || !d_starts || !d_offsets || !d_out) { set_error("null pointer"); return ARCHON_E_ARG; }
     if (!f->rate) { set_error("FM index: the handle has no samples (archon_hip_fm_sample)"); return ARCHON_E_ARG; }
     if (!k) return ARCHON_OK;
-    Ctx *c;
-    ARCHON_TRY(ctx_get(f->dev, &c));
-    std::lock_guard<std::mutex> lk(c->mu);
-    ARCHON_HIP_TRY(hipSetDevice(f->dev));
-    archon_hip_fm_walk_stats st = {};
-    fmw_handle_stats(f, &st);
-    const uint32_t syncs0 = t_sync_count;
-    FmqArena L;
-    int rc = ctx_carve(c, [&](Carve &a) { return fmq_layout(a, L, k, 0, false); });
-    if (rc == ARCHON_OK) rc = fm_extract_run(c, stream ? (hipStream_t)stream : c->own_stream, f, d_starts, d_offsets, k, d_out, 0, L, &st);
-    st.host_syncs = t_sync_count - syncs0;
-    fmw_keep_stats(f->dev, st);
-    return rc;
+    return with_ctx(f->dev, stream, [&](Ctx *c, hipStream_t s) -> int {
+        archon_hip_fm_walk_stats st = {};
+        fmw_handle_stats(f, &st);
+        const uint32_t syncs0 = t_sync_count;
+        FmqArena L;
+        int rc = ctx_carve(c, [&](Carve &a) { return fmq_layout(a, L, k, 0, false); });
+        if (rc == ARCHON_OK) rc = fm_extract_run(c, s, f, d_starts, d_offsets, k, d_out, 0, L, &st);
+        st.host_syncs = t_sync_count - syncs0;
+        t_fmw_stats.keep(f->dev, st);
+        return rc;
+    });
 }
 
 int archon_hip_get_fm_walk_stats(int dev, archon_hip_fm_walk_stats *out)
 {
     if (!out) { set_error("null pointer"); return ARCHON_E_ARG; }
-    if (dev < 0 || dev >= kMaxDev || !t_fmw_stats_set[dev]) { set_error("the calling thread has run no sampled FM call on device %d", dev); return ARCHON_E_ARG; }
-    *out = t_fmw_stats[dev];
-    return ARCHON_OK;
+    return t_fmw_stats.get(dev, out, "sampled FM call");
 }
 
 // ---- resident blocks ---------------------------------------------------------------------------------------------------
@@ -2348,9 +2303,7 @@ static int block_reserve(archon_hip_block *b, uint32_t n, bool want_sa)
 int archon_hip_block_create(int dev, archon_hip_block **out)
 {
     if (!out) { set_error("null pointer"); return ARCHON_E_ARG; }
-    const int ndev = device_count();
-    if (ndev <= 0) { set_error("no HIP device available (libarchon_hip has no CPU fallback)"); return ARCHON_E_NODEVICE; }
-    if (dev < 0 || dev >= ndev || dev >= kMaxDev) { set_error("device %d out of range (have %d)", dev, ndev); return ARCHON_E_NODEVICE; }
+    ARCHON_TRY(check_device(dev));
     archon_hip_block *b = new archon_hip_block();
     b->dev = dev;
     memset(&b->stats, 0, sizeof b->stats);
@@ -2382,27 +2335,23 @@ int archon_hip_block_forward(archon_hip_block *b, const uint8_t *x, uint32_t n, 
     b->valid = false;
     fm_release(b->fm);
     b->fm = nullptr;
-    Ctx *c;
-    ARCHON_TRY(ctx_get(b->dev, &c));
-    std::lock_guard<std::mutex> lk(c->mu);
-    ARCHON_HIP_TRY(hipSetDevice(b->dev));
-    ARCHON_TRY(block_reserve(b, n, sa_or_null != nullptr));
-    hipStream_t s = c->own_stream;
-    uint32_t *d_sa = sa_or_null ? b->d_sa : nullptr;
-    uint32_t *d_base = c->d_mail + mail::kDevBase.at;
-    ARCHON_HIP_TRY(hipMemcpyAsync(b->d_x, x, n, hipMemcpyHostToDevice, s));
-    ARCHON_TRY(forward_run(c, s, b->d_x, n, d_sa, b->d_bwt, d_base));
-    ARCHON_HIP_TRY(hipMemcpyAsync(base_id, d_base, 4, hipMemcpyDeviceToHost, s));
-    if (sa_or_null) ARCHON_HIP_TRY(hipMemcpyAsync(sa_or_null, d_sa, (size_t)n * 4, hipMemcpyDeviceToHost, s));
-    ARCHON_SYNC(s);
-    b->n = n;
-    b->base = *base_id;
-    b->has_sa = sa_or_null != nullptr;
-    b->valid = true;
-    b->stats = c->stats;
-    t_stats[b->dev] = c->stats;
-    t_stats_set[b->dev] = true;
-    return ARCHON_OK;
+    return with_ctx(b->dev, nullptr, [&](Ctx *c, hipStream_t s) -> int {
+        ARCHON_TRY(block_reserve(b, n, sa_or_null != nullptr));
+        uint32_t *d_sa = sa_or_null ? b->d_sa : nullptr;
+        uint32_t *d_base = c->d_mail + mail::kDevBase.at;
+        ARCHON_HIP_TRY(hipMemcpyAsync(b->d_x, x, n, hipMemcpyHostToDevice, s));
+        ARCHON_TRY(forward_run(c, s, b->d_x, n, d_sa, b->d_bwt, d_base));
+        ARCHON_HIP_TRY(hipMemcpyAsync(base_id, d_base, 4, hipMemcpyDeviceToHost, s));
+        if (sa_or_null) ARCHON_HIP_TRY(hipMemcpyAsync(sa_or_null, d_sa, (size_t)n * 4, hipMemcpyDeviceToHost, s));
+        ARCHON_SYNC(s);
+        b->n = n;
+        b->base = *base_id;
+        b->has_sa = sa_or_null != nullptr;
+        b->valid = true;
+        b->stats = c->stats;
+        t_stats.keep(b->dev, c->stats);
+        return ARCHON_OK;
+    });
 }
 
 int archon_hip_block_read_bwt(archon_hip_block *b, uint32_t offset, uint32_t len, uint8_t *dst)
@@ -2420,40 +2369,39 @@ int archon_hip_block_validate(archon_hip_block *b)
     if (!b) { set_error("null pointer"); return ARCHON_E_ARG; }
     std::lock_guard<std::mutex> lkb(b->mu);
     if (!b->valid || !b->has_sa) { set_error("no resident block with its suffix array"); return ARCHON_E_ARG; }
-    Ctx *c;
-    ARCHON_TRY(ctx_get(b->dev, &c));
-    std::lock_guard<std::mutex> lk(c->mu);
-    ARCHON_HIP_TRY(hipSetDevice(b->dev));
-    return validate_resident_run(c, c->own_stream, b->d_x, b->n, b->d_sa, b->d_bwt, b->base);
+    return with_ctx(b->dev, nullptr, [&](Ctx *c, hipStream_t s) -> int { return validate_resident_run(c, s, b->d_x, b->n, b->d_sa, b->d_bwt, b->base); });
 }
 
+// the result through a staging buffer
 int archon_hip_block_lcp(archon_hip_block *b, uint32_t *lcp)
 {
     if (!b || !lcp) { set_error("null pointer"); return ARCHON_E_ARG; }
     std::lock_guard<std::mutex> lkb(b->mu);
     if (!b->valid || !b->has_sa) { set_error("no resident block with its suffix array"); return ARCHON_E_ARG; }
-    return lcp_call(b->dev, nullptr, b->d_x, b->n, b->d_sa, b->d_bwt, nullptr, nullptr, lcp, nullptr);
-}
-
-// the block's FM handle over its own BWT: built on the first FM call after a forward (b->mu and the context held)
-static int block_fm(archon_hip_block *b, Ctx *c, archon_hip_fm_stats *st)
-{
-    if (b->fm) return ARCHON_OK;
-    return fm_build(c, c->own_stream, nullptr, b->d_bwt, false, b->n, b->base, &b->fm, st);
+    return with_ctx(b->dev, nullptr, [&](Ctx *c, hipStream_t s) -> int {
+        uint32_t *d_lcp = nullptr;
+        ARCHON_TRY(ctx_io(c, 1, (size_t)b->n * 4 + 64, (void **)&d_lcp));
+        archon_hip_lcp_stats st = {};
+        const int rc = lcp_run(c, s, b->d_x, b->n, b->d_sa, b->d_bwt, d_lcp, &st);
+        t_lcp_stats.keep(b->dev, st);
+        ARCHON_TRY(rc);
+        ARCHON_HIP_TRY(hipMemcpyAsync(lcp, d_lcp, (size_t)b->n * 4, hipMemcpyDeviceToHost, s));
+        ARCHON_SYNC(s);
+        return ARCHON_OK;
+    });
 }
 
 static int block_fm_query(archon_hip_block *b, const uint8_t *patterns, const uint32_t *offsets, uint32_t k, uint32_t *lo, uint32_t *hi,
                           const FmLocate *loc)
 {
-    Ctx *c;
-    ARCHON_TRY(ctx_get(b->dev, &c));
-    std::lock_guard<std::mutex> lk(c->mu);
-    ARCHON_HIP_TRY(hipSetDevice(b->dev));
-    archon_hip_fm_stats st = {};
-    int rc = block_fm(b, c, &st);
-    if (rc == ARCHON_OK) rc = fm_host_query(c, c->own_stream, b->fm, patterns, offsets, k, lo, hi, loc, &st);
-    fm_keep_stats(b->dev, st);
-    return rc;
+    return with_ctx(b->dev, nullptr, [&](Ctx *c, hipStream_t s) -> int {
+        archon_hip_fm_stats st = {};
+        // the block's FM handle over its own BWT: built on the first FM call after a forward
+        int rc = b->fm ? ARCHON_OK : fm_build(c, s, nullptr, b->d_bwt, false, b->n, b->base, &b->fm, &st);
+        if (rc == ARCHON_OK) rc = fm_host_query(c, s, b->fm, patterns, offsets, k, lo, hi, loc, &st);
+        t_fm_stats.keep(b->dev, st);
+        return rc;
+    });
 }
 
 int archon_hip_block_fm_count(archon_hip_block *b, const uint8_t *patterns, const uint32_t *offsets, uint32_t k, uint32_t *lo, uint32_t *hi)
@@ -2487,23 +2435,21 @@ int archon_hip_block_fm_index(archon_hip_block *b, uint32_t rate, archon_hip_fm 
     ARCHON_TRY(fmw_rate_bits(rate, &rbits));
     std::lock_guard<std::mutex> lkb(b->mu);
     if (!b->valid) { set_error("no resident block"); return ARCHON_E_ARG; }
-    Ctx *c;
-    ARCHON_TRY(ctx_get(b->dev, &c));
-    std::lock_guard<std::mutex> lk(c->mu);
-    ARCHON_HIP_TRY(hipSetDevice(b->dev));
-    archon_hip_fm_stats st = {};
-    archon_hip_fm_walk_stats wst = {};
-    archon_hip_fm *f = nullptr;
-    int rc = fm_build(c, c->own_stream, nullptr, b->d_bwt, true, b->n, b->base, &f, &st);
-    fm_keep_stats(b->dev, st);
-    if (rc == ARCHON_OK) {
-        const bool from_sa = b->has_sa && !g_route.fm_sample_walk;
-        rc = fm_sample_run(c, c->own_stream, f, rbits, from_sa ? b->d_sa : nullptr, &wst);
-        fmw_keep_stats(b->dev, wst);
-        if (rc != ARCHON_OK) fm_release(f);
-        else *out = f;
-    }
-    return rc;
+    return with_ctx(b->dev, nullptr, [&](Ctx *c, hipStream_t s) -> int {
+        archon_hip_fm_stats st = {};
+        archon_hip_fm_walk_stats wst = {};
+        archon_hip_fm *f = nullptr;
+        int rc = fm_build(c, s, nullptr, b->d_bwt, true, b->n, b->base, &f, &st);
+        t_fm_stats.keep(b->dev, st);
+        if (rc == ARCHON_OK) {
+            const bool from_sa = b->has_sa && !g_route.fm_sample_walk;
+            rc = fm_sample_run(c, s, f, rbits, from_sa ? b->d_sa : nullptr, &wst);
+            t_fmw_stats.keep(b->dev, wst);
+            if (rc != ARCHON_OK) fm_release(f);
+            else *out = f;
+        }
+        return rc;
+    });
 }
 
 int archon_hip_block_stats(archon_hip_block *b, archon_hip_stats *out)
@@ -2614,12 +2560,7 @@ int archon_hip_inverse_dev(const uint8_t *d_bwt, uint32_t n, uint32_t base_id, u
     if (!d_bwt || !d_x_out) { set_error("null pointer"); return ARCHON_E_ARG; }
     ARCHON_TRY(check_n(n));
     if (base_id >= n) { set_error("base_id %u >= n %u", base_id, n); return ARCHON_E_ARG; }
-    Ctx *c;
-    ARCHON_TRY(ctx_get(dev, &c));
-    std::lock_guard<std::mutex> lk(c->mu);
-    ARCHON_HIP_TRY(hipSetDevice(dev));
-    hipStream_t s = stream ? (hipStream_t)stream : c->own_stream;
-    return keep_stats(c, inverse_run(c, s, d_bwt, n, base_id, d_x_out));
+    return with_ctx(dev, stream, [&](Ctx *c, hipStream_t s) -> int { return keep_stats(c, inverse_run(c, s, d_bwt, n, base_id, d_x_out)); });
 }
 
 int archon_hip_inverse(const uint8_t *bwt, uint32_t n, uint32_t base_id, uint8_t *x_out, int dev)
@@ -2627,95 +2568,73 @@ int archon_hip_inverse(const uint8_t *bwt, uint32_t n, uint32_t base_id, uint8_t
     if (!bwt || !x_out) { set_error("null pointer"); return ARCHON_E_ARG; }
     ARCHON_TRY(check_n(n));
     if (base_id >= n) { set_error("base_id %u >= n %u", base_id, n); return ARCHON_E_ARG; }
-    Ctx *c;
-    ARCHON_TRY(ctx_get(dev, &c));
-    std::lock_guard<std::mutex> lk(c->mu);
-    ARCHON_HIP_TRY(hipSetDevice(dev));
-    hipStream_t s = c->own_stream;
-    uint8_t *d_in = nullptr, *d_out = nullptr;
-    ARCHON_TRY(ctx_io(c, 0, (size_t)n + 64, (void **)&d_in));
-    ARCHON_TRY(ctx_io(c, 1, (size_t)n + 64, (void **)&d_out));
-    ARCHON_HIP_TRY(hipMemcpyAsync(d_in, bwt, n, hipMemcpyHostToDevice, s));
-    ARCHON_TRY(keep_stats(c, inverse_run(c, s, d_in, n, base_id, d_out)));
-    ARCHON_HIP_TRY(hipMemcpyAsync(x_out, d_out, n, hipMemcpyDeviceToHost, s));
-    ARCHON_SYNC(s);
-    return ARCHON_OK;
+    return with_ctx(dev, nullptr, [&](Ctx *c, hipStream_t s) -> int {
+        uint8_t *d_in = nullptr, *d_out = nullptr;
+        ARCHON_TRY(ctx_io(c, 0, (size_t)n + 64, (void **)&d_in));
+        ARCHON_TRY(ctx_io(c, 1, (size_t)n + 64, (void **)&d_out));
+        ARCHON_HIP_TRY(hipMemcpyAsync(d_in, bwt, n, hipMemcpyHostToDevice, s));
+        ARCHON_TRY(keep_stats(c, inverse_run(c, s, d_in, n, base_id, d_out)));
+        ARCHON_HIP_TRY(hipMemcpyAsync(x_out, d_out, n, hipMemcpyDeviceToHost, s));
+        ARCHON_SYNC(s);
+        return ARCHON_OK;
+    });
 }
 
 int archon_hip_hist256_dev(const uint8_t *d_x, size_t n, uint32_t *d_out256, int dev, void *stream)
 {
     if (!d_x || !d_out256) { set_error("null pointer"); return ARCHON_E_ARG; }
-    Ctx *c;
-    ARCHON_TRY(ctx_get(dev, &c));
-    std::lock_guard<std::mutex> lk(c->mu);
-    ARCHON_HIP_TRY(hipSetDevice(dev));
-    hipStream_t s = stream ? (hipStream_t)stream : c->own_stream;
-    ARCHON_TRY(launch_hist256(s, d_x, n, d_out256, n));
-    ARCHON_SYNC(s);
-    return ARCHON_OK;
+    return with_ctx(dev, stream, [&](Ctx *, hipStream_t s) -> int {
+        ARCHON_TRY(launch_hist256(s, d_x, n, d_out256, n));
+        ARCHON_SYNC(s);
+        return ARCHON_OK;
+    });
 }
 
 int archon_hip_hist256(const uint8_t *x, size_t n, uint32_t out[256], int dev)
 {
     if (!x || !out) { set_error("null pointer"); return ARCHON_E_ARG; }
-    Ctx *c;
-    ARCHON_TRY(ctx_get(dev, &c));
-    std::lock_guard<std::mutex> lk(c->mu);
-    ARCHON_HIP_TRY(hipSetDevice(dev));
-    hipStream_t s = c->own_stream;
-    uint8_t *d_x = nullptr;
-    ARCHON_HIP_TRY(hipMalloc((void **)&d_x, n + 64));
-    hipError_t e = hipMemcpyAsync(d_x, x, n, hipMemcpyHostToDevice, s);
-    int rc = ARCHON_OK;
-    uint32_t *d_counts = c->d_mail + mail::kDevCounts.at;
-    if (e == hipSuccess) rc = launch_hist256(s, d_x, n, d_counts, n);
-    if (e == hipSuccess && rc == ARCHON_OK) e = hipMemcpyAsync(out, d_counts, 256 * 4, hipMemcpyDeviceToHost, s);
-    if (e == hipSuccess) e = hipStreamSynchronize(s);
-    (void)hipFree(d_x);
-    if (e != hipSuccess) { set_error("HIP call failed: %s", hipGetErrorString(e)); return ARCHON_E_HIP; }
-    return rc;
+    return with_ctx(dev, nullptr, [&](Ctx *c, hipStream_t s) -> int {
+        uint8_t *d_x = nullptr;
+        ARCHON_HIP_TRY(hipMalloc((void **)&d_x, n + 64));
+        hipError_t e = hipMemcpyAsync(d_x, x, n, hipMemcpyHostToDevice, s);
+        int rc = ARCHON_OK;
+        uint32_t *d_counts = c->d_mail + mail::kDevCounts.at;
+        if (e == hipSuccess) rc = launch_hist256(s, d_x, n, d_counts, n);
+        if (e == hipSuccess && rc == ARCHON_OK) e = hipMemcpyAsync(out, d_counts, 256 * 4, hipMemcpyDeviceToHost, s);
+        if (e == hipSuccess) e = hipStreamSynchronize(s);
+        (void)hipFree(d_x);
+        if (e != hipSuccess) { set_error("HIP call failed: %s", hipGetErrorString(e)); return ARCHON_E_HIP; }
+        return rc;
+    });
 }
 
 int archon_hip_validate_dev(const uint8_t *d_x, uint32_t n, const uint32_t *d_sa, int dev, void *stream)
 {
     if (!d_x || !d_sa) { set_error("null pointer"); return ARCHON_E_ARG; }
     ARCHON_TRY(check_n(n));
-    Ctx *c;
-    ARCHON_TRY(ctx_get(dev, &c));
-    std::lock_guard<std::mutex> lk(c->mu);
-    ARCHON_HIP_TRY(hipSetDevice(dev));
-    hipStream_t s = stream ? (hipStream_t)stream : c->own_stream;
-    return validate_run(c, s, d_x, n, d_sa);
+    return with_ctx(dev, stream, [&](Ctx *c, hipStream_t s) -> int { return validate_run(c, s, d_x, n, d_sa); });
 }
 
 int archon_hip_validate_resident_dev(const uint8_t *d_x, uint32_t n, const uint32_t *d_sa, const uint8_t *d_bwt, uint32_t base_id, int dev, void *stream)
 {
     if (!d_x || !d_sa || !d_bwt) { set_error("null pointer"); return ARCHON_E_ARG; }
     ARCHON_TRY(check_n(n));
-    Ctx *c;
-    ARCHON_TRY(ctx_get(dev, &c));
-    std::lock_guard<std::mutex> lk(c->mu);
-    ARCHON_HIP_TRY(hipSetDevice(dev));
-    hipStream_t s = stream ? (hipStream_t)stream : c->own_stream;
-    return validate_resident_run(c, s, d_x, n, d_sa, d_bwt, base_id);
+    return with_ctx(dev, stream, [&](Ctx *c, hipStream_t s) -> int { return validate_resident_run(c, s, d_x, n, d_sa, d_bwt, base_id); });
 }
 
 int archon_hip_validate(const uint8_t *x, uint32_t n, const uint32_t *sa, int dev)
 {
     if (!x || !sa) { set_error("null pointer"); return ARCHON_E_ARG; }
     ARCHON_TRY(check_n(n));
-    Ctx *c;
-    ARCHON_TRY(ctx_get(dev, &c));
-    std::lock_guard<std::mutex> lk(c->mu);
-    ARCHON_HIP_TRY(hipSetDevice(dev));
-    hipStream_t s = c->own_stream;
-    uint8_t *d_x = nullptr;
-    uint32_t *d_sa = nullptr;
-    ARCHON_TRY(ctx_io(c, 0, (size_t)n + 64, (void **)&d_x));
-    ARCHON_TRY(ctx_io(c, 2, (size_t)n * 4, (void **)&d_sa));
-    ARCHON_HIP_TRY(hipMemcpyAsync(d_x, x, n, hipMemcpyHostToDevice, s));
-    ARCHON_HIP_TRY(hipMemcpyAsync(d_sa, sa, (size_t)n * 4, hipMemcpyHostToDevice, s));
-    return validate_run(c, s, d_x, n, d_sa);
+    return with_ctx(dev, nullptr, [&](Ctx *c, hipStream_t s) -> int {
+        uint8_t *d_x = nullptr;
+        uint32_t *d_sa = nullptr;
+        ARCHON_TRY(ctx_io(c, 0, (size_t)n + 64, (void **)&d_x));
+        ARCHON_TRY(ctx_io(c, 2, (size_t)n * 4, (void **)&d_sa));
+        ARCHON_HIP_TRY(hipMemcpyAsync(d_x, x, n, hipMemcpyHostToDevice, s));
+        ARCHON_HIP_TRY(hipMemcpyAsync(d_sa, sa, (size_t)n * 4, hipMemcpyHostToDevice, s));
+        return validate_run(c, s, d_x, n, d_sa);
+    });
 }
 
 static int sa_to_bwt_run(Ctx *c, hipStream_t s, const uint8_t *d_x, uint32_t n, const uint32_t *d_sa, uint8_t *d_bwt,
@@ -2742,35 +2661,27 @@ int archon_hip_sa_to_bwt_dev(const uint8_t *d_x, uint32_t n, const uint32_t *d_s
 {
     if (!d_x || !d_sa || !d_bwt || !d_base_id) { set_error("null pointer"); return ARCHON_E_ARG; }
     ARCHON_TRY(check_n(n));
-    Ctx *c;
-    ARCHON_TRY(ctx_get(dev, &c));
-    std::lock_guard<std::mutex> lk(c->mu);
-    ARCHON_HIP_TRY(hipSetDevice(dev));
-    hipStream_t s = stream ? (hipStream_t)stream : c->own_stream;
-    return sa_to_bwt_run(c, s, d_x, n, d_sa, d_bwt, d_base_id);
+    return with_ctx(dev, stream, [&](Ctx *c, hipStream_t s) -> int { return sa_to_bwt_run(c, s, d_x, n, d_sa, d_bwt, d_base_id); });
 }
 
 int archon_hip_sa_to_bwt(const uint8_t *x, uint32_t n, const uint32_t *sa, uint8_t *bwt, uint32_t *base_id, int dev)
 {
     if (!x || !sa || !bwt || !base_id) { set_error("null pointer"); return ARCHON_E_ARG; }
     ARCHON_TRY(check_n(n));
-    Ctx *c;
-    ARCHON_TRY(ctx_get(dev, &c));
-    std::lock_guard<std::mutex> lk(c->mu);
-    ARCHON_HIP_TRY(hipSetDevice(dev));
-    hipStream_t s = c->own_stream;
-    uint8_t *d_x = nullptr, *d_bwt = nullptr;
-    uint32_t *d_sa = nullptr;
-    ARCHON_TRY(ctx_io(c, 0, (size_t)n + 64, (void **)&d_x));
-    ARCHON_TRY(ctx_io(c, 1, (size_t)n + 64, (void **)&d_bwt));
-    ARCHON_TRY(ctx_io(c, 2, (size_t)n * 4 + 64, (void **)&d_sa));
-    ARCHON_HIP_TRY(hipMemcpyAsync(d_x, x, n, hipMemcpyHostToDevice, s));
-    ARCHON_HIP_TRY(hipMemcpyAsync(d_sa, sa, (size_t)n * 4, hipMemcpyHostToDevice, s));
-    ARCHON_TRY(sa_to_bwt_run(c, s, d_x, n, d_sa, d_bwt, c->d_mail + mail::kDevSaBase.at));
-    ARCHON_HIP_TRY(hipMemcpyAsync(bwt, d_bwt, n, hipMemcpyDeviceToHost, s));
-    ARCHON_HIP_TRY(hipMemcpyAsync(base_id, c->d_mail + mail::kDevSaBase.at, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
-    ARCHON_SYNC(s);
-    return ARCHON_OK;
+    return with_ctx(dev, nullptr, [&](Ctx *c, hipStream_t s) -> int {
+        uint8_t *d_x = nullptr, *d_bwt = nullptr;
+        uint32_t *d_sa = nullptr;
+        ARCHON_TRY(ctx_io(c, 0, (size_t)n + 64, (void **)&d_x));
+        ARCHON_TRY(ctx_io(c, 1, (size_t)n + 64, (void **)&d_bwt));
+        ARCHON_TRY(ctx_io(c, 2, (size_t)n * 4 + 64, (void **)&d_sa));
+        ARCHON_HIP_TRY(hipMemcpyAsync(d_x, x, n, hipMemcpyHostToDevice, s));
+        ARCHON_HIP_TRY(hipMemcpyAsync(d_sa, sa, (size_t)n * 4, hipMemcpyHostToDevice, s));
+        ARCHON_TRY(sa_to_bwt_run(c, s, d_x, n, d_sa, d_bwt, c->d_mail + mail::kDevSaBase.at));
+        ARCHON_HIP_TRY(hipMemcpyAsync(bwt, d_bwt, n, hipMemcpyDeviceToHost, s));
+        ARCHON_HIP_TRY(hipMemcpyAsync(base_id, c->d_mail + mail::kDevSaBase.at, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+        ARCHON_SYNC(s);
+        return ARCHON_OK;
+    });
 }
 
 // ---- SURVEY 8(f) N4 on the device (post.hiph; parity unpinned -- the host stage host/archon_post.cpp states the format)
@@ -2827,37 +2738,29 @@ static int post_decode_run(Ctx *c, hipStream_t s, const uint8_t *d_in, size_t in
 int archon_hip_post_decode_dev(const uint8_t *d_in, size_t in_bytes, uint8_t *d_bwt, uint32_t cap, uint32_t *n_out, int dev, void *stream)
 {
     if (!d_in || !d_bwt || !n_out) { set_error("null pointer"); return ARCHON_E_ARG; }
-    Ctx *c;
-    ARCHON_TRY(ctx_get(dev, &c));
-    std::lock_guard<std::mutex> lk(c->mu);
-    ARCHON_HIP_TRY(hipSetDevice(dev));
-    hipStream_t s = stream ? (hipStream_t)stream : c->own_stream;
-    return post_decode_run(c, s, d_in, in_bytes, d_bwt, cap, n_out);
+    return with_ctx(dev, stream, [&](Ctx *c, hipStream_t s) -> int { return post_decode_run(c, s, d_in, in_bytes, d_bwt, cap, n_out); });
 }
 
 int archon_hip_inverse_post(const uint8_t *in, size_t in_bytes, uint32_t base_id, uint8_t *x_out, uint32_t cap, uint32_t *n_out, int dev)
 {
     if (!in || !x_out || !n_out) { set_error("null pointer"); return ARCHON_E_ARG; }
     if (cap > ARCHON_HIP_MAX_N) { set_error("block size %u out of range", cap); return ARCHON_E_ARG; }
-    Ctx *c;
-    ARCHON_TRY(ctx_get(dev, &c));
-    std::lock_guard<std::mutex> lk(c->mu);
-    ARCHON_HIP_TRY(hipSetDevice(dev));
-    hipStream_t s = c->own_stream;
-    uint8_t *d_in = nullptr, *d_bwt = nullptr, *d_out = nullptr;
-    ARCHON_TRY(ctx_io(c, 0, in_bytes + 64, (void **)&d_in));
-    ARCHON_TRY(ctx_io(c, 1, (size_t)cap + 64, (void **)&d_bwt));
-    ARCHON_TRY(ctx_io(c, 2, (size_t)cap + 64, (void **)&d_out));
-    // only the packed stream crosses the link on the way in
-    ARCHON_HIP_TRY(hipMemcpyAsync(d_in, in, in_bytes, hipMemcpyHostToDevice, s));
-    ARCHON_TRY(post_decode_run(c, s, d_in, in_bytes, d_bwt, cap, n_out));
-    const uint32_t n = *n_out;
-    if (n == 0) return ARCHON_OK;
-    if (base_id >= n) { set_error("base_id %u >= n %u", base_id, n); return ARCHON_E_ARG; }
-    ARCHON_TRY(keep_stats(c, inverse_run(c, s, d_bwt, n, base_id, d_out)));
-    ARCHON_HIP_TRY(hipMemcpyAsync(x_out, d_out, n, hipMemcpyDeviceToHost, s));
-    ARCHON_SYNC(s);
-    return ARCHON_OK;
+    return with_ctx(dev, nullptr, [&](Ctx *c, hipStream_t s) -> int {
+        uint8_t *d_in = nullptr, *d_bwt = nullptr, *d_out = nullptr;
+        ARCHON_TRY(ctx_io(c, 0, in_bytes + 64, (void **)&d_in));
+        ARCHON_TRY(ctx_io(c, 1, (size_t)cap + 64, (void **)&d_bwt));
+        ARCHON_TRY(ctx_io(c, 2, (size_t)cap + 64, (void **)&d_out));
+        // only the packed stream crosses the link on the way in
+        ARCHON_HIP_TRY(hipMemcpyAsync(d_in, in, in_bytes, hipMemcpyHostToDevice, s));
+        ARCHON_TRY(post_decode_run(c, s, d_in, in_bytes, d_bwt, cap, n_out));
+        const uint32_t n = *n_out;
+        if (n == 0) return ARCHON_OK;
+        if (base_id >= n) { set_error("base_id %u >= n %u", base_id, n); return ARCHON_E_ARG; }
+        ARCHON_TRY(keep_stats(c, inverse_run(c, s, d_bwt, n, base_id, d_out)));
+        ARCHON_HIP_TRY(hipMemcpyAsync(x_out, d_out, n, hipMemcpyDeviceToHost, s));
+        ARCHON_SYNC(s);
+        return ARCHON_OK;
+    });
 }
 
 size_t archon_hip_post_bound(uint32_t n) { return post::block_bound(n); }
@@ -2867,12 +2770,7 @@ int archon_hip_post_encode_dev(const uint8_t *d_bwt, uint32_t n, uint8_t *d_out,
     if ((!d_bwt && n) || !d_out || !out_bytes) { set_error("null pointer"); return ARCHON_E_ARG; }
     if (n > ARCHON_HIP_MAX_N) { set_error("block size %u out of range [0, %u]", n, ARCHON_HIP_MAX_N); return ARCHON_E_ARG; }
     if (cap < post::block_bound(n)) { set_error("post stage: output buffer of %zu bytes, %zu needed (archon_hip_post_bound)", cap, post::block_bound(n)); return ARCHON_E_ARG; }
-    Ctx *c;
-    ARCHON_TRY(ctx_get(dev, &c));
-    std::lock_guard<std::mutex> lk(c->mu);
-    ARCHON_HIP_TRY(hipSetDevice(dev));
-    hipStream_t s = stream ? (hipStream_t)stream : c->own_stream;
-    return post_run(c, s, d_bwt, n, d_out, out_bytes);
+    return with_ctx(dev, stream, [&](Ctx *c, hipStream_t s) -> int { return post_run(c, s, d_bwt, n, d_out, out_bytes); });
 }
 
 int archon_hip_forward_post(const uint8_t *x, uint32_t n, uint8_t *out, size_t cap, size_t *out_bytes, uint32_t *base_id, int dev)
@@ -2881,25 +2779,22 @@ int archon_hip_forward_post(const uint8_t *x, uint32_t n, uint8_t *out, size_t c
     ARCHON_TRY(check_n(n));
     // (cap may be smaller than archon_hip_post_bound(n), the format's worst case of 20 bits per symbol: the stream is built on the
     //  device at full size and a stream longer than cap is an error of this call -- nothing is truncated)
-    Ctx *c;
-    ARCHON_TRY(ctx_get(dev, &c));
-    std::lock_guard<std::mutex> lk(c->mu);
-    ARCHON_HIP_TRY(hipSetDevice(dev));
-    hipStream_t s = c->own_stream;
-    uint8_t *d_x = nullptr, *d_bwt = nullptr, *d_pk = nullptr;
-    ARCHON_TRY(ctx_io(c, 0, (size_t)n + 64, (void **)&d_x));
-    ARCHON_TRY(ctx_io(c, 1, (size_t)n + 64, (void **)&d_bwt));
-    ARCHON_TRY(ctx_io(c, 2, post::block_bound(n) + 64, (void **)&d_pk));
-    uint32_t *d_base = c->d_mail + mail::kDevBase.at;
-    ARCHON_HIP_TRY(hipMemcpyAsync(d_x, x, n, hipMemcpyHostToDevice, s));
-    ARCHON_TRY(keep_stats(c, forward_run(c, s, d_x, n, nullptr, d_bwt, d_base)));
-    ARCHON_TRY(post_run(c, s, d_bwt, n, d_pk, out_bytes));
-    if (*out_bytes > cap) { set_error("post stage: stream of %zu bytes, output buffer of %zu (archon_hip_post_bound gives the worst case)", *out_bytes, cap); return ARCHON_E_ARG; }
-    // only the packed stream crosses the link
-    ARCHON_HIP_TRY(hipMemcpyAsync(out, d_pk, *out_bytes, hipMemcpyDeviceToHost, s));
-    ARCHON_HIP_TRY(hipMemcpyAsync(base_id, d_base, 4, hipMemcpyDeviceToHost, s));
-    ARCHON_SYNC(s);
-    return ARCHON_OK;
+    return with_ctx(dev, nullptr, [&](Ctx *c, hipStream_t s) -> int {
+        uint8_t *d_x = nullptr, *d_bwt = nullptr, *d_pk = nullptr;
+        ARCHON_TRY(ctx_io(c, 0, (size_t)n + 64, (void **)&d_x));
+        ARCHON_TRY(ctx_io(c, 1, (size_t)n + 64, (void **)&d_bwt));
+        ARCHON_TRY(ctx_io(c, 2, post::block_bound(n) + 64, (void **)&d_pk));
+        uint32_t *d_base = c->d_mail + mail::kDevBase.at;
+        ARCHON_HIP_TRY(hipMemcpyAsync(d_x, x, n, hipMemcpyHostToDevice, s));
+        ARCHON_TRY(keep_stats(c, forward_run(c, s, d_x, n, nullptr, d_bwt, d_base)));
+        ARCHON_TRY(post_run(c, s, d_bwt, n, d_pk, out_bytes));
+        if (*out_bytes > cap) { set_error("post stage: stream of %zu bytes, output buffer of %zu (archon_hip_post_bound gives the worst case)", *out_bytes, cap); return ARCHON_E_ARG; }
+        // only the packed stream crosses the link
+        ARCHON_HIP_TRY(hipMemcpyAsync(out, d_pk, *out_bytes, hipMemcpyDeviceToHost, s));
+        ARCHON_HIP_TRY(hipMemcpyAsync(base_id, d_base, 4, hipMemcpyDeviceToHost, s));
+        ARCHON_SYNC(s);
+        return ARCHON_OK;
+    });
 }
 
 static int lms_select_run(Ctx *c, hipStream_t s, const uint8_t *d_x, uint32_t n, uint32_t *d_count, uint32_t *d_items, uint32_t *n1_out)
@@ -2955,69 +2850,56 @@ int archon_hip_lms_select_dev(const uint8_t *d_x, uint32_t n, uint32_t *d_count2
 {
     if (!d_x || !d_count256 || !d_items || !n1) { set_error("null pointer"); return ARCHON_E_ARG; }
     ARCHON_TRY(check_n(n));
-    Ctx *c;
-    ARCHON_TRY(ctx_get(dev, &c));
-    std::lock_guard<std::mutex> lk(c->mu);
-    ARCHON_HIP_TRY(hipSetDevice(dev));
-    hipStream_t s = stream ? (hipStream_t)stream : c->own_stream;
-    return lms_select_run(c, s, d_x, n, d_count256, d_items, n1);
+    return with_ctx(dev, stream, [&](Ctx *c, hipStream_t s) -> int { return lms_select_run(c, s, d_x, n, d_count256, d_items, n1); });
 }
 
 int archon_hip_lms_select(const uint8_t *x, uint32_t n, uint32_t count[256], uint32_t *items, uint32_t *n1, int dev)
 {
     if (!x || !count || !items || !n1) { set_error("null pointer"); return ARCHON_E_ARG; }
     ARCHON_TRY(check_n(n));
-    Ctx *c;
-    ARCHON_TRY(ctx_get(dev, &c));
-    std::lock_guard<std::mutex> lk(c->mu);
-    ARCHON_HIP_TRY(hipSetDevice(dev));
-    hipStream_t s = c->own_stream;
-    uint8_t *d_x = nullptr;
-    uint32_t *d_items = nullptr;
-    ARCHON_TRY(ctx_io(c, 0, (size_t)n + 64, (void **)&d_x));
-    ARCHON_TRY(ctx_io(c, 2, ((size_t)n / 2 + 8) * 4, (void **)&d_items));
-    ARCHON_HIP_TRY(hipMemcpyAsync(d_x, x, n, hipMemcpyHostToDevice, s));
-    ARCHON_TRY(lms_select_run(c, s, d_x, n, c->d_mail + mail::kDevLmsCount.at, d_items, n1));
-    ARCHON_HIP_TRY(hipMemcpyAsync(count, c->d_mail + mail::kDevLmsCount.at, 256 * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
-    if (*n1) ARCHON_HIP_TRY(hipMemcpyAsync(items, d_items, (size_t)*n1 * 4, hipMemcpyDeviceToHost, s));
-    ARCHON_SYNC(s);
-    return ARCHON_OK;
+    return with_ctx(dev, nullptr, [&](Ctx *c, hipStream_t s) -> int {
+        uint8_t *d_x = nullptr;
+        uint32_t *d_items = nullptr;
+        ARCHON_TRY(ctx_io(c, 0, (size_t)n + 64, (void **)&d_x));
+        ARCHON_TRY(ctx_io(c, 2, ((size_t)n / 2 + 8) * 4, (void **)&d_items));
+        ARCHON_HIP_TRY(hipMemcpyAsync(d_x, x, n, hipMemcpyHostToDevice, s));
+        ARCHON_TRY(lms_select_run(c, s, d_x, n, c->d_mail + mail::kDevLmsCount.at, d_items, n1));
+        ARCHON_HIP_TRY(hipMemcpyAsync(count, c->d_mail + mail::kDevLmsCount.at, 256 * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+        if (*n1) ARCHON_HIP_TRY(hipMemcpyAsync(items, d_items, (size_t)*n1 * 4, hipMemcpyDeviceToHost, s));
+        ARCHON_SYNC(s);
+        return ARCHON_OK;
+    });
 }
 
 int archon_hip_radix_scatter_dev(const uint8_t *d_src, size_t n, uint8_t *d_dst, int dev, void *stream)
 {
     if (!d_src || !d_dst) { set_error("null pointer"); return ARCHON_E_ARG; }
-    Ctx *c;
-    ARCHON_TRY(ctx_get(dev, &c));
-    std::lock_guard<std::mutex> lk(c->mu);
-    ARCHON_HIP_TRY(hipSetDevice(dev));
-    hipStream_t s = stream ? (hipStream_t)stream : c->own_stream;
-    uint32_t *d_counts = c->d_mail + mail::kDevCounts.at, *d_starts = c->d_mail + mail::kDevStarts.at;
-    ARCHON_TRY(launch_hist256(s, d_src, n, d_counts, n));
-    hipLaunchKernelGGL(k_scan257, dim3(1), dim3(64), 0, s, d_counts, d_starts);
-    uint32_t grid = div_up(n, 256 * 16);
-    if (grid < 1) grid = 1;
-    if (grid > (uint32_t)kNumCU * 8) grid = kNumCU * 8;
-    hipLaunchKernelGGL(k_fill_runs, dim3(grid), dim3(256), 0, s, d_starts, d_dst, n);
-    ARCHON_HIP_TRY(hipGetLastError());
-    ARCHON_SYNC(s);
-    return ARCHON_OK;
+    return with_ctx(dev, stream, [&](Ctx *c, hipStream_t s) -> int {
+        uint32_t *d_counts = c->d_mail + mail::kDevCounts.at, *d_starts = c->d_mail + mail::kDevStarts.at;
+        ARCHON_TRY(launch_hist256(s, d_src, n, d_counts, n));
+        hipLaunchKernelGGL(k_scan257, dim3(1), dim3(64), 0, s, d_counts, d_starts);
+        uint32_t grid = div_up(n, 256 * 16);
+        if (grid < 1) grid = 1;
+        if (grid > (uint32_t)kNumCU * 8) grid = kNumCU * 8;
+        hipLaunchKernelGGL(k_fill_runs, dim3(grid), dim3(256), 0, s, d_starts, d_dst, n);
+        ARCHON_HIP_TRY(hipGetLastError());
+        ARCHON_SYNC(s);
+        return ARCHON_OK;
+    });
 }
 
 int archon_hip_radix_scatter(const uint8_t *src, size_t n, uint8_t *dst, int dev)
 {
     if (!src || !dst) { set_error("null pointer"); return ARCHON_E_ARG; }
     if (n >= 0xFFFFFFFFull) { set_error("n too large"); return ARCHON_E_ARG; }
-    Ctx *c;
-    ARCHON_TRY(ctx_get(dev, &c));
     uint8_t *d_a = nullptr, *d_b = nullptr;
-    {
-        std::lock_guard<std::mutex> lk(c->mu);
-        ARCHON_HIP_TRY(hipSetDevice(dev));
+    // the context only for the allocations and the upload: the _dev call takes it again
+    ARCHON_TRY(with_ctx(dev, nullptr, [&](Ctx *, hipStream_t) -> int {
         ARCHON_HIP_TRY(hipMalloc((void **)&d_a, n + 64));
         if (hipMalloc((void **)&d_b, n + 64) != hipSuccess) { (void)hipFree(d_a); set_error("alloc"); return ARCHON_E_NOMEM; }
         if (hipMemcpy(d_a, src, n, hipMemcpyHostToDevice) != hipSuccess) { (void)hipFree(d_a); (void)hipFree(d_b); set_error("copy"); return ARCHON_E_HIP; }
-    }
+        return ARCHON_OK;
+    }));
     int rc = archon_hip_radix_scatter_dev(d_a, n, d_b, dev, nullptr);
     if (rc == ARCHON_OK && hipMemcpy(dst, d_b, n, hipMemcpyDeviceToHost) != hipSuccess) { set_error("copy"); rc = ARCHON_E_HIP; }
     (void)hipFree(d_a);
@@ -3103,21 +2985,19 @@ int archon_hip_inverse_batch_dev(const uint8_t *const *d_bwt, const uint32_t *n,
 int archon_hip_reserve(uint32_t n, int dev, size_t *bytes_or_null)
 {
     ARCHON_TRY(check_n(n));
-    Ctx *c;
-    ARCHON_TRY(ctx_get(dev, &c));
-    std::lock_guard<std::mutex> lk(c->mu);
-    ARCHON_HIP_TRY(hipSetDevice(dev));
-    // (reserving means: no allocation inside a later call, whatever the block) -- the layouts counted, not carved
-    FwdBuf B{};
-    InvArena L;
-    Carve f1, f2, i1;
-    size_t need = fwd_tier1(f1, B, n, dev, true);
-    const size_t inv = inv_layout(i1, L, n);
-    if (inv > need) need = inv;
-    ARCHON_TRY(ctx_ensure_arena(c, need));
-    ARCHON_TRY(ctx_ensure_arena2(c, fwd_tier2(f2, B, n)));
-    if (bytes_or_null) *bytes_or_null = c->arena_bytes + c->arena2_bytes;
-    return ARCHON_OK;
+    return with_ctx(dev, nullptr, [&](Ctx *c, hipStream_t) -> int {
+        // (reserving means: no allocation inside a later call, whatever the block) -- the layouts counted, not carved
+        FwdBuf B{};
+        InvArena L;
+        Carve f1, f2, i1;
+        size_t need = fwd_tier1(f1, B, n, dev, true);
+        const size_t inv = inv_layout(i1, L, n);
+        if (inv > need) need = inv;
+        ARCHON_TRY(ctx_ensure_arena(c, need));
+        ARCHON_TRY(ctx_ensure_arena2(c, fwd_tier2(f2, B, n)));
+        if (bytes_or_null) *bytes_or_null = c->arena_bytes + c->arena2_bytes;
+        return ARCHON_OK;
+    });
 }
 
 int archon_hip_release(int dev)
@@ -3241,17 +3121,13 @@ int archon_hip_test_route(const char *name, long value)
 int archon_hip_get_lcp_stats(int dev, archon_hip_lcp_stats *out)
 {
     if (!out) { set_error("null pointer"); return ARCHON_E_ARG; }
-    if (dev < 0 || dev >= kMaxDev || !t_lcp_stats_set[dev]) { set_error("the calling thread has run no LCP call on device %d", dev); return ARCHON_E_ARG; }
-    *out = t_lcp_stats[dev];
-    return ARCHON_OK;
+    return t_lcp_stats.get(dev, out, "LCP call");
 }
 
 int archon_hip_get_stats(int dev, archon_hip_stats *out)
 {
     if (!out) { set_error("null pointer"); return ARCHON_E_ARG; }
-    if (dev < 0 || dev >= kMaxDev || !t_stats_set[dev]) { set_error("the calling thread has run no transform on device %d", dev); return ARCHON_E_ARG; }
-    *out = t_stats[dev];
-    return ARCHON_OK;
+    return t_stats.get(dev, out, "transform");
 }
 
 }  // extern "C"
