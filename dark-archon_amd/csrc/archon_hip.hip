@@ -14,6 +14,7 @@
 #include "lcp.hiph"
 #include "fm.hiph"
 #include "fm_walk.hiph"
+#include "fm_approx.hiph"
 
 #include <stdarg.h>
 #include <atomic>
@@ -79,6 +80,7 @@ static thread_local LastStats<archon_hip_stats> t_stats;                // trans
 static thread_local LastStats<archon_hip_lcp_stats> t_lcp_stats;        // LCP calls: they leave archon_hip_stats alone
 static thread_local LastStats<archon_hip_fm_stats> t_fm_stats;          // FM calls: they leave both of the others alone
 static thread_local LastStats<archon_hip_fm_walk_stats> t_fmw_stats;    // sampled-index calls: sample, block_fm_index, locate, extract
+static thread_local LastStats<archon_hip_fm_approx_stats> t_fma_stats;  // approximate calls: approx, locate_hits
 
 static inline int keep_stats(Ctx *c, int rc)
 {
@@ -1880,13 +1882,14 @@ static int fm_host_query(Ctx *c, hipStream_t s, const archon_hip_fm *f, const ui
         const int e2 = tm.mark();
         if (t && loc->d_sa) {
             const uint64_t g = (t + 255) / 256;
-            hipLaunchKernelGGL(k_fm_locate, dim3(g < kLocateGrid ? (uint32_t)g : kLocateGrid), dim3(256), 0, s, loc->d_sa, L.off, L.lo, L.first, k, L.pos);
+            hipLaunchKernelGGL(k_fm_locate<PatternRows>, dim3(g < kLocateGrid ? (uint32_t)g : kLocateGrid), dim3(256), 0, s, loc->d_sa,
+                               PatternRows{L.off, L.lo}, L.first, k, L.pos);
             ARCHON_HIP_TRY(hipGetLastError());
             st->kernel_launches += 1;
         } else if (t) {
             const uint64_t g = (t + 3) / 4;
-            hipLaunchKernelGGL(fmw::k_fm_walk_locate, dim3(g < fmw::kWalkGrid ? (uint32_t)g : fmw::kWalkGrid), dim3(256), 0, s, f->table(), f->samples(),
-                               L.off, L.lo, L.first, k, L.pos, wmail);
+            hipLaunchKernelGGL(fmw::k_fm_walk_locate<PatternRows>, dim3(g < fmw::kWalkGrid ? (uint32_t)g : fmw::kWalkGrid), dim3(256), 0, s, f->table(),
+                               f->samples(), PatternRows{L.off, L.lo}, L.first, k, L.pos, wmail);
             ARCHON_HIP_TRY(hipGetLastError());
             st->kernel_launches += 1;
         }
@@ -2255,6 +2258,240 @@ int archon_hip_get_fm_walk_stats(int dev, archon_hip_fm_walk_stats *out)
     return t_fmw_stats.get(dev, out, "sampled FM call");
 }
 
+// ---- approximate search (fm_approx.hiph)
+static_assert(sizeof(archon_hip_fm_hit) == sizeof(fma::FmHit) && offsetof(archon_hip_fm_hit, lo) == offsetof(fma::FmHit, lo) &&
+                  offsetof(archon_hip_fm_hit, hi) == offsetof(fma::FmHit, hi) &&
+                  offsetof(archon_hip_fm_hit, mismatches) == offsetof(fma::FmHit, mismatches) &&
+                  offsetof(archon_hip_fm_hit, pattern) == offsetof(fma::FmHit, pattern),
+              "the device hit is the ABI's");
+
+static int fma_check_k(uint32_t K)
+{
+    if (K > fma::kMaxMismatches) { set_error("FM approx: %u mismatches, at most %u", K, fma::kMaxMismatches); return ARCHON_E_ARG; }
+    return ARCHON_OK;
+}
+
+// The count pass over device patterns and offsets: nhits / nocc on the device and on the host, the work counters into *st,
+// first[] the exclusive sums of nhits (first[k] the total).  Decreasing offsets (found on the device) are ARCHON_E_ARG.
+static int fma_count(Ctx *c, hipStream_t s, const archon_hip_fm *f, const uint8_t *d_pat, const uint32_t *d_off, uint32_t k, uint32_t K,
+                     uint32_t *d_nhits, uint32_t *d_nocc, uint32_t *nhits, uint32_t *nocc, std::vector<uint64_t> &first, StageTimer &tm,
+                     archon_hip_fm_approx_stats *st)
+{
+    using namespace fma;
+    uint32_t *mail = c->d_mail + mail::kDevFmApprox.at, *rd = c->h_mail + mail::kRead.at;
+    static_assert(kWords <= mail::kDevFmApprox.len && kWords <= mail::kRead.len, "the approximate FM words in the mailbox");
+    ARCHON_HIP_TRY(hipMemsetAsync(mail, 0, kWords * sizeof(uint32_t), s));
+    const uint32_t g = div_up(k, 4);
+    const int e0 = tm.mark();
+    hipLaunchKernelGGL(k_fm_approx<false>, dim3(g < kGrid ? g : kGrid), dim3(256), lds_bytes(K), s, f->table(), d_pat, d_off, k, K, d_nhits, d_nocc,
+                       nullptr, nullptr, 0, mail);
+    ARCHON_HIP_TRY(hipGetLastError());
+    const int e1 = tm.mark();
+    ARCHON_HIP_TRY(hipMemcpyAsync(rd, mail, kWords * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+    ARCHON_HIP_TRY(hipMemcpyAsync(nhits, d_nhits, (size_t)k * 4, hipMemcpyDeviceToHost, s));
+    ARCHON_HIP_TRY(hipMemcpyAsync(nocc, d_nocc, (size_t)k * 4, hipMemcpyDeviceToHost, s));
+    ARCHON_SYNC(s);
+    st->kernel_launches += 1;
+    st->ms_count = tm.ms(e0, e1);
+    memcpy(&st->expansions, rd + kExpansions, sizeof(uint64_t));
+    memcpy(&st->steps, rd + kSteps, sizeof(uint64_t));
+    if (rd[kBadOffsets]) { set_error("FM approx: offsets decrease"); return ARCHON_E_ARG; }
+    first.assign((size_t)k + 1, 0);
+    uint64_t t = 0, occ = 0;
+    for (uint32_t j = 0; j < k; ++j) {
+        first[j] = t;
+        t += nhits[j];
+        occ += nocc[j];
+    }
+    first[k] = t;
+    st->hits = t;
+    st->occurrences = occ;
+    return ARCHON_OK;
+}
+
+// The emit pass: the same search again, hit i of pattern j into d_hits[first[j] + i]
+static int fma_emit(Ctx *c, hipStream_t s, const archon_hip_fm *f, const uint8_t *d_pat, const uint32_t *d_off, uint32_t k, uint32_t K,
+                    uint64_t *d_first, const std::vector<uint64_t> &first, fma::FmHit *d_hits, StageTimer &tm, archon_hip_fm_approx_stats *st)
+{
+    using namespace fma;
+    ARCHON_HIP_TRY(hipMemcpyAsync(d_first, first.data(), ((size_t)k + 1) * 8, hipMemcpyHostToDevice, s));
+    const uint32_t g = div_up(k, 4);
+    const int e0 = tm.mark();
+    hipLaunchKernelGGL(k_fm_approx<true>, dim3(g < kGrid ? g : kGrid), dim3(256), lds_bytes(K), s, f->table(), d_pat, d_off, k, K, nullptr, nullptr,
+                       d_first, d_hits, first[k], nullptr);
+    ARCHON_HIP_TRY(hipGetLastError());
+    const int e1 = tm.mark();
+    ARCHON_SYNC(s);
+    st->kernel_launches += 1;
+    st->ms_emit = tm.ms(e0, e1);
+    return ARCHON_OK;
+}
+
+// Host patterns and results through the context's arena (the arena may move for the hits: patterns and offsets go up again)
+static int fma_host(Ctx *c, hipStream_t s, const archon_hip_fm *f, const uint8_t *patterns, const uint32_t *offsets, uint32_t k, uint32_t K,
+                    uint32_t *nhits, uint32_t *nocc, archon_hip_fm_hit *hits, uint64_t cap, uint64_t *total, archon_hip_fm_approx_stats *st)
+{
+    const size_t pat_bytes = offsets[k];
+    st->pattern_bytes = (uint64_t)offsets[k] - offsets[0];
+    FmaArena L;
+    ARCHON_TRY(ctx_carve(c, [&](Carve &a) { return fma_layout(a, L, pat_bytes, k, true, 0); }));
+    if (pat_bytes) ARCHON_HIP_TRY(hipMemcpyAsync(L.pat, patterns, pat_bytes, hipMemcpyHostToDevice, s));
+    ARCHON_HIP_TRY(hipMemcpyAsync(L.off, offsets, ((size_t)k + 1) * 4, hipMemcpyHostToDevice, s));
+    StageTimer tm(c, 72, s);
+    std::vector<uint64_t> first;
+    ARCHON_TRY(fma_count(c, s, f, L.pat, L.off, k, K, L.nhits, L.nocc, nhits, nocc, first, tm, st));
+    *total = first[k];
+    if (!hits || !first[k]) return ARCHON_OK;
+    if (first[k] > cap) { set_error("FM approx: %llu hits, room for %llu", (unsigned long long)first[k], (unsigned long long)cap); return ARCHON_E_ARG; }
+    ARCHON_TRY(ctx_carve(c, [&](Carve &a) { return fma_layout(a, L, pat_bytes, k, true, first[k]); }));
+    if (pat_bytes) ARCHON_HIP_TRY(hipMemcpyAsync(L.pat, patterns, pat_bytes, hipMemcpyHostToDevice, s));
+    ARCHON_HIP_TRY(hipMemcpyAsync(L.off, offsets, ((size_t)k + 1) * 4, hipMemcpyHostToDevice, s));
+    ARCHON_TRY(fma_emit(c, s, f, L.pat, L.off, k, K, L.first, first, L.hits, tm, st));
+    ARCHON_HIP_TRY(hipMemcpyAsync(hits, L.hits, first[k] * sizeof(fma::FmHit), hipMemcpyDeviceToHost, s));
+    ARCHON_SYNC(s);
+    return ARCHON_OK;
+}
+
+// The statistics of one approximate call: kept for the calling thread, with the call's host waits, when it returns
+struct FmaKeep {
+    int dev;
+    uint32_t syncs0 = t_sync_count;
+    archon_hip_fm_approx_stats st = {};
+    FmaKeep(int d, uint32_t n, uint32_t k, uint32_t K) : dev(d)
+    {
+        st.n = n;
+        st.patterns = k;
+        st.max_mismatches = K;
+    }
+    ~FmaKeep()
+    {
+        st.host_syncs = t_sync_count - syncs0;
+        t_fma_stats.keep(dev, st);
+    }
+};
+
+int archon_hip_fm_approx(archon_hip_fm *f, const uint8_t *patterns, const uint32_t *offsets, uint32_t k, uint32_t max_mismatches, uint32_t *nhits,
+                         uint32_t *nocc, archon_hip_fm_hit *hits_or_null, uint64_t cap, uint64_t *total)
+{
+    if (!f || !patterns || !offsets || !nhits || !nocc || !total) { set_error("null pointer"); return ARCHON_E_ARG; }
+    ARCHON_TRY(fma_check_k(max_mismatches));
+    ARCHON_TRY(fm_check_offsets(offsets, k));
+    *total = 0;
+    if (!k) return ARCHON_OK;
+    return with_ctx(f->dev, nullptr, [&](Ctx *c, hipStream_t s) -> int {
+        FmaKeep keep(f->dev, f->n, k, max_mismatches);
+        return fma_host(c, s, f, patterns, offsets, k, max_mismatches, nhits, nocc, hits_or_null, cap, total, &keep.st);
+    });
+}
+
+int archon_hip_fm_approx_dev(archon_hip_fm *f, const uint8_t *d_patterns, const uint32_t *d_offsets, uint32_t k, uint32_t max_mismatches,
+                             uint32_t *d_nhits, uint32_t *d_nocc, archon_hip_fm_hit *d_hits_or_null, uint64_t cap, uint64_t *total, void *stream)
+{
+    if (!f || !d_patterns || !d_offsets || !d_nhits || !d_nocc || !total) { set_error("null pointer"); return ARCHON_E_ARG; }
+    ARCHON_TRY(fma_check_k(max_mismatches));
+    *total = 0;
+    if (!k) return ARCHON_OK;
+    return with_ctx(f->dev, stream, [&](Ctx *c, hipStream_t s) -> int {
+        FmaKeep keep(f->dev, f->n, k, max_mismatches);
+        archon_hip_fm_approx_stats *st = &keep.st;
+        uint32_t *ends = c->h_mail + mail::kRead.at + fma::kWords;     // offsets[0] and offsets[k], for the statistics
+        static_assert(fma::kWords + 2 <= mail::kRead.len, "the approximate FM words and the offsets' ends in the readback words");
+        ARCHON_HIP_TRY(hipMemcpyAsync(&ends[0], d_offsets, 4, hipMemcpyDeviceToHost, s));
+        ARCHON_HIP_TRY(hipMemcpyAsync(&ends[1], d_offsets + k, 4, hipMemcpyDeviceToHost, s));
+        FmaArena L;
+        ARCHON_TRY(ctx_carve(c, [&](Carve &a) { return fma_layout(a, L, 0, k, false, 0); }));
+        StageTimer tm(c, 72, s);
+        std::vector<uint32_t> nh(k), no(k);
+        std::vector<uint64_t> first;
+        ARCHON_TRY(fma_count(c, s, f, d_patterns, d_offsets, k, max_mismatches, d_nhits, d_nocc, nh.data(), no.data(), first, tm, st));
+        st->pattern_bytes = ends[1] >= ends[0] ? ends[1] - ends[0] : 0;
+        *total = first[k];
+        if (!d_hits_or_null || !first[k]) return ARCHON_OK;
+        if (first[k] > cap) { set_error("FM approx: %llu hits, room for %llu", (unsigned long long)first[k], (unsigned long long)cap); return ARCHON_E_ARG; }
+        return fma_emit(c, s, f, d_patterns, d_offsets, k, max_mismatches, L.first, first, reinterpret_cast<fma::FmHit *>(d_hits_or_null), tm, st);
+    });
+}
+
+// The starts of the hits' occurrences: a gather from a resident SA (d_sa), or the LF walks of a sampled handle
+static int fma_check_hits(const uint32_t *offsets, uint32_t k, const archon_hip_fm_hit *hits, uint64_t nhits, uint32_t n)
+{
+    ARCHON_TRY(fm_check_offsets(offsets, k));
+    if (nhits >= (1ull << 32)) { set_error("FM locate hits: %llu hits in one call", (unsigned long long)nhits); return ARCHON_E_ARG; }
+    for (uint64_t i = 0; i < nhits; ++i) {
+        const archon_hip_fm_hit &h = hits[i];
+        if (h.pattern >= k || h.lo > h.hi || h.hi > n) {
+            set_error("FM locate hits: hit %llu (pattern %u, rows [%u, %u)) outside %u patterns / [0, %u]", (unsigned long long)i, h.pattern, h.lo, h.hi, k, n);
+            return ARCHON_E_ARG;
+        }
+    }
+    return ARCHON_OK;
+}
+
+static int fma_locate(Ctx *c, hipStream_t s, const archon_hip_fm *f, const uint32_t *d_sa, const uint32_t *offsets, uint32_t k,
+                      const archon_hip_fm_hit *hits, uint64_t nhits, uint32_t *pos, uint64_t cap, uint64_t *total, archon_hip_fm_approx_stats *st)
+{
+    std::vector<uint64_t> first(nhits + 1);
+    uint64_t t = 0;
+    for (uint64_t i = 0; i < nhits; ++i) {
+        first[i] = t;
+        t += hits[i].hi - hits[i].lo;
+    }
+    first[nhits] = t;
+    *total = t;
+    st->hits = nhits;
+    st->occurrences = t;
+    if (t > cap) { set_error("FM locate hits: %llu starts, room for %llu", (unsigned long long)t, (unsigned long long)cap); return ARCHON_E_ARG; }
+    if (!t) return ARCHON_OK;
+    FmhArena L;
+    ARCHON_TRY(ctx_carve(c, [&](Carve &a) { return fmh_layout(a, L, k, nhits, t); }));
+    ARCHON_HIP_TRY(hipMemcpyAsync(L.off, offsets, ((size_t)k + 1) * 4, hipMemcpyHostToDevice, s));
+    ARCHON_HIP_TRY(hipMemcpyAsync(L.hits, hits, nhits * sizeof(fma::FmHit), hipMemcpyHostToDevice, s));
+    ARCHON_HIP_TRY(hipMemcpyAsync(L.first, first.data(), (nhits + 1) * 8, hipMemcpyHostToDevice, s));
+    uint32_t *mail = c->d_mail + mail::kDevFmApprox.at, *rd = c->h_mail + mail::kRead.at;
+    static_assert(fmw::kWords <= mail::kDevFmApprox.len, "the walks' words in the approximate FM region");
+    ARCHON_HIP_TRY(hipMemsetAsync(mail, 0, fmw::kWords * sizeof(uint32_t), s));
+    const fma::HitRows q{L.hits, L.off};
+    StageTimer tm(c, 72, s);
+    const int e0 = tm.mark();
+    if (d_sa) {
+        const uint64_t g = (t + 255) / 256;
+        hipLaunchKernelGGL(fmk::k_fm_locate<fma::HitRows>, dim3(g < fmk::kLocateGrid ? (uint32_t)g : fmk::kLocateGrid), dim3(256), 0, s, d_sa, q, L.first,
+                           (uint32_t)nhits, L.pos);
+    } else {
+        const uint64_t g = (t + 3) / 4;
+        hipLaunchKernelGGL(fmw::k_fm_walk_locate<fma::HitRows>, dim3(g < fmw::kWalkGrid ? (uint32_t)g : fmw::kWalkGrid), dim3(256), 0, s, f->table(),
+                           f->samples(), q, L.first, (uint32_t)nhits, L.pos, mail);
+    }
+    ARCHON_HIP_TRY(hipGetLastError());
+    const int e1 = tm.mark();
+    ARCHON_HIP_TRY(hipMemcpyAsync(pos, L.pos, t * 4, hipMemcpyDeviceToHost, s));
+    ARCHON_HIP_TRY(hipMemcpyAsync(rd, mail, fmw::kWords * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+    ARCHON_SYNC(s);
+    st->kernel_launches = 1;
+    st->ms_locate = tm.ms(e0, e1);
+    if (!d_sa) memcpy(&st->lf_steps, rd + fmw::kSteps, sizeof(uint64_t));
+    return ARCHON_OK;
+}
+
+int archon_hip_fm_locate_hits(archon_hip_fm *f, const uint32_t *offsets, uint32_t k, const archon_hip_fm_hit *hits, uint64_t nhits, uint32_t *pos,
+                              uint64_t cap, uint64_t *total)
+{
+    if (!f || !offsets || (!hits && nhits) || !pos || !total) { set_error("null pointer"); return ARCHON_E_ARG; }
+    if (!f->rate) { set_error("FM index: the handle has no samples (archon_hip_fm_sample)"); return ARCHON_E_ARG; }
+    ARCHON_TRY(fma_check_hits(offsets, k, hits, nhits, f->n));
+    *total = 0;
+    return with_ctx(f->dev, nullptr, [&](Ctx *c, hipStream_t s) -> int {
+        FmaKeep keep(f->dev, f->n, k, 0);
+        return fma_locate(c, s, f, nullptr, offsets, k, hits, nhits, pos, cap, total, &keep.st);
+    });
+}
+
+int archon_hip_get_fm_approx_stats(int dev, archon_hip_fm_approx_stats *out)
+{
+    if (!out) { set_error("null pointer"); return ARCHON_E_ARG; }
+    return t_fma_stats.get(dev, out, "approximate FM call");
+}
+
 // ---- resident blocks ---------------------------------------------------------------------------------------------------
 // What a block-coder object keeps on the device between enCompute, validate and enWrite (bwt/a7/src/main.cpp:39-46): the
 // block, its suffix array and its BWT, in buffers of its own.  The state belongs to the HANDLE -- any number of objects on
@@ -2449,6 +2686,45 @@ int archon_hip_block_fm_index(archon_hip_block *b, uint32_t rate, archon_hip_fm 
             else *out = f;
         }
         return rc;
+    });
+}
+
+int archon_hip_block_fm_approx(archon_hip_block *b, const uint8_t *patterns, const uint32_t *offsets, uint32_t k, uint32_t max_mismatches,
+                               uint32_t *nhits, uint32_t *nocc, archon_hip_fm_hit *hits_or_null, uint64_t cap, uint64_t *total)
+{
+    if (!b || !patterns || !offsets || !nhits || !nocc || !total) { set_error("null pointer"); return ARCHON_E_ARG; }
+    ARCHON_TRY(fma_check_k(max_mismatches));
+    ARCHON_TRY(fm_check_offsets(offsets, k));
+    std::lock_guard<std::mutex> lkb(b->mu);
+    if (!b->valid) { set_error("no resident block"); return ARCHON_E_ARG; }
+    *total = 0;
+    if (!k) return ARCHON_OK;
+    return with_ctx(b->dev, nullptr, [&](Ctx *c, hipStream_t s) -> int {
+        FmaKeep keep(b->dev, b->n, k, max_mismatches);
+        archon_hip_fm_approx_stats *st = &keep.st;
+        if (!b->fm) {
+            // the block's table, as block_fm_count builds it; its statistics are this call's (fm_stats stays as it was)
+            archon_hip_fm_stats fst = {};
+            ARCHON_TRY(fm_build(c, s, nullptr, b->d_bwt, false, b->n, b->base, &b->fm, &fst));
+            st->built = 1;
+            st->ms_build = fst.ms_build;
+            st->kernel_launches += fst.kernel_launches;
+        }
+        return fma_host(c, s, b->fm, patterns, offsets, k, max_mismatches, nhits, nocc, hits_or_null, cap, total, st);
+    });
+}
+
+int archon_hip_block_fm_locate_hits(archon_hip_block *b, const uint32_t *offsets, uint32_t k, const archon_hip_fm_hit *hits, uint64_t nhits,
+                                    uint32_t *pos, uint64_t cap, uint64_t *total)
+{
+    if (!b || !offsets || (!hits && nhits) || !pos || !total) { set_error("null pointer"); return ARCHON_E_ARG; }
+    std::lock_guard<std::mutex> lkb(b->mu);
+    if (!b->valid || !b->has_sa) { set_error("no resident block with its suffix array"); return ARCHON_E_ARG; }
+    ARCHON_TRY(fma_check_hits(offsets, k, hits, nhits, b->n));
+    *total = 0;
+    return with_ctx(b->dev, nullptr, [&](Ctx *c, hipStream_t s) -> int {
+        FmaKeep keep(b->dev, b->n, k, 0);
+        return fma_locate(c, s, nullptr, b->d_sa, offsets, k, hits, nhits, pos, cap, total, &keep.st);
     });
 }
 

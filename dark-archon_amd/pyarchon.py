@@ -37,7 +37,12 @@ SYMBOLS = [
     "archon_hip_block_fm_count", "archon_hip_block_fm_locate", "archon_hip_get_fm_stats",
     "archon_hip_fm_sample", "archon_hip_block_fm_index", "archon_hip_fm_read_samples", "archon_hip_fm_locate", "archon_hip_fm_extract",
     "archon_hip_fm_extract_dev", "archon_hip_get_fm_walk_stats",
+    "archon_hip_fm_approx", "archon_hip_fm_approx_dev", "archon_hip_block_fm_approx", "archon_hip_fm_locate_hits",
+    "archon_hip_block_fm_locate_hits", "archon_hip_get_fm_approx_stats",
 ]
+
+# archon_hip_fm_hit: one distinct string within the distance of a pattern (FmIndex.approx, Block.fm_approx)
+FM_HIT = np.dtype([("lo", "<u4"), ("hi", "<u4"), ("mismatches", "<u4"), ("pattern", "<u4")])
 
 
 class Stats(ctypes.Structure):
@@ -94,6 +99,19 @@ class FmWalkStats(ctypes.Structure):
         ("host_syncs", ctypes.c_uint32), ("samples", ctypes.c_uint64), ("sample_bytes", ctypes.c_uint64), ("walks", ctypes.c_uint64),
         ("lf_steps", ctypes.c_uint64), ("max_walk", ctypes.c_uint32), ("reserved0", ctypes.c_uint32), ("ms_build", ctypes.c_float),
         ("ms_query", ctypes.c_float),
+    ]
+
+    def asdict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
+class FmApproxStats(ctypes.Structure):
+    """archon_hip_fm_approx_stats: the calling thread's last approximate call (approx, locate_hits) on a device"""
+    _fields_ = [
+        ("n", ctypes.c_uint32), ("patterns", ctypes.c_uint32), ("max_mismatches", ctypes.c_uint32), ("built", ctypes.c_uint32),
+        ("pattern_bytes", ctypes.c_uint64), ("expansions", ctypes.c_uint64), ("steps", ctypes.c_uint64), ("hits", ctypes.c_uint64),
+        ("occurrences", ctypes.c_uint64), ("lf_steps", ctypes.c_uint64), ("kernel_launches", ctypes.c_uint32), ("host_syncs", ctypes.c_uint32),
+        ("ms_build", ctypes.c_float), ("ms_count", ctypes.c_float), ("ms_emit", ctypes.c_float), ("ms_locate", ctypes.c_float),
     ]
 
     def asdict(self):
@@ -177,6 +195,12 @@ def load():
         "archon_hip_fm_extract": [vp, vp, vp, u32, vp],
         "archon_hip_fm_extract_dev": [vp, vp, vp, u32, vp, vp],
         "archon_hip_get_fm_walk_stats": [i32, ctypes.POINTER(FmWalkStats)],
+        "archon_hip_fm_approx": [vp, vp, vp, u32, u32, vp, vp, vp, ctypes.c_uint64, vp],
+        "archon_hip_fm_approx_dev": [vp, vp, vp, u32, u32, vp, vp, vp, ctypes.c_uint64, vp, vp],
+        "archon_hip_block_fm_approx": [vp, vp, vp, u32, u32, vp, vp, vp, ctypes.c_uint64, vp],
+        "archon_hip_fm_locate_hits": [vp, vp, u32, vp, ctypes.c_uint64, vp, ctypes.c_uint64, vp],
+        "archon_hip_block_fm_locate_hits": [vp, vp, u32, vp, ctypes.c_uint64, vp, ctypes.c_uint64, vp],
+        "archon_hip_get_fm_approx_stats": [i32, ctypes.POINTER(FmApproxStats)],
     }.items():
         fn = getattr(lib, name)
         fn.argtypes = args
@@ -327,6 +351,46 @@ def fm_walk_stats(dev=0):
     return s
 
 
+def fm_approx_stats(dev=0):
+    """FmApproxStats of the calling thread's last approximate call (approx, locate_hits) on dev"""
+    s = FmApproxStats()
+    _check(lib().archon_hip_get_fm_approx_stats(dev, ctypes.byref(s)))
+    return s
+
+
+def _approx(fn, h, patterns, k, hits):
+    """(nhits, nocc, hits or None) of an approximate call: counting first, then the hits into an array of the size it gave"""
+    packed, offsets = _pack_patterns(patterns)
+    npat = offsets.size - 1
+    nhits, nocc = np.zeros(npat, np.uint32), np.zeros(npat, np.uint32)
+    total = ctypes.c_uint64(0)
+    tp = ctypes.cast(ctypes.byref(total), ctypes.c_void_p)
+    if not hits:
+        _check(fn(h, _p(packed), _p(offsets), npat, int(k), _p(nhits), _p(nocc), None, 0, tp))
+        return nhits, nocc, None
+    # one call when the hits fit a first guess, a second with the exact size when they do not
+    out = np.zeros(max(4 * npat, 1), FM_HIT)
+    rc = fn(h, _p(packed), _p(offsets), npat, int(k), _p(nhits), _p(nocc), _p(out), out.size, tp)
+    if rc == E_ARG and total.value > out.size:
+        out = np.zeros(total.value, FM_HIT)
+        rc = fn(h, _p(packed), _p(offsets), npat, int(k), _p(nhits), _p(nocc), _p(out), out.size, tp)
+    _check(rc)
+    return nhits, nocc, out[:total.value]
+
+
+def _locate_hits(fn, h, patterns, hits):
+    """the starts of every hit's occurrences: a list of uint32 arrays, one per hit, each in row order"""
+    _, offsets = _pack_patterns(patterns)
+    hits = np.ascontiguousarray(hits, FM_HIT)
+    cuts = np.zeros(hits.size + 1, np.int64)
+    np.cumsum(hits["hi"].astype(np.int64) - hits["lo"], out=cuts[1:])
+    pos = np.zeros(max(int(cuts[-1]), 1), np.uint32)
+    total = ctypes.c_uint64(0)
+    _check(fn(h, _p(offsets), offsets.size - 1, _p(hits) if hits.size else None, hits.size, _p(pos), int(cuts[-1]),
+              ctypes.cast(ctypes.byref(total), ctypes.c_void_p)))
+    return [pos[cuts[i]:cuts[i + 1]] for i in range(hits.size)]
+
+
 def _pack_patterns(patterns):
     """a list of bytes / uint8 arrays -> (packed bytes, uint32 offsets[k + 1])"""
     parts = [np.frombuffer(bytes(p), np.uint8) if isinstance(p, (bytes, bytearray)) else np.ascontiguousarray(p, dtype=np.uint8).ravel()
@@ -402,6 +466,26 @@ class FmIndex:
         _check(lib().archon_hip_fm_locate(self.h, _p(packed), _p(offsets), lo.size, _p(pos), int(cuts[-1]),
                                           ctypes.cast(ctypes.byref(total), ctypes.c_void_p)))
         return [pos[cuts[j]:cuts[j + 1]] for j in range(lo.size)]
+
+    def approx(self, patterns, k, hits=True):
+        """every distinct string within k substituted bytes of each pattern: (nhits, nocc, hits), hits an FM_HIT array in the
+        order of the header's rule (None with hits=False: counting only)"""
+        return _approx(lib().archon_hip_fm_approx, self.h, patterns, k, hits)
+
+    def approx_dev(self, patterns_t, offsets_t, k, nhits_t, nocc_t, hits_t=None):
+        """torch tensors on the device: patterns uint8, offsets int32[n + 1], nhits and nocc int32[n] (written), hits an int32
+        tensor of 4 words per hit or None; current stream.  Returns the number of hits"""
+        total = ctypes.c_uint64(0)
+        cap = hits_t.numel() // 4 if hits_t is not None else 0
+        _check(lib().archon_hip_fm_approx_dev(self.h, ctypes.c_void_p(patterns_t.data_ptr()), ctypes.c_void_p(offsets_t.data_ptr()), nhits_t.numel(),
+                                              int(k), ctypes.c_void_p(nhits_t.data_ptr()), ctypes.c_void_p(nocc_t.data_ptr()),
+                                              ctypes.c_void_p(hits_t.data_ptr()) if hits_t is not None else None, cap,
+                                              ctypes.cast(ctypes.byref(total), ctypes.c_void_p), _stream_ptr()))
+        return total.value
+
+    def locate_hits(self, patterns, hits):
+        """the starts of every hit's occurrences from the samples (a list of uint32 arrays, one per hit, in the shape of locate)"""
+        return _locate_hits(lib().archon_hip_fm_locate_hits, self.h, patterns, hits)
 
     def extract(self, starts, lengths):
         """x[starts[j] .. starts[j] + lengths[j]) for every j: a list of uint8 arrays"""
@@ -539,6 +623,14 @@ class Block:
         _check(lib().archon_hip_block_fm_locate(self.h, _p(packed), _p(offsets), lo.size, _p(pos), int(cuts[-1]),
                                                 ctypes.cast(ctypes.byref(total), ctypes.c_void_p)))
         return [pos[cuts[j]:cuts[j + 1]] for j in range(lo.size)]
+
+    def fm_approx(self, patterns, k, hits=True):
+        """FmIndex.approx on the resident block's BWT (its FM index built on the first FM call after a forward)"""
+        return _approx(lib().archon_hip_block_fm_approx, self.h, patterns, k, hits)
+
+    def fm_locate_hits(self, patterns, hits):
+        """the starts of every hit's occurrences from the resident SA (needs forward(want_sa=True)): a list of uint32 arrays"""
+        return _locate_hits(lib().archon_hip_block_fm_locate_hits, self.h, patterns, hits)
 
     def fm_index(self, rate):
         """a standalone sampled FmIndex of the last forward's BWT (samples from the SA when that forward kept one, else by the

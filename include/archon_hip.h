@@ -15,7 +15,8 @@
  *   archon_hip_lms_select   Constructor::findLMS (160-172): the subset a7 sorts directly (a4 IT-2: bwt/a4/src/archon.c:163-169)
  *   archon_hip_lcp          nothing: the LCP array of the suffix array, below
  *   archon_hip_fm_*         nothing: counting and locating patterns by backward search on the BWT (an FM index), below;
- *                           with a sampled SA and ISA it locates and extracts without the block's suffix array
+ *                           with a sampled SA and ISA it locates and extracts without the block's suffix array, and it
+ *                           finds patterns with up to K substituted bytes (archon_hip_fm_approx)
  *
  * Ordering convention ("a7 order"): item s in 1..N names the
  * reversed prefix x[s-1],x[s-2],...,x[0],INF with INF > 255; sa[0..N) lists the
@@ -364,6 +365,82 @@ typedef struct archon_hip_fm_walk_stats {
     float ms_build, ms_query;    /* HIP events on the call's stream */
 } archon_hip_fm_walk_stats;
 int  archon_hip_get_fm_walk_stats(int dev, archon_hip_fm_walk_stats *out);   /* calling thread's last sample/locate/extract call */
+
+/* ---- approximate search: patterns with up to K substituted bytes --------------------------------------------------------
+ * Keys, R and occ' are those of the search rule above; a pattern is consumed in TEXT order, P[0] first, and the primary row
+ * is excluded from occ'.  A HIT of pattern P (length m) at distance K is a distinct string w of length m that occurs in x
+ * with Hamming distance d(w, P) <= K.  Its rows [lo, hi) are exactly what archon_hip_fm_count(w) returns; distinct hits have
+ * disjoint ranges; the occurrences of w start at sa[r] - m for r in [lo, hi).
+ * The search and its output order are this depth-first procedure, frame(d, t, lo, hi) called first as frame(0, 0, 0, n):
+ *   loop:
+ *     if t == m: emit hit (lo, hi, d); return
+ *     if d < K:                      an EXPANSION: every child at once
+ *         child[c] = [R[c], R[c+1])                           if t == 0 (the buckets: no rank step, not counted)
+ *                  = [R[c] + occ'(c,lo), R[c] + occ'(c,hi))   if t >= 1 (counted in `expansions`)
+ *         for c = 0 .. 255 ascending, c != P[t], child[c] nonempty: frame(d+1, t+1, child[c])
+ *         (lo, hi) = child[P[t]]
+ *     else:                          d == K: one rank step, as archon_hip_fm_count takes it
+ *         (lo, hi) = the bucket of P[0] if t == 0, else the rank step for P[t] (counted in `steps`)
+ *     if lo >= hi: return
+ *     t += 1
+ * So the hits of one pattern are ordered by their mismatch lists (p1, w[p1]), (p2, w[p2]), ... (p1 < p2 < ...), compared
+ * element by element, a list that ends coming AFTER every longer list that starts with it: the exact occurrence, if any,
+ * comes last.  This is not row order; it is deterministic and what every entry point returns.
+ * m = 0 gives the single hit (0, n, 0); m > n gives no hits and does no work; K = 0 gives one hit exactly when
+ * archon_hip_fm_count finds the pattern, with its range and its steps.  0 <= K <= 4, else ARCHON_E_ARG.
+ * The work counters follow from x, P and K alone (Sub_t(x): the distinct substrings of length t):
+ *   expansions = sum over t = 1 .. m-1 of |{u in Sub_t(x) : d(u, P[0 .. t)) <  K}|
+ *   steps      = sum over t = 1 .. m-1 of |{u in Sub_t(x) : d(u, P[0 .. t)) == K}|
+ * Example: "banana" (BWT nnbaaa, primary row 2, sa = 2 4 6 1 3 5): "bn" at K = 1 gives the hits (4, 6, 1) ("an", starts 1
+ * and 3) and then (0, 1, 1) ("ba", start 0), with 1 expansion and 2 steps; "an" at K = 1 gives only (4, 6, 0).
+ * Device work: one wave per pattern, at most K suspended frames (a 2 KiB LDS child table each); an expansion costs about
+ * as much as a rank step over all 256 symbols at once, a node at d == K one rank step. */
+typedef struct archon_hip_fm_hit {
+    uint32_t lo, hi;            /* the rows of the hit's string w */
+    uint32_t mismatches;        /* d(w, P) */
+    uint32_t pattern;           /* j: the pattern it belongs to */
+} archon_hip_fm_hit;
+/* nhits[k] and nocc[k] (distinct hits, rows summed over them) always written; *total = the sum of nhits.  hits_or_null NULL:
+ * counting only (no emit pass).  cap < *total with hits given: ARCHON_E_ARG, counts and *total written, hits untouched.
+ * Patterns and offsets as for archon_hip_fm_count; k = 0 writes *total = 0 and nothing else. */
+int  archon_hip_fm_approx(archon_hip_fm *f, const uint8_t *patterns, const uint32_t *offsets, uint32_t k, uint32_t max_mismatches,
+                          uint32_t *nhits, uint32_t *nocc, archon_hip_fm_hit *hits_or_null, uint64_t cap, uint64_t *total);
+/* device patterns, offsets, nhits, nocc and hits, *total a host pointer; on `stream` (NULL = the context's own), complete on
+ * return; decreasing offsets are found on the device (ARCHON_E_ARG, nothing emitted) */
+int  archon_hip_fm_approx_dev(archon_hip_fm *f, const uint8_t *d_patterns, const uint32_t *d_offsets, uint32_t k, uint32_t max_mismatches,
+                              uint32_t *d_nhits, uint32_t *d_nocc, archon_hip_fm_hit *d_hits_or_null, uint64_t cap, uint64_t *total,
+                              void *stream);
+/* the resident block's BWT; its table is built on the first FM call after a forward, as for archon_hip_block_fm_count */
+int  archon_hip_block_fm_approx(archon_hip_block *b, const uint8_t *patterns, const uint32_t *offsets, uint32_t k, uint32_t max_mismatches,
+                                uint32_t *nhits, uint32_t *nocc, archon_hip_fm_hit *hits_or_null, uint64_t cap, uint64_t *total);
+/* the starts of every hit's occurrences, hit by hit, each in row order: sa[r] - m for r in [lo, hi), m the length of pattern
+ * hit.pattern (patterns' offsets[k + 1] as given to the search).  *total = their number; cap < *total: ARCHON_E_ARG,
+ * nothing written.  hit.pattern >= k, lo > hi or hi > n, or nhits >= 2^32: ARCHON_E_ARG.  A sampled handle (else
+ * ARCHON_E_ARG) walks LF to the samples; a block needs the suffix array of its last forward (else ARCHON_E_ARG). */
+int  archon_hip_fm_locate_hits(archon_hip_fm *f, const uint32_t *offsets, uint32_t k, const archon_hip_fm_hit *hits, uint64_t nhits,
+                               uint32_t *pos, uint64_t cap, uint64_t *total);
+int  archon_hip_block_fm_locate_hits(archon_hip_block *b, const uint32_t *offsets, uint32_t k, const archon_hip_fm_hit *hits, uint64_t nhits,
+                                     uint32_t *pos, uint64_t cap, uint64_t *total);
+/* the CALLING THREAD's last approximate call (approx or locate_hits) on `dev`; approximate calls leave archon_hip_fm_stats,
+ * archon_hip_fm_walk_stats and the rest alone */
+typedef struct archon_hip_fm_approx_stats {
+    uint32_t n;                 /* block size of the index */
+    uint32_t patterns;          /* k of the call */
+    uint32_t max_mismatches;    /* K (0 for locate_hits) */
+    uint32_t built;             /* 1 when the call built the block's table */
+    uint64_t pattern_bytes;     /* bytes of the patterns */
+    uint64_t expansions;        /* expansions at t >= 1 (count pass) */
+    uint64_t steps;             /* single rank steps at t >= 1 (count pass) */
+    uint64_t hits;              /* hits found (approx) or located (locate_hits) */
+    uint64_t occurrences;       /* rows summed over those hits */
+    uint64_t lf_steps;          /* locate_hits on a sampled handle: LF steps of all walks */
+    uint32_t kernel_launches;   /* launches issued by the call */
+    uint32_t host_syncs;        /* times the host waited for the stream inside the call */
+    float ms_build;             /* device time of the table build, 0 without one */
+    float ms_count, ms_emit;    /* device time of the count and the emit pass (HIP events) */
+    float ms_locate;            /* device time of locate_hits' kernel */
+} archon_hip_fm_approx_stats;
+int  archon_hip_get_fm_approx_stats(int dev, archon_hip_fm_approx_stats *out);
 
 /* ---- measurement ------------------------------------------------------------- */
 
