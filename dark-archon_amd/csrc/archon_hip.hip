@@ -15,6 +15,7 @@
 #include "fm.hiph"
 #include "fm_walk.hiph"
 #include "fm_approx.hiph"
+#include "fm_host.hiph"
 
 #include <stdarg.h>
 #include <atomic>
@@ -81,6 +82,22 @@ static thread_local LastStats<archon_hip_lcp_stats> t_lcp_stats;        // LCP c
 static thread_local LastStats<archon_hip_fm_stats> t_fm_stats;          // FM calls: they leave both of the others alone
 static thread_local LastStats<archon_hip_fm_walk_stats> t_fmw_stats;    // sampled-index calls: sample, block_fm_index, locate, extract
 static thread_local LastStats<archon_hip_fm_approx_stats> t_fma_stats;  // approximate calls: approx, locate_hits
+
+// The record of one FM call: kept for the calling thread when the scope ends, on whichever path the call leaves it, with the
+// host waits since the scope began.
+template <class T>
+struct KeepStats {
+    LastStats<T> &last;
+    int dev;
+    uint32_t syncs0 = t_sync_count;
+    T st = {};
+    KeepStats(LastStats<T> &l, int d) : last(l), dev(d) {}
+    ~KeepStats()
+    {
+        st.host_syncs = t_sync_count - syncs0;
+        last.keep(dev, st);
+    }
+};
 
 static inline int keep_stats(Ctx *c, int rc)
 {
@@ -1694,232 +1711,15 @@ int archon_hip_lcp(const uint8_t *x, uint32_t n, const uint32_t *sa, uint32_t *l
     });
 }
 
-// ---- the FM index (fm.hiph)
-// The handle owns one device allocation: [its copy of the BWT] | super | sub | R.  A resident block's handle reads the
-// block's own d_bwt (n + 64 bytes, so 16-byte loads that start below n stay inside it) and has no copy.  A sampled handle
-// (fm_walk.hiph) owns a second one: isa | sa | marks | dir, rate 0 without it.
-struct archon_hip_fm {
-    int dev = 0;
-    uint32_t n = 0, base = 0, base_sym = 0, sbits = 0, bbits = 0;
-    char *mem = nullptr;
-    const uint8_t *bwt = nullptr;
-    uint32_t *super = nullptr, *R = nullptr;
-    uint16_t *sub = nullptr;
-    uint64_t table_bytes = 0;
-    uint32_t rate = 0, rbits = 0, ns = 0;
-    char *smem = nullptr;
-    uint32_t *isa = nullptr, *sa_s = nullptr, *marks = nullptr, *dir = nullptr;
-    uint64_t sample_bytes = 0;
-    fmk::FmTable table() const { return fmk::FmTable{bwt, super, sub, R, n, base, base_sym, sbits, bbits}; }
-    fmw::FmSamples samples() const { return fmw::FmSamples{isa, sa_s, marks, dir, rbits, ns}; }
-};
-
-static void fm_release(archon_hip_fm *f)
-{
-    if (!f) return;
-    if (f->mem || f->smem) {
-        (void)hipSetDevice(f->dev);
-        if (f->mem) (void)hipFree(f->mem);
-        if (f->smem) (void)hipFree(f->smem);
-    }
-    delete f;
-}
-
-static inline size_t round256(size_t b) { return (b + 255) & ~size_t(255); }
-
-static inline int log2_exact(uint32_t v)
-{
-    int b = 0;
-    while ((1u << b) < v) ++b;
-    return b;
-}
-
-// Builds a table over a BWT: h_bwt (host) or d_bwt (device) is copied into the handle's memory when `copy`; otherwise the
-// handle reads d_bwt where it is.  The stream holds the build until the one wait at its end (the primary row's byte).
-static int fm_build(Ctx *c, hipStream_t s, const uint8_t *h_bwt, const uint8_t *d_bwt, bool copy, uint32_t n, uint32_t base,
-                    archon_hip_fm **out, archon_hip_fm_stats *st)
-{
-    using namespace fmk;
-    const uint32_t sub_rows = g_route.fm_sub_rows > 0 ? (uint32_t)g_route.fm_sub_rows : 1u << kSubBits;
-    const uint32_t super_rows = g_route.fm_super_rows > 0 ? (uint32_t)g_route.fm_super_rows : 1u << kSuperBits;
-    if (super_rows < sub_rows) { set_error("FM_SUPER_ROWS=%u is not a multiple of FM_SUB_ROWS=%u", super_rows, sub_rows); return ARCHON_E_ARG; }
-    FmArena L;
-    ARCHON_TRY(ctx_carve(c, [&](Carve &a) { return fm_layout(a, L, 0, 0, 0); }));
-    const uint32_t syncs0 = t_sync_count;
-    archon_hip_fm *f = new archon_hip_fm();
-    f->dev = c->dev;
-    f->n = n;
-    f->base = base;
-    f->sbits = (uint32_t)log2_exact(super_rows);
-    f->bbits = (uint32_t)log2_exact(sub_rows);
-    const uint32_t nsuper = (n >> f->sbits) + 1, nsub = (n >> f->bbits) + 1;
-    const size_t own = copy ? round256((size_t)n + 64) : 0;
-    const size_t super_b = (size_t)nsuper * 256 * 4, sub_b = round256((size_t)nsub * 256 * 2), r_b = round256(257 * 4);
-    f->table_bytes = super_b + sub_b + r_b;
-    if (hipMalloc((void **)&f->mem, own + f->table_bytes) != hipSuccess) {
-        (void)hipGetLastError();
-        delete f;
-        set_error("FM index: device allocation of %zu bytes failed", own + (size_t)f->table_bytes);
-        return ARCHON_E_NOMEM;
-    }
-    f->bwt = copy ? reinterpret_cast<const uint8_t *>(f->mem) : d_bwt;
-    f->super = reinterpret_cast<uint32_t *>(f->mem + own);
-    f->sub = reinterpret_cast<uint16_t *>(f->mem + own + super_b);
-    f->R = reinterpret_cast<uint32_t *>(f->mem + own + super_b + sub_b);
-    auto fail = [&](int rc) { fm_release(f); return rc; };
-    if (copy && hipMemcpyAsync(f->mem, h_bwt ? (const void *)h_bwt : (const void *)d_bwt, n,
-                               h_bwt ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice, s) != hipSuccess) {
-        set_error("FM index: copy of the BWT failed: %s", hipGetErrorString(hipGetLastError()));
-        return fail(ARCHON_E_HIP);
-    }
-    StageTimer tm(c, 72, s);
-    const int e0 = tm.mark();
-    hipLaunchKernelGGL(inv::k_chunk_hist, dim3(nsuper), dim3(kHistBlock), 0, s, f->bwt, n, base, super_rows, f->super);
-    hipLaunchKernelGGL(inv::k_chunk_scan, dim3(1), dim3(1024), 0, s, f->super, nsuper, f->bwt, base, L.totals, f->R);
-    hipLaunchKernelGGL(k_fm_sub, dim3(nsuper), dim3(256), 0, s, f->bwt, n, base, f->sbits, f->bbits, nsub, f->sub);
-    const int e1 = tm.mark();
-    uint32_t *rd = c->h_mail + mail::kRead.at;
-    rd[0] = 0;
-    if (hipGetLastError() != hipSuccess || hipMemcpyAsync(rd, f->bwt + base, 1, hipMemcpyDeviceToHost, s) != hipSuccess ||
-        hipStreamSynchronize(s) != hipSuccess) {
-        set_error("FM index: table build failed: %s", hipGetErrorString(hipGetLastError()));
-        return fail(ARCHON_E_HIP);
-    }
-    ++t_sync_count;
-    f->base_sym = rd[0] & 0xFFu;
-    st->n = n;
-    st->built = 1;
-    st->table_bytes = f->table_bytes;
-    st->kernel_launches += 3;
-    st->host_syncs += t_sync_count - syncs0;
-    st->ms_build = tm.ms(e0, e1);
-    *out = f;
-    return ARCHON_OK;
-}
-
-// The count kernel over device patterns, offsets and ranges; the step counters and the bad-offsets flag into *st / the return.
-static int fm_count_run(Ctx *c, hipStream_t s, const archon_hip_fm *f, const uint8_t *d_pat, const uint32_t *d_off, uint32_t k,
-                        uint32_t *d_lo, uint32_t *d_hi, StageTimer &tm, archon_hip_fm_stats *st)
-{
-    using namespace fmk;
-    uint32_t *mail = c->d_mail + mail::kDevFm.at, *rd = c->h_mail + mail::kRead.at;
-    static_assert(kWords <= mail::kDevFm.len && kWords <= mail::kRead.len, "the FM words in the mailbox");
-    ARCHON_HIP_TRY(hipMemsetAsync(mail, 0, kWords * sizeof(uint32_t), s));
-    const uint32_t g = div_up(k, 4);
-    hipLaunchKernelGGL(k_fm_count, dim3(g < kCountGrid ? g : kCountGrid), dim3(256), 0, s, f->table(), d_pat, d_off, k, d_lo, d_hi, mail);
-    ARCHON_HIP_TRY(hipGetLastError());
-    tm.mark();
-    ARCHON_HIP_TRY(hipMemcpyAsync(rd, mail, kWords * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
-    ARCHON_SYNC(s);
-    st->kernel_launches += 1;
-    memcpy(&st->steps, rd + kSteps, sizeof(uint64_t));
-    memcpy(&st->shared_steps, rd + kShared, sizeof(uint64_t));
-    if (rd[kBadOffsets]) { set_error("FM index: offsets decrease"); return ARCHON_E_ARG; }
-    return ARCHON_OK;
-}
-
-static int fm_check_offsets(const uint32_t *offsets, uint32_t k)
-{
-    for (uint32_t j = 0; j < k; ++j)
-        if (offsets[j + 1] < offsets[j]) { set_error("FM index: offsets[%u] < offsets[%u]", j + 1, j); return ARCHON_E_ARG; }
-    return ARCHON_OK;
-}
-
-// Host patterns and ranges through the context's arena.  When `locate` is given (a resident block's suffix array, or the
-// samples of a sampled handle: d_sa null), the ranges come back, the host sums them, and a gather or the LF walks write the
-// starts (the walks' counters into *wst).
-struct FmLocate {
-    const uint32_t *d_sa;
-    uint32_t *pos;
-    uint64_t cap;
-    uint64_t *total;
-    archon_hip_fm_walk_stats *wst;
-};
-static int fm_host_query(Ctx *c, hipStream_t s, const archon_hip_fm *f, const uint8_t *patterns, const uint32_t *offsets, uint32_t k,
-                         uint32_t *lo, uint32_t *hi, const FmLocate *loc, archon_hip_fm_stats *st)
-{
-    using namespace fmk;
-    const size_t pat_bytes = offsets[k];
-    st->n = f->n;
-    st->patterns = k;
-    st->pattern_bytes = (uint64_t)offsets[k] - offsets[0];
-    st->table_bytes = f->table_bytes;
-    FmArena L;
-    ARCHON_TRY(ctx_carve(c, [&](Carve &a) { return fm_layout(a, L, pat_bytes, k, 0); }));
-    const uint32_t syncs0 = t_sync_count;
-    if (pat_bytes) ARCHON_HIP_TRY(hipMemcpyAsync(L.pat, patterns, pat_bytes, hipMemcpyHostToDevice, s));
-    ARCHON_HIP_TRY(hipMemcpyAsync(L.off, offsets, ((size_t)k + 1) * 4, hipMemcpyHostToDevice, s));
-    StageTimer tm(c, 72, s);
-    const int e0 = tm.mark();
-    ARCHON_TRY(fm_count_run(c, s, f, L.pat, L.off, k, L.lo, L.hi, tm, st));
-    const int e1 = tm.n - 1;
-    ARCHON_HIP_TRY(hipMemcpyAsync(lo, L.lo, (size_t)k * 4, hipMemcpyDeviceToHost, s));
-    ARCHON_HIP_TRY(hipMemcpyAsync(hi, L.hi, (size_t)k * 4, hipMemcpyDeviceToHost, s));
-    ARCHON_SYNC(s);
-    st->ms_query = tm.ms(e0, e1);
-    if (loc) {
-        std::vector<uint64_t> first((size_t)k + 1);
-        uint64_t t = 0;
-        for (uint32_t j = 0; j < k; ++j) {
-            first[j] = t;
-            t += hi[j] > lo[j] ? hi[j] - lo[j] : 0;
-        }
-        first[k] = t;
-        *loc->total = t;
-        if (t > loc->cap) {
-            st->host_syncs += t_sync_count - syncs0;
-            set_error("FM locate: %llu starts, room for %llu", (unsigned long long)t, (unsigned long long)loc->cap);
-            return ARCHON_E_ARG;
-        }
-        // the arena may move for the positions: the offsets, lo and the sums go up again
-        ARCHON_TRY(ctx_carve(c, [&](Carve &a) { return fm_layout(a, L, 0, k, t); }));
-        ARCHON_HIP_TRY(hipMemcpyAsync(L.off, offsets, ((size_t)k + 1) * 4, hipMemcpyHostToDevice, s));
-        ARCHON_HIP_TRY(hipMemcpyAsync(L.lo, lo, (size_t)k * 4, hipMemcpyHostToDevice, s));
-        ARCHON_HIP_TRY(hipMemcpyAsync(L.first, first.data(), ((size_t)k + 1) * 8, hipMemcpyHostToDevice, s));
-        uint32_t *wmail = c->d_mail + mail::kDevFmWalk.at, *rd = c->h_mail + mail::kRead.at;
-        static_assert(fmw::kWords <= mail::kDevFmWalk.len && fmw::kWords <= mail::kRead.len, "the sampled FM words in the mailbox");
-        if (!loc->d_sa) ARCHON_HIP_TRY(hipMemsetAsync(wmail, 0, fmw::kWords * sizeof(uint32_t), s));
-        const int e2 = tm.mark();
-        if (t && loc->d_sa) {
-            const uint64_t g = (t + 255) / 256;
-            hipLaunchKernelGGL(k_fm_locate<PatternRows>, dim3(g < kLocateGrid ? (uint32_t)g : kLocateGrid), dim3(256), 0, s, loc->d_sa,
-                               PatternRows{L.off, L.lo}, L.first, k, L.pos);
-            ARCHON_HIP_TRY(hipGetLastError());
-            st->kernel_launches += 1;
-        } else if (t) {
-            const uint64_t g = (t + 3) / 4;
-            hipLaunchKernelGGL(fmw::k_fm_walk_locate<PatternRows>, dim3(g < fmw::kWalkGrid ? (uint32_t)g : fmw::kWalkGrid), dim3(256), 0, s, f->table(),
-                               f->samples(), PatternRows{L.off, L.lo}, L.first, k, L.pos, wmail);
-            ARCHON_HIP_TRY(hipGetLastError());
-            st->kernel_launches += 1;
-        }
-        const int e3 = tm.mark();
-        if (t) ARCHON_HIP_TRY(hipMemcpyAsync(loc->pos, L.pos, t * 4, hipMemcpyDeviceToHost, s));
-        if (!loc->d_sa) ARCHON_HIP_TRY(hipMemcpyAsync(rd, wmail, fmw::kWords * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
-        ARCHON_SYNC(s);
-        st->ms_query += tm.ms(e2, e3);
-        if (loc->wst) {
-            loc->wst->walks = t;
-            memcpy(&loc->wst->lf_steps, rd + fmw::kSteps, sizeof(uint64_t));
-            loc->wst->max_walk = rd[fmw::kMaxWalk];
-            loc->wst->kernel_launches = t ? 1 : 0;
-            loc->wst->ms_query = tm.ms(e2, e3);
-        }
-    }
-    st->host_syncs += t_sync_count - syncs0;
-    return ARCHON_OK;
-}
-
+// ---- the FM index (fm_host.hiph: the handle and every driver; here the argument checks and the statistics)
 int archon_hip_fm_create(const uint8_t *bwt, uint32_t n, uint32_t base_id, int dev, archon_hip_fm **out)
 {
     if (!bwt || !out) { set_error("null pointer"); return ARCHON_E_ARG; }
     ARCHON_TRY(check_n(n));
     if (base_id >= n) { set_error("primary row %u out of range [0, %u)", base_id, n); return ARCHON_E_ARG; }
     return with_ctx(dev, nullptr, [&](Ctx *c, hipStream_t s) -> int {
-        archon_hip_fm_stats st = {};
-        const int rc = fm_build(c, s, bwt, nullptr, true, n, base_id, out, &st);
-        t_fm_stats.keep(dev, st);
-        return rc;
+        KeepStats<archon_hip_fm_stats> keep(t_fm_stats, dev);
+        return fm_build(c, s, bwt, nullptr, true, n, base_id, out, &keep.st);
     });
 }
 
@@ -1929,10 +1729,8 @@ int archon_hip_fm_create_dev(const uint8_t *d_bwt, uint32_t n, uint32_t base_id,
     ARCHON_TRY(check_n(n));
     if (base_id >= n) { set_error("primary row %u out of range [0, %u)", base_id, n); return ARCHON_E_ARG; }
     return with_ctx(dev, stream, [&](Ctx *c, hipStream_t s) -> int {
-        archon_hip_fm_stats st = {};
-        const int rc = fm_build(c, s, nullptr, d_bwt, true, n, base_id, out, &st);
-        t_fm_stats.keep(dev, st);
-        return rc;
+        KeepStats<archon_hip_fm_stats> keep(t_fm_stats, dev);
+        return fm_build(c, s, nullptr, d_bwt, true, n, base_id, out, &keep.st);
     });
 }
 
@@ -1944,10 +1742,8 @@ int archon_hip_fm_count(archon_hip_fm *f, const uint8_t *patterns, const uint32_
     if (!k) return ARCHON_OK;
     ARCHON_TRY(fm_check_offsets(offsets, k));
     return with_ctx(f->dev, nullptr, [&](Ctx *c, hipStream_t s) -> int {
-        archon_hip_fm_stats st = {};
-        const int rc = fm_host_query(c, s, f, patterns, offsets, k, lo, hi, nullptr, &st);
-        t_fm_stats.keep(f->dev, st);
-        return rc;
+        KeepStats<archon_hip_fm_stats> keep(t_fm_stats, f->dev);
+        return fm_count_host(c, s, f, patterns, offsets, k, lo, hi, &keep.st);
     });
 }
 
@@ -1957,23 +1753,8 @@ int archon_hip_fm_count_dev(archon_hip_fm *f, const uint8_t *d_patterns, const u
     if (!f || !d_patterns || !d_offsets || !d_lo || !d_hi) { set_error("null pointer"); return ARCHON_E_ARG; }
     if (!k) return ARCHON_OK;
     return with_ctx(f->dev, stream, [&](Ctx *c, hipStream_t s) -> int {
-        archon_hip_fm_stats st = {};
-        st.n = f->n;
-        st.patterns = k;
-        st.table_bytes = f->table_bytes;
-        const uint32_t syncs0 = t_sync_count;
-        uint32_t *ends = c->h_mail + mail::kRead.at + fmk::kWords;     // offsets[0] and offsets[k], for the statistics
-        static_assert(fmk::kWords + 2 <= mail::kRead.len, "the FM words and the offsets' ends in the readback words");
-        ARCHON_HIP_TRY(hipMemcpyAsync(&ends[0], d_offsets, 4, hipMemcpyDeviceToHost, s));
-        ARCHON_HIP_TRY(hipMemcpyAsync(&ends[1], d_offsets + k, 4, hipMemcpyDeviceToHost, s));
-        StageTimer tm(c, 72, s);
-        const int e0 = tm.mark();
-        const int rc = fm_count_run(c, s, f, d_patterns, d_offsets, k, d_lo, d_hi, tm, &st);
-        st.ms_query = tm.ms(e0, tm.n - 1);
-        st.pattern_bytes = ends[1] >= ends[0] ? ends[1] - ends[0] : 0;
-        st.host_syncs = t_sync_count - syncs0;
-        t_fm_stats.keep(f->dev, st);
-        return rc;
+        KeepStats<archon_hip_fm_stats> keep(t_fm_stats, f->dev);
+        return fm_count_dev(c, s, f, d_patterns, d_offsets, k, d_lo, d_hi, &keep.st);
     });
 }
 
@@ -1983,162 +1764,22 @@ int archon_hip_get_fm_stats(int dev, archon_hip_fm_stats *out)
     return t_fm_stats.get(dev, out, "FM call");
 }
 
-// ---- the sampled FM index (fm_walk.hiph)
-
-static int fmw_rate_bits(uint32_t rate, uint32_t *rbits)
-{
-    if (rate == 0 || (rate & (rate - 1)) || rate > (1u << fmw::kMaxRateBits)) {
-        set_error("sample rate %u: not a power of two in [1, 65536]", rate);
-        return ARCHON_E_ARG;
-    }
-    *rbits = (uint32_t)log2_exact(rate);
-    return ARCHON_OK;
-}
-
-// The ISA samples by the LF walk over the handle's own BWT: the inverse's LF table and cut, a measuring walk (the inverse's
-// first walk with no slab), the list ranking, then k_walk_sample.  One wait at the end tells whether the cut has to be made
-// again (as inverse_run) or the bytes are no BWT.
-static int fm_sample_walk(Ctx *c, hipStream_t s, const archon_hip_fm *f, uint32_t rbits, uint32_t *isa, const FmwArena &L, uint32_t *launches)
-{
-    const uint32_t n = f->n, base = f->base;
-    uint32_t *small = L.small, *rd = c->h_mail + mail::kRead.at;
-    ARCHON_HIP_TRY(hipMemsetAsync(small, 0, inv_small::kWords * sizeof(uint32_t), s));
-    ARCHON_TRY(lf_build_launch(c, s, f->bwt, n, base, L.T, L.status, small));
-    *launches += 3;
-    uint32_t lut_shift = 0;
-    while (((uint64_t)(n - 1) >> lut_shift) >= (1u << inv::kSymLutBits)) ++lut_shift;
-    const uint32_t sbits = inv_sbits(n), nreg = div_up(n, 1u << sbits), nchains = nreg + 1;
-    const uint32_t gc = div_up(nchains, 256);
-    const uint32_t max_steps = (4096u << sbits) < n ? (4096u << sbits) : n;
-    const uint32_t gq = (uint32_t)kNumCU * 3, gs = div_up(nchains, inv::kWalkLanes) < gq ? div_up(nchains, inv::kWalkLanes) : gq;
-    inv::Cut cut;
-    cut.n = n; cut.base = base; cut.sbits = sbits; cut.nreg = nreg;
-    uint2 *nd[2] = {L.nd[0], L.nd[1]};
-    for (uint32_t attempt = 0;; ++attempt) {
-        cut.salt = attempt * 0x85EBCA6Bu;
-        if (nchains >= (uint32_t)kNumCU * 64u)
-            hipLaunchKernelGGL(inv::k_walk_queue, dim3(gq), dim3(inv::kWalkLanes), 0, s, L.T, cut, nchains, max_steps, small + inv_small::kStarts, lut_shift,
-                               0u, (uint8_t *)nullptr, L.next, L.len, small + inv_small::kErr, 0u);
-        else
-            hipLaunchKernelGGL(inv::k_walk_store, dim3(gc), dim3(256), 0, s, L.T, cut, nchains, max_steps, small + inv_small::kStarts, lut_shift, 0u,
-                               (uint8_t *)nullptr, L.next, L.len, small + inv_small::kErr);
-        const uint32_t head = (inv::cut_row(cut, base >> sbits) == base) ? (base >> sbits) : nreg;
-        hipLaunchKernelGGL(inv::k_rank_init, dim3(gc), dim3(256), 0, s, L.next, L.len, nchains, head, nd[0]);
-        *launches += 2;
-        int cur = 0;
-        for (uint64_t span = 1; span < nchains; span *= (inv::kRankHops + 1)) {
-            hipLaunchKernelGGL(inv::k_rank_jump, dim3(gc), dim3(256), 0, s, nd[cur], nchains, nd[cur ^ 1]);
-            cur ^= 1;
-            ++*launches;
-        }
-        hipLaunchKernelGGL(fmw::k_walk_sample, dim3(gs), dim3(inv::kWalkLanes), 0, s, L.T, cut, nchains, L.len, nd[cur], rbits, isa,
-                           small + inv_small::kErr);
-        ++*launches;
-        ARCHON_HIP_TRY(hipGetLastError());
-        ARCHON_HIP_TRY(hipMemcpyAsync(rd, small + inv_small::kErr, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
-        ARCHON_HIP_TRY(hipMemcpyAsync(rd + 1, &nd[cur][head].y, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
-        ARCHON_SYNC(s);
-        if (rd[0] & 1u) { set_error("device consistency flag (look-back spin bound)"); return ARCHON_E_INTERNAL; }
-        if (!(rd[0] & 2u)) {
-            if (rd[1] != n) { set_error("LF walk closes after %u of %u rows: not a BWT in a7 format", rd[1], n); return ARCHON_E_CORRUPT; }
-            return ARCHON_OK;
-        }
-        if (attempt == 1) { set_error("LF walk does not reach a cut row: not a BWT in a7 format"); return ARCHON_E_CORRUPT; }
-        ARCHON_HIP_TRY(hipMemsetAsync(small + inv_small::kErr, 0, sizeof(uint32_t), s));
-    }
-}
-
-// Samples of rate 2^rbits for f: from d_sa (a suffix array of f's BWT) when given, else by the LF walk.  They replace f's
-// earlier samples only when the build succeeds.
-static int fm_sample_run(Ctx *c, hipStream_t s, archon_hip_fm *f, uint32_t rbits, const uint32_t *d_sa, archon_hip_fm_walk_stats *st)
-{
-    using namespace fmw;
-    const uint32_t n = f->n, rate = 1u << rbits;
-    const uint32_t ns = (uint32_t)(((uint64_t)n + rate - 1) >> rbits), nblk = (n >> kDirBits) + 1;
-    const bool walk = d_sa == nullptr;
-    st->n = n;
-    st->rate = rate;
-    st->route = walk ? 2 : 1;
-    FmwArena L;
-    ARCHON_TRY(ctx_carve(c, [&](Carve &a) { return fmw_layout(a, L, n, walk); }));
-    const size_t isa_b = round256((size_t)ns * 4), marks_b = round256((size_t)nblk * 32), dir_b = round256((size_t)nblk * 4);
-    const size_t bytes = 2 * isa_b + marks_b + dir_b;
-    struct Owned {
-        char *p = nullptr;
-        ~Owned() { if (p) (void)hipFree(p); }
-    } mem;
-    if (hipMalloc((void **)&mem.p, bytes) != hipSuccess) {
-        (void)hipGetLastError();
-        set_error("FM samples: device allocation of %zu bytes failed", bytes);
-        return ARCHON_E_NOMEM;
-    }
-    uint32_t *isa = reinterpret_cast<uint32_t *>(mem.p), *sa_s = reinterpret_cast<uint32_t *>(mem.p + isa_b);
-    uint32_t *marks = reinterpret_cast<uint32_t *>(mem.p + 2 * isa_b), *dir = reinterpret_cast<uint32_t *>(mem.p + 2 * isa_b + marks_b);
-    const uint32_t syncs0 = t_sync_count;
-    uint32_t launches = 0;
-    StageTimer tm(c, 72, s);
-    const int e0 = tm.mark();
-    if (walk) {
-        ARCHON_TRY(fm_sample_walk(c, s, f, rbits, isa, L, &launches));
-    } else {
-        const uint32_t g = div_up(n, 256);
-        hipLaunchKernelGGL(k_samp_from_sa, dim3(g < 8192u ? g : 8192u), dim3(256), 0, s, d_sa, n, f->base, rbits, ns, isa);
-        ++launches;
-    }
-    ARCHON_HIP_TRY(hipMemsetAsync(marks, 0, marks_b, s));
-    const uint32_t gk = div_up(ns, 256), gb = div_up(nblk, 256);
-    hipLaunchKernelGGL(k_samp_mark, dim3(gk < 8192u ? gk : 8192u), dim3(256), 0, s, isa, ns, n, marks);
-    hipLaunchKernelGGL(k_samp_dir, dim3(gb < 8192u ? gb : 8192u), dim3(256), 0, s, marks, nblk, dir);
-    ARCHON_TRY(launch_scan<0>(s, dir, dir, nblk, L.scan, nullptr));
-    hipLaunchKernelGGL(k_samp_sa, dim3(gk < 8192u ? gk : 8192u), dim3(256), 0, s, isa, ns, n, rbits, marks, dir, sa_s);
-    launches += 6;
-    const int e1 = tm.mark();
-    ARCHON_HIP_TRY(hipGetLastError());
-    ARCHON_SYNC(s);
-    if (f->smem) (void)hipFree(f->smem);
-    f->smem = mem.p;
-    mem.p = nullptr;
-    f->rate = rate;
-    f->rbits = rbits;
-    f->ns = ns;
-    f->isa = isa;
-    f->sa_s = sa_s;
-    f->marks = marks;
-    f->dir = dir;
-    f->sample_bytes = bytes;
-    st->samples = ns;
-    st->sample_bytes = bytes;
-    st->kernel_launches = launches;
-    st->host_syncs = t_sync_count - syncs0;
-    st->ms_build = tm.ms(e0, e1);
-    return ARCHON_OK;
-}
-
-static void fmw_handle_stats(const archon_hip_fm *f, archon_hip_fm_walk_stats *st)
-{
-    st->n = f->n;
-    st->rate = f->rate;
-    st->samples = f->ns;
-    st->sample_bytes = f->sample_bytes;
-}
-
+// ---- the sampled FM index
 int archon_hip_fm_sample(archon_hip_fm *f, uint32_t rate)
 {
     if (!f) { set_error("null pointer"); return ARCHON_E_ARG; }
     uint32_t rbits;
     ARCHON_TRY(fmw_rate_bits(rate, &rbits));
     return with_ctx(f->dev, nullptr, [&](Ctx *c, hipStream_t s) -> int {
-        archon_hip_fm_walk_stats st = {};
-        const int rc = fm_sample_run(c, s, f, rbits, nullptr, &st);
-        t_fmw_stats.keep(f->dev, st);
-        return rc;
+        KeepStats<archon_hip_fm_walk_stats> keep(t_fmw_stats, f->dev);
+        return fm_sample_run(c, s, f, rbits, nullptr, &keep.st);
     });
 }
 
 int archon_hip_fm_read_samples(archon_hip_fm *f, uint32_t *isa, uint32_t cap, uint32_t *count)
 {
     if (!f || !isa || !count) { set_error("null pointer"); return ARCHON_E_ARG; }
-    if (!f->rate) { set_error("FM index: the handle has no samples (archon_hip_fm_sample)"); return ARCHON_E_ARG; }
+    ARCHON_TRY(fm_check_sampled(f));
     *count = f->ns;
     if (cap < f->ns) { set_error("FM samples: %u ISA entries, room for %u", f->ns, cap); return ARCHON_E_ARG; }
     ARCHON_HIP_TRY(hipSetDevice(f->dev));
@@ -2149,57 +1790,22 @@ int archon_hip_fm_read_samples(archon_hip_fm *f, uint32_t *isa, uint32_t cap, ui
 int archon_hip_fm_locate(archon_hip_fm *f, const uint8_t *patterns, const uint32_t *offsets, uint32_t k, uint32_t *pos, uint64_t cap, uint64_t *total)
 {
     if (!f || !patterns || !offsets || !pos || !total) { set_error("null pointer"); return ARCHON_E_ARG; }
-    if (!f->rate) { set_error("FM index: the handle has no samples (archon_hip_fm_sample)"); return ARCHON_E_ARG; }
+    ARCHON_TRY(fm_check_sampled(f));
     *total = 0;
     if (!k) return ARCHON_OK;
     ARCHON_TRY(fm_check_offsets(offsets, k));
     return with_ctx(f->dev, nullptr, [&](Ctx *c, hipStream_t s) -> int {
-        archon_hip_fm_stats st = {};
-        archon_hip_fm_walk_stats wst = {};
-        fmw_handle_stats(f, &wst);
-        std::vector<uint32_t> lo(k), hi(k);
-        const FmLocate loc{nullptr, pos, cap, total, &wst};
-        const uint32_t syncs0 = t_sync_count;
-        const int rc = fm_host_query(c, s, f, patterns, offsets, k, lo.data(), hi.data(), &loc, &st);
-        wst.host_syncs = t_sync_count - syncs0;
-        t_fm_stats.keep(f->dev, st);
-        t_fmw_stats.keep(f->dev, wst);
-        return rc;
+        KeepStats<archon_hip_fm_stats> keep(t_fm_stats, f->dev);
+        KeepStats<archon_hip_fm_walk_stats> walk(t_fmw_stats, f->dev);
+        fmw_handle_stats(f, &walk.st);
+        return fm_locate_host(c, s, f, nullptr, patterns, offsets, k, pos, cap, total, &keep.st, &walk.st);
     });
-}
-
-// Requests on the device (d_starts, d_off) into d_out[off[j] - shift ..): checks, segment counts and their sums, the walks.
-static int fm_extract_run(Ctx *c, hipStream_t s, const archon_hip_fm *f, const uint32_t *d_starts, const uint32_t *d_off, uint32_t k,
-                          uint8_t *d_out, uint32_t shift, const FmqArena &L, archon_hip_fm_walk_stats *st)
-{
-    using namespace fmw;
-    uint32_t *mail = c->d_mail + mail::kDevFmWalk.at, *rd = c->h_mail + mail::kRead.at;
-    static_assert(kWords + 1 <= mail::kRead.len, "the sampled FM words and the segment total in the readback words");
-    ARCHON_HIP_TRY(hipMemsetAsync(mail, 0, kWords * sizeof(uint32_t), s));
-    StageTimer tm(c, 72, s);
-    const int e0 = tm.mark();
-    const uint32_t g = div_up(k, 256);
-    hipLaunchKernelGGL(k_ext_prep, dim3(g < 4096u ? g : 4096u), dim3(256), 0, s, d_starts, d_off, k, f->n, f->rbits, L.seg, mail);
-    ARCHON_TRY(launch_scan<0>(s, L.seg, L.seg, k, L.scan, L.seg + k));
-    hipLaunchKernelGGL(k_fm_walk_extract, dim3(kWalkGrid), dim3(256), 0, s, f->table(), f->samples(), d_starts, d_off, L.seg, k, d_out, shift, mail);
-    ARCHON_HIP_TRY(hipGetLastError());
-    const int e1 = tm.mark();
-    ARCHON_HIP_TRY(hipMemcpyAsync(rd, mail, kWords * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
-    ARCHON_HIP_TRY(hipMemcpyAsync(rd + kWords, L.seg + k, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
-    ARCHON_SYNC(s);
-    st->kernel_launches = 5;
-    st->ms_query = tm.ms(e0, e1);
-    if (rd[kBad]) { set_error("FM extract: a request lies outside [0, %u] or the offsets decrease", f->n); return ARCHON_E_ARG; }
-    st->walks = rd[kWords];
-    memcpy(&st->lf_steps, rd + kSteps, sizeof(uint64_t));
-    st->max_walk = rd[kMaxWalk];
-    return ARCHON_OK;
 }
 
 int archon_hip_fm_extract(archon_hip_fm *f, const uint32_t *starts, const uint32_t *offsets, uint32_t k, uint8_t *out)
 {
     if (!f || !starts || !offsets || !out) { set_error("null pointer"); return ARCHON_E_ARG; }
-    if (!f->rate) { set_error("FM index: the handle has no samples (archon_hip_fm_sample)"); return ARCHON_E_ARG; }
+    ARCHON_TRY(fm_check_sampled(f));
     if (!k) return ARCHON_OK;
     for (uint32_t j = 0; j < k; ++j) {
         if (offsets[j + 1] < offsets[j]) { set_error("FM extract: offsets[%u] < offsets[%u]", j + 1, j); return ARCHON_E_ARG; }
@@ -2209,46 +1815,21 @@ int archon_hip_fm_extract(archon_hip_fm *f, const uint32_t *starts, const uint32
         }
     }
     return with_ctx(f->dev, nullptr, [&](Ctx *c, hipStream_t s) -> int {
-        archon_hip_fm_walk_stats st = {};
-        fmw_handle_stats(f, &st);
-        const uint32_t syncs0 = t_sync_count;
-        const size_t bytes = (size_t)offsets[k] - offsets[0];
-        FmqArena L;
-        int rc = ctx_carve(c, [&](Carve &a) { return fmq_layout(a, L, k, bytes, true); });
-        if (rc == ARCHON_OK) {
-            auto up = [&]() -> int {
-                ARCHON_HIP_TRY(hipMemcpyAsync(L.starts, starts, (size_t)k * 4, hipMemcpyHostToDevice, s));
-                ARCHON_HIP_TRY(hipMemcpyAsync(L.off, offsets, ((size_t)k + 1) * 4, hipMemcpyHostToDevice, s));
-                ARCHON_TRY(fm_extract_run(c, s, f, L.starts, L.off, k, L.out, offsets[0], L, &st));
-                if (bytes) {
-                    ARCHON_HIP_TRY(hipMemcpyAsync(out + offsets[0], L.out, bytes, hipMemcpyDeviceToHost, s));
-                    ARCHON_SYNC(s);
-                }
-                return ARCHON_OK;
-            };
-            rc = up();
-        }
-        st.host_syncs = t_sync_count - syncs0;
-        t_fmw_stats.keep(f->dev, st);
-        return rc;
+        KeepStats<archon_hip_fm_walk_stats> keep(t_fmw_stats, f->dev);
+        fmw_handle_stats(f, &keep.st);
+        return fm_extract_host(c, s, f, starts, offsets, k, out, &keep.st);
     });
 }
 
 int archon_hip_fm_extract_dev(archon_hip_fm *f, const uint32_t *d_starts, const uint32_t *d_offsets, uint32_t k, uint8_t *d_out, void *stream)
 {
     if (!f || !d_starts || !d_offsets || !d_out) { set_error("null pointer"); return ARCHON_E_ARG; }
-    if (!f->rate) { set_error("FM index: the handle has no samples (archon_hip_fm_sample)"); return ARCHON_E_ARG; }
+    ARCHON_TRY(fm_check_sampled(f));
     if (!k) return ARCHON_OK;
     return with_ctx(f->dev, stream, [&](Ctx *c, hipStream_t s) -> int {
-        archon_hip_fm_walk_stats st = {};
-        fmw_handle_stats(f, &st);
-        const uint32_t syncs0 = t_sync_count;
-        FmqArena L;
-        int rc = ctx_carve(c, [&](Carve &a) { return fmq_layout(a, L, k, 0, false); });
-        if (rc == ARCHON_OK) rc = fm_extract_run(c, s, f, d_starts, d_offsets, k, d_out, 0, L, &st);
-        st.host_syncs = t_sync_count - syncs0;
-        t_fmw_stats.keep(f->dev, st);
-        return rc;
+        KeepStats<archon_hip_fm_walk_stats> keep(t_fmw_stats, f->dev);
+        fmw_handle_stats(f, &keep.st);
+        return fm_extract_dev(c, s, f, d_starts, d_offsets, k, d_out, &keep.st);
     });
 }
 
@@ -2258,118 +1839,7 @@ int archon_hip_get_fm_walk_stats(int dev, archon_hip_fm_walk_stats *out)
     return t_fmw_stats.get(dev, out, "sampled FM call");
 }
 
-// ---- approximate search (fm_approx.hiph)
-static_assert(sizeof(archon_hip_fm_hit) == sizeof(fma::FmHit) && offsetof(archon_hip_fm_hit, lo) == offsetof(fma::FmHit, lo) &&
-                  offsetof(archon_hip_fm_hit, hi) == offsetof(fma::FmHit, hi) &&
-                  offsetof(archon_hip_fm_hit, mismatches) == offsetof(fma::FmHit, mismatches) &&
-                  offsetof(archon_hip_fm_hit, pattern) == offsetof(fma::FmHit, pattern),
-              "the device hit is the ABI's");
-
-static int fma_check_k(uint32_t K)
-{
-    if (K > fma::kMaxMismatches) { set_error("FM approx: %u mismatches, at most %u", K, fma::kMaxMismatches); return ARCHON_E_ARG; }
-    return ARCHON_OK;
-}
-
-// The count pass over device patterns and offsets: nhits / nocc on the device and on the host, the work counters into *st,
-// first[] the exclusive sums of nhits (first[k] the total).  Decreasing offsets (found on the device) are ARCHON_E_ARG.
-static int fma_count(Ctx *c, hipStream_t s, const archon_hip_fm *f, const uint8_t *d_pat, const uint32_t *d_off, uint32_t k, uint32_t K,
-                     uint32_t *d_nhits, uint32_t *d_nocc, uint32_t *nhits, uint32_t *nocc, std::vector<uint64_t> &first, StageTimer &tm,
-                     archon_hip_fm_approx_stats *st)
-{
-    using namespace fma;
-    uint32_t *mail = c->d_mail + mail::kDevFmApprox.at, *rd = c->h_mail + mail::kRead.at;
-    static_assert(kWords <= mail::kDevFmApprox.len && kWords <= mail::kRead.len, "the approximate FM words in the mailbox");
-    ARCHON_HIP_TRY(hipMemsetAsync(mail, 0, kWords * sizeof(uint32_t), s));
-    const uint32_t g = div_up(k, 4);
-    const int e0 = tm.mark();
-    hipLaunchKernelGGL(k_fm_approx<false>, dim3(g < kGrid ? g : kGrid), dim3(256), lds_bytes(K), s, f->table(), d_pat, d_off, k, K, d_nhits, d_nocc,
-                       nullptr, nullptr, 0, mail);
-    ARCHON_HIP_TRY(hipGetLastError());
-    const int e1 = tm.mark();
-    ARCHON_HIP_TRY(hipMemcpyAsync(rd, mail, kWords * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
-    ARCHON_HIP_TRY(hipMemcpyAsync(nhits, d_nhits, (size_t)k * 4, hipMemcpyDeviceToHost, s));
-    ARCHON_HIP_TRY(hipMemcpyAsync(nocc, d_nocc, (size_t)k * 4, hipMemcpyDeviceToHost, s));
-    ARCHON_SYNC(s);
-    st->kernel_launches += 1;
-    st->ms_count = tm.ms(e0, e1);
-    memcpy(&st->expansions, rd + kExpansions, sizeof(uint64_t));
-    memcpy(&st->steps, rd + kSteps, sizeof(uint64_t));
-    if (rd[kBadOffsets]) { set_error("FM approx: offsets decrease"); return ARCHON_E_ARG; }
-    first.assign((size_t)k + 1, 0);
-    uint64_t t = 0, occ = 0;
-    for (uint32_t j = 0; j < k; ++j) {
-        first[j] = t;
-        t += nhits[j];
-        occ += nocc[j];
-    }
-    first[k] = t;
-    st->hits = t;
-    st->occurrences = occ;
-    return ARCHON_OK;
-}
-
-// The emit pass: the same search again, hit i of pattern j into d_hits[first[j] + i]
-static int fma_emit(Ctx *c, hipStream_t s, const archon_hip_fm *f, const uint8_t *d_pat, const uint32_t *d_off, uint32_t k, uint32_t K,
-                    uint64_t *d_first, const std::vector<uint64_t> &first, fma::FmHit *d_hits, StageTimer &tm, archon_hip_fm_approx_stats *st)
-{
-    using namespace fma;
-    ARCHON_HIP_TRY(hipMemcpyAsync(d_first, first.data(), ((size_t)k + 1) * 8, hipMemcpyHostToDevice, s));
-    const uint32_t g = div_up(k, 4);
-    const int e0 = tm.mark();
-    hipLaunchKernelGGL(k_fm_approx<true>, dim3(g < kGrid ? g : kGrid), dim3(256), lds_bytes(K), s, f->table(), d_pat, d_off, k, K, nullptr, nullptr,
-                       d_first, d_hits, first[k], nullptr);
-    ARCHON_HIP_TRY(hipGetLastError());
-    const int e1 = tm.mark();
-    ARCHON_SYNC(s);
-    st->kernel_launches += 1;
-    st->ms_emit = tm.ms(e0, e1);
-    return ARCHON_OK;
-}
-
-// Host patterns and results through the context's arena (the arena may move for the hits: patterns and offsets go up again)
-static int fma_host(Ctx *c, hipStream_t s, const archon_hip_fm *f, const uint8_t *patterns, const uint32_t *offsets, uint32_t k, uint32_t K,
-                    uint32_t *nhits, uint32_t *nocc, archon_hip_fm_hit *hits, uint64_t cap, uint64_t *total, archon_hip_fm_approx_stats *st)
-{
-    const size_t pat_bytes = offsets[k];
-    st->pattern_bytes = (uint64_t)offsets[k] - offsets[0];
-    FmaArena L;
-    ARCHON_TRY(ctx_carve(c, [&](Carve &a) { return fma_layout(a, L, pat_bytes, k, true, 0); }));
-    if (pat_bytes) ARCHON_HIP_TRY(hipMemcpyAsync(L.pat, patterns, pat_bytes, hipMemcpyHostToDevice, s));
-    ARCHON_HIP_TRY(hipMemcpyAsync(L.off, offsets, ((size_t)k + 1) * 4, hipMemcpyHostToDevice, s));
-    StageTimer tm(c, 72, s);
-    std::vector<uint64_t> first;
-    ARCHON_TRY(fma_count(c, s, f, L.pat, L.off, k, K, L.nhits, L.nocc, nhits, nocc, first, tm, st));
-    *total = first[k];
-    if (!hits || !first[k]) return ARCHON_OK;
-    if (first[k] > cap) { set_error("FM approx: %llu hits, room for %llu", (unsigned long long)first[k], (unsigned long long)cap); return ARCHON_E_ARG; }
-    ARCHON_TRY(ctx_carve(c, [&](Carve &a) { return fma_layout(a, L, pat_bytes, k, true, first[k]); }));
-    if (pat_bytes) ARCHON_HIP_TRY(hipMemcpyAsync(L.pat, patterns, pat_bytes, hipMemcpyHostToDevice, s));
-    ARCHON_HIP_TRY(hipMemcpyAsync(L.off, offsets, ((size_t)k + 1) * 4, hipMemcpyHostToDevice, s));
-    ARCHON_TRY(fma_emit(c, s, f, L.pat, L.off, k, K, L.first, first, L.hits, tm, st));
-    ARCHON_HIP_TRY(hipMemcpyAsync(hits, L.hits, first[k] * sizeof(fma::FmHit), hipMemcpyDeviceToHost, s));
-    ARCHON_SYNC(s);
-    return ARCHON_OK;
-}
-
-// The statistics of one approximate call: kept for the calling thread, with the call's host waits, when it returns
-struct FmaKeep {
-    int dev;
-    uint32_t syncs0 = t_sync_count;
-    archon_hip_fm_approx_stats st = {};
-    FmaKeep(int d, uint32_t n, uint32_t k, uint32_t K) : dev(d)
-    {
-        st.n = n;
-        st.patterns = k;
-        st.max_mismatches = K;
-    }
-    ~FmaKeep()
-    {
-        st.host_syncs = t_sync_count - syncs0;
-        t_fma_stats.keep(dev, st);
-    }
-};
-
+// ---- approximate search
 int archon_hip_fm_approx(archon_hip_fm *f, const uint8_t *patterns, const uint32_t *offsets, uint32_t k, uint32_t max_mismatches, uint32_t *nhits,
                          uint32_t *nocc, archon_hip_fm_hit *hits_or_null, uint64_t cap, uint64_t *total)
 {
@@ -2379,7 +1849,8 @@ int archon_hip_fm_approx(archon_hip_fm *f, const uint8_t *patterns, const uint32
     *total = 0;
     if (!k) return ARCHON_OK;
     return with_ctx(f->dev, nullptr, [&](Ctx *c, hipStream_t s) -> int {
-        FmaKeep keep(f->dev, f->n, k, max_mismatches);
+        KeepStats<archon_hip_fm_approx_stats> keep(t_fma_stats, f->dev);
+        fma_call_stats(&keep.st, f->n, k, max_mismatches);
         return fma_host(c, s, f, patterns, offsets, k, max_mismatches, nhits, nocc, hits_or_null, cap, total, &keep.st);
     });
 }
@@ -2392,96 +1863,22 @@ int archon_hip_fm_approx_dev(archon_hip_fm *f, const uint8_t *d_patterns, const 
     *total = 0;
     if (!k) return ARCHON_OK;
     return with_ctx(f->dev, stream, [&](Ctx *c, hipStream_t s) -> int {
-        FmaKeep keep(f->dev, f->n, k, max_mismatches);
-        archon_hip_fm_approx_stats *st = &keep.st;
-        uint32_t *ends = c->h_mail + mail::kRead.at + fma::kWords;     // offsets[0] and offsets[k], for the statistics
-        static_assert(fma::kWords + 2 <= mail::kRead.len, "the approximate FM words and the offsets' ends in the readback words");
-        ARCHON_HIP_TRY(hipMemcpyAsync(&ends[0], d_offsets, 4, hipMemcpyDeviceToHost, s));
-        ARCHON_HIP_TRY(hipMemcpyAsync(&ends[1], d_offsets + k, 4, hipMemcpyDeviceToHost, s));
-        FmaArena L;
-        ARCHON_TRY(ctx_carve(c, [&](Carve &a) { return fma_layout(a, L, 0, k, false, 0); }));
-        StageTimer tm(c, 72, s);
-        std::vector<uint32_t> nh(k), no(k);
-        std::vector<uint64_t> first;
-        ARCHON_TRY(fma_count(c, s, f, d_patterns, d_offsets, k, max_mismatches, d_nhits, d_nocc, nh.data(), no.data(), first, tm, st));
-        st->pattern_bytes = ends[1] >= ends[0] ? ends[1] - ends[0] : 0;
-        *total = first[k];
-        if (!d_hits_or_null || !first[k]) return ARCHON_OK;
-        if (first[k] > cap) { set_error("FM approx: %llu hits, room for %llu", (unsigned long long)first[k], (unsigned long long)cap); return ARCHON_E_ARG; }
-        return fma_emit(c, s, f, d_patterns, d_offsets, k, max_mismatches, L.first, first, reinterpret_cast<fma::FmHit *>(d_hits_or_null), tm, st);
+        KeepStats<archon_hip_fm_approx_stats> keep(t_fma_stats, f->dev);
+        fma_call_stats(&keep.st, f->n, k, max_mismatches);
+        return fma_dev(c, s, f, d_patterns, d_offsets, k, max_mismatches, d_nhits, d_nocc, d_hits_or_null, cap, total, &keep.st);
     });
-}
-
-// The starts of the hits' occurrences: a gather from a resident SA (d_sa), or the LF walks of a sampled handle
-static int fma_check_hits(const uint32_t *offsets, uint32_t k, const archon_hip_fm_hit *hits, uint64_t nhits, uint32_t n)
-{
-    ARCHON_TRY(fm_check_offsets(offsets, k));
-    if (nhits >= (1ull << 32)) { set_error("FM locate hits: %llu hits in one call", (unsigned long long)nhits); return ARCHON_E_ARG; }
-    for (uint64_t i = 0; i < nhits; ++i) {
-        const archon_hip_fm_hit &h = hits[i];
-        if (h.pattern >= k || h.lo > h.hi || h.hi > n) {
-            set_error("FM locate hits: hit %llu (pattern %u, rows [%u, %u)) outside %u patterns / [0, %u]", (unsigned long long)i, h.pattern, h.lo, h.hi, k, n);
-            return ARCHON_E_ARG;
-        }
-    }
-    return ARCHON_OK;
-}
-
-static int fma_locate(Ctx *c, hipStream_t s, const archon_hip_fm *f, const uint32_t *d_sa, const uint32_t *offsets, uint32_t k,
-                      const archon_hip_fm_hit *hits, uint64_t nhits, uint32_t *pos, uint64_t cap, uint64_t *total, archon_hip_fm_approx_stats *st)
-{
-    std::vector<uint64_t> first(nhits + 1);
-    uint64_t t = 0;
-    for (uint64_t i = 0; i < nhits; ++i) {
-        first[i] = t;
-        t += hits[i].hi - hits[i].lo;
-    }
-    first[nhits] = t;
-    *total = t;
-    st->hits = nhits;
-    st->occurrences = t;
-    if (t > cap) { set_error("FM locate hits: %llu starts, room for %llu", (unsigned long long)t, (unsigned long long)cap); return ARCHON_E_ARG; }
-    if (!t) return ARCHON_OK;
-    FmhArena L;
-    ARCHON_TRY(ctx_carve(c, [&](Carve &a) { return fmh_layout(a, L, k, nhits, t); }));
-    ARCHON_HIP_TRY(hipMemcpyAsync(L.off, offsets, ((size_t)k + 1) * 4, hipMemcpyHostToDevice, s));
-    ARCHON_HIP_TRY(hipMemcpyAsync(L.hits, hits, nhits * sizeof(fma::FmHit), hipMemcpyHostToDevice, s));
-    ARCHON_HIP_TRY(hipMemcpyAsync(L.first, first.data(), (nhits + 1) * 8, hipMemcpyHostToDevice, s));
-    uint32_t *mail = c->d_mail + mail::kDevFmApprox.at, *rd = c->h_mail + mail::kRead.at;
-    static_assert(fmw::kWords <= mail::kDevFmApprox.len, "the walks' words in the approximate FM region");
-    ARCHON_HIP_TRY(hipMemsetAsync(mail, 0, fmw::kWords * sizeof(uint32_t), s));
-    const fma::HitRows q{L.hits, L.off};
-    StageTimer tm(c, 72, s);
-    const int e0 = tm.mark();
-    if (d_sa) {
-        const uint64_t g = (t + 255) / 256;
-        hipLaunchKernelGGL(fmk::k_fm_locate<fma::HitRows>, dim3(g < fmk::kLocateGrid ? (uint32_t)g : fmk::kLocateGrid), dim3(256), 0, s, d_sa, q, L.first,
-                           (uint32_t)nhits, L.pos);
-    } else {
-        const uint64_t g = (t + 3) / 4;
-        hipLaunchKernelGGL(fmw::k_fm_walk_locate<fma::HitRows>, dim3(g < fmw::kWalkGrid ? (uint32_t)g : fmw::kWalkGrid), dim3(256), 0, s, f->table(),
-                           f->samples(), q, L.first, (uint32_t)nhits, L.pos, mail);
-    }
-    ARCHON_HIP_TRY(hipGetLastError());
-    const int e1 = tm.mark();
-    ARCHON_HIP_TRY(hipMemcpyAsync(pos, L.pos, t * 4, hipMemcpyDeviceToHost, s));
-    ARCHON_HIP_TRY(hipMemcpyAsync(rd, mail, fmw::kWords * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
-    ARCHON_SYNC(s);
-    st->kernel_launches = 1;
-    st->ms_locate = tm.ms(e0, e1);
-    if (!d_sa) memcpy(&st->lf_steps, rd + fmw::kSteps, sizeof(uint64_t));
-    return ARCHON_OK;
 }
 
 int archon_hip_fm_locate_hits(archon_hip_fm *f, const uint32_t *offsets, uint32_t k, const archon_hip_fm_hit *hits, uint64_t nhits, uint32_t *pos,
                               uint64_t cap, uint64_t *total)
 {
     if (!f || !offsets || (!hits && nhits) || !pos || !total) { set_error("null pointer"); return ARCHON_E_ARG; }
-    if (!f->rate) { set_error("FM index: the handle has no samples (archon_hip_fm_sample)"); return ARCHON_E_ARG; }
+    ARCHON_TRY(fm_check_sampled(f));
     ARCHON_TRY(fma_check_hits(offsets, k, hits, nhits, f->n));
     *total = 0;
     return with_ctx(f->dev, nullptr, [&](Ctx *c, hipStream_t s) -> int {
-        FmaKeep keep(f->dev, f->n, k, 0);
+        KeepStats<archon_hip_fm_approx_stats> keep(t_fma_stats, f->dev);
+        fma_call_stats(&keep.st, f->n, k, 0);
         return fma_locate(c, s, f, nullptr, offsets, k, hits, nhits, pos, cap, total, &keep.st);
     });
 }
@@ -2507,6 +1904,14 @@ struct archon_hip_block {
     archon_hip_stats stats;
     archon_hip_fm *fm = nullptr;        // the FM index over d_bwt, built by the first FM call after a forward
 };
+
+// what a call that reads the resident block (with_sa: and its suffix array) asks first, under the block's lock
+static int block_check(const archon_hip_block *b, bool with_sa)
+{
+    if (with_sa && !(b->valid && b->has_sa)) { set_error("no resident block with its suffix array"); return ARCHON_E_ARG; }
+    if (!b->valid) { set_error("no resident block"); return ARCHON_E_ARG; }
+    return ARCHON_OK;
+}
 
 static int block_reserve(archon_hip_block *b, uint32_t n, bool want_sa)
 {
@@ -2605,7 +2010,7 @@ int archon_hip_block_validate(archon_hip_block *b)
 {
     if (!b) { set_error("null pointer"); return ARCHON_E_ARG; }
     std::lock_guard<std::mutex> lkb(b->mu);
-    if (!b->valid || !b->has_sa) { set_error("no resident block with its suffix array"); return ARCHON_E_ARG; }
+    ARCHON_TRY(block_check(b, true));
     return with_ctx(b->dev, nullptr, [&](Ctx *c, hipStream_t s) -> int { return validate_resident_run(c, s, b->d_x, b->n, b->d_sa, b->d_bwt, b->base); });
 }
 
@@ -2614,7 +2019,7 @@ int archon_hip_block_lcp(archon_hip_block *b, uint32_t *lcp)
 {
     if (!b || !lcp) { set_error("null pointer"); return ARCHON_E_ARG; }
     std::lock_guard<std::mutex> lkb(b->mu);
-    if (!b->valid || !b->has_sa) { set_error("no resident block with its suffix array"); return ARCHON_E_ARG; }
+    ARCHON_TRY(block_check(b, true));
     return with_ctx(b->dev, nullptr, [&](Ctx *c, hipStream_t s) -> int {
         uint32_t *d_lcp = nullptr;
         ARCHON_TRY(ctx_io(c, 1, (size_t)b->n * 4 + 64, (void **)&d_lcp));
@@ -2628,27 +2033,24 @@ int archon_hip_block_lcp(archon_hip_block *b, uint32_t *lcp)
     });
 }
 
-static int block_fm_query(archon_hip_block *b, const uint8_t *patterns, const uint32_t *offsets, uint32_t k, uint32_t *lo, uint32_t *hi,
-                          const FmLocate *loc)
+// The block's FM handle over its own BWT, built by the first FM call after a forward: its build into *st, which then says built
+static int block_fm_table(Ctx *c, hipStream_t s, archon_hip_block *b, archon_hip_fm_stats *st)
 {
-    return with_ctx(b->dev, nullptr, [&](Ctx *c, hipStream_t s) -> int {
-        archon_hip_fm_stats st = {};
-        // the block's FM handle over its own BWT: built on the first FM call after a forward
-        int rc = b->fm ? ARCHON_OK : fm_build(c, s, nullptr, b->d_bwt, false, b->n, b->base, &b->fm, &st);
-        if (rc == ARCHON_OK) rc = fm_host_query(c, s, b->fm, patterns, offsets, k, lo, hi, loc, &st);
-        t_fm_stats.keep(b->dev, st);
-        return rc;
-    });
+    return b->fm ? ARCHON_OK : fm_build(c, s, nullptr, b->d_bwt, false, b->n, b->base, &b->fm, st);
 }
 
 int archon_hip_block_fm_count(archon_hip_block *b, const uint8_t *patterns, const uint32_t *offsets, uint32_t k, uint32_t *lo, uint32_t *hi)
 {
     if (!b || !patterns || !offsets || !lo || !hi) { set_error("null pointer"); return ARCHON_E_ARG; }
     std::lock_guard<std::mutex> lkb(b->mu);
-    if (!b->valid) { set_error("no resident block"); return ARCHON_E_ARG; }
+    ARCHON_TRY(block_check(b, false));
     if (!k) return ARCHON_OK;
     ARCHON_TRY(fm_check_offsets(offsets, k));
-    return block_fm_query(b, patterns, offsets, k, lo, hi, nullptr);
+    return with_ctx(b->dev, nullptr, [&](Ctx *c, hipStream_t s) -> int {
+        KeepStats<archon_hip_fm_stats> keep(t_fm_stats, b->dev);
+        ARCHON_TRY(block_fm_table(c, s, b, &keep.st));
+        return fm_count_host(c, s, b->fm, patterns, offsets, k, lo, hi, &keep.st);
+    });
 }
 
 int archon_hip_block_fm_locate(archon_hip_block *b, const uint8_t *patterns, const uint32_t *offsets, uint32_t k, uint32_t *pos, uint64_t cap,
@@ -2656,13 +2058,15 @@ int archon_hip_block_fm_locate(archon_hip_block *b, const uint8_t *patterns, con
 {
     if (!b || !patterns || !offsets || !pos || !total) { set_error("null pointer"); return ARCHON_E_ARG; }
     std::lock_guard<std::mutex> lkb(b->mu);
-    if (!b->valid || !b->has_sa) { set_error("no resident block with its suffix array"); return ARCHON_E_ARG; }
+    ARCHON_TRY(block_check(b, true));
     *total = 0;
     if (!k) return ARCHON_OK;
     ARCHON_TRY(fm_check_offsets(offsets, k));
-    std::vector<uint32_t> lo(k), hi(k);
-    const FmLocate loc{b->d_sa, pos, cap, total, nullptr};
-    return block_fm_query(b, patterns, offsets, k, lo.data(), hi.data(), &loc);
+    return with_ctx(b->dev, nullptr, [&](Ctx *c, hipStream_t s) -> int {
+        KeepStats<archon_hip_fm_stats> keep(t_fm_stats, b->dev);
+        ARCHON_TRY(block_fm_table(c, s, b, &keep.st));
+        return fm_locate_host(c, s, b->fm, b->d_sa, patterns, offsets, k, pos, cap, total, &keep.st, nullptr);
+    });
 }
 
 int archon_hip_block_fm_index(archon_hip_block *b, uint32_t rate, archon_hip_fm **out)
@@ -2671,20 +2075,19 @@ int archon_hip_block_fm_index(archon_hip_block *b, uint32_t rate, archon_hip_fm 
     uint32_t rbits;
     ARCHON_TRY(fmw_rate_bits(rate, &rbits));
     std::lock_guard<std::mutex> lkb(b->mu);
-    if (!b->valid) { set_error("no resident block"); return ARCHON_E_ARG; }
+    ARCHON_TRY(block_check(b, false));
     return with_ctx(b->dev, nullptr, [&](Ctx *c, hipStream_t s) -> int {
-        archon_hip_fm_stats st = {};
-        archon_hip_fm_walk_stats wst = {};
         archon_hip_fm *f = nullptr;
-        int rc = fm_build(c, s, nullptr, b->d_bwt, true, b->n, b->base, &f, &st);
-        t_fm_stats.keep(b->dev, st);
-        if (rc == ARCHON_OK) {
-            const bool from_sa = b->has_sa && !g_route.fm_sample_walk;
-            rc = fm_sample_run(c, s, f, rbits, from_sa ? b->d_sa : nullptr, &wst);
-            t_fmw_stats.keep(b->dev, wst);
-            if (rc != ARCHON_OK) fm_release(f);
-            else *out = f;
+        {
+            KeepStats<archon_hip_fm_stats> keep(t_fm_stats, b->dev);
+            ARCHON_TRY(fm_build(c, s, nullptr, b->d_bwt, true, b->n, b->base, &f, &keep.st));
         }
+        // the samples' record is kept once there is a table to sample
+        KeepStats<archon_hip_fm_walk_stats> keep(t_fmw_stats, b->dev);
+        const bool from_sa = b->has_sa && !g_route.fm_sample_walk;
+        const int rc = fm_sample_run(c, s, f, rbits, from_sa ? b->d_sa : nullptr, &keep.st);
+        if (rc != ARCHON_OK) fm_release(f);
+        else *out = f;
         return rc;
     });
 }
@@ -2696,21 +2099,19 @@ int archon_hip_block_fm_approx(archon_hip_block *b, const uint8_t *patterns, con
     ARCHON_TRY(fma_check_k(max_mismatches));
     ARCHON_TRY(fm_check_offsets(offsets, k));
     std::lock_guard<std::mutex> lkb(b->mu);
-    if (!b->valid) { set_error("no resident block"); return ARCHON_E_ARG; }
+    ARCHON_TRY(block_check(b, false));
     *total = 0;
     if (!k) return ARCHON_OK;
     return with_ctx(b->dev, nullptr, [&](Ctx *c, hipStream_t s) -> int {
-        FmaKeep keep(b->dev, b->n, k, max_mismatches);
-        archon_hip_fm_approx_stats *st = &keep.st;
-        if (!b->fm) {
-            // the block's table, as block_fm_count builds it; its statistics are this call's (fm_stats stays as it was)
-            archon_hip_fm_stats fst = {};
-            ARCHON_TRY(fm_build(c, s, nullptr, b->d_bwt, false, b->n, b->base, &b->fm, &fst));
-            st->built = 1;
-            st->ms_build = fst.ms_build;
-            st->kernel_launches += fst.kernel_launches;
-        }
-        return fma_host(c, s, b->fm, patterns, offsets, k, max_mismatches, nhits, nocc, hits_or_null, cap, total, st);
+        KeepStats<archon_hip_fm_approx_stats> keep(t_fma_stats, b->dev);
+        fma_call_stats(&keep.st, b->n, k, max_mismatches);
+        // a table built here is this call's work: into its own record, while fm_stats stays as it was
+        archon_hip_fm_stats fst = {};
+        ARCHON_TRY(block_fm_table(c, s, b, &fst));
+        keep.st.built = fst.built;
+        keep.st.ms_build = fst.ms_build;
+        keep.st.kernel_launches += fst.kernel_launches;
+        return fma_host(c, s, b->fm, patterns, offsets, k, max_mismatches, nhits, nocc, hits_or_null, cap, total, &keep.st);
     });
 }
 
@@ -2719,11 +2120,12 @@ int archon_hip_block_fm_locate_hits(archon_hip_block *b, const uint32_t *offsets
 {
     if (!b || !offsets || (!hits && nhits) || !pos || !total) { set_error("null pointer"); return ARCHON_E_ARG; }
     std::lock_guard<std::mutex> lkb(b->mu);
-    if (!b->valid || !b->has_sa) { set_error("no resident block with its suffix array"); return ARCHON_E_ARG; }
+    ARCHON_TRY(block_check(b, true));
     ARCHON_TRY(fma_check_hits(offsets, k, hits, nhits, b->n));
     *total = 0;
     return with_ctx(b->dev, nullptr, [&](Ctx *c, hipStream_t s) -> int {
-        FmaKeep keep(b->dev, b->n, k, 0);
+        KeepStats<archon_hip_fm_approx_stats> keep(t_fma_stats, b->dev);
+        fma_call_stats(&keep.st, b->n, k, 0);
         return fma_locate(c, s, nullptr, b->d_sa, offsets, k, hits, nhits, pos, cap, total, &keep.st);
     });
 }

@@ -4,29 +4,16 @@ tests are pinned to the definition: tests/fm_naive.c against brute force, the se
 against every occurrence of every short pattern in every short string."""
 import ctypes
 import itertools
-import os
-import re
-import subprocess
 
 import numpy as np
 import pytest
 
+from fm_abi_util import declared as _declared, layout as _layout, p as _p
 import fm_naive
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 FM_FUNCTIONS = ["archon_hip_fm_create", "archon_hip_fm_create_dev", "archon_hip_fm_destroy", "archon_hip_fm_count", "archon_hip_fm_count_dev",
                 "archon_hip_block_fm_count", "archon_hip_block_fm_locate", "archon_hip_get_fm_stats"]
 BANANA_BWT = b"nnbaaa"          # a7 order of "banana": primary row 2, sa = 2 4 6 1 3 5 (test_abi.py)
-
-
-def _declared(header):
-    src = open(os.path.join(ROOT, "include", header)).read()
-    src = re.sub(r"/\*.*?\*/", "", src, flags=re.S)
-    return set(re.findall(r"\b(archon_[a-z0-9_]+)\s*\(", src))
-
-
-def _p(a):
-    return ctypes.c_void_p(a.ctypes.data)
 
 
 def test_fm_functions_declared_exported_and_bound():
@@ -51,12 +38,7 @@ def test_fm_stats_struct_layout(tmp_path):
     """the ctypes mirror of archon_hip_fm_stats has the size and the field offsets the C header gives it"""
     import pyarchon
     names = [k for k, _ in pyarchon.FmStats._fields_]
-    src = tmp_path / "sz.c"
-    src.write_text('#include <stdio.h>\n#include <stddef.h>\n#include "archon_hip.h"\nint main(void){printf("%zu", sizeof(archon_hip_fm_stats));'
-                   + "".join('printf(" %%zu", offsetof(archon_hip_fm_stats, %s));' % k for k in names) + "return 0;}\n")
-    exe = tmp_path / "sz"
-    subprocess.run(["gcc", "-I", os.path.join(ROOT, "include"), str(src), "-o", str(exe)], check=True)
-    got = [int(t) for t in subprocess.run([str(exe)], check=True, capture_output=True, text=True).stdout.split()]
+    got = _layout(tmp_path, "archon_hip_fm_stats", names)
     assert got[0] == ctypes.sizeof(pyarchon.FmStats)
     assert got[1:] == [getattr(pyarchon.FmStats, k).offset for k in names]
 

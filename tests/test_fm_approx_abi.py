@@ -5,29 +5,16 @@ of the header (fm_approx_naive.Rule) is pinned to brute force on every short str
 and both work counters; the C brute force the GPU tests use (fm_approx_naive.c) agrees with it."""
 import ctypes
 import itertools
-import os
-import re
-import subprocess
 
 import numpy as np
 import pytest
 
+from fm_abi_util import declared as _declared, layout as _layout, p as _p
 import fm_approx_naive as A
 import fm_sampled_naive as M
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 FUNCTIONS = ["archon_hip_fm_approx", "archon_hip_fm_approx_dev", "archon_hip_block_fm_approx", "archon_hip_fm_locate_hits",
              "archon_hip_block_fm_locate_hits", "archon_hip_get_fm_approx_stats"]
-
-
-def _declared(header):
-    src = open(os.path.join(ROOT, "include", header)).read()
-    src = re.sub(r"/\*.*?\*/", "", src, flags=re.S)
-    return set(re.findall(r"\b(archon_[a-z0-9_]+)\s*\(", src))
-
-
-def _p(a):
-    return ctypes.c_void_p(a.ctypes.data)
 
 
 def test_approx_functions_declared_exported_and_bound():
@@ -45,15 +32,6 @@ def test_approx_functions_declared_exported_and_bound():
         assert hasattr(pyarchon.FmIndex, name), name
     for name in ("fm_approx", "fm_locate_hits"):
         assert hasattr(pyarchon.Block, name), name
-
-
-def _layout(tmp_path, struct, names):
-    src = tmp_path / "sz.c"
-    src.write_text('#include <stdio.h>\n#include <stddef.h>\n#include "archon_hip.h"\nint main(void){printf("%%zu", sizeof(%s));' % struct
-                   + "".join('printf(" %%zu", offsetof(%s, %s));' % (struct, k) for k in names) + "return 0;}\n")
-    exe = tmp_path / "sz"
-    subprocess.run(["gcc", "-I", os.path.join(ROOT, "include"), str(src), "-o", str(exe)], check=True)
-    return [int(t) for t in subprocess.run([str(exe)], check=True, capture_output=True, text=True).stdout.split()]
 
 
 def test_fm_approx_stats_struct_layout(tmp_path):

@@ -4,30 +4,17 @@ the C layout; they refuse bad arguments and, without a GPU, fail loudly.  And th
 is pinned to brute force on every short string: samples, locate with its exact LF steps, extract."""
 import ctypes
 import itertools
-import os
-import re
-import subprocess
 
 import numpy as np
 import pytest
 
+from fm_abi_util import declared as _declared, layout as _layout, p as _p
 import fm_naive
 import fm_sampled_naive as M
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 FUNCTIONS = ["archon_hip_fm_sample", "archon_hip_block_fm_index", "archon_hip_fm_read_samples", "archon_hip_fm_locate",
              "archon_hip_fm_extract", "archon_hip_fm_extract_dev", "archon_hip_get_fm_walk_stats"]
 RATES = (1, 2, 4, 8, 64)
-
-
-def _declared(header):
-    src = open(os.path.join(ROOT, "include", header)).read()
-    src = re.sub(r"/\*.*?\*/", "", src, flags=re.S)
-    return set(re.findall(r"\b(archon_[a-z0-9_]+)\s*\(", src))
-
-
-def _p(a):
-    return ctypes.c_void_p(a.ctypes.data)
 
 
 def test_sampled_functions_declared_exported_and_bound():
@@ -51,12 +38,7 @@ def test_fm_walk_stats_struct_layout(tmp_path):
     """the ctypes mirror of archon_hip_fm_walk_stats has the size and the field offsets the C header gives it"""
     import pyarchon
     names = [k for k, _ in pyarchon.FmWalkStats._fields_]
-    src = tmp_path / "sz.c"
-    src.write_text('#include <stdio.h>\n#include <stddef.h>\n#include "archon_hip.h"\nint main(void){printf("%zu", sizeof(archon_hip_fm_walk_stats));'
-                   + "".join('printf(" %%zu", offsetof(archon_hip_fm_walk_stats, %s));' % k for k in names) + "return 0;}\n")
-    exe = tmp_path / "sz"
-    subprocess.run(["gcc", "-I", os.path.join(ROOT, "include"), str(src), "-o", str(exe)], check=True)
-    got = [int(t) for t in subprocess.run([str(exe)], check=True, capture_output=True, text=True).stdout.split()]
+    got = _layout(tmp_path, "archon_hip_fm_walk_stats", names)
     assert got[0] == ctypes.sizeof(pyarchon.FmWalkStats)
     assert got[1:] == [getattr(pyarchon.FmWalkStats, k).offset for k in names]
 
