@@ -15,6 +15,7 @@
 #include "fm.hiph"
 #include "fm_walk.hiph"
 #include "fm_approx.hiph"
+#include "fm_mem.hiph"
 #include "fm_host.hiph"
 
 #include <stdarg.h>
@@ -82,6 +83,7 @@ static thread_local LastStats<archon_hip_lcp_stats> t_lcp_stats;        // LCP c
 static thread_local LastStats<archon_hip_fm_stats> t_fm_stats;          // FM calls: they leave both of the others alone
 static thread_local LastStats<archon_hip_fm_walk_stats> t_fmw_stats;    // sampled-index calls: sample, block_fm_index, locate, extract
 static thread_local LastStats<archon_hip_fm_approx_stats> t_fma_stats;  // approximate calls: approx, locate_hits
+static thread_local LastStats<archon_hip_fm_mem_stats> t_fmm_stats;     // SMEM calls: mirror, smems, locate_mems
 
 // The record of one FM call: kept for the calling thread when the scope ends, on whichever path the call leaves it, with the
 // host waits since the scope began.
@@ -297,6 +299,15 @@ static size_t fwd_tier1(Carve &a, FwdBuf &B, uint32_t n, int dev, bool own_sa)
     B.small = a.take<uint32_t>(fwd_small::kWords);
     return a.off + kClosedTail + (1u << 16);
 }
+
+// what a caller that keeps buffers of its own above a nested forward call has to leave free (fm_host.hiph: the mirror build)
+static size_t fwd_tier1_need(uint32_t n, int dev)
+{
+    Carve count;
+    FwdBuf B{};
+    return fwd_tier1(count, B, n, dev, true);
+}
+static size_t fwd_closed_tail() { return kClosedTail; }
 
 // Tier 2: what only the general stage needs.  Returns the bytes to ask for.
 static size_t fwd_tier2(Carve &a, FwdBuf &B, uint32_t n)
@@ -1889,6 +1900,86 @@ int archon_hip_get_fm_approx_stats(int dev, archon_hip_fm_approx_stats *out)
     return t_fma_stats.get(dev, out, "approximate FM call");
 }
 
+// ---- the mirror and the SMEM search
+int archon_hip_fm_mirror(archon_hip_fm *f)
+{
+    if (!f) { set_error("null pointer"); return ARCHON_E_ARG; }
+    return with_ctx(f->dev, nullptr, [&](Ctx *c, hipStream_t s) -> int {
+        KeepStats<archon_hip_fm_mem_stats> keep(t_fmm_stats, f->dev);
+        fmm_call_stats(&keep.st, f, f->n, 0, 0);
+        return fmm_mirror_run(c, s, f, nullptr, false, &keep.st);
+    });
+}
+
+int archon_hip_fm_mirror_dev(archon_hip_fm *f, const uint8_t *d_x, void *stream)
+{
+    if (!f || !d_x) { set_error("null pointer"); return ARCHON_E_ARG; }
+    return with_ctx(f->dev, stream, [&](Ctx *c, hipStream_t s) -> int {
+        KeepStats<archon_hip_fm_mem_stats> keep(t_fmm_stats, f->dev);
+        fmm_call_stats(&keep.st, f, f->n, 0, 0);
+        return fmm_mirror_run(c, s, f, d_x, true, &keep.st);
+    });
+}
+
+int archon_hip_fm_read_mirror(archon_hip_fm *f, uint8_t *bwt, uint32_t cap, uint32_t *base_id)
+{
+    if (!f || !bwt || !base_id) { set_error("null pointer"); return ARCHON_E_ARG; }
+    ARCHON_TRY(fmm_check_mirror(f));
+    *base_id = f->mirror->base;
+    if (cap < f->n) { set_error("FM mirror: %u bytes, room for %u", f->n, cap); return ARCHON_E_ARG; }
+    ARCHON_HIP_TRY(hipSetDevice(f->dev));
+    ARCHON_HIP_TRY(hipMemcpy(bwt, f->mirror->bwt, f->n, hipMemcpyDeviceToHost));
+    return ARCHON_OK;
+}
+
+int archon_hip_fm_smems(archon_hip_fm *f, const uint8_t *patterns, const uint32_t *offsets, uint32_t k, uint32_t min_len, uint32_t *nmems,
+                        uint32_t *nocc, archon_hip_fm_mem *mems_or_null, uint64_t cap, uint64_t *total)
+{
+    if (!f || !patterns || !offsets || !nmems || !nocc || !total) { set_error("null pointer"); return ARCHON_E_ARG; }
+    ARCHON_TRY(fm_check_offsets(offsets, k));
+    ARCHON_TRY(fmm_check_mirror(f));
+    *total = 0;
+    if (!k) return ARCHON_OK;
+    return with_ctx(f->dev, nullptr, [&](Ctx *c, hipStream_t s) -> int {
+        KeepStats<archon_hip_fm_mem_stats> keep(t_fmm_stats, f->dev);
+        fmm_call_stats(&keep.st, f, f->n, k, min_len);
+        return fmm_host(c, s, f, patterns, offsets, k, min_len, nmems, nocc, mems_or_null, cap, total, &keep.st);
+    });
+}
+
+int archon_hip_fm_smems_dev(archon_hip_fm *f, const uint8_t *d_patterns, const uint32_t *d_offsets, uint32_t k, uint32_t min_len, uint32_t *d_nmems,
+                            uint32_t *d_nocc, archon_hip_fm_mem *d_mems_or_null, uint64_t cap, uint64_t *total, void *stream)
+{
+    if (!f || !d_patterns || !d_offsets || !d_nmems || !d_nocc || !total) { set_error("null pointer"); return ARCHON_E_ARG; }
+    ARCHON_TRY(fmm_check_mirror(f));
+    *total = 0;
+    if (!k) return ARCHON_OK;
+    return with_ctx(f->dev, stream, [&](Ctx *c, hipStream_t s) -> int {
+        KeepStats<archon_hip_fm_mem_stats> keep(t_fmm_stats, f->dev);
+        fmm_call_stats(&keep.st, f, f->n, k, min_len);
+        return fmm_dev(c, s, f, d_patterns, d_offsets, k, min_len, d_nmems, d_nocc, d_mems_or_null, cap, total, &keep.st);
+    });
+}
+
+int archon_hip_fm_locate_mems(archon_hip_fm *f, const archon_hip_fm_mem *mems, uint64_t nmems, uint32_t *pos, uint64_t cap, uint64_t *total)
+{
+    if (!f || (!mems && nmems) || !pos || !total) { set_error("null pointer"); return ARCHON_E_ARG; }
+    ARCHON_TRY(fm_check_sampled(f));
+    ARCHON_TRY(fmm_check_mems(mems, nmems, f->n));
+    *total = 0;
+    return with_ctx(f->dev, nullptr, [&](Ctx *c, hipStream_t s) -> int {
+        KeepStats<archon_hip_fm_mem_stats> keep(t_fmm_stats, f->dev);
+        fmm_call_stats(&keep.st, f, f->n, 0, 0);
+        return fmm_locate(c, s, f, nullptr, mems, nmems, pos, cap, total, &keep.st);
+    });
+}
+
+int archon_hip_get_fm_mem_stats(int dev, archon_hip_fm_mem_stats *out)
+{
+    if (!out) { set_error("null pointer"); return ARCHON_E_ARG; }
+    return t_fmm_stats.get(dev, out, "SMEM call");
+}
+
 // ---- resident blocks ---------------------------------------------------------------------------------------------------
 // What a block-coder object keeps on the device between enCompute, validate and enWrite (bwt/a7/src/main.cpp:39-46): the
 // block, its suffix array and its BWT, in buffers of its own.  The state belongs to the HANDLE -- any number of objects on
@@ -2127,6 +2218,36 @@ int archon_hip_block_fm_locate_hits(archon_hip_block *b, const uint32_t *offsets
         KeepStats<archon_hip_fm_approx_stats> keep(t_fma_stats, b->dev);
         fma_call_stats(&keep.st, b->n, k, 0);
         return fma_locate(c, s, nullptr, b->d_sa, offsets, k, hits, nhits, pos, cap, total, &keep.st);
+    });
+}
+
+int archon_hip_block_fm_mirror(archon_hip_block *b, archon_hip_fm *f)
+{
+    if (!b || !f) { set_error("null pointer"); return ARCHON_E_ARG; }
+    std::lock_guard<std::mutex> lkb(b->mu);
+    ARCHON_TRY(block_check(b, false));
+    if (f->dev != b->dev || f->n != b->n || f->base != b->base) {
+        set_error("FM mirror: the handle (%u bytes, primary row %u) is not of this block (%u bytes, primary row %u)", f->n, f->base, b->n, b->base);
+        return ARCHON_E_ARG;
+    }
+    return with_ctx(b->dev, nullptr, [&](Ctx *c, hipStream_t s) -> int {
+        KeepStats<archon_hip_fm_mem_stats> keep(t_fmm_stats, b->dev);
+        fmm_call_stats(&keep.st, f, f->n, 0, 0);
+        return fmm_mirror_run(c, s, f, b->d_x, false, &keep.st);
+    });
+}
+
+int archon_hip_block_fm_locate_mems(archon_hip_block *b, const archon_hip_fm_mem *mems, uint64_t nmems, uint32_t *pos, uint64_t cap, uint64_t *total)
+{
+    if (!b || (!mems && nmems) || !pos || !total) { set_error("null pointer"); return ARCHON_E_ARG; }
+    std::lock_guard<std::mutex> lkb(b->mu);
+    ARCHON_TRY(block_check(b, true));
+    ARCHON_TRY(fmm_check_mems(mems, nmems, b->n));
+    *total = 0;
+    return with_ctx(b->dev, nullptr, [&](Ctx *c, hipStream_t s) -> int {
+        KeepStats<archon_hip_fm_mem_stats> keep(t_fmm_stats, b->dev);
+        fmm_call_stats(&keep.st, nullptr, b->n, 0, 0);
+        return fmm_locate(c, s, nullptr, b->d_sa, mems, nmems, pos, cap, total, &keep.st);
     });
 }
 

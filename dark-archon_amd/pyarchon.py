@@ -39,10 +39,14 @@ SYMBOLS = [
     "archon_hip_fm_extract_dev", "archon_hip_get_fm_walk_stats",
     "archon_hip_fm_approx", "archon_hip_fm_approx_dev", "archon_hip_block_fm_approx", "archon_hip_fm_locate_hits",
     "archon_hip_block_fm_locate_hits", "archon_hip_get_fm_approx_stats",
+    "archon_hip_fm_mirror", "archon_hip_fm_mirror_dev", "archon_hip_block_fm_mirror", "archon_hip_fm_read_mirror", "archon_hip_fm_smems",
+    "archon_hip_fm_smems_dev", "archon_hip_fm_locate_mems", "archon_hip_block_fm_locate_mems", "archon_hip_get_fm_mem_stats",
 ]
 
 # archon_hip_fm_hit: one distinct string within the distance of a pattern (FmIndex.approx, Block.fm_approx)
 FM_HIT = np.dtype([("lo", "<u4"), ("hi", "<u4"), ("mismatches", "<u4"), ("pattern", "<u4")])
+# archon_hip_fm_mem: one super-maximal exact match of a pattern (FmIndex.smems): rows [lo, hi) of the piece [start, end)
+FM_MEM = np.dtype([("lo", "<u4"), ("hi", "<u4"), ("start", "<u4"), ("end", "<u4"), ("pattern", "<u4"), ("reserved0", "<u4")])
 
 
 class Stats(ctypes.Structure):
@@ -112,6 +116,20 @@ class FmApproxStats(ctypes.Structure):
         ("pattern_bytes", ctypes.c_uint64), ("expansions", ctypes.c_uint64), ("steps", ctypes.c_uint64), ("hits", ctypes.c_uint64),
         ("occurrences", ctypes.c_uint64), ("lf_steps", ctypes.c_uint64), ("kernel_launches", ctypes.c_uint32), ("host_syncs", ctypes.c_uint32),
         ("ms_build", ctypes.c_float), ("ms_count", ctypes.c_float), ("ms_emit", ctypes.c_float), ("ms_locate", ctypes.c_float),
+    ]
+
+    def asdict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
+class FmMemStats(ctypes.Structure):
+    """archon_hip_fm_mem_stats: the calling thread's last SMEM call (mirror, smems, locate_mems) on a device"""
+    _fields_ = [
+        ("n", ctypes.c_uint32), ("patterns", ctypes.c_uint32), ("min_len", ctypes.c_uint32), ("built", ctypes.c_uint32),
+        ("pattern_bytes", ctypes.c_uint64), ("fwd_steps", ctypes.c_uint64), ("bwd_steps", ctypes.c_uint64), ("found", ctypes.c_uint64),
+        ("mems", ctypes.c_uint64), ("occurrences", ctypes.c_uint64), ("lf_steps", ctypes.c_uint64), ("mirror_bytes", ctypes.c_uint64),
+        ("kernel_launches", ctypes.c_uint32), ("host_syncs", ctypes.c_uint32), ("ms_mirror", ctypes.c_float), ("ms_count", ctypes.c_float),
+        ("ms_emit", ctypes.c_float), ("ms_locate", ctypes.c_float),
     ]
 
     def asdict(self):
@@ -201,6 +219,15 @@ def load():
         "archon_hip_fm_locate_hits": [vp, vp, u32, vp, ctypes.c_uint64, vp, ctypes.c_uint64, vp],
         "archon_hip_block_fm_locate_hits": [vp, vp, u32, vp, ctypes.c_uint64, vp, ctypes.c_uint64, vp],
         "archon_hip_get_fm_approx_stats": [i32, ctypes.POINTER(FmApproxStats)],
+        "archon_hip_fm_mirror": [vp],
+        "archon_hip_fm_mirror_dev": [vp, vp, vp],
+        "archon_hip_block_fm_mirror": [vp, vp],
+        "archon_hip_fm_read_mirror": [vp, vp, u32, vp],
+        "archon_hip_fm_smems": [vp, vp, vp, u32, u32, vp, vp, vp, ctypes.c_uint64, vp],
+        "archon_hip_fm_smems_dev": [vp, vp, vp, u32, u32, vp, vp, vp, ctypes.c_uint64, vp, vp],
+        "archon_hip_fm_locate_mems": [vp, vp, ctypes.c_uint64, vp, ctypes.c_uint64, vp],
+        "archon_hip_block_fm_locate_mems": [vp, vp, ctypes.c_uint64, vp, ctypes.c_uint64, vp],
+        "archon_hip_get_fm_mem_stats": [i32, ctypes.POINTER(FmMemStats)],
     }.items():
         fn = getattr(lib, name)
         fn.argtypes = args
@@ -358,6 +385,24 @@ def fm_approx_stats(dev=0):
     return s
 
 
+def fm_mem_stats(dev=0):
+    """FmMemStats of the calling thread's last SMEM call (mirror, smems, locate_mems) on dev"""
+    s = FmMemStats()
+    _check(lib().archon_hip_get_fm_mem_stats(dev, ctypes.byref(s)))
+    return s
+
+
+def _locate_mems(fn, h, mems):
+    """the starts of every SMEM's occurrences: a list of uint32 arrays, one per SMEM, each in row order"""
+    mems = np.ascontiguousarray(mems, FM_MEM)
+    cuts = np.zeros(mems.size + 1, np.int64)
+    np.cumsum(mems["hi"].astype(np.int64) - mems["lo"], out=cuts[1:])
+    pos = np.zeros(max(int(cuts[-1]), 1), np.uint32)
+    total = ctypes.c_uint64(0)
+    _check(fn(h, _p(mems) if mems.size else None, mems.size, _p(pos), int(cuts[-1]), ctypes.cast(ctypes.byref(total), ctypes.c_void_p)))
+    return [pos[cuts[i]:cuts[i + 1]] for i in range(mems.size)]
+
+
 def _approx(fn, h, patterns, k, hits):
     """(nhits, nocc, hits or None) of an approximate call: counting first, then the hits into an array of the size it gave"""
     packed, offsets = _pack_patterns(patterns)
@@ -409,6 +454,7 @@ class FmIndex:
 
     def __init__(self, bwt=None, base_id=0, dev=0, _handle=None):
         self.h = _handle
+        self.dev = dev
         if self.h is None:
             bwt = np.ascontiguousarray(bwt, dtype=np.uint8)
             h = ctypes.c_void_p(None)
@@ -422,7 +468,7 @@ class FmIndex:
         dev = bwt_t.device.index or 0
         h = ctypes.c_void_p(None)
         _check(lib().archon_hip_fm_create_dev(ctypes.c_void_p(bwt_t.data_ptr()), bwt_t.numel(), int(base_id), dev, _stream_ptr(), ctypes.byref(h)))
-        f = cls(_handle=h)
+        f = cls(dev=dev, _handle=h)
         f.n = bwt_t.numel()
         return f
 
@@ -486,6 +532,67 @@ class FmIndex:
     def locate_hits(self, patterns, hits):
         """the starts of every hit's occurrences from the samples (a list of uint32 arrays, one per hit, in the shape of locate)"""
         return _locate_hits(lib().archon_hip_fm_locate_hits, self.h, patterns, hits)
+
+    def mirror(self, text=None):
+        """builds the mirror (the index of the reversed block) that smems() needs: from the handle's own BWT, or from the
+        block's text -- a host uint8 array or a torch uint8 tensor on the device -- which saves the inverse; returns self"""
+        if text is None:
+            _check(lib().archon_hip_fm_mirror(self.h))
+        elif hasattr(text, "data_ptr"):
+            if text.numel() != self.n:
+                raise ValueError("mirror: the text has %d bytes, the index %d" % (text.numel(), self.n))
+            _check(lib().archon_hip_fm_mirror_dev(self.h, ctypes.c_void_p(text.data_ptr()), _stream_ptr()))
+        else:
+            import torch
+            text = np.ascontiguousarray(text, dtype=np.uint8)
+            if text.size != self.n:
+                raise ValueError("mirror: the text has %d bytes, the index %d" % (text.size, self.n))
+            t = torch.from_numpy(text).to("cuda:%d" % self.dev)
+            _check(lib().archon_hip_fm_mirror_dev(self.h, ctypes.c_void_p(t.data_ptr()), _stream_ptr()))
+        return self
+
+    def read_mirror(self):
+        """(bwt, base_id) of the mirror: the a7 transform of the reversed block"""
+        out = np.zeros(max(self.n, 1), np.uint8)
+        base = ctypes.c_uint32(0)
+        _check(lib().archon_hip_fm_read_mirror(self.h, _p(out), self.n, ctypes.cast(ctypes.byref(base), ctypes.c_void_p)))
+        return out[:self.n], base.value
+
+    def smems(self, patterns, min_len=1, mems=True):
+        """the super-maximal exact matches of every pattern: (nmems, nocc, mems), mems an FM_MEM array in the order of the
+        header's procedure (None with mems=False: counting only).  Needs mirror()"""
+        packed, offsets = _pack_patterns(patterns)
+        npat = offsets.size - 1
+        nmems, nocc = np.zeros(npat, np.uint32), np.zeros(npat, np.uint32)
+        total = ctypes.c_uint64(0)
+        tp = ctypes.cast(ctypes.byref(total), ctypes.c_void_p)
+        fn = lib().archon_hip_fm_smems
+        if not mems:
+            _check(fn(self.h, _p(packed), _p(offsets), npat, int(min_len), _p(nmems), _p(nocc), None, 0, tp))
+            return nmems, nocc, None
+        # one call when the SMEMs fit a first guess, a second with the exact size when they do not
+        out = np.zeros(max(4 * npat, 1), FM_MEM)
+        rc = fn(self.h, _p(packed), _p(offsets), npat, int(min_len), _p(nmems), _p(nocc), _p(out), out.size, tp)
+        if rc == E_ARG and total.value > out.size:
+            out = np.zeros(total.value, FM_MEM)
+            rc = fn(self.h, _p(packed), _p(offsets), npat, int(min_len), _p(nmems), _p(nocc), _p(out), out.size, tp)
+        _check(rc)
+        return nmems, nocc, out[:total.value]
+
+    def smems_dev(self, patterns_t, offsets_t, min_len, nmems_t, nocc_t, mems_t=None):
+        """torch tensors on the device: patterns uint8, offsets int32[k + 1], nmems and nocc int32[k] (written), mems an int32
+        tensor of 6 words per SMEM or None; current stream.  Returns the number of SMEMs"""
+        total = ctypes.c_uint64(0)
+        cap = mems_t.numel() // 6 if mems_t is not None else 0
+        _check(lib().archon_hip_fm_smems_dev(self.h, ctypes.c_void_p(patterns_t.data_ptr()), ctypes.c_void_p(offsets_t.data_ptr()), nmems_t.numel(),
+                                             int(min_len), ctypes.c_void_p(nmems_t.data_ptr()), ctypes.c_void_p(nocc_t.data_ptr()),
+                                             ctypes.c_void_p(mems_t.data_ptr()) if mems_t is not None else None, cap,
+                                             ctypes.cast(ctypes.byref(total), ctypes.c_void_p), _stream_ptr()))
+        return total.value
+
+    def locate_mems(self, mems):
+        """the starts of every SMEM's occurrences from the samples (a list of uint32 arrays, one per SMEM, each in row order)"""
+        return _locate_mems(lib().archon_hip_fm_locate_mems, self.h, mems)
 
     def extract(self, starts, lengths):
         """x[starts[j] .. starts[j] + lengths[j]) for every j: a list of uint8 arrays"""
@@ -567,6 +674,7 @@ class Block:
         h = ctypes.c_void_p(None)
         _check(lib().archon_hip_block_create(dev, ctypes.byref(h)))
         self.h = h
+        self.dev = dev
 
     def close(self):
         if self.h:
@@ -632,13 +740,20 @@ class Block:
         """the starts of every hit's occurrences from the resident SA (needs forward(want_sa=True)): a list of uint32 arrays"""
         return _locate_hits(lib().archon_hip_block_fm_locate_hits, self.h, patterns, hits)
 
-    def fm_index(self, rate):
+    def fm_locate_mems(self, mems):
+        """the starts of every SMEM's occurrences from the resident SA (needs forward(want_sa=True)): a list of uint32 arrays"""
+        return _locate_mems(lib().archon_hip_block_fm_locate_mems, self.h, mems)
+
+    def fm_index(self, rate, mirror=False):
         """a standalone sampled FmIndex of the last forward's BWT (samples from the SA when that forward kept one, else by the
-        LF walk); it outlives later forwards and close()"""
+        LF walk); it outlives later forwards and close().  mirror=True: with its mirror, built from the resident block"""
         h = ctypes.c_void_p(None)
         _check(lib().archon_hip_block_fm_index(self.h, int(rate), ctypes.byref(h)))
         f = FmIndex(_handle=h)
         f.n = self.n
+        f.dev = self.dev
+        if mirror:
+            _check(lib().archon_hip_block_fm_mirror(self.h, f.h))
         return f
 
     def stats(self):

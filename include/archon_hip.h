@@ -442,6 +442,105 @@ typedef struct archon_hip_fm_approx_stats {
 } archon_hip_fm_approx_stats;
 int  archon_hip_get_fm_approx_stats(int dev, archon_hip_fm_approx_stats *out);
 
+/* ---- super-maximal exact matches: which pieces of a pattern occur, with a mirror index ------------------------------------
+ * Keys, R and occ' are those of the search rule above.  An SMEM of a pattern P of length m is a pair (b, e), 0 <= b < e <= m,
+ * such that P[b .. e) occurs in x, and b == 0 or P[b-1 .. e) does not occur, and e == m or P[b .. e+1) does not occur: an
+ * occurring piece of P that no other occurring piece of P contains.  Ordered by b the SMEMs of a pattern have strictly
+ * increasing e, so a pattern has at most m of them.  A position of P whose byte does not occur in x lies in no SMEM.
+ * The MIRROR of a handle is the a7 transform (BWT and primary row) of xr = x reversed, with a rank table of its own in the
+ * layout above.  A rank step on the primary index extends a match to the right; one on the mirror extends it to the left:
+ * P[b' .. e] occurs in x exactly when the search rule finds P[e], P[e-1], ..., P[b'] in the mirror.
+ * The search, its output order and its work counters are this procedure:
+ *   b = 0
+ *   while b < m:
+ *     F: the search rule on the primary index from P[b]: the bucket of P[b] (no step), then one rank step per further byte,
+ *        until the range is empty or P ends.  l = the bytes matched, [lo, hi) the last range that held rows.
+ *        l == 0 (P[b] is not in x): b += 1; continue
+ *        fwd_steps += l if b + l < m, else l - 1          (the failing step counts, as in archon_hip_fm_count)
+ *        e = b + l; found += 1; if e - b >= min_len: emit (lo, hi, b, e)
+ *        if e == m: stop
+ *     B: the search rule on the mirror with P[e], P[e-1], ..., at most down to P[b+1] (P[b .. e] is known not to occur).
+ *        g = the bytes matched
+ *        g == 0 (P[e] is not in x): b = e + 1; continue
+ *        b' = e - g + 1; bwd_steps += g if b' > b + 1, else g - 1          (no step is spent on P[b])
+ *        b = b'
+ * The SMEMs of a pattern are emitted in ascending b, the patterns in ascending j.  The rows [lo, hi) are rows of the PRIMARY
+ * index: exactly what archon_hip_fm_count returns for P[b .. e), so every occurrence starts at sa[r] - (e - b).  m = 0 gives
+ * no SMEM and no step; a pattern longer than the block is searched like any other.  min_len only filters the output: it
+ * changes neither counter nor `found`.
+ * Example: "banana" (BWT nnbaaa, primary row 2, sa = 2 4 6 1 3 5; mirror: "ananab", BWT bnnaaa, primary row 3): "nanb" gives
+ * F from 0: n, a, n match (rows [5, 6)), b fails: 3 steps, the SMEM (5, 6, 0, 3) ("nan", start sa[5] - 3 = 2).  B with
+ * "b", then "n": "nb" does not occur, g = 1, 1 step, b' = 3.  F from 3: the bucket of b, the SMEM (3, 4, 3, 4) (start
+ * sa[3] - 1 = 0) and the end of P.  fwd_steps = 3, bwd_steps = 1, found = 2.
+ * Memory: the mirror is one more device allocation of the handle, its BWT (n + 64 bytes) and rank table: at most
+ * 1.5 n + n / 64 + 4096 bytes at the table's default sizes, freed by archon_hip_fm_destroy.  Handles without a mirror behave
+ * exactly as before and refuse the SMEM search (ARCHON_E_ARG).
+ * Device work: one wave per pattern, every step one rank step of archon_hip_fm_count; a single long pattern runs on one
+ * wave, one dependent step after the other.
+ * A handle serves one thread at a time (as above): a mirror build frees the handle's earlier mirror, so archon_hip_fm_mirror,
+ * _fm_mirror_dev and archon_hip_block_fm_mirror must not run while another call uses the same handle. */
+/* the mirror from the handle's own BWT: its inverse, the reversed text, a forward transform and the table, all in the calling
+ * thread's context arena (about 32 n bytes for the nested forward).  Replaces an earlier mirror.  ARCHON_E_CORRUPT when the
+ * handle's bytes are no BWT in a7 format. */
+int  archon_hip_fm_mirror(archon_hip_fm *f);
+/* the same from a device copy of the text x (n bytes, any address), which saves the inverse; on `stream` (NULL = the context's
+ * own), complete on return.  A text whose 256 byte counts differ from the handle's is refused with ARCHON_E_ARG: a cheap guard,
+ * not a proof -- a different text with the same counts gives a mirror of that text, and SMEMs that mean nothing.  The text is
+ * read in aligned 16-byte granules: at an address that is no multiple of 16 the call also reads (and ignores) the up to 15
+ * bytes of the granules of d_x[0] and d_x[n-1] that lie outside the text; they share those bytes' 16-byte granule. */
+int  archon_hip_fm_mirror_dev(archon_hip_fm *f, const uint8_t *d_x, void *stream);
+/* for a handle made by archon_hip_block_fm_index from this block's last forward: the mirror from the resident x.  A handle of
+ * another length or primary row is ARCHON_E_ARG. */
+int  archon_hip_block_fm_mirror(archon_hip_block *b, archon_hip_fm *f);
+/* the mirror's BWT (n bytes) and primary row to the host; *base_id set even when cap < n (ARCHON_E_ARG) */
+int  archon_hip_fm_read_mirror(archon_hip_fm *f, uint8_t *bwt, uint32_t cap, uint32_t *base_id);
+typedef struct archon_hip_fm_mem {
+    uint32_t lo, hi;            /* the rows of P[start .. end) in the primary index */
+    uint32_t start, end;        /* b and e: the piece of the pattern */
+    uint32_t pattern;           /* j: the pattern it belongs to */
+    uint32_t reserved0;
+} archon_hip_fm_mem;
+/* nmems[k] and nocc[k] (SMEMs of at least min_len bytes, rows summed over them) always written; *total = the sum of nmems.
+ * nocc[j] saturates at 2^32 - 1 (a long pattern's pieces can hold more rows than that; the SMEMs carry the exact ranges).
+ * mems_or_null NULL: counting only (no emit pass).  cap < *total with mems given: ARCHON_E_ARG, counts and *total written, mems
+ * untouched.  Patterns and offsets as for archon_hip_fm_count; k = 0 writes *total = 0 and nothing else. */
+int  archon_hip_fm_smems(archon_hip_fm *f, const uint8_t *patterns, const uint32_t *offsets, uint32_t k, uint32_t min_len,
+                         uint32_t *nmems, uint32_t *nocc, archon_hip_fm_mem *mems_or_null, uint64_t cap, uint64_t *total);
+/* device patterns, offsets, nmems, nocc and mems, *total a host pointer; on `stream` (NULL = the context's own), complete on
+ * return; decreasing offsets are found on the device (ARCHON_E_ARG, nothing emitted) */
+int  archon_hip_fm_smems_dev(archon_hip_fm *f, const uint8_t *d_patterns, const uint32_t *d_offsets, uint32_t k, uint32_t min_len,
+                             uint32_t *d_nmems, uint32_t *d_nocc, archon_hip_fm_mem *d_mems_or_null, uint64_t cap, uint64_t *total,
+                             void *stream);
+/* the starts of every SMEM's occurrences, SMEM by SMEM, each in row order: sa[r] - (end - start) for r in [lo, hi).  *total =
+ * their number; cap < *total: ARCHON_E_ARG, nothing written.  lo > hi, hi > n, end < start or nmems >= 2^32: ARCHON_E_ARG.  A
+ * sampled handle (else ARCHON_E_ARG) walks LF to the samples and needs no mirror; a block needs the suffix array of its last
+ * forward (else ARCHON_E_ARG), the rows being rows of that block's BWT. */
+int  archon_hip_fm_locate_mems(archon_hip_fm *f, const archon_hip_fm_mem *mems, uint64_t nmems, uint32_t *pos, uint64_t cap, uint64_t *total);
+int  archon_hip_block_fm_locate_mems(archon_hip_block *b, const archon_hip_fm_mem *mems, uint64_t nmems, uint32_t *pos, uint64_t cap,
+                                     uint64_t *total);
+/* the CALLING THREAD's last SMEM call (mirror, smems or locate_mems) on `dev`; SMEM calls leave archon_hip_stats,
+ * archon_hip_fm_stats, archon_hip_fm_walk_stats, archon_hip_fm_approx_stats and the rest alone */
+typedef struct archon_hip_fm_mem_stats {
+    uint32_t n;                 /* block size of the index */
+    uint32_t patterns;          /* k of the call */
+    uint32_t min_len;           /* of the call (0 for mirror and locate_mems) */
+    uint32_t built;             /* 1 when the call built a mirror */
+    uint64_t pattern_bytes;     /* bytes of the patterns */
+    uint64_t fwd_steps;         /* rank steps on the primary index (count pass) */
+    uint64_t bwd_steps;         /* rank steps on the mirror (count pass) */
+    uint64_t found;             /* SMEMs of any length */
+    uint64_t mems;              /* SMEMs of at least min_len bytes (smems) or located (locate_mems) */
+    uint64_t occurrences;       /* rows summed over those */
+    uint64_t lf_steps;          /* locate_mems on a sampled handle: LF steps of all walks */
+    uint64_t mirror_bytes;      /* device bytes of the handle's mirror: BWT and rank table */
+    uint32_t kernel_launches;   /* launches issued by the call, those of a mirror's nested transforms included */
+    uint32_t host_syncs;        /* times the host waited for the stream inside the call */
+    float ms_mirror;            /* device time of a mirror build, end to end (HIP events) */
+    float ms_count, ms_emit;    /* device time of the count and the emit pass */
+    float ms_locate;            /* device time of locate_mems' kernel */
+} archon_hip_fm_mem_stats;
+int  archon_hip_get_fm_mem_stats(int dev, archon_hip_fm_mem_stats *out);
+
 /* ---- measurement ------------------------------------------------------------- */
 
 /* Per-stage device times (HIP events on the stream the kernels ran on) and
