@@ -17,6 +17,7 @@
 #include "fm_approx.hiph"
 #include "fm_mem.hiph"
 #include "fm_host.hiph"
+#include "repeats.hiph"
 
 #include <stdarg.h>
 #include <atomic>
@@ -84,6 +85,7 @@ static thread_local LastStats<archon_hip_fm_stats> t_fm_stats;          // FM ca
 static thread_local LastStats<archon_hip_fm_walk_stats> t_fmw_stats;    // sampled-index calls: sample, block_fm_index, locate, extract
 static thread_local LastStats<archon_hip_fm_approx_stats> t_fma_stats;  // approximate calls: approx, locate_hits
 static thread_local LastStats<archon_hip_fm_mem_stats> t_fmm_stats;     // SMEM calls: mirror, smems, locate_mems
+static thread_local LastStats<archon_hip_repeat_stats> t_rep_stats;     // repeats calls
 
 // The record of one FM call: kept for the calling thread when the scope ends, on whichever path the call leaves it, with the
 // host waits since the scope began.
@@ -1722,6 +1724,54 @@ int archon_hip_lcp(const uint8_t *x, uint32_t n, const uint32_t *sa, uint32_t *l
     });
 }
 
+// ---- the repeats of a block (repeats.hiph: the kernels and their drivers; here the argument checks and the statistics)
+static int rep_check(const void *lcp, const void *bwt, const void *total, uint32_t n, uint32_t base_id, uint32_t kind)
+{
+    if (!lcp || !bwt || !total) { set_error("null pointer"); return ARCHON_E_ARG; }
+    ARCHON_TRY(check_n(n));
+    if (base_id >= n) { set_error("primary row %u out of range [0, %u)", base_id, n); return ARCHON_E_ARG; }
+    return rep_check_kind(kind);
+}
+
+int archon_hip_repeats_dev(const uint32_t *d_lcp, const uint8_t *d_bwt, uint32_t n, uint32_t base_id, uint32_t kind, uint32_t min_len, uint32_t min_occ,
+                           archon_hip_repeat *d_out_or_null, uint64_t cap, uint64_t *total, int dev, void *stream)
+{
+    ARCHON_TRY(rep_check(d_lcp, d_bwt, total, n, base_id, kind));
+    *total = 0;
+    return with_ctx(dev, stream, [&](Ctx *c, hipStream_t s) -> int {
+        KeepStats<archon_hip_repeat_stats> keep(t_rep_stats, dev);
+        rep_call_stats(&keep.st, n, kind, min_len, min_occ);
+        RepCall q = {d_lcp, d_bwt, n, base_id, kind, min_len, min_occ};
+        return rep_dev(c, s, q, d_out_or_null, cap, total, &keep.st);
+    });
+}
+
+// host buffers: the BWT and the LCP array through the context's staging buffers
+int archon_hip_repeats(const uint32_t *lcp, const uint8_t *bwt, uint32_t n, uint32_t base_id, uint32_t kind, uint32_t min_len, uint32_t min_occ,
+                       archon_hip_repeat *out_or_null, uint64_t cap, uint64_t *total, int dev)
+{
+    ARCHON_TRY(rep_check(lcp, bwt, total, n, base_id, kind));
+    *total = 0;
+    return with_ctx(dev, nullptr, [&](Ctx *c, hipStream_t s) -> int {
+        KeepStats<archon_hip_repeat_stats> keep(t_rep_stats, dev);
+        rep_call_stats(&keep.st, n, kind, min_len, min_occ);
+        uint8_t *d_bwt = nullptr;
+        uint32_t *d_lcp = nullptr;
+        ARCHON_TRY(ctx_io(c, 0, (size_t)n + 64, (void **)&d_bwt));
+        ARCHON_TRY(ctx_io(c, 1, (size_t)n * 4 + 64, (void **)&d_lcp));
+        ARCHON_HIP_TRY(hipMemcpyAsync(d_bwt, bwt, n, hipMemcpyHostToDevice, s));
+        ARCHON_HIP_TRY(hipMemcpyAsync(d_lcp, lcp, (size_t)n * 4, hipMemcpyHostToDevice, s));
+        RepCall q = {d_lcp, d_bwt, n, base_id, kind, min_len, min_occ};
+        return rep_to_host(c, s, q, out_or_null, cap, total, &keep.st);
+    });
+}
+
+int archon_hip_get_repeat_stats(int dev, archon_hip_repeat_stats *out)
+{
+    if (!out) { set_error("null pointer"); return ARCHON_E_ARG; }
+    return t_rep_stats.get(dev, out, "repeats call");
+}
+
 // ---- the FM index (fm_host.hiph: the handle and every driver; here the argument checks and the statistics)
 int archon_hip_fm_create(const uint8_t *bwt, uint32_t n, uint32_t base_id, int dev, archon_hip_fm **out)
 {
@@ -2121,6 +2171,30 @@ int archon_hip_block_lcp(archon_hip_block *b, uint32_t *lcp)
         ARCHON_HIP_TRY(hipMemcpyAsync(lcp, d_lcp, (size_t)b->n * 4, hipMemcpyDeviceToHost, s));
         ARCHON_SYNC(s);
         return ARCHON_OK;
+    });
+}
+
+// the LCP array into staging buffer 1, as archon_hip_block_lcp makes it, and from there into the repeats' count pass
+int archon_hip_block_repeats(archon_hip_block *b, uint32_t kind, uint32_t min_len, uint32_t min_occ, archon_hip_repeat *out_or_null, uint64_t cap,
+                             uint64_t *total)
+{
+    if (!b || !total) { set_error("null pointer"); return ARCHON_E_ARG; }
+    ARCHON_TRY(rep_check_kind(kind));
+    std::lock_guard<std::mutex> lkb(b->mu);
+    ARCHON_TRY(block_check(b, true));
+    *total = 0;
+    return with_ctx(b->dev, nullptr, [&](Ctx *c, hipStream_t s) -> int {
+        KeepStats<archon_hip_repeat_stats> keep(t_rep_stats, b->dev);
+        rep_call_stats(&keep.st, b->n, kind, min_len, min_occ);
+        uint32_t *d_lcp = nullptr;
+        ARCHON_TRY(ctx_io(c, 1, (size_t)b->n * 4 + 64, (void **)&d_lcp));
+        archon_hip_lcp_stats st = {};
+        const int rc = lcp_run(c, s, b->d_x, b->n, b->d_sa, b->d_bwt, d_lcp, &st);
+        t_lcp_stats.keep(b->dev, st);
+        ARCHON_TRY(rc);
+        keep.st.ms_lcp = st.ms_total;
+        RepCall q = {d_lcp, b->d_bwt, b->n, b->base, kind, min_len, min_occ};
+        return rep_to_host(c, s, q, out_or_null, cap, total, &keep.st);
     });
 }
 
@@ -2897,6 +2971,14 @@ int archon_hip_test_route(const char *name, long value)
             return ARCHON_E_ARG;
         }
         g_route.fm_sub_rows = (int)value;
+        return ARCHON_OK;
+    }
+    if (!strcmp(name, "REP_FAN")) {
+        if (value && (value < 2 || value > 64 || (value & (value - 1)))) {
+            set_error("REP_FAN=%ld: not a power of two in [2, 64]", value);
+            return ARCHON_E_ARG;
+        }
+        g_route.rep_fan = (int)value;
         return ARCHON_OK;
     }
     if (!strcmp(name, "FM_SAMPLE_WALK")) { g_route.fm_sample_walk = value ? 1 : 0; return ARCHON_OK; }

@@ -41,12 +41,15 @@ SYMBOLS = [
     "archon_hip_block_fm_locate_hits", "archon_hip_get_fm_approx_stats",
     "archon_hip_fm_mirror", "archon_hip_fm_mirror_dev", "archon_hip_block_fm_mirror", "archon_hip_fm_read_mirror", "archon_hip_fm_smems",
     "archon_hip_fm_smems_dev", "archon_hip_fm_locate_mems", "archon_hip_block_fm_locate_mems", "archon_hip_get_fm_mem_stats",
+    "archon_hip_repeats", "archon_hip_repeats_dev", "archon_hip_block_repeats", "archon_hip_get_repeat_stats",
 ]
 
 # archon_hip_fm_hit: one distinct string within the distance of a pattern (FmIndex.approx, Block.fm_approx)
 FM_HIT = np.dtype([("lo", "<u4"), ("hi", "<u4"), ("mismatches", "<u4"), ("pattern", "<u4")])
 # archon_hip_fm_mem: one super-maximal exact match of a pattern (FmIndex.smems): rows [lo, hi) of the piece [start, end)
 FM_MEM = np.dtype([("lo", "<u4"), ("hi", "<u4"), ("start", "<u4"), ("end", "<u4"), ("pattern", "<u4"), ("reserved0", "<u4")])
+# archon_hip_repeat: one repeat of a block (repeats, Block.repeats): rows [lo, hi) of a string of len bytes, its representative row
+REPEAT = np.dtype([("lo", "<u4"), ("hi", "<u4"), ("len", "<u4"), ("row", "<u4")])
 
 
 class Stats(ctypes.Structure):
@@ -130,6 +133,21 @@ class FmMemStats(ctypes.Structure):
         ("mems", ctypes.c_uint64), ("occurrences", ctypes.c_uint64), ("lf_steps", ctypes.c_uint64), ("mirror_bytes", ctypes.c_uint64),
         ("kernel_launches", ctypes.c_uint32), ("host_syncs", ctypes.c_uint32), ("ms_mirror", ctypes.c_float), ("ms_count", ctypes.c_float),
         ("ms_emit", ctypes.c_float), ("ms_locate", ctypes.c_float),
+    ]
+
+    def asdict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
+class RepeatStats(ctypes.Structure):
+    """archon_hip_repeat_stats: the calling thread's last repeats call on a device"""
+    _fields_ = [
+        ("n", ctypes.c_uint32), ("kind", ctypes.c_uint32), ("min_len", ctypes.c_uint32), ("min_occ", ctypes.c_uint32),
+        ("fan", ctypes.c_uint32), ("levels", ctypes.c_uint32), ("longest", ctypes.c_uint32), ("kernel_launches", ctypes.c_uint32),
+        ("host_syncs", ctypes.c_uint32), ("reserved0", ctypes.c_uint32),
+        ("intervals", ctypes.c_uint64), ("repeats", ctypes.c_uint64), ("occurrences", ctypes.c_uint64), ("sum_lcp", ctypes.c_uint64),
+        ("distinct_substrings", ctypes.c_uint64), ("probes", ctypes.c_uint64),
+        ("ms_lcp", ctypes.c_float), ("ms_count", ctypes.c_float), ("ms_emit", ctypes.c_float), ("reserved1", ctypes.c_float),
     ]
 
     def asdict(self):
@@ -228,6 +246,10 @@ def load():
         "archon_hip_fm_locate_mems": [vp, vp, ctypes.c_uint64, vp, ctypes.c_uint64, vp],
         "archon_hip_block_fm_locate_mems": [vp, vp, ctypes.c_uint64, vp, ctypes.c_uint64, vp],
         "archon_hip_get_fm_mem_stats": [i32, ctypes.POINTER(FmMemStats)],
+        "archon_hip_repeats": [vp, vp, u32, u32, u32, u32, u32, vp, ctypes.c_uint64, vp, i32],
+        "archon_hip_repeats_dev": [vp, vp, u32, u32, u32, u32, u32, vp, ctypes.c_uint64, vp, i32, vp],
+        "archon_hip_block_repeats": [vp, u32, u32, u32, vp, ctypes.c_uint64, vp],
+        "archon_hip_get_repeat_stats": [i32, ctypes.POINTER(RepeatStats)],
     }.items():
         fn = getattr(lib, name)
         fn.argtypes = args
@@ -251,7 +273,7 @@ _routes_seen = None
 _ROUTE_NAMES = ("FORCE_PATH", "SMALL_BLOCK", "PASS_RANGES", "INV_ROWS", "INV_SLAB", "INV_SBITS", "INV_WALK_WGS", "NO_ALIGNED", "NO_CHAINS", "NO_DEEP_HINT",
                 "NO_PACK", "NO_PACK_STREAM", "NO_PAIR_CHAINS", "NO_PERIOD_HINT", "NO_BREAK_ROUND", "NO_PERIOD_PROBE", "NO_PERIOD_STREAM", "NO_PROBE",
                 "NO_RANK_WRITER", "NO_TEXT_ROUNDS", "NO_MID", "NO_SHALLOW", "NO_CLOSED_FORM", "NO_REL_RECORDS", "ALIGNED_MIN", "REL_MIN_SEG", "KEY_BYTES",
-                "LCP_CAP", "LCP_WINDOW", "FM_SUB_ROWS", "FM_SUPER_ROWS", "FM_SAMPLE_WALK")
+                "LCP_CAP", "LCP_WINDOW", "FM_SUB_ROWS", "FM_SUPER_ROWS", "FM_SAMPLE_WALK", "REP_FAN")
 
 
 def _sync_routes(L):
@@ -390,6 +412,46 @@ def fm_mem_stats(dev=0):
     s = FmMemStats()
     _check(lib().archon_hip_get_fm_mem_stats(dev, ctypes.byref(s)))
     return s
+
+
+def repeat_stats(dev=0):
+    """RepeatStats of the calling thread's last repeats call on dev"""
+    s = RepeatStats()
+    _check(lib().archon_hip_get_repeat_stats(dev, ctypes.byref(s)))
+    return s
+
+
+def _repeats(call, count_only):
+    """call(out pointer or None, cap, total pointer) -> rc: the count, or the repeats in an array of the size a first call gave"""
+    total = ctypes.c_uint64(0)
+    tp = ctypes.cast(ctypes.byref(total), ctypes.c_void_p)
+    _check(call(None, 0, tp))
+    if count_only:
+        return total.value
+    out = np.zeros(total.value, REPEAT)
+    if total.value:
+        _check(call(_p(out), out.size, tp))
+    return out[:total.value]
+
+
+def repeats(lcp, bwt, base_id, kind=1, min_len=1, min_occ=2, count_only=False, dev=0):
+    """the repeats of a block from its LCP array and BWT (include/archon_hip.h: archon_hip_repeats): a REPEAT array in
+    ascending representative row; kind 0 = every LCP interval, 1 = maximal, 2 = supermaximal.  count_only: their number"""
+    lcp = np.ascontiguousarray(lcp, dtype=np.uint32)
+    bwt = np.ascontiguousarray(bwt, dtype=np.uint8)
+    if lcp.size != bwt.size:
+        raise ValueError("repeats: lcp has %d rows, bwt %d" % (lcp.size, bwt.size))
+    fn = lib().archon_hip_repeats
+    return _repeats(lambda out, cap, tp: fn(_p(lcp), _p(bwt), bwt.size, int(base_id), int(kind), int(min_len), int(min_occ), out, cap, tp, dev),
+                    count_only)
+
+
+def _as_mems(reps):
+    """REPEAT records as the FM_MEM records the locate calls take: rows [lo, hi) of a piece of len bytes"""
+    reps = np.ascontiguousarray(reps, REPEAT)
+    mems = np.zeros(reps.size, FM_MEM)
+    mems["lo"], mems["hi"], mems["end"] = reps["lo"], reps["hi"], reps["len"]
+    return mems
 
 
 def _locate_mems(fn, h, mems):
@@ -594,6 +656,11 @@ class FmIndex:
         """the starts of every SMEM's occurrences from the samples (a list of uint32 arrays, one per SMEM, each in row order)"""
         return _locate_mems(lib().archon_hip_fm_locate_mems, self.h, mems)
 
+    def locate_repeats(self, reps):
+        """the starts of every repeat's occurrences (REPEAT records of the block this index was made from) from the samples: a
+        list of uint32 arrays, one per repeat, each in row order"""
+        return _locate_mems(lib().archon_hip_fm_locate_mems, self.h, _as_mems(reps))
+
     def extract(self, starts, lengths):
         """x[starts[j] .. starts[j] + lengths[j]) for every j: a list of uint8 arrays"""
         starts = np.ascontiguousarray(starts, dtype=np.uint32).ravel()
@@ -744,6 +811,16 @@ class Block:
         """the starts of every SMEM's occurrences from the resident SA (needs forward(want_sa=True)): a list of uint32 arrays"""
         return _locate_mems(lib().archon_hip_block_fm_locate_mems, self.h, mems)
 
+    def repeats(self, kind=1, min_len=1, min_occ=2, count_only=False):
+        """the repeats of the resident block (needs forward(want_sa=True)): its LCP array is made and consumed on the device.
+        A REPEAT array in ascending representative row, or their number with count_only"""
+        fn = lib().archon_hip_block_repeats
+        return _repeats(lambda out, cap, tp: fn(self.h, int(kind), int(min_len), int(min_occ), out, cap, tp), count_only)
+
+    def locate_repeats(self, reps):
+        """the starts of every repeat's occurrences from the resident SA: a list of uint32 arrays, one per repeat, in row order"""
+        return _locate_mems(lib().archon_hip_block_fm_locate_mems, self.h, _as_mems(reps))
+
     def fm_index(self, rate, mirror=False):
         """a standalone sampled FmIndex of the last forward's BWT (samples from the SA when that forward kept one, else by the
         LF walk); it outlives later forwards and close().  mirror=True: with its mirror, built from the resident block"""
@@ -801,6 +878,18 @@ def lcp_dev(x_t, sa_t, lcp_t):
     dev = x_t.device.index or 0
     _check(lib().archon_hip_lcp_dev(ctypes.c_void_p(x_t.data_ptr()), x_t.numel(), ctypes.c_void_p(sa_t.data_ptr()),
                                     ctypes.c_void_p(lcp_t.data_ptr()), dev, _stream_ptr()))
+
+
+def repeats_dev(lcp_t, bwt_t, base_id, kind=1, min_len=1, min_occ=2, out_t=None):
+    """torch CUDA tensors: lcp int32[n], bwt uint8[n], out an int32 tensor of 4 words per repeat or None (counting only); on the
+    current stream.  Returns the number of repeats (raises when out_t holds fewer)"""
+    dev = lcp_t.device.index or 0
+    total = ctypes.c_uint64(0)
+    cap = out_t.numel() // 4 if out_t is not None else 0
+    _check(lib().archon_hip_repeats_dev(ctypes.c_void_p(lcp_t.data_ptr()), ctypes.c_void_p(bwt_t.data_ptr()), bwt_t.numel(), int(base_id), int(kind),
+                                        int(min_len), int(min_occ), ctypes.c_void_p(out_t.data_ptr()) if out_t is not None else None, cap,
+                                        ctypes.cast(ctypes.byref(total), ctypes.c_void_p), dev, _stream_ptr()))
+    return total.value
 
 
 def validate_resident_dev(x_t, sa_t, bwt_t, base_id):

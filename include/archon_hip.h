@@ -17,6 +17,7 @@
  *   archon_hip_fm_*         nothing: counting and locating patterns by backward search on the BWT (an FM index), below;
  *                           with a sampled SA and ISA it locates and extracts without the block's suffix array, and it
  *                           finds patterns with up to K substituted bytes (archon_hip_fm_approx)
+ *   archon_hip_repeats*     nothing: the LCP intervals, maximal and supermaximal repeats of a block from its LCP array and BWT
  *
  * Ordering convention ("a7 order"): item s in 1..N names the
  * reversed prefix x[s-1],x[s-2],...,x[0],INF with INF > 255; sa[0..N) lists the
@@ -540,6 +541,82 @@ typedef struct archon_hip_fm_mem_stats {
     float ms_locate;            /* device time of locate_mems' kernel */
 } archon_hip_fm_mem_stats;
 int  archon_hip_get_fm_mem_stats(int dev, archon_hip_fm_mem_stats *out);
+
+/* ---- the repeats of a block: LCP intervals, maximal and supermaximal repeats (no counterpart in the reference) -----------
+ * What a caller computes next from the suffix array, its LCP array and the BWT: which strings repeat in the block, how often
+ * and where.  Rows, sa, lcp, bwt and the primary row `base` are those above (row r holds item sa[r], bwt[r] = x[sa[r]], the
+ * primary row holds item n and stores x[0] as a stand-in); lcp[0] is taken as 0 whatever it holds.
+ * LCP interval: a row k in 1 .. n-1 with l = lcp[k] > 0 defines
+ *   lo = the greatest p < k with lcp[p] < l (row 0 at the latest), hi = the least q > k with lcp[q] < l, or n if there is none.
+ * Row k REPRESENTS the interval when no k' in (lo, k) has lcp[k'] == l: every interval has exactly one representative, and a
+ * block has at most n - 1 intervals.  The rows [lo, hi) are exactly the occurrences of the string u = x[s-l .. s), s = sa[r]
+ * of any of them: each occurrence starts at sa[r] - l, and [lo, hi) is what archon_hip_fm_count(u) returns.
+ *   kind 0  every LCP interval: the repeats u that cannot be extended to the left (their occurrences are not all preceded by
+ *           the same byte; an occurrence at the start of the text counts as different from all others)
+ *   kind 1  maximal repeats: a kind 0 interval whose occurrences are not all followed by the same byte: bwt[lo .. hi) are not
+ *           all equal, or base lies in [lo, hi) (the primary row has no following byte)
+ *   kind 2  supermaximal repeats: a kind 1 interval where every lcp[k], lo < k < hi, equals l and the following bytes are
+ *           pairwise distinct, the primary row distinct from every byte (hence hi - lo <= 257): a maximal repeat that is a
+ *           substring of no other maximal repeat
+ * Examples.  "banana" (sa = 2 4 6 1 3 5, lcp = 0 1 3 0 0 2, BWT nnbaaa, base 2): kind 0 gives (lo, hi, len, row) = (0,3,1,1)
+ * "a", (1,3,3,2) "ana", (4,6,2,5) "an"; kind 1 the first two; kind 2 (1,3,3,2) only.  "abracadabra": kind 1 gives (0,5,1,1)
+ * "a" and (2,4,4,3) "abra", kind 2 (2,4,4,3).
+ * Output order: ascending representative row.  Filters: min_len keeps len >= min_len (0 behaves as 1), min_occ keeps
+ * hi - lo >= min_occ (0 and 1 behave as 2); they change the output and the `repeats`, `occurrences` and `longest` counters
+ * only, never `intervals`.
+ * Cap rule (that of archon_hip_fm_smems): *total is a host pointer and always written.  out NULL: counting only, no emit pass.
+ * cap < *total with out given: ARCHON_E_ARG, *total written, out untouched.  ARCHON_E_ARG for a null lcp or bwt, n = 0,
+ * base_id >= n or kind > 2; n = 1 gives *total = 0.
+ * Work: both ends of an interval are nearest-smaller-value searches in a minimum hierarchy over lcp with fan-out F = 16 (level
+ * j holds the minimum of each F^j rows, L = ceil(log_F n) levels): a search reads at most F - 1 entries per level on the way up
+ * and F on the way down, a row takes at most two searches, so for ANY data
+ *   probes <= 2 (2 F - 1) L (n - 1)
+ * (a block of one repeated byte, lcp = 0, n-1, n-2, ..., 1, sends every left search to row 0).  The supermaximal check reads
+ * at most 257 rows of lcp and bwt per interval, not counted in probes.
+ * Bad input: an lcp that is not the LCP array of anything returns ARCHON_OK with unspecified contents; every access stays
+ * inside the buffers and every emitted lo < row < hi <= n.
+ * Workspace, from the calling thread's context arena: 4 n / (F - 1) bytes of hierarchy, 4 n + 4 bytes of change-flag sums (kind
+ * 1 only) and n / 400 bytes of tile words: about 4.3 n bytes.  The host forms stage lcp, bwt and the repeats besides.
+ * Locating needs no new call: a repeat (lo, hi, len) is located by archon_hip_block_fm_locate_mems / archon_hip_fm_locate_mems
+ * with an archon_hip_fm_mem {lo, hi, start 0, end len}: the starts sa[r] - len, r in [lo, hi).  The rows of a handle made by
+ * archon_hip_block_fm_index are the block's rows. */
+typedef struct archon_hip_repeat {
+    uint32_t lo, hi;            /* the rows of the repeat's occurrences */
+    uint32_t len;               /* its length l */
+    uint32_t row;               /* its representative row k */
+} archon_hip_repeat;
+/* device lcp[n], bwt[n] (any address) and out; on `stream` (NULL = the context's own), complete on return */
+int  archon_hip_repeats_dev(const uint32_t *d_lcp, const uint8_t *d_bwt, uint32_t n, uint32_t base_id, uint32_t kind, uint32_t min_len,
+                            uint32_t min_occ, archon_hip_repeat *d_out_or_null, uint64_t cap, uint64_t *total, int dev, void *stream);
+/* host lcp[n], bwt[n] and out */
+int  archon_hip_repeats(const uint32_t *lcp, const uint8_t *bwt, uint32_t n, uint32_t base_id, uint32_t kind, uint32_t min_len,
+                        uint32_t min_occ, archon_hip_repeat *out_or_null, uint64_t cap, uint64_t *total, int dev);
+/* the resident block of the handle's last forward: its LCP array is computed on the device (as archon_hip_block_lcp does, and
+ * with the same record in archon_hip_lcp_stats) and consumed there, it never visits the host: 4 n bytes of staging beside the
+ * 8 n bytes of arena the LCP call takes and the repeats call takes over.  out is a host buffer.  ARCHON_E_ARG when that
+ * forward kept no suffix array. */
+int  archon_hip_block_repeats(archon_hip_block *b, uint32_t kind, uint32_t min_len, uint32_t min_occ, archon_hip_repeat *out_or_null,
+                              uint64_t cap, uint64_t *total);
+/* the CALLING THREAD's last repeats call on `dev`; repeats calls leave every other record alone (archon_hip_block_repeats
+ * also keeps the LCP record of its LCP step) */
+typedef struct archon_hip_repeat_stats {
+    uint32_t n, kind, min_len, min_occ;     /* of the call, as given */
+    uint32_t fan, levels;       /* F and L of the hierarchy */
+    uint32_t longest;           /* the longest repeat that passed kind and filters */
+    uint32_t kernel_launches;   /* launches issued by the call (block form: without those of its LCP step) */
+    uint32_t host_syncs;        /* times the host waited for the stream inside the call (block form: the LCP step's included) */
+    uint32_t reserved0;
+    uint64_t intervals;         /* all LCP intervals: follows from lcp alone */
+    uint64_t repeats;           /* those that passed kind and filters: *total */
+    uint64_t occurrences;       /* hi - lo summed over them */
+    uint64_t sum_lcp;           /* lcp[1] + ... + lcp[n-1] */
+    uint64_t distinct_substrings;   /* n (n + 1) / 2 - sum_lcp */
+    uint64_t probes;            /* entries of lcp and of the hierarchy the searches of the count pass read */
+    float ms_lcp;               /* block form: device time of the LCP step */
+    float ms_count, ms_emit;    /* device time of the count pass (hierarchy and flag sums included) and of the emit pass */
+    float reserved1;
+} archon_hip_repeat_stats;
+int  archon_hip_get_repeat_stats(int dev, archon_hip_repeat_stats *out);
 
 /* ---- measurement ------------------------------------------------------------- */
 

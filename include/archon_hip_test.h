@@ -24,6 +24,8 @@
  *   FM_SAMPLE_WALK 0 / nonzero    sampled FM index: nonzero makes archon_hip_block_fm_index take the LF walk route even when the
  *                                 block's SA is resident (the walk route honours INV_SBITS; it stores no slabs, so INV_SLAB has
  *                                 nothing to change there).  Neither route changes a sample
+ *   REP_FAN        2..64 / 0      repeats: fan-out of the minimum hierarchy over lcp, a power of two (0: 16).  It changes no result:
+ *                                 at 2, blocks of seven bytes cross three levels
  *   NO_ALIGNED NO_BREAK_ROUND NO_CHAINS NO_DEEP_HINT NO_PACK NO_PACK_STREAM NO_PAIR_CHAINS NO_PERIOD_HINT NO_PERIOD_PROBE
  *   NO_PERIOD_STREAM NO_PROBE NO_RANK_WRITER NO_TEXT_ROUNDS NO_MID NO_SHALLOW NO_CLOSED_FORM NO_REL_RECORDS      nonzero switches the named step off
  * Returns 0, or ARCHON_E_ARG for an unknown name / a value out of range.  Process-wide; not thread-safe against
