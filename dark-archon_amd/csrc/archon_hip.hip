@@ -18,6 +18,7 @@
 #include "fm_mem.hiph"
 #include "fm_host.hiph"
 #include "repeats.hiph"
+#include "lz.hiph"
 
 #include <stdarg.h>
 #include <atomic>
@@ -86,6 +87,7 @@ static thread_local LastStats<archon_hip_fm_walk_stats> t_fmw_stats;    // sampl
 static thread_local LastStats<archon_hip_fm_approx_stats> t_fma_stats;  // approximate calls: approx, locate_hits
 static thread_local LastStats<archon_hip_fm_mem_stats> t_fmm_stats;     // SMEM calls: mirror, smems, locate_mems
 static thread_local LastStats<archon_hip_repeat_stats> t_rep_stats;     // repeats calls
+static thread_local LastStats<archon_hip_lz_stats> t_lz_stats;          // LZ calls: lpf, lz_parse, block_lz
 
 // The record of one FM call: kept for the calling thread when the scope ends, on whichever path the call leaves it, with the
 // host waits since the scope began.
@@ -1772,6 +1774,91 @@ int archon_hip_get_repeat_stats(int dev, archon_hip_repeat_stats *out)
     return t_rep_stats.get(dev, out, "repeats call");
 }
 
+// ---- longest previous factors and the LZ77 parse (lz.hiph: the kernels and their drivers; here the argument checks and the statistics)
+static int lpf_check(const void *sa, const void *lcp, const void *lpf, uint32_t n, uint32_t dir)
+{
+    if (!sa || !lcp || !lpf) { set_error("null pointer"); return ARCHON_E_ARG; }
+    ARCHON_TRY(check_n(n));
+    return lz_check_dir(dir);
+}
+
+int archon_hip_lpf_dev(const uint32_t *d_sa, const uint32_t *d_lcp, uint32_t n, uint32_t dir, archon_hip_lpf_rec *d_lpf, int dev, void *stream)
+{
+    ARCHON_TRY(lpf_check(d_sa, d_lcp, d_lpf, n, dir));
+    if ((uintptr_t)d_lpf & 7u) { set_error("lpf: the records are not 8-byte aligned"); return ARCHON_E_ARG; }
+    return with_ctx(dev, stream, [&](Ctx *c, hipStream_t s) -> int {
+        KeepStats<archon_hip_lz_stats> keep(t_lz_stats, dev);
+        lz_call_stats(&keep.st, n, dir);
+        StageTimer tm(c, 96, s);
+        return lpf_run(c, s, tm, d_sa, d_lcp, n, dir, d_lpf, &keep.st);
+    });
+}
+
+// host buffers: sa, lcp and the records through the context's staging buffers
+int archon_hip_lpf(const uint32_t *sa, const uint32_t *lcp, uint32_t n, uint32_t dir, archon_hip_lpf_rec *lpf, int dev)
+{
+    ARCHON_TRY(lpf_check(sa, lcp, lpf, n, dir));
+    return with_ctx(dev, nullptr, [&](Ctx *c, hipStream_t s) -> int {
+        KeepStats<archon_hip_lz_stats> keep(t_lz_stats, dev);
+        lz_call_stats(&keep.st, n, dir);
+        uint32_t *d_sa = nullptr, *d_lcp = nullptr;
+        archon_hip_lpf_rec *d_lpf = nullptr;
+        ARCHON_TRY(ctx_io(c, 0, (size_t)n * 4 + 64, (void **)&d_sa));
+        ARCHON_TRY(ctx_io(c, 1, (size_t)n * 4 + 64, (void **)&d_lcp));
+        ARCHON_TRY(ctx_io(c, 2, (size_t)n * 8 + 64, (void **)&d_lpf));
+        ARCHON_HIP_TRY(hipMemcpyAsync(d_sa, sa, (size_t)n * 4, hipMemcpyHostToDevice, s));
+        ARCHON_HIP_TRY(hipMemcpyAsync(d_lcp, lcp, (size_t)n * 4, hipMemcpyHostToDevice, s));
+        StageTimer tm(c, 96, s);
+        ARCHON_TRY(lpf_run(c, s, tm, d_sa, d_lcp, n, dir, d_lpf, &keep.st));
+        ARCHON_HIP_TRY(hipMemcpyAsync(lpf, d_lpf, (size_t)n * 8, hipMemcpyDeviceToHost, s));
+        ARCHON_SYNC(s);
+        return ARCHON_OK;
+    });
+}
+
+// *total is written whenever it is given: 0 before any refusal (the cap rule's "always written")
+static int parse_check(const void *lpf, uint64_t *total, uint32_t n)
+{
+    if (total) *total = 0;
+    if (!lpf || !total) { set_error("null pointer"); return ARCHON_E_ARG; }
+    return check_n(n);
+}
+
+int archon_hip_lz_parse_dev(const archon_hip_lpf_rec *d_lpf, uint32_t n, archon_hip_phrase *d_out_or_null, uint64_t cap, uint64_t *total, int dev,
+                            void *stream)
+{
+    ARCHON_TRY(parse_check(d_lpf, total, n));
+    return with_ctx(dev, stream, [&](Ctx *c, hipStream_t s) -> int {
+        KeepStats<archon_hip_lz_stats> keep(t_lz_stats, dev);
+        lz_call_stats(&keep.st, n, 0);
+        StageTimer tm(c, 96, s);
+        ParseCall q = {reinterpret_cast<const uint32_t *>(d_lpf), n};
+        return parse_dev(c, s, tm, q, d_out_or_null, cap, total, &keep.st);
+    });
+}
+
+// host buffers: the records through staging buffer 0, the phrases through 2
+int archon_hip_lz_parse(const archon_hip_lpf_rec *lpf, uint32_t n, archon_hip_phrase *out_or_null, uint64_t cap, uint64_t *total, int dev)
+{
+    ARCHON_TRY(parse_check(lpf, total, n));
+    return with_ctx(dev, nullptr, [&](Ctx *c, hipStream_t s) -> int {
+        KeepStats<archon_hip_lz_stats> keep(t_lz_stats, dev);
+        lz_call_stats(&keep.st, n, 0);
+        uint32_t *d_lpf = nullptr;
+        ARCHON_TRY(ctx_io(c, 0, (size_t)n * 8 + 64, (void **)&d_lpf));
+        ARCHON_HIP_TRY(hipMemcpyAsync(d_lpf, lpf, (size_t)n * 8, hipMemcpyHostToDevice, s));
+        StageTimer tm(c, 96, s);
+        ParseCall q = {d_lpf, n};
+        return parse_to_host(c, s, tm, q, out_or_null, cap, total, &keep.st);
+    });
+}
+
+int archon_hip_get_lz_stats(int dev, archon_hip_lz_stats *out)
+{
+    if (!out) { set_error("null pointer"); return ARCHON_E_ARG; }
+    return t_lz_stats.get(dev, out, "LZ call");
+}
+
 // ---- the FM index (fm_host.hiph: the handle and every driver; here the argument checks and the statistics)
 int archon_hip_fm_create(const uint8_t *bwt, uint32_t n, uint32_t base_id, int dev, archon_hip_fm **out)
 {
@@ -2195,6 +2282,35 @@ int archon_hip_block_repeats(archon_hip_block *b, uint32_t kind, uint32_t min_le
         keep.st.ms_lcp = st.ms_total;
         RepCall q = {d_lcp, b->d_bwt, b->n, b->base, kind, min_len, min_occ};
         return rep_to_host(c, s, q, out_or_null, cap, total, &keep.st);
+    });
+}
+
+// the LCP array into staging buffer 1, the LPF records into staging buffer 0, the phrases through 2: neither array visits the
+// host unless the caller asks for it
+int archon_hip_block_lz(archon_hip_block *b, uint32_t dir, archon_hip_lpf_rec *lpf_or_null, archon_hip_phrase *out_or_null, uint64_t cap, uint64_t *total)
+{
+    if (total) *total = 0;          // (written before any refusal, as in parse_check)
+    if (!b || !total) { set_error("null pointer"); return ARCHON_E_ARG; }
+    ARCHON_TRY(lz_check_dir(dir));
+    std::lock_guard<std::mutex> lkb(b->mu);
+    ARCHON_TRY(block_check(b, true));
+    return with_ctx(b->dev, nullptr, [&](Ctx *c, hipStream_t s) -> int {
+        KeepStats<archon_hip_lz_stats> keep(t_lz_stats, b->dev);
+        lz_call_stats(&keep.st, b->n, dir);
+        uint32_t *d_lcp = nullptr;
+        archon_hip_lpf_rec *d_lpf = nullptr;
+        ARCHON_TRY(ctx_io(c, 1, (size_t)b->n * 4 + 64, (void **)&d_lcp));
+        ARCHON_TRY(ctx_io(c, 0, (size_t)b->n * 8 + 64, (void **)&d_lpf));
+        archon_hip_lcp_stats st = {};
+        const int rc = lcp_run(c, s, b->d_x, b->n, b->d_sa, b->d_bwt, d_lcp, &st);
+        t_lcp_stats.keep(b->dev, st);
+        ARCHON_TRY(rc);
+        keep.st.ms_lcp = st.ms_total;
+        StageTimer tm(c, 96, s);
+        ARCHON_TRY(lpf_run(c, s, tm, b->d_sa, d_lcp, b->n, dir, d_lpf, &keep.st));
+        if (lpf_or_null) ARCHON_HIP_TRY(hipMemcpyAsync(lpf_or_null, d_lpf, (size_t)b->n * 8, hipMemcpyDeviceToHost, s));
+        ParseCall q = {reinterpret_cast<const uint32_t *>(d_lpf), b->n};
+        return parse_to_host(c, s, tm, q, out_or_null, cap, total, &keep.st);     // (its count waits for the stream: the records have arrived)
     });
 }
 
@@ -2979,6 +3095,22 @@ int archon_hip_test_route(const char *name, long value)
             return ARCHON_E_ARG;
         }
         g_route.rep_fan = (int)value;
+        return ARCHON_OK;
+    }
+    if (!strcmp(name, "LZ_FAN")) {
+        if (value && (value < 2 || value > 64 || (value & (value - 1)))) {
+            set_error("LZ_FAN=%ld: not a power of two in [2, 64]", value);
+            return ARCHON_E_ARG;
+        }
+        g_route.lz_fan = (int)value;
+        return ARCHON_OK;
+    }
+    if (!strcmp(name, "LZ_TILE")) {
+        if (value && (value < 2 || value > (long)lz::kMaxTile || (value & (value - 1)))) {
+            set_error("LZ_TILE=%ld: not a power of two in [2, %u]", value, lz::kMaxTile);
+            return ARCHON_E_ARG;
+        }
+        g_route.lz_tile = (int)value;
         return ARCHON_OK;
     }
     if (!strcmp(name, "FM_SAMPLE_WALK")) { g_route.fm_sample_walk = value ? 1 : 0; return ARCHON_OK; }

@@ -42,6 +42,7 @@ SYMBOLS = [
     "archon_hip_fm_mirror", "archon_hip_fm_mirror_dev", "archon_hip_block_fm_mirror", "archon_hip_fm_read_mirror", "archon_hip_fm_smems",
     "archon_hip_fm_smems_dev", "archon_hip_fm_locate_mems", "archon_hip_block_fm_locate_mems", "archon_hip_get_fm_mem_stats",
     "archon_hip_repeats", "archon_hip_repeats_dev", "archon_hip_block_repeats", "archon_hip_get_repeat_stats",
+    "archon_hip_lpf", "archon_hip_lpf_dev", "archon_hip_lz_parse", "archon_hip_lz_parse_dev", "archon_hip_block_lz", "archon_hip_get_lz_stats",
 ]
 
 # archon_hip_fm_hit: one distinct string within the distance of a pattern (FmIndex.approx, Block.fm_approx)
@@ -50,6 +51,12 @@ FM_HIT = np.dtype([("lo", "<u4"), ("hi", "<u4"), ("mismatches", "<u4"), ("patter
 FM_MEM = np.dtype([("lo", "<u4"), ("hi", "<u4"), ("start", "<u4"), ("end", "<u4"), ("pattern", "<u4"), ("reserved0", "<u4")])
 # archon_hip_repeat: one repeat of a block (repeats, Block.repeats): rows [lo, hi) of a string of len bytes, its representative row
 REPEAT = np.dtype([("lo", "<u4"), ("hi", "<u4"), ("len", "<u4"), ("row", "<u4")])
+# struct archon_hip_lpf: the longest previous factor that ends at an item and the item where a copy of it ends (lpf, Block.lz)
+LPF = np.dtype([("len", "<u4"), ("src", "<u4")])
+# archon_hip_phrase: one phrase of the parse (lz_parse, Block.lz): it ends at item `end`; len 0 is a literal
+PHRASE = np.dtype([("end", "<u4"), ("len", "<u4"), ("src", "<u4")])
+# one phrase of lz77(): it starts at z[pos] and copies len bytes from z[src] (len 0: the literal z[pos])
+LZ77 = np.dtype([("pos", "<u4"), ("len", "<u4"), ("src", "<u4")])
 
 
 class Stats(ctypes.Structure):
@@ -154,6 +161,20 @@ class RepeatStats(ctypes.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_}
 
 
+class LzStats(ctypes.Structure):
+    """archon_hip_lz_stats: the calling thread's last LZ call on a device"""
+    _fields_ = [
+        ("n", ctypes.c_uint32), ("dir", ctypes.c_uint32), ("fan", ctypes.c_uint32), ("levels", ctypes.c_uint32),
+        ("tile", ctypes.c_uint32), ("parse_levels", ctypes.c_uint32), ("longest", ctypes.c_uint32), ("kernel_launches", ctypes.c_uint32),
+        ("host_syncs", ctypes.c_uint32), ("reserved0", ctypes.c_uint32),
+        ("phrases", ctypes.c_uint64), ("literals", ctypes.c_uint64), ("probes", ctypes.c_uint64), ("hops", ctypes.c_uint64),
+        ("ms_lcp", ctypes.c_float), ("ms_lpf", ctypes.c_float), ("ms_parse", ctypes.c_float), ("ms_emit", ctypes.c_float),
+    ]
+
+    def asdict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
 class ArchonError(RuntimeError):
     def __init__(self, code, msg):
         super().__init__("archon_hip error %d: %s" % (code, msg))
@@ -250,6 +271,12 @@ def load():
         "archon_hip_repeats_dev": [vp, vp, u32, u32, u32, u32, u32, vp, ctypes.c_uint64, vp, i32, vp],
         "archon_hip_block_repeats": [vp, u32, u32, u32, vp, ctypes.c_uint64, vp],
         "archon_hip_get_repeat_stats": [i32, ctypes.POINTER(RepeatStats)],
+        "archon_hip_lpf": [vp, vp, u32, u32, vp, i32],
+        "archon_hip_lpf_dev": [vp, vp, u32, u32, vp, i32, vp],
+        "archon_hip_lz_parse": [vp, u32, vp, ctypes.c_uint64, vp, i32],
+        "archon_hip_lz_parse_dev": [vp, u32, vp, ctypes.c_uint64, vp, i32, vp],
+        "archon_hip_block_lz": [vp, u32, vp, vp, ctypes.c_uint64, vp],
+        "archon_hip_get_lz_stats": [i32, ctypes.POINTER(LzStats)],
     }.items():
         fn = getattr(lib, name)
         fn.argtypes = args
@@ -273,7 +300,7 @@ _routes_seen = None
 _ROUTE_NAMES = ("FORCE_PATH", "SMALL_BLOCK", "PASS_RANGES", "INV_ROWS", "INV_SLAB", "INV_SBITS", "INV_WALK_WGS", "NO_ALIGNED", "NO_CHAINS", "NO_DEEP_HINT",
                 "NO_PACK", "NO_PACK_STREAM", "NO_PAIR_CHAINS", "NO_PERIOD_HINT", "NO_BREAK_ROUND", "NO_PERIOD_PROBE", "NO_PERIOD_STREAM", "NO_PROBE",
                 "NO_RANK_WRITER", "NO_TEXT_ROUNDS", "NO_MID", "NO_SHALLOW", "NO_CLOSED_FORM", "NO_REL_RECORDS", "ALIGNED_MIN", "REL_MIN_SEG", "KEY_BYTES",
-                "LCP_CAP", "LCP_WINDOW", "FM_SUB_ROWS", "FM_SUPER_ROWS", "FM_SAMPLE_WALK", "REP_FAN")
+                "LCP_CAP", "LCP_WINDOW", "FM_SUB_ROWS", "FM_SUPER_ROWS", "FM_SAMPLE_WALK", "REP_FAN", "LZ_FAN", "LZ_TILE")
 
 
 def _sync_routes(L):
@@ -444,6 +471,64 @@ def repeats(lcp, bwt, base_id, kind=1, min_len=1, min_occ=2, count_only=False, d
     fn = lib().archon_hip_repeats
     return _repeats(lambda out, cap, tp: fn(_p(lcp), _p(bwt), bwt.size, int(base_id), int(kind), int(min_len), int(min_occ), out, cap, tp, dev),
                     count_only)
+
+
+def lz_stats(dev=0):
+    """LzStats of the calling thread's last LZ call on dev"""
+    s = LzStats()
+    _check(lib().archon_hip_get_lz_stats(dev, ctypes.byref(s)))
+    return s
+
+
+def lpf(sa, lcp, dir=0, dev=0):
+    """the longest previous factor of every item from the suffix array and its LCP array (include/archon_hip.h: archon_hip_lpf):
+    an LPF array, the record of item s at index s - 1; dir 0 = copies end at earlier items, 1 = at later items"""
+    sa = np.ascontiguousarray(sa, dtype=np.uint32)
+    lcp = np.ascontiguousarray(lcp, dtype=np.uint32)
+    if sa.size != lcp.size:
+        raise ValueError("lpf: sa has %d rows, lcp %d" % (sa.size, lcp.size))
+    out = np.zeros(sa.size, LPF)
+    _check(lib().archon_hip_lpf(_p(sa), _p(lcp), sa.size, int(dir), _p(out), dev))
+    return out
+
+
+def _phrases(call, count_only):
+    """call(out pointer or None, cap, total pointer) -> rc: the count, or the phrases in an array of the size a first call gave"""
+    total = ctypes.c_uint64(0)
+    tp = ctypes.cast(ctypes.byref(total), ctypes.c_void_p)
+    _check(call(None, 0, tp))
+    if count_only:
+        return total.value
+    out = np.zeros(total.value, PHRASE)
+    _check(call(_p(out), out.size, tp))
+    return out[:total.value]
+
+
+def lz_parse(lpf, count_only=False, dev=0):
+    """the parse of an LPF array (archon_hip_lz_parse): a PHRASE array in chain order, the phrase ending at n first; only the len
+    words decide the chain.  count_only: the number of phrases"""
+    lpf = np.ascontiguousarray(lpf, dtype=LPF)
+    fn = lib().archon_hip_lz_parse
+    return _phrases(lambda out, cap, tp: fn(_p(lpf), lpf.size, out, cap, tp, dev), count_only)
+
+
+def lz77(z, dev=0):
+    """the textbook greedy LZ77 parse of z, left to right: an LZ77 array of (pos, len, src) -- the phrase starts at z[pos] and
+    copies len bytes from z[src], src < pos, the two may overlap; len 0 is the literal z[pos].  The reversed text goes through a
+    forward on a Block and Block.lz(dir=1)"""
+    z = np.frombuffer(z, np.uint8) if isinstance(z, (bytes, bytearray)) else np.ascontiguousarray(z, dtype=np.uint8)
+    n = z.size
+    blk = Block(dev)
+    try:
+        blk.forward(z[::-1].copy(), want_sa=True)
+        ph = blk.lz(dir=1)
+    finally:
+        blk.close()
+    out = np.zeros(ph.size, LZ77)
+    out["pos"] = n - ph["end"]
+    out["len"] = ph["len"]
+    out["src"] = np.where(ph["len"] > 0, n - ph["src"], 0)
+    return out
 
 
 def _as_mems(reps):
@@ -821,6 +906,16 @@ class Block:
         """the starts of every repeat's occurrences from the resident SA: a list of uint32 arrays, one per repeat, in row order"""
         return _locate_mems(lib().archon_hip_block_fm_locate_mems, self.h, _as_mems(reps))
 
+    def lz(self, dir=0, want_lpf=False, count_only=False):
+        """the LZ77 parse of the resident block (needs forward(want_sa=True)): its LCP array and its LPF records are made and
+        consumed on the device.  A PHRASE array in chain order (the phrase ending at n first), or the number of phrases with
+        count_only; with want_lpf a pair (the LPF array, that result).  Without count_only the block is parsed twice: once
+        for the count, once with room for the phrases"""
+        fn = lib().archon_hip_block_lz
+        rec = np.zeros(self.n, LPF) if want_lpf else None
+        got = _phrases(lambda out, cap, tp: fn(self.h, int(dir), _p(rec) if rec is not None and out is None else None, out, cap, tp), count_only)
+        return (rec, got) if want_lpf else got
+
     def fm_index(self, rate, mirror=False):
         """a standalone sampled FmIndex of the last forward's BWT (samples from the SA when that forward kept one, else by the
         LF walk); it outlives later forwards and close().  mirror=True: with its mirror, built from the resident block"""
@@ -889,6 +984,24 @@ def repeats_dev(lcp_t, bwt_t, base_id, kind=1, min_len=1, min_occ=2, out_t=None)
     _check(lib().archon_hip_repeats_dev(ctypes.c_void_p(lcp_t.data_ptr()), ctypes.c_void_p(bwt_t.data_ptr()), bwt_t.numel(), int(base_id), int(kind),
                                         int(min_len), int(min_occ), ctypes.c_void_p(out_t.data_ptr()) if out_t is not None else None, cap,
                                         ctypes.cast(ctypes.byref(total), ctypes.c_void_p), dev, _stream_ptr()))
+    return total.value
+
+
+def lpf_dev(sa_t, lcp_t, dir, lpf_t):
+    """torch CUDA tensors: sa and lcp int32[n], lpf an int32 tensor of 2 words per item (8-byte aligned); on the current stream"""
+    dev = sa_t.device.index or 0
+    _check(lib().archon_hip_lpf_dev(ctypes.c_void_p(sa_t.data_ptr()), ctypes.c_void_p(lcp_t.data_ptr()), sa_t.numel(), int(dir),
+                                    ctypes.c_void_p(lpf_t.data_ptr()), dev, _stream_ptr()))
+
+
+def lz_parse_dev(lpf_t, out_t=None):
+    """torch CUDA tensors: lpf an int32 tensor of 2 words per item, out an int32 tensor of 3 words per phrase or None (counting
+    only); on the current stream.  Returns the number of phrases (raises when out_t holds fewer)"""
+    dev = lpf_t.device.index or 0
+    total = ctypes.c_uint64(0)
+    cap = out_t.numel() // 3 if out_t is not None else 0
+    _check(lib().archon_hip_lz_parse_dev(ctypes.c_void_p(lpf_t.data_ptr()), lpf_t.numel() // 2, ctypes.c_void_p(out_t.data_ptr()) if out_t is not None else None,
+                                         cap, ctypes.cast(ctypes.byref(total), ctypes.c_void_p), dev, _stream_ptr()))
     return total.value
 
 

@@ -18,6 +18,7 @@
  *                           with a sampled SA and ISA it locates and extracts without the block's suffix array, and it
  *                           finds patterns with up to K substituted bytes (archon_hip_fm_approx)
  *   archon_hip_repeats*     nothing: the LCP intervals, maximal and supermaximal repeats of a block from its LCP array and BWT
+ *   archon_hip_lpf*, _lz_*  nothing: the longest previous factor of every item and the LZ77 parse, from the SA and LCP array
  *
  * Ordering convention ("a7 order"): item s in 1..N names the
  * reversed prefix x[s-1],x[s-2],...,x[0],INF with INF > 255; sa[0..N) lists the
@@ -617,6 +618,95 @@ typedef struct archon_hip_repeat_stats {
     float reserved1;
 } archon_hip_repeat_stats;
 int  archon_hip_get_repeat_stats(int dev, archon_hip_repeat_stats *out);
+
+/* ---- longest previous factors and the LZ77 parse of a block (no counterpart in the reference) ---------------------------
+ * What a caller computes next from the suffix array and its LCP array: how far back every prefix of the block repeats, and the
+ * greedy parse into phrases that follows from it -- the phrase count z as a measure of repetitiveness, the phrases for relative
+ * compression, LZ-based indexes or the front half of an LZ coder.  Rows, items, sa, lcp and a7 order are those above: row r
+ * holds item sa[r] in 1..n, the key of item s is x[s-1], x[s-2], ..., x[0], INF; lcp[0] is taken as 0 whatever it holds.
+ * Direction: with dir = 0 (earlier) an item t is admissible for s when t < s, with dir = 1 (later) when t > s.
+ * LPF of item s: the largest l such that x[s-l .. s) = x[t-l .. t) for an admissible t.  On the arrays, with r the row of s:
+ *   p = the greatest row < r holding an admissible item, L = min lcp[p+1 .. r], or 0 if there is no such p;
+ *   q = the least row > r holding an admissible item,    R = min lcp[r+1 .. q], or 0 if there is no such q;
+ *   source rule: if L >= R and L > 0 then len = L, src = sa[p]; else if R > 0 then len = R, src = sa[q]; else len = src = 0.
+ * The output is one struct archon_hip_lpf {len, src} per item, stored at index s - 1: text order, not row order.
+ * Parse: start with e = n; while e > 0 emit the phrase {end, len, src} = (e, len(e), src(e)) and set e -= min(max(1, len(e)), e).
+ * A phrase with len 0 is the literal x[e-1]; otherwise x[e-len .. e) = x[src-len .. src).  Output order is chain order, the
+ * phrase ending at n first.  The min with e is a guard, taken although a true LPF never exceeds e: the parse is a rule about
+ * the len words of ANY array, it stays inside the buffers and emits at most n phrases whatever they hold.  With true LPF
+ * records the phrase lengths, a literal read as 1, sum to n.
+ * The two directions: dir 0 parses x itself, every phrase copies from strictly earlier text (overlap allowed), so the parse
+ * decodes left to right.  For a text z pass x = reverse(z) with dir 1: the chain is then the textbook greedy LZ77 of z, left to
+ * right; a phrase (end, len, src) starts at z position n - end and copies from z position n - src.
+ * Examples.  "banana" (sa = 2 4 6 1 3 5, lcp = 0 1 3 0 0 2): dir 0 gives (len, src) for items 1..6 = (0,0) (0,0) (0,0) (1,2)
+ * (2,3) (3,4) and the phrases (6,3,4) (3,0,0) (2,0,0) (1,0,0); dir 1 gives (0,0) (1,4) (2,5) (3,6) (0,0) (0,0) and the phrases
+ * (6,0,0) (5,0,0) (4,3,6) (1,0,0).  "abracadabra" with dir 0 gives the phrases (11,4,4) (7,0,0) (6,1,4) (5,0,0) (4,1,1)
+ * (3,0,0) (2,0,0) (1,0,0).
+ * Cap rule of the parse (that of archon_hip_repeats): *total is a host pointer and always written.  out NULL: counting only,
+ * no emit pass.  cap < *total with out given: ARCHON_E_ARG, *total written, out untouched.  ARCHON_E_ARG for a null sa, lcp or
+ * lpf, n = 0 or dir > 1; n = 1 gives one literal.
+ * Work of the LPF pass: p and q are nearest-smaller-value searches over sa, L and R range minima over lcp.  Two hierarchies
+ * with fan-out F = 16 (level j holds the minimum of each F^j rows of lcp, and the least -- dir 1: the greatest -- item of them;
+ * L = ceil(log_F n) levels) answer both in one walk per side: at most F - 1 node pairs per level on the way up and F on the way
+ * down, so for ANY data
+ *   probes <= 2 (2 F - 1) L n
+ * (a block of one repeated byte has sa descending: with dir 0 every left search runs to row 0).
+ * Work of the parse: tiles of T = 256 items in K levels, T^K >= n.  F_k[e], the first chain node below e's level-k tile, costs
+ * one gather per item and level (k = 1 in LDS, every higher level in T launches); the descent marks the path from n with one
+ * walker per tile and level.  `hops` is the longest walk of each level of the descent, summed -- the dependent steps on the
+ * call's critical path -- and for ANY data
+ *   hops <= ceil(n / T^(K-1)) + (K - 1) T <= K T.
+ * Bad input.  An sa value outside 1..n is never used as an index: ARCHON_E_CORRUPT, the output untouched.  A value that occurs
+ * twice, or an lcp that is not the LCP array of anything, returns ARCHON_OK with unspecified contents; every access stays inside
+ * the buffers.  The parse accepts any len words (above).
+ * Workspace, from the calling thread's context arena: the LPF pass 8 n / (F - 1) bytes (0.54 n); the parse 4 (K - 1) n bytes of
+ * F arrays, n bytes of marks and n / 60 bytes of entry and tile words: 5 n up to 2^16 items, 9 n up to 2^24, 13 n above.  The
+ * host forms stage sa, lcp, the records and the phrases besides. */
+struct archon_hip_lpf {         /* (a tag only: the name is also that of the call below) */
+    uint32_t len;               /* the longest previous factor that ends at the item */
+    uint32_t src;               /* the item where a copy of it ends (0 when len is 0) */
+};
+typedef struct archon_hip_lpf archon_hip_lpf_rec;
+typedef struct archon_hip_phrase {
+    uint32_t end;               /* the item the phrase ends at: it covers x[end - max(1, len) .. end) */
+    uint32_t len, src;          /* the record of that item: len 0 is the literal x[end-1] */
+} archon_hip_phrase;
+/* device sa[n], lcp[n] (any address) and lpf[n] (8-byte aligned); on `stream` (NULL = the context's own), complete on return */
+int  archon_hip_lpf_dev(const uint32_t *d_sa, const uint32_t *d_lcp, uint32_t n, uint32_t dir, archon_hip_lpf_rec *d_lpf, int dev, void *stream);
+/* host sa[n], lcp[n] and lpf[n] */
+int  archon_hip_lpf(const uint32_t *sa, const uint32_t *lcp, uint32_t n, uint32_t dir, archon_hip_lpf_rec *lpf, int dev);
+/* device lpf[n] (any 4-byte aligned address: only the len words decide the chain, len and src of the chain's items are copied)
+ * and out; on `stream`, complete on return */
+int  archon_hip_lz_parse_dev(const archon_hip_lpf_rec *d_lpf, uint32_t n, archon_hip_phrase *d_out_or_null, uint64_t cap, uint64_t *total,
+                             int dev, void *stream);
+/* host lpf[n] and out */
+int  archon_hip_lz_parse(const archon_hip_lpf_rec *lpf, uint32_t n, archon_hip_phrase *out_or_null, uint64_t cap, uint64_t *total, int dev);
+/* the resident block of the handle's last forward: its LCP array is computed on the device (as archon_hip_block_lcp does, and
+ * with the same record in archon_hip_lcp_stats), the LPF pass and the parse run there; neither array visits the host unless
+ * asked for: lpf_or_null (host, n records) is written when the LPF pass succeeded, out_or_null (host) under the cap rule.
+ * 12 n bytes of staging (the LCP array and the records) beside the arena.  ARCHON_E_ARG when that forward kept no suffix array. */
+int  archon_hip_block_lz(archon_hip_block *b, uint32_t dir, archon_hip_lpf_rec *lpf_or_null, archon_hip_phrase *out_or_null, uint64_t cap,
+                         uint64_t *total);
+/* the CALLING THREAD's last LZ call on `dev` (an LPF call leaves the parse's fields 0, a parse call those of the LPF pass); LZ
+ * calls leave every other record alone (archon_hip_block_lz also keeps the LCP record of its LCP step) */
+typedef struct archon_hip_lz_stats {
+    uint32_t n, dir;            /* of the call, as given (dir: 0 for a parse call) */
+    uint32_t fan, levels;       /* F and L of the LPF pass's hierarchies */
+    uint32_t tile, parse_levels;    /* T and K of the parse */
+    uint32_t longest;           /* the largest len among the phrases */
+    uint32_t kernel_launches;   /* launches issued by the call (block form: without those of its LCP step) */
+    uint32_t host_syncs;        /* times the host waited for the stream inside the call (block form: the LCP step's included) */
+    uint32_t reserved0;
+    uint64_t phrases;           /* z: *total */
+    uint64_t literals;          /* phrases with len 0 */
+    uint64_t probes;            /* node pairs the searches of the LPF pass read */
+    uint64_t hops;              /* the longest walk of each level of the descent, summed */
+    float ms_lcp;               /* block form: device time of the LCP step */
+    float ms_lpf;               /* device time of the LPF pass, its hierarchies included */
+    float ms_parse;             /* device time of the F arrays, the descent and the count pass */
+    float ms_emit;              /* device time of the scan and the emit pass */
+} archon_hip_lz_stats;
+int  archon_hip_get_lz_stats(int dev, archon_hip_lz_stats *out);
 
 /* ---- measurement ------------------------------------------------------------- */
 
