@@ -13,7 +13,12 @@
  *   SMALL_BLOCK  bytes / -1   blocks below this size take the byte count + LSB passes instead of the streaming stage (-1: 8 MiB)
  *   ALIGNED_MIN  bytes / -1   blocks from this size on may run pass B in bucket mode (-1: 16 MiB)
  *   REL_MIN_SEG  places / -1  bucket mode moves range-relative records when a bucket's segments average at least this many places (-1: 4096)
- *   INV_SLAB, INV_SBITS, INV_WALK_WGS   inverse: slab bytes per chain, log2 rows per chain head, walk workgroups per CU
+ *   INV_SLAB, INV_SBITS, INV_WALK_WGS   inverse: slab bytes per chain, log2 rows per chain head, walk workgroups per CU.
+ *                                       INV_SBITS is clamped to 3..12 (any value >= 0 counts as set; negative: the product's rule).
+ *                                       INV_SLAB is cut to a multiple of 16 and taken only where it is at least 16 and below the
+ *                                       default of 16 << sbits.  INV_WALK_WGS = 0 means one chain per lane (k_walk_store whatever
+ *                                       the number of chains and INV_ROWS); 1.. = workgroups of 512 lanes per CU of the queue and
+ *                                       rows walks (128-byte rows take at most 2); negative: the product's 3
  *   INV_ROWS                            inverse: 0 = every lane of the walk stores its own 16 bytes, 1 / 2 = slabs written by quads through
  *                                       128- / 64-byte rows of LDS, -1 = the product's rule (rows above 128 MiB)
  *   LCP_CAP      1..4096 / 0  LCP: key bytes a lane of stage A compares before a row goes to the long list (0: 32)

@@ -3,6 +3,7 @@ import numpy as np
 import pytest
 
 import archon_synth as S
+import inv_chain_model as M
 
 pytestmark = pytest.mark.gpu
 
@@ -71,3 +72,88 @@ def test_inverse_unaligned_device_buffers(archon, oracle):
         buf[off_in:off_in + x.size] = torch.from_numpy(B).cuda()
         archon.inverse_dev(buf[off_in:off_in + x.size], base, out[off_out:off_out + x.size])
         assert (out[off_out:off_out + x.size].cpu().numpy() == x).all(), (off_in, off_out)
+
+
+# ---------------------------------------------------------------- the walk at every chain geometry the product uses
+# tests/inv_chain_model.py holds the table of (input, geometry, edges) and the model that says which kernel a case runs
+# and which chain lengths its input holds there; tests/test_inv_chain_model.py proves the edges on the CPU.
+
+@pytest.fixture(scope="module")
+def chain_inputs(oracle):
+    """name -> (x, B, base) of every input of the table, from the oracle, computed once"""
+    out = {}
+    for name in M.INPUTS:
+        x = M.gen_input(name)
+        _, B, base = oracle.forward(x)
+        out[name] = (x, B, base)
+    return out
+
+
+def _run_case(archon, case, x, B, base, monkeypatch):
+    """inverse under the case's routes = x, with the chains of the model and the launches of one closed cut"""
+    for k, v in case.env.items():
+        monkeypatch.setenv(k, v)
+    sbits, _ = M.route_of_env(x.size, case.env)
+    out = archon.inverse(B, base)
+    st = archon.stats()
+    bad = np.flatnonzero(out != x)
+    assert bad.size == 0, (case.id, "first wrong byte at", int(bad[0]), "of", x.size, "wrong bytes:", bad.size)
+    nchains = M.nchains_of(x.size, sbits)
+    assert st["walk_chains"] == nchains, (case.id, st["walk_chains"], nchains)
+    assert st["kernel_launches"] == 3 + 1 + M.rank_rounds(nchains) + 3, (case.id, st["kernel_launches"], nchains)
+
+
+@pytest.mark.parametrize("case", M.cases("geometry"), ids=[c.id for c in M.cases("geometry")])
+def test_inverse_chain_geometries(archon, chain_inputs, case, monkeypatch):
+    """each row of the table: sbits 4..6 on the queue walk, several rows per slab and exactly full slabs on both rows
+    kernels, 64-byte rows where 128 do not divide the slab, 0 / 1 / 2 walk workgroups per CU, few long chains on a small
+    block.  walk_chains shows that INV_SBITS took effect, the launch count that the first cut closed"""
+    _run_case(archon, case, *chain_inputs[case.input], monkeypatch)
+
+
+@pytest.mark.parametrize("case", M.cases("base"), ids=[c.id for c in M.cases("base")])
+def test_inverse_base_edges(archon, chain_inputs, case, monkeypatch):
+    """row `base` on a regular head (the unused slot of the extra chain), base == 0, base == n - 1, the last region's cut row
+    clamped to n - 1, the chain from `base` filling the last slab: on k_walk_store, k_walk_queue and both k_walk_rows"""
+    _run_case(archon, case, *chain_inputs[case.input], monkeypatch)
+
+
+@pytest.mark.parametrize("geometry", ["rows128_s5", "rows64_s4_slab64"])
+def test_inverse_unaligned_under_rows(archon, chain_inputs, geometry, monkeypatch):
+    """the caller's buffers at any byte offset while the slabs are written through LDS rows: the block comes back, and not a
+    byte in front of it or behind it changes"""
+    import torch
+    cs = [c for c in M.cases("unaligned") if c.id.startswith("unaligned_" + geometry)]
+    assert [(c.in_offset, c.out_offset) for c in cs] == list(M.OFFSETS)
+    x, B, base = chain_inputs[cs[0].input]
+    for k, v in cs[0].env.items():
+        monkeypatch.setenv(k, v)
+    n, pad, sentinel = x.size, 64, 0xA5
+    B_t = torch.from_numpy(B).cuda()
+    buf = torch.zeros(n + pad, dtype=torch.uint8, device="cuda")
+    out = torch.empty(n + pad, dtype=torch.uint8, device="cuda")
+    assert out.data_ptr() % 16 == 0 and buf.data_ptr() % 16 == 0          # (the census took the output's alignment from the offset)
+    sbits, _ = M.route_of_env(n, cs[0].env)
+    for c in cs:
+        oi, oo = c.in_offset, c.out_offset
+        buf[oi:oi + n] = B_t
+        out.fill_(sentinel)
+        archon.inverse_dev(buf[oi:oi + n], base, out[oo:oo + n])
+        got = out.cpu().numpy()
+        assert (got[oo:oo + n] == x).all(), c.id
+        assert (got[:oo] == sentinel).all() and (got[oo + n:] == sentinel).all(), c.id
+        assert archon.stats()["walk_chains"] == M.nchains_of(n, sbits), c.id
+
+
+@pytest.mark.parametrize("shape,n", [(s, n) for n in ((4 << 20) + 1, (8 << 20) + 3, (16 << 20) + 5) for s in ("text", "dna")])
+def test_round_trip_product_geometry(archon, shape, n):
+    """forward -> inverse on the GPU with nothing forced: the product's own sbits 4, 5 and 6 (no oracle involved)"""
+    x = S.gen_shape(shape, n)
+    _, bwt, base = archon.forward(x, want_sa=False)
+    out = archon.inverse(bwt, base)
+    st = archon.stats()
+    assert (out == x).all()
+    sbits = M.inv_sbits(n)
+    assert sbits == {4 << 20: 4, 8 << 20: 5, 16 << 20: 6}[n & ~0xFF]
+    assert st["walk_chains"] == M.nchains_of(n, sbits)
+    assert st["kernel_launches"] == M.inverse_launches(st["walk_chains"])

@@ -370,7 +370,10 @@ def _three_row_swaps(B, P, base, rng):
 
 
 INVERSE_ROUTES = [("walk_store", 100003, {}), ("queue_walk", (1 << 20) + 5, {}), ("inv_slab_16", 300001, {"ARCHON_INV_SLAB": "16"}),
-                  ("walk_rows", (128 << 20) + 4099, {})]
+                  ("walk_rows", (128 << 20) + 4099, {}),
+                  ("sbits6_rows128", (1 << 20) + 5, {"ARCHON_INV_SBITS": "6", "ARCHON_INV_ROWS": "1"}),
+                  ("sbits5_rows64_full_slab", (1 << 20) + 5, {"ARCHON_INV_SBITS": "5", "ARCHON_INV_ROWS": "2", "ARCHON_INV_SLAB": "64"}),
+                  ("one_chain_per_lane", (1 << 20) + 5, {"ARCHON_INV_WALK_WGS": "0"})]
 
 
 @pytest.mark.parametrize("route,n,env", INVERSE_ROUTES, ids=[r[0] for r in INVERSE_ROUTES])
