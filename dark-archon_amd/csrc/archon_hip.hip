@@ -16,6 +16,7 @@
 #include "fm_walk.hiph"
 #include "fm_approx.hiph"
 #include "fm_mem.hiph"
+#include "fm_ms.hiph"
 #include "fm_host.hiph"
 #include "repeats.hiph"
 #include "lz.hiph"
@@ -86,6 +87,7 @@ static thread_local LastStats<archon_hip_fm_stats> t_fm_stats;          // FM ca
 static thread_local LastStats<archon_hip_fm_walk_stats> t_fmw_stats;    // sampled-index calls: sample, block_fm_index, locate, extract
 static thread_local LastStats<archon_hip_fm_approx_stats> t_fma_stats;  // approximate calls: approx, locate_hits
 static thread_local LastStats<archon_hip_fm_mem_stats> t_fmm_stats;     // SMEM calls: mirror, smems, locate_mems
+static thread_local LastStats<archon_hip_fm_ms_stats> t_fms_stats;      // matching-statistics calls: attach_lcp, ms
 static thread_local LastStats<archon_hip_repeat_stats> t_rep_stats;     // repeats calls
 static thread_local LastStats<archon_hip_lz_stats> t_lz_stats;          // LZ calls: lpf, lz_parse, block_lz
 
@@ -2117,6 +2119,62 @@ int archon_hip_get_fm_mem_stats(int dev, archon_hip_fm_mem_stats *out)
     return t_fmm_stats.get(dev, out, "SMEM call");
 }
 
+// ---- the attached LCP array and the matching statistics
+int archon_hip_fm_attach_lcp(archon_hip_fm *f, const uint32_t *lcp)
+{
+    if (!f || !lcp) { set_error("null pointer"); return ARCHON_E_ARG; }
+    return with_ctx(f->dev, nullptr, [&](Ctx *c, hipStream_t s) -> int {
+        KeepStats<archon_hip_fm_ms_stats> keep(t_fms_stats, f->dev);
+        fms_call_stats(&keep.st, f, 0);
+        return fms_attach_run(c, s, f, lcp, nullptr, &keep.st);
+    });
+}
+
+int archon_hip_fm_attach_lcp_dev(archon_hip_fm *f, const uint32_t *d_lcp, void *stream)
+{
+    if (!f || !d_lcp) { set_error("null pointer"); return ARCHON_E_ARG; }
+    return with_ctx(f->dev, stream, [&](Ctx *c, hipStream_t s) -> int {
+        KeepStats<archon_hip_fm_ms_stats> keep(t_fms_stats, f->dev);
+        fms_call_stats(&keep.st, f, 0);
+        return fms_attach_run(c, s, f, nullptr, d_lcp, &keep.st);
+    });
+}
+
+int archon_hip_fm_ms(archon_hip_fm *f, const uint8_t *patterns, const uint32_t *offsets, uint32_t k, uint32_t *len, uint32_t *lo_or_null,
+                     uint32_t *hi_or_null)
+{
+    if (!f || !patterns || !offsets || !len) { set_error("null pointer"); return ARCHON_E_ARG; }
+    if (!lo_or_null != !hi_or_null) { set_error("FM ms: lo and hi are both given or both null"); return ARCHON_E_ARG; }
+    ARCHON_TRY(fm_check_offsets(offsets, k));
+    ARCHON_TRY(fms_check_attached(f));
+    if (!k) return ARCHON_OK;
+    return with_ctx(f->dev, nullptr, [&](Ctx *c, hipStream_t s) -> int {
+        KeepStats<archon_hip_fm_ms_stats> keep(t_fms_stats, f->dev);
+        fms_call_stats(&keep.st, f, k);
+        return fms_host(c, s, f, patterns, offsets, k, len, lo_or_null, hi_or_null, &keep.st);
+    });
+}
+
+int archon_hip_fm_ms_dev(archon_hip_fm *f, const uint8_t *d_patterns, const uint32_t *d_offsets, uint32_t k, uint32_t *d_len, uint32_t *d_lo_or_null,
+                         uint32_t *d_hi_or_null, void *stream)
+{
+    if (!f || !d_patterns || !d_offsets || !d_len) { set_error("null pointer"); return ARCHON_E_ARG; }
+    if (!d_lo_or_null != !d_hi_or_null) { set_error("FM ms: lo and hi are both given or both null"); return ARCHON_E_ARG; }
+    ARCHON_TRY(fms_check_attached(f));
+    if (!k) return ARCHON_OK;
+    return with_ctx(f->dev, stream, [&](Ctx *c, hipStream_t s) -> int {
+        KeepStats<archon_hip_fm_ms_stats> keep(t_fms_stats, f->dev);
+        fms_call_stats(&keep.st, f, k);
+        return fms_dev(c, s, f, d_patterns, d_offsets, k, d_len, d_lo_or_null, d_hi_or_null, &keep.st);
+    });
+}
+
+int archon_hip_get_fm_ms_stats(int dev, archon_hip_fm_ms_stats *out)
+{
+    if (!out) { set_error("null pointer"); return ARCHON_E_ARG; }
+    return t_fms_stats.get(dev, out, "matching-statistics call");
+}
+
 // ---- resident blocks ---------------------------------------------------------------------------------------------------
 // What a block-coder object keeps on the device between enCompute, validate and enWrite (bwt/a7/src/main.cpp:39-46): the
 // block, its suffix array and its BWT, in buffers of its own.  The state belongs to the HANDLE -- any number of objects on
@@ -2424,6 +2482,30 @@ int archon_hip_block_fm_mirror(archon_hip_block *b, archon_hip_fm *f)
         KeepStats<archon_hip_fm_mem_stats> keep(t_fmm_stats, b->dev);
         fmm_call_stats(&keep.st, f, f->n, 0, 0);
         return fmm_mirror_run(c, s, f, b->d_x, false, &keep.st);
+    });
+}
+
+// the LCP array into staging buffer 1, as archon_hip_block_lcp makes it, and from there into the handle: it never visits the host
+int archon_hip_block_fm_attach_lcp(archon_hip_block *b, archon_hip_fm *f)
+{
+    if (!b || !f) { set_error("null pointer"); return ARCHON_E_ARG; }
+    std::lock_guard<std::mutex> lkb(b->mu);
+    ARCHON_TRY(block_check(b, true));
+    if (f->dev != b->dev || f->n != b->n || f->base != b->base) {
+        set_error("FM attach lcp: the handle (%u bytes, primary row %u) is not of this block (%u bytes, primary row %u)", f->n, f->base, b->n, b->base);
+        return ARCHON_E_ARG;
+    }
+    return with_ctx(b->dev, nullptr, [&](Ctx *c, hipStream_t s) -> int {
+        KeepStats<archon_hip_fm_ms_stats> keep(t_fms_stats, b->dev);
+        fms_call_stats(&keep.st, f, 0);
+        uint32_t *d_lcp = nullptr;
+        ARCHON_TRY(ctx_io(c, 1, (size_t)b->n * 4 + 64, (void **)&d_lcp));
+        archon_hip_lcp_stats st = {};
+        const int rc = lcp_run(c, s, b->d_x, b->n, b->d_sa, b->d_bwt, d_lcp, &st);
+        t_lcp_stats.keep(b->dev, st);
+        ARCHON_TRY(rc);
+        keep.st.ms_lcp = st.ms_total;
+        return fms_attach_run(c, s, f, nullptr, d_lcp, &keep.st);
     });
 }
 

@@ -41,6 +41,8 @@ SYMBOLS = [
     "archon_hip_block_fm_locate_hits", "archon_hip_get_fm_approx_stats",
     "archon_hip_fm_mirror", "archon_hip_fm_mirror_dev", "archon_hip_block_fm_mirror", "archon_hip_fm_read_mirror", "archon_hip_fm_smems",
     "archon_hip_fm_smems_dev", "archon_hip_fm_locate_mems", "archon_hip_block_fm_locate_mems", "archon_hip_get_fm_mem_stats",
+    "archon_hip_fm_attach_lcp", "archon_hip_fm_attach_lcp_dev", "archon_hip_block_fm_attach_lcp", "archon_hip_fm_ms", "archon_hip_fm_ms_dev",
+    "archon_hip_get_fm_ms_stats",
     "archon_hip_repeats", "archon_hip_repeats_dev", "archon_hip_block_repeats", "archon_hip_get_repeat_stats",
     "archon_hip_lpf", "archon_hip_lpf_dev", "archon_hip_lz_parse", "archon_hip_lz_parse_dev", "archon_hip_block_lz", "archon_hip_get_lz_stats",
 ]
@@ -140,6 +142,19 @@ class FmMemStats(ctypes.Structure):
         ("mems", ctypes.c_uint64), ("occurrences", ctypes.c_uint64), ("lf_steps", ctypes.c_uint64), ("mirror_bytes", ctypes.c_uint64),
         ("kernel_launches", ctypes.c_uint32), ("host_syncs", ctypes.c_uint32), ("ms_mirror", ctypes.c_float), ("ms_count", ctypes.c_float),
         ("ms_emit", ctypes.c_float), ("ms_locate", ctypes.c_float),
+    ]
+
+    def asdict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
+class FmMsStats(ctypes.Structure):
+    """archon_hip_fm_ms_stats: the calling thread's last attach or matching-statistics call (attach_lcp, ms) on a device"""
+    _fields_ = [
+        ("n", ctypes.c_uint32), ("patterns", ctypes.c_uint32), ("fan", ctypes.c_uint32), ("levels", ctypes.c_uint32), ("attached", ctypes.c_uint32),
+        ("pattern_bytes", ctypes.c_uint64), ("steps", ctypes.c_uint64), ("parents", ctypes.c_uint64), ("probes", ctypes.c_uint64),
+        ("matched", ctypes.c_uint64), ("longest", ctypes.c_uint32), ("lcp_bytes", ctypes.c_uint64), ("kernel_launches", ctypes.c_uint32),
+        ("host_syncs", ctypes.c_uint32), ("ms_lcp", ctypes.c_float), ("ms_attach", ctypes.c_float), ("ms_query", ctypes.c_float),
     ]
 
     def asdict(self):
@@ -267,6 +282,12 @@ def load():
         "archon_hip_fm_locate_mems": [vp, vp, ctypes.c_uint64, vp, ctypes.c_uint64, vp],
         "archon_hip_block_fm_locate_mems": [vp, vp, ctypes.c_uint64, vp, ctypes.c_uint64, vp],
         "archon_hip_get_fm_mem_stats": [i32, ctypes.POINTER(FmMemStats)],
+        "archon_hip_fm_attach_lcp": [vp, vp],
+        "archon_hip_fm_attach_lcp_dev": [vp, vp, vp],
+        "archon_hip_block_fm_attach_lcp": [vp, vp],
+        "archon_hip_fm_ms": [vp, vp, vp, u32, vp, vp, vp],
+        "archon_hip_fm_ms_dev": [vp, vp, vp, u32, vp, vp, vp, vp],
+        "archon_hip_get_fm_ms_stats": [i32, ctypes.POINTER(FmMsStats)],
         "archon_hip_repeats": [vp, vp, u32, u32, u32, u32, u32, vp, ctypes.c_uint64, vp, i32],
         "archon_hip_repeats_dev": [vp, vp, u32, u32, u32, u32, u32, vp, ctypes.c_uint64, vp, i32, vp],
         "archon_hip_block_repeats": [vp, u32, u32, u32, vp, ctypes.c_uint64, vp],
@@ -439,6 +460,37 @@ def fm_mem_stats(dev=0):
     s = FmMemStats()
     _check(lib().archon_hip_get_fm_mem_stats(dev, ctypes.byref(s)))
     return s
+
+
+def fm_ms_stats(dev=0):
+    """FmMsStats of the calling thread's last attach or matching-statistics call (attach_lcp, ms) on dev"""
+    s = FmMsStats()
+    _check(lib().archon_hip_get_fm_ms_stats(dev, ctypes.byref(s)))
+    return s
+
+
+def ms_smems(len, lo, hi, offsets, min_len=1):
+    """the super-maximal exact matches that follow from matching statistics (FmIndex.ms): P[e - len .. e) is one exactly when
+    len > 0 and e is the pattern's end or the next record's len is no larger.  An FM_MEM array of those of at least min_len
+    bytes, in the order FmIndex.smems returns.  numpy only"""
+    length = np.ascontiguousarray(len, np.uint32).ravel()
+    lo, hi = np.ascontiguousarray(lo, np.uint32).ravel(), np.ascontiguousarray(hi, np.uint32).ravel()
+    offsets = np.asarray(offsets, np.int64).ravel()
+    o0, o1 = (int(offsets[0]), int(offsets[-1])) if offsets.size else (0, 0)
+    idx = np.arange(o0, o1, dtype=np.int64)
+    pattern = np.searchsorted(offsets, idx, side="right") - 1        # the j with offsets[j] <= i < offsets[j + 1]
+    last = idx + 1 == offsets[pattern + 1]
+    nxt = np.zeros(idx.size, np.uint32)
+    nxt[:-1] = length[o0 + 1:o1]
+    here = length[o0:o1]
+    keep = (here > 0) & (last | (nxt <= here)) & (here >= max(int(min_len), 1))
+    out = np.zeros(int(keep.sum()), FM_MEM)
+    end = (idx - offsets[pattern] + 1)[keep]
+    out["lo"], out["hi"] = lo[o0:o1][keep], hi[o0:o1][keep]
+    out["end"] = end
+    out["start"] = end - here[keep]
+    out["pattern"] = pattern[keep]
+    return out
 
 
 def repeat_stats(dev=0):
@@ -737,6 +789,46 @@ class FmIndex:
                                              ctypes.cast(ctypes.byref(total), ctypes.c_void_p), _stream_ptr()))
         return total.value
 
+    def attach_lcp(self, lcp):
+        """attaches the block's LCP array (uint32[n], host) that ms() needs: copied into the handle, a minimum hierarchy built
+        behind it; replaces an earlier one; returns self"""
+        lcp = np.ascontiguousarray(lcp, dtype=np.uint32).ravel()
+        if lcp.size != self.n:
+            raise ValueError("attach_lcp: the array has %d entries, the index %d" % (lcp.size, self.n))
+        _check(lib().archon_hip_fm_attach_lcp(self.h, _p(lcp)))
+        return self
+
+    def attach_lcp_dev(self, ptr, stream=None):
+        """the same from n words on the device: a raw device pointer (or a torch int32 tensor), on `stream` (a raw HIP stream;
+        None: the current torch stream); returns self"""
+        if hasattr(ptr, "data_ptr"):
+            if ptr.numel() != self.n:
+                raise ValueError("attach_lcp_dev: the array has %d entries, the index %d" % (ptr.numel(), self.n))
+            ptr = ptr.data_ptr()
+        _check(lib().archon_hip_fm_attach_lcp_dev(self.h, ctypes.c_void_p(int(ptr)), _stream_ptr() if stream is None else ctypes.c_void_p(stream)))
+        return self
+
+    def ms(self, patterns, rows=True):
+        """the matching statistics of every pattern: (len, lo, hi, offsets), uint32 arrays with the record of end e of pattern j
+        at offsets[j] + e - 1: the longest piece ending there that occurs in the block, and its rows [lo, hi) (both None with
+        rows=False).  Needs attach_lcp()"""
+        packed, offsets = _pack_patterns(patterns)
+        k = offsets.size - 1
+        total = max(int(offsets[-1]), 1)
+        length = np.zeros(total, np.uint32)
+        lo, hi = (np.zeros(total, np.uint32), np.zeros(total, np.uint32)) if rows else (None, None)
+        _check(lib().archon_hip_fm_ms(self.h, _p(packed), _p(offsets), k, _p(length), _p(lo) if rows else None, _p(hi) if rows else None))
+        t = int(offsets[-1])
+        return length[:t], (lo[:t] if rows else None), (hi[:t] if rows else None), offsets
+
+    def ms_dev(self, patterns_t, offsets_t, len_t, lo_t=None, hi_t=None):
+        """torch tensors on the device: patterns uint8, offsets int32[k + 1], len and (both or neither) lo and hi int32 of
+        offsets[k] words (written); current stream"""
+        _check(lib().archon_hip_fm_ms_dev(self.h, ctypes.c_void_p(patterns_t.data_ptr()), ctypes.c_void_p(offsets_t.data_ptr()),
+                                          offsets_t.numel() - 1, ctypes.c_void_p(len_t.data_ptr()),
+                                          ctypes.c_void_p(lo_t.data_ptr()) if lo_t is not None else None,
+                                          ctypes.c_void_p(hi_t.data_ptr()) if hi_t is not None else None, _stream_ptr()))
+
     def locate_mems(self, mems):
         """the starts of every SMEM's occurrences from the samples (a list of uint32 arrays, one per SMEM, each in row order)"""
         return _locate_mems(lib().archon_hip_fm_locate_mems, self.h, mems)
@@ -916,9 +1008,10 @@ class Block:
         got = _phrases(lambda out, cap, tp: fn(self.h, int(dir), _p(rec) if rec is not None and out is None else None, out, cap, tp), count_only)
         return (rec, got) if want_lpf else got
 
-    def fm_index(self, rate, mirror=False):
+    def fm_index(self, rate, mirror=False, lcp=False):
         """a standalone sampled FmIndex of the last forward's BWT (samples from the SA when that forward kept one, else by the
-        LF walk); it outlives later forwards and close().  mirror=True: with its mirror, built from the resident block"""
+        LF walk); it outlives later forwards and close().  mirror=True: with its mirror, built from the resident block.
+        lcp=True: with the block's LCP array attached (needs forward(want_sa=True)); the array is made on the device"""
         h = ctypes.c_void_p(None)
         _check(lib().archon_hip_block_fm_index(self.h, int(rate), ctypes.byref(h)))
         f = FmIndex(_handle=h)
@@ -926,6 +1019,8 @@ class Block:
         f.dev = self.dev
         if mirror:
             _check(lib().archon_hip_block_fm_mirror(self.h, f.h))
+        if lcp:
+            _check(lib().archon_hip_block_fm_attach_lcp(self.h, f.h))
         return f
 
     def stats(self):

@@ -17,6 +17,9 @@
  *   archon_hip_fm_*         nothing: counting and locating patterns by backward search on the BWT (an FM index), below;
  *                           with a sampled SA and ISA it locates and extracts without the block's suffix array, and it
  *                           finds patterns with up to K substituted bytes (archon_hip_fm_approx)
+ *   archon_hip_fm_smems     nothing: the super-maximal exact matches of patterns, with a mirror index (archon_hip_fm_mirror)
+ *   archon_hip_fm_ms        nothing: the matching statistics of patterns -- for every position the longest piece ending there
+ *                           that occurs, and its rows -- with the block's LCP array beside the index (archon_hip_fm_attach_lcp)
  *   archon_hip_repeats*     nothing: the LCP intervals, maximal and supermaximal repeats of a block from its LCP array and BWT
  *   archon_hip_lpf*, _lz_*  nothing: the longest previous factor of every item and the LZ77 parse, from the SA and LCP array
  *
@@ -542,6 +545,86 @@ typedef struct archon_hip_fm_mem_stats {
     float ms_locate;            /* device time of locate_mems' kernel */
 } archon_hip_fm_mem_stats;
 int  archon_hip_get_fm_mem_stats(int dev, archon_hip_fm_mem_stats *out);
+
+/* ---- matching statistics: the longest occurring piece that ends at every position of a pattern, with the block's LCP array ----
+ * Keys, R, occ', rows and the primary row are those of the search rule above.  lcp is the block's LCP array (archon_hip_lcp);
+ * lcp[0] is read as 0 and lcp[n] as 0.  For a pattern P of length m and every end e in 1 .. m, the record of e is (len, lo, hi):
+ * len is the largest l <= e such that P[e-l .. e) occurs in x, [lo, hi) exactly what archon_hip_fm_count returns for that piece,
+ * and (0, 0, n) when P[e-1] is not in x.
+ * A rank step extends a match to the right, so the pattern is read once, forward; the parent LCP interval shortens the match.
+ * There is no second transform and no mirror.  The search and its work counters are this procedure (Ohlebusch, Gog and Kuegel
+ * 2010), from the state (lo, hi, l) = (0, n, 0):
+ *   for t = 0 .. m-1, c = P[t]:
+ *     loop:
+ *       if l == 0:  [a, b) = [R[c], R[c+1]) (no step);  nonempty: (lo, hi, l) = (a, b, 1), else (0, n, 0);  break
+ *       steps += 1;  [a, b) = the rank step of c on [lo, hi)
+ *       if a < b:   (lo, hi, l) = (a, b, l + 1);  break
+ *       parents += 1
+ *       l' = min(max(lcp[lo], lcp[hi]), l - 1)      (the min changes nothing for a true LCP array: it makes any array terminate)
+ *       if l' == 0: (lo, hi, l) = (0, n, 0)
+ *       else:       lo = the greatest p <= lo with lcp[p] < l';  hi = the least q >= hi with lcp[q] < l', or n;  l = l'
+ *     the record of e = t + 1 is (l, lo, hi)
+ * Every length in (l', l] has the same rows as l, so skipping them loses nothing.  A parent move lowers l by at least 1 and a
+ * byte raises it by at most 1: for ANY data and pattern parents <= m and steps <= 2 m, and both follow from x and P alone.
+ * The SMEMs follow from the records: P[e-len .. e) is an SMEM exactly when len > 0 and (e == m or len(e+1) <= len(e)), its rows
+ * the record's: the set and the order of archon_hip_fm_smems.
+ * Example: "banana" (lcp 0 1 3 0 0 2) and "nanb": the records are (1,4,6) (2,1,3) (3,5,6) (1,3,4).  n is a bucket; a and n are
+ * two steps; b fails on [5, 6) and the state moves to l' = 2, rows [4, 6); b fails again and the state moves to l' = 0; b is then
+ * a bucket: 4 steps and 2 parents.  The SMEMs from the records are (0, 3) and (3, 4), as in the example above.
+ * Each parent move is two nearest-smaller-value searches in a minimum hierarchy over lcp of fan-out F (that of
+ * archon_hip_repeats: 16): at most 2 (2 F - 1) entries of lcp and the hierarchy per level.
+ * Memory: the attached array is one more device allocation of the handle, the n words (4 n + 64 bytes) and the hierarchy's
+ * levels behind them: 4 n + 64 + 4 tree_words bytes, tree_words = the sum over the levels of their entries (about n / (F - 1)):
+ * about 4.27 n at F = 16.  archon_hip_fm_destroy frees it.  Handles without one behave exactly as before and refuse
+ * archon_hip_fm_ms (ARCHON_E_ARG).
+ * Device work: one wave per pattern, every step one rank step of archon_hip_fm_count; a single long pattern runs on one wave.
+ * The worst case is a pattern a a ... a b against a block of one repeated byte a: the last byte takes a parent move per a.
+ * Example: "aaaa" (lcp 0 3 2 1) and "aaaab": the records are (1,0,4) (2,0,3) (3,0,2) (4,0,1) (0,0,4).  The a's are a bucket and 3
+ * steps; b fails at l = 4, 3, 2 and 1 (4 steps, 4 parents) and is then an empty bucket: 7 steps and 4 parents.
+ * A handle serves one thread at a time (as above): an attach frees the handle's earlier array. */
+/* lcp[n] on the host: copied into the handle, the hierarchy built behind it.  Replaces an earlier attachment.  An entry
+ * lcp[i], i >= 1, of n or more (a true one is at most n - 1) is ARCHON_E_CORRUPT and leaves an earlier attachment in place: a
+ * cheap guard, not a proof -- any other wrong array returns ARCHON_OK and gives unspecified records, every access inside the
+ * buffers and every range inside [0, n]. */
+int  archon_hip_fm_attach_lcp(archon_hip_fm *f, const uint32_t *lcp);
+/* the same from a device array; on `stream` (NULL = the context's own), complete on return */
+int  archon_hip_fm_attach_lcp_dev(archon_hip_fm *f, const uint32_t *d_lcp, void *stream);
+/* for a handle made by archon_hip_block_fm_index from this block's last forward, which must have kept its suffix array (else
+ * ARCHON_E_ARG): the LCP array is computed on the device (its record in archon_hip_lcp_stats) and attached from there; it never
+ * visits the host.  A handle of another length or primary row is ARCHON_E_ARG. */
+int  archon_hip_block_fm_attach_lcp(archon_hip_block *b, archon_hip_fm *f);
+/* len, lo, hi: arrays of offsets[k] words; the record of end e of pattern j goes to index offsets[j] + e - 1, nothing else is
+ * written.  lo_or_null and hi_or_null are both given or both NULL (lengths only); one without the other is ARCHON_E_ARG.
+ * Patterns and offsets as for archon_hip_fm_count; k = 0 and m = 0 write nothing; a pattern longer than the block is searched
+ * like any other.  A handle without an attached LCP array is ARCHON_E_ARG. */
+int  archon_hip_fm_ms(archon_hip_fm *f, const uint8_t *patterns, const uint32_t *offsets, uint32_t k, uint32_t *len, uint32_t *lo_or_null,
+                      uint32_t *hi_or_null);
+/* device patterns, offsets and records; on `stream` (NULL = the context's own), complete on return; decreasing offsets are
+ * found on the device (ARCHON_E_ARG, nothing promised about the records) */
+int  archon_hip_fm_ms_dev(archon_hip_fm *f, const uint8_t *d_patterns, const uint32_t *d_offsets, uint32_t k, uint32_t *d_len,
+                          uint32_t *d_lo_or_null, uint32_t *d_hi_or_null, void *stream);
+/* the CALLING THREAD's last attach or matching-statistics call on `dev`; these calls leave every other statistics record alone
+ * (archon_hip_block_fm_attach_lcp keeps the LCP step's record in archon_hip_lcp_stats, as archon_hip_block_repeats does) */
+typedef struct archon_hip_fm_ms_stats {
+    uint32_t n;                 /* block size of the index */
+    uint32_t patterns;          /* k of the call (0 for an attach) */
+    uint32_t fan;               /* F: fan-out of the hierarchy of the handle's attached array (0 without one) */
+    uint32_t levels;            /* its levels above lcp: ceil(log_F n) */
+    uint32_t attached;          /* 1 when the call attached an array */
+    uint64_t pattern_bytes;     /* bytes of the patterns */
+    uint64_t steps;             /* rank steps */
+    uint64_t parents;           /* parent moves */
+    uint64_t probes;            /* entries of lcp and the hierarchy the parent moves read, counted as the kernel reads them */
+    uint64_t matched;           /* the sum of all len */
+    uint32_t longest;           /* the largest len */
+    uint64_t lcp_bytes;         /* device bytes of the attached array and its hierarchy */
+    uint32_t kernel_launches;   /* launches issued by the call (those of the block form's LCP step are in archon_hip_lcp_stats) */
+    uint32_t host_syncs;        /* times the host waited for the stream inside the call */
+    float ms_lcp;               /* block form only: device time of the LCP array */
+    float ms_attach;            /* device time of the guard and the hierarchy (HIP events) */
+    float ms_query;             /* device time of the search */
+} archon_hip_fm_ms_stats;
+int  archon_hip_get_fm_ms_stats(int dev, archon_hip_fm_ms_stats *out);
 
 /* ---- the repeats of a block: LCP intervals, maximal and supermaximal repeats (no counterpart in the reference) -----------
  * What a caller computes next from the suffix array, its LCP array and the BWT: which strings repeat in the block, how often
