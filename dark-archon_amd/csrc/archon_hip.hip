@@ -17,6 +17,7 @@
 #include "fm_approx.hiph"
 #include "fm_mem.hiph"
 #include "fm_ms.hiph"
+#include "fm_text.hiph"
 #include "fm_host.hiph"
 #include "repeats.hiph"
 #include "lz.hiph"
@@ -88,6 +89,7 @@ static thread_local LastStats<archon_hip_fm_walk_stats> t_fmw_stats;    // sampl
 static thread_local LastStats<archon_hip_fm_approx_stats> t_fma_stats;  // approximate calls: approx, locate_hits
 static thread_local LastStats<archon_hip_fm_mem_stats> t_fmm_stats;     // SMEM calls: mirror, smems, locate_mems
 static thread_local LastStats<archon_hip_fm_ms_stats> t_fms_stats;      // matching-statistics calls: attach_lcp, ms
+static thread_local LastStats<archon_hip_fm_text_stats> t_fmt_stats;    // text calls: attach_sa, ms_text, rlz
 static thread_local LastStats<archon_hip_repeat_stats> t_rep_stats;     // repeats calls
 static thread_local LastStats<archon_hip_lz_stats> t_lz_stats;          // LZ calls: lpf, lz_parse, block_lz
 
@@ -2175,6 +2177,94 @@ int archon_hip_get_fm_ms_stats(int dev, archon_hip_fm_ms_stats *out)
     return t_fms_stats.get(dev, out, "matching-statistics call");
 }
 
+// ---- the attached suffix array, the matching statistics of a long text and its relative LZ parse
+int archon_hip_fm_attach_sa(archon_hip_fm *f, const uint32_t *sa)
+{
+    if (!f || !sa) { set_error("null pointer"); return ARCHON_E_ARG; }
+    return with_ctx(f->dev, nullptr, [&](Ctx *c, hipStream_t s) -> int {
+        KeepStats<archon_hip_fm_text_stats> keep(t_fmt_stats, f->dev);
+        fmt_call_stats(&keep.st, f, 0);
+        return fmt_attach_run(c, s, f, sa, nullptr, &keep.st);
+    });
+}
+
+int archon_hip_fm_attach_sa_dev(archon_hip_fm *f, const uint32_t *d_sa, void *stream)
+{
+    if (!f || !d_sa) { set_error("null pointer"); return ARCHON_E_ARG; }
+    return with_ctx(f->dev, stream, [&](Ctx *c, hipStream_t s) -> int {
+        KeepStats<archon_hip_fm_text_stats> keep(t_fmt_stats, f->dev);
+        fmt_call_stats(&keep.st, f, 0);
+        return fmt_attach_run(c, s, f, nullptr, d_sa, &keep.st);
+    });
+}
+
+static int fmt_check(const archon_hip_fm *f, const void *text, const void *len, const void *lo, const void *hi)
+{
+    if (!f || !text || !len) { set_error("null pointer"); return ARCHON_E_ARG; }
+    if (!lo != !hi) { set_error("FM ms text: lo and hi are both given or both null"); return ARCHON_E_ARG; }
+    return fmt_check_attached(f);
+}
+
+int archon_hip_fm_ms_text(archon_hip_fm *f, const uint8_t *text, uint32_t m, uint32_t *len, uint32_t *lo_or_null, uint32_t *hi_or_null)
+{
+    ARCHON_TRY(fmt_check(f, text, len, lo_or_null, hi_or_null));
+    if (!m) return ARCHON_OK;
+    return with_ctx(f->dev, nullptr, [&](Ctx *c, hipStream_t s) -> int {
+        KeepStats<archon_hip_fm_text_stats> keep(t_fmt_stats, f->dev);
+        fmt_call_stats(&keep.st, f, m);
+        return fmt_host(c, s, f, text, m, len, lo_or_null, hi_or_null, &keep.st);
+    });
+}
+
+int archon_hip_fm_ms_text_dev(archon_hip_fm *f, const uint8_t *d_text, uint32_t m, uint32_t *d_len, uint32_t *d_lo_or_null, uint32_t *d_hi_or_null,
+                              void *stream)
+{
+    ARCHON_TRY(fmt_check(f, d_text, d_len, d_lo_or_null, d_hi_or_null));
+    if (!m) return ARCHON_OK;
+    return with_ctx(f->dev, stream, [&](Ctx *c, hipStream_t s) -> int {
+        KeepStats<archon_hip_fm_text_stats> keep(t_fmt_stats, f->dev);
+        fmt_call_stats(&keep.st, f, m);
+        return fmt_dev(c, s, f, d_text, m, d_len, d_lo_or_null, d_hi_or_null, &keep.st);
+    });
+}
+
+// *total is written whenever it is given: 0 before any refusal
+static int rlz_check(const archon_hip_fm *f, const void *text, uint64_t *total)
+{
+    if (total) *total = 0;
+    if (!f || !text || !total) { set_error("null pointer"); return ARCHON_E_ARG; }
+    return fmt_check_attached(f);
+}
+
+int archon_hip_fm_rlz(archon_hip_fm *f, const uint8_t *text, uint32_t m, archon_hip_phrase *out_or_null, uint64_t cap, uint64_t *total)
+{
+    ARCHON_TRY(rlz_check(f, text, total));
+    if (!m) return ARCHON_OK;
+    return with_ctx(f->dev, nullptr, [&](Ctx *c, hipStream_t s) -> int {
+        KeepStats<archon_hip_fm_text_stats> keep(t_fmt_stats, f->dev);
+        fmt_call_stats(&keep.st, f, m);
+        return fmt_rlz(c, s, f, text, nullptr, m, out_or_null, nullptr, cap, total, &keep.st);
+    });
+}
+
+int archon_hip_fm_rlz_dev(archon_hip_fm *f, const uint8_t *d_text, uint32_t m, archon_hip_phrase *d_out_or_null, uint64_t cap, uint64_t *total,
+                          void *stream)
+{
+    ARCHON_TRY(rlz_check(f, d_text, total));
+    if (!m) return ARCHON_OK;
+    return with_ctx(f->dev, stream, [&](Ctx *c, hipStream_t s) -> int {
+        KeepStats<archon_hip_fm_text_stats> keep(t_fmt_stats, f->dev);
+        fmt_call_stats(&keep.st, f, m);
+        return fmt_rlz(c, s, f, nullptr, d_text, m, nullptr, d_out_or_null, cap, total, &keep.st);
+    });
+}
+
+int archon_hip_get_fm_text_stats(int dev, archon_hip_fm_text_stats *out)
+{
+    if (!out) { set_error("null pointer"); return ARCHON_E_ARG; }
+    return t_fmt_stats.get(dev, out, "text call");
+}
+
 // ---- resident blocks ---------------------------------------------------------------------------------------------------
 // What a block-coder object keeps on the device between enCompute, validate and enWrite (bwt/a7/src/main.cpp:39-46): the
 // block, its suffix array and its BWT, in buffers of its own.  The state belongs to the HANDLE -- any number of objects on
@@ -2506,6 +2596,23 @@ int archon_hip_block_fm_attach_lcp(archon_hip_block *b, archon_hip_fm *f)
         ARCHON_TRY(rc);
         keep.st.ms_lcp = st.ms_total;
         return fms_attach_run(c, s, f, nullptr, d_lcp, &keep.st);
+    });
+}
+
+// the resident suffix array into the handle, device to device (the LCP step reads b->d_sa and leaves it as it is)
+int archon_hip_block_fm_attach_sa(archon_hip_block *b, archon_hip_fm *f)
+{
+    if (!b || !f) { set_error("null pointer"); return ARCHON_E_ARG; }
+    std::lock_guard<std::mutex> lkb(b->mu);
+    ARCHON_TRY(block_check(b, true));
+    if (f->dev != b->dev || f->n != b->n || f->base != b->base) {
+        set_error("FM attach sa: the handle (%u bytes, primary row %u) is not of this block (%u bytes, primary row %u)", f->n, f->base, b->n, b->base);
+        return ARCHON_E_ARG;
+    }
+    return with_ctx(b->dev, nullptr, [&](Ctx *c, hipStream_t s) -> int {
+        KeepStats<archon_hip_fm_text_stats> keep(t_fmt_stats, b->dev);
+        fmt_call_stats(&keep.st, f, 0);
+        return fmt_attach_run(c, s, f, nullptr, b->d_sa, &keep.st);
     });
 }
 
@@ -3193,6 +3300,11 @@ int archon_hip_test_route(const char *name, long value)
             return ARCHON_E_ARG;
         }
         g_route.lz_tile = (int)value;
+        return ARCHON_OK;
+    }
+    if (!strcmp(name, "MS_CHUNK")) {
+        if (value < 0 || value > 0xFFFFFFFFl) { set_error("MS_CHUNK=%ld: not a chunk of 1 .. 2^32 - 1 bytes (0: the default)", value); return ARCHON_E_ARG; }
+        g_route.ms_chunk = value;
         return ARCHON_OK;
     }
     if (!strcmp(name, "FM_SAMPLE_WALK")) { g_route.fm_sample_walk = value ? 1 : 0; return ARCHON_OK; }

@@ -43,6 +43,8 @@ SYMBOLS = [
     "archon_hip_fm_smems_dev", "archon_hip_fm_locate_mems", "archon_hip_block_fm_locate_mems", "archon_hip_get_fm_mem_stats",
     "archon_hip_fm_attach_lcp", "archon_hip_fm_attach_lcp_dev", "archon_hip_block_fm_attach_lcp", "archon_hip_fm_ms", "archon_hip_fm_ms_dev",
     "archon_hip_get_fm_ms_stats",
+    "archon_hip_fm_attach_sa", "archon_hip_fm_attach_sa_dev", "archon_hip_block_fm_attach_sa", "archon_hip_fm_ms_text", "archon_hip_fm_ms_text_dev",
+    "archon_hip_fm_rlz", "archon_hip_fm_rlz_dev", "archon_hip_get_fm_text_stats",
     "archon_hip_repeats", "archon_hip_repeats_dev", "archon_hip_block_repeats", "archon_hip_get_repeat_stats",
     "archon_hip_lpf", "archon_hip_lpf_dev", "archon_hip_lz_parse", "archon_hip_lz_parse_dev", "archon_hip_block_lz", "archon_hip_get_lz_stats",
 ]
@@ -155,6 +157,21 @@ class FmMsStats(ctypes.Structure):
         ("pattern_bytes", ctypes.c_uint64), ("steps", ctypes.c_uint64), ("parents", ctypes.c_uint64), ("probes", ctypes.c_uint64),
         ("matched", ctypes.c_uint64), ("longest", ctypes.c_uint32), ("lcp_bytes", ctypes.c_uint64), ("kernel_launches", ctypes.c_uint32),
         ("host_syncs", ctypes.c_uint32), ("ms_lcp", ctypes.c_float), ("ms_attach", ctypes.c_float), ("ms_query", ctypes.c_float),
+    ]
+
+    def asdict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
+class FmTextStats(ctypes.Structure):
+    """archon_hip_fm_text_stats: the calling thread's last attach_sa, ms_text or rlz call on a device"""
+    _fields_ = [
+        ("n", ctypes.c_uint32), ("m", ctypes.c_uint32), ("chunk", ctypes.c_uint32), ("chunks", ctypes.c_uint32), ("fan", ctypes.c_uint32),
+        ("levels", ctypes.c_uint32), ("saturated", ctypes.c_uint64), ("full_chunks", ctypes.c_uint32), ("runs", ctypes.c_uint32),
+        ("longest_run", ctypes.c_uint32), ("sa_probes", ctypes.c_uint64), ("lcp_probes", ctypes.c_uint64), ("matched", ctypes.c_uint64),
+        ("longest", ctypes.c_uint32), ("phrases", ctypes.c_uint64), ("sa_bytes", ctypes.c_uint64), ("kernel_launches", ctypes.c_uint32),
+        ("host_syncs", ctypes.c_uint32), ("ms_walk", ctypes.c_float), ("ms_sweep", ctypes.c_float), ("ms_fix", ctypes.c_float),
+        ("ms_parse", ctypes.c_float),
     ]
 
     def asdict(self):
@@ -288,6 +305,14 @@ def load():
         "archon_hip_fm_ms": [vp, vp, vp, u32, vp, vp, vp],
         "archon_hip_fm_ms_dev": [vp, vp, vp, u32, vp, vp, vp, vp],
         "archon_hip_get_fm_ms_stats": [i32, ctypes.POINTER(FmMsStats)],
+        "archon_hip_fm_attach_sa": [vp, vp],
+        "archon_hip_fm_attach_sa_dev": [vp, vp, vp],
+        "archon_hip_block_fm_attach_sa": [vp, vp],
+        "archon_hip_fm_ms_text": [vp, vp, u32, vp, vp, vp],
+        "archon_hip_fm_ms_text_dev": [vp, vp, u32, vp, vp, vp, vp],
+        "archon_hip_fm_rlz": [vp, vp, u32, vp, ctypes.c_uint64, vp],
+        "archon_hip_fm_rlz_dev": [vp, vp, u32, vp, ctypes.c_uint64, vp, vp],
+        "archon_hip_get_fm_text_stats": [i32, ctypes.POINTER(FmTextStats)],
         "archon_hip_repeats": [vp, vp, u32, u32, u32, u32, u32, vp, ctypes.c_uint64, vp, i32],
         "archon_hip_repeats_dev": [vp, vp, u32, u32, u32, u32, u32, vp, ctypes.c_uint64, vp, i32, vp],
         "archon_hip_block_repeats": [vp, u32, u32, u32, vp, ctypes.c_uint64, vp],
@@ -321,7 +346,7 @@ _routes_seen = None
 _ROUTE_NAMES = ("FORCE_PATH", "SMALL_BLOCK", "PASS_RANGES", "INV_ROWS", "INV_SLAB", "INV_SBITS", "INV_WALK_WGS", "NO_ALIGNED", "NO_CHAINS", "NO_DEEP_HINT",
                 "NO_PACK", "NO_PACK_STREAM", "NO_PAIR_CHAINS", "NO_PERIOD_HINT", "NO_BREAK_ROUND", "NO_PERIOD_PROBE", "NO_PERIOD_STREAM", "NO_PROBE",
                 "NO_RANK_WRITER", "NO_TEXT_ROUNDS", "NO_MID", "NO_SHALLOW", "NO_CLOSED_FORM", "NO_REL_RECORDS", "ALIGNED_MIN", "REL_MIN_SEG", "KEY_BYTES",
-                "LCP_CAP", "LCP_WINDOW", "FM_SUB_ROWS", "FM_SUPER_ROWS", "FM_SAMPLE_WALK", "REP_FAN", "LZ_FAN", "LZ_TILE")
+                "LCP_CAP", "LCP_WINDOW", "FM_SUB_ROWS", "FM_SUPER_ROWS", "FM_SAMPLE_WALK", "REP_FAN", "LZ_FAN", "LZ_TILE", "MS_CHUNK")
 
 
 def _sync_routes(L):
@@ -467,6 +492,36 @@ def fm_ms_stats(dev=0):
     s = FmMsStats()
     _check(lib().archon_hip_get_fm_ms_stats(dev, ctypes.byref(s)))
     return s
+
+
+def fm_text_stats(dev=0):
+    """FmTextStats of the calling thread's last attach_sa, ms_text or rlz call on dev"""
+    s = FmTextStats()
+    _check(lib().archon_hip_get_fm_text_stats(dev, ctypes.byref(s)))
+    return s
+
+
+def rlz_decode(x, phrases, m, literals=None):
+    """the text of m bytes from the block x and the PHRASE array of FmIndex.rlz: a phrase (end, len, src) copies x[src-len .. src)
+    to [end-len .. end).  A literal (len 0) is a byte the block does not hold, and the parse says where it is, not what:
+    `literals` gives those bytes in phrase order (text[end - 1] of every phrase with len 0); a parse with literals and none given
+    raises ValueError.  numpy only"""
+    x = np.frombuffer(x, np.uint8) if isinstance(x, (bytes, bytearray)) else np.ascontiguousarray(x, dtype=np.uint8)
+    phrases = np.ascontiguousarray(phrases, PHRASE)
+    lit = phrases["len"] == 0
+    nlit = int(lit.sum())
+    if nlit:
+        if literals is None:
+            raise ValueError("rlz_decode: %d literals in the parse and no bytes for them" % nlit)
+        literals = np.frombuffer(bytes(literals), np.uint8) if isinstance(literals, (bytes, bytearray)) else np.asarray(literals, np.uint8)
+        if literals.size != nlit:
+            raise ValueError("rlz_decode: %d literals in the parse, %d bytes given" % (nlit, literals.size))
+    out = np.zeros(int(m), np.uint8)
+    if nlit:
+        out[phrases["end"][lit].astype(np.int64) - 1] = literals
+    for end, ln, src in zip(phrases["end"][~lit].tolist(), phrases["len"][~lit].tolist(), phrases["src"][~lit].tolist()):
+        out[end - ln:end] = x[src - ln:src]
+    return out
 
 
 def ms_smems(len, lo, hi, offsets, min_len=1):
@@ -829,6 +884,63 @@ class FmIndex:
                                           ctypes.c_void_p(lo_t.data_ptr()) if lo_t is not None else None,
                                           ctypes.c_void_p(hi_t.data_ptr()) if hi_t is not None else None, _stream_ptr()))
 
+    def attach_sa(self, sa):
+        """attaches the block's suffix array (uint32[n], host, values 1 .. n) that ms_text() and rlz() need beside attach_lcp():
+        copied into the handle with its inverse behind it; replaces an earlier one; returns self"""
+        sa = np.ascontiguousarray(sa, dtype=np.uint32).ravel()
+        if sa.size != self.n:
+            raise ValueError("attach_sa: the array has %d entries, the index %d" % (sa.size, self.n))
+        _check(lib().archon_hip_fm_attach_sa(self.h, _p(sa)))
+        return self
+
+    def attach_sa_dev(self, ptr, stream=None):
+        """the same from n words on the device: a raw device pointer (or a torch int32 tensor), on `stream` (a raw HIP stream;
+        None: the current torch stream); returns self"""
+        if hasattr(ptr, "data_ptr"):
+            if ptr.numel() != self.n:
+                raise ValueError("attach_sa_dev: the array has %d entries, the index %d" % (ptr.numel(), self.n))
+            ptr = ptr.data_ptr()
+        _check(lib().archon_hip_fm_attach_sa_dev(self.h, ctypes.c_void_p(int(ptr)), _stream_ptr() if stream is None else ctypes.c_void_p(stream)))
+        return self
+
+    def ms_text(self, text, rows=True):
+        """the matching statistics of ONE long text, spread over the device: (len, lo, hi), uint32 arrays with the record of end
+        e at e - 1, exactly what ms([text]) gives (lo and hi None with rows=False).  Needs attach_lcp() and attach_sa()"""
+        text = np.frombuffer(bytes(text), np.uint8) if isinstance(text, (bytes, bytearray)) else np.ascontiguousarray(text, dtype=np.uint8).ravel()
+        m = text.size
+        text = np.concatenate([text, np.zeros(1, np.uint8)])
+        length = np.zeros(max(m, 1), np.uint32)
+        lo, hi = (np.zeros(max(m, 1), np.uint32), np.zeros(max(m, 1), np.uint32)) if rows else (None, None)
+        _check(lib().archon_hip_fm_ms_text(self.h, _p(text), m, _p(length), _p(lo) if rows else None, _p(hi) if rows else None))
+        return length[:m], (lo[:m] if rows else None), (hi[:m] if rows else None)
+
+    def ms_text_dev(self, text_t, len_t, lo_t=None, hi_t=None):
+        """torch tensors on the device: text uint8[m], len and (both or neither) lo and hi int32[m] (written); current stream"""
+        _check(lib().archon_hip_fm_ms_text_dev(self.h, ctypes.c_void_p(text_t.data_ptr()), text_t.numel(), ctypes.c_void_p(len_t.data_ptr()),
+                                               ctypes.c_void_p(lo_t.data_ptr()) if lo_t is not None else None,
+                                               ctypes.c_void_p(hi_t.data_ptr()) if hi_t is not None else None, _stream_ptr()))
+
+    def rlz(self, text, count_only=False):
+        """the relative LZ parse of a text against the block, greedy from the right: a PHRASE array in chain order, the phrase
+        ending at m first; (end, len, src) says text[end-len .. end) = x[src-len .. src), len 0 is the literal text[end-1].
+        count_only: the number of phrases.  Without count_only the text is parsed twice: once for the count, once with room for
+        the phrases.  Needs attach_lcp() and attach_sa()"""
+        text = np.frombuffer(bytes(text), np.uint8) if isinstance(text, (bytes, bytearray)) else np.ascontiguousarray(text, dtype=np.uint8).ravel()
+        m = text.size
+        text = np.concatenate([text, np.zeros(1, np.uint8)])
+        fn = lib().archon_hip_fm_rlz
+        return _phrases(lambda out, cap, tp: fn(self.h, _p(text), m, out, cap, tp), count_only)
+
+    def rlz_dev(self, text_t, out_t=None):
+        """torch tensors on the device: text uint8[m], out an int32 tensor of 3 words per phrase or None (counting only); on the
+        current stream.  Returns the number of phrases (raises when out_t holds fewer)"""
+        total = ctypes.c_uint64(0)
+        cap = out_t.numel() // 3 if out_t is not None else 0
+        _check(lib().archon_hip_fm_rlz_dev(self.h, ctypes.c_void_p(text_t.data_ptr()), text_t.numel(),
+                                           ctypes.c_void_p(out_t.data_ptr()) if out_t is not None else None, cap,
+                                           ctypes.cast(ctypes.byref(total), ctypes.c_void_p), _stream_ptr()))
+        return total.value
+
     def locate_mems(self, mems):
         """the starts of every SMEM's occurrences from the samples (a list of uint32 arrays, one per SMEM, each in row order)"""
         return _locate_mems(lib().archon_hip_fm_locate_mems, self.h, mems)
@@ -1008,10 +1120,11 @@ class Block:
         got = _phrases(lambda out, cap, tp: fn(self.h, int(dir), _p(rec) if rec is not None and out is None else None, out, cap, tp), count_only)
         return (rec, got) if want_lpf else got
 
-    def fm_index(self, rate, mirror=False, lcp=False):
+    def fm_index(self, rate, mirror=False, sa=False, lcp=False):
         """a standalone sampled FmIndex of the last forward's BWT (samples from the SA when that forward kept one, else by the
         LF walk); it outlives later forwards and close().  mirror=True: with its mirror, built from the resident block.
-        lcp=True: with the block's LCP array attached (needs forward(want_sa=True)); the array is made on the device"""
+        lcp=True: with the block's LCP array attached (needs forward(want_sa=True)); the array is made on the device.
+        sa=True: with the block's suffix array attached, device to device (needs forward(want_sa=True))"""
         h = ctypes.c_void_p(None)
         _check(lib().archon_hip_block_fm_index(self.h, int(rate), ctypes.byref(h)))
         f = FmIndex(_handle=h)
@@ -1021,6 +1134,8 @@ class Block:
             _check(lib().archon_hip_block_fm_mirror(self.h, f.h))
         if lcp:
             _check(lib().archon_hip_block_fm_attach_lcp(self.h, f.h))
+        if sa:
+            _check(lib().archon_hip_block_fm_attach_sa(self.h, f.h))
         return f
 
     def stats(self):

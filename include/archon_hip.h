@@ -577,7 +577,8 @@ int  archon_hip_get_fm_mem_stats(int dev, archon_hip_fm_mem_stats *out);
  * levels behind them: 4 n + 64 + 4 tree_words bytes, tree_words = the sum over the levels of their entries (about n / (F - 1)):
  * about 4.27 n at F = 16.  archon_hip_fm_destroy frees it.  Handles without one behave exactly as before and refuse
  * archon_hip_fm_ms (ARCHON_E_ARG).
- * Device work: one wave per pattern, every step one rank step of archon_hip_fm_count; a single long pattern runs on one wave.
+ * Device work: one wave per pattern, every step one rank step of archon_hip_fm_count; a single long pattern runs on one wave
+ * (archon_hip_fm_ms_text, further down, spreads one long text over the device).
  * The worst case is a pattern a a ... a b against a block of one repeated byte a: the last byte takes a parent move per a.
  * Example: "aaaa" (lcp 0 3 2 1) and "aaaab": the records are (1,0,4) (2,0,3) (3,0,2) (4,0,1) (0,0,4).  The a's are a bucket and 3
  * steps; b fails at l = 4, 3, 2 and 1 (4 steps, 4 parents) and is then an empty bucket: 7 steps and 4 parents.
@@ -790,6 +791,101 @@ typedef struct archon_hip_lz_stats {
     float ms_emit;              /* device time of the scan and the emit pass */
 } archon_hip_lz_stats;
 int  archon_hip_get_lz_stats(int dev, archon_hip_lz_stats *out);
+
+/* ---- matching statistics of a long text, and its relative LZ parse against the block ------------------------------------------
+ * archon_hip_fm_ms runs one wave per pattern, so one long pattern runs on one wave.  These calls take ONE text P of m bytes --
+ * another version of a file, a read set, the next block of a container -- and spread it over the device.  The result is defined
+ * by the text and the block alone: for every end e in 1 .. m the record (len, lo, hi) is exactly the record archon_hip_fm_ms
+ * defines for P as one pattern (len the largest l <= e with P[e-l .. e) in x, [lo, hi) what archon_hip_fm_count returns for that
+ * piece, (0, 0, n) when P[e-1] is not in x).  No record shows where the text was cut.
+ * Method.  P is cut into chunks of C bytes (1024); chunk c covers the ends in (cC, min(m, (c+1)C)] and s_c = cC.
+ *   walk   the procedure above over the chunks as ceil(m / C) patterns, one wave each.  Chunk c starts from the empty match at
+ *          s_c, so its record at e is that of the longest suffix of P[s_c .. e) in x: its len is min(ms(e), e - s_c).  A record
+ *          is SATURATED when its len == e - s_c; every other record is already exact, and so is all of chunk 0.  Saturation is
+ *          prefix-closed within a chunk.  A chunk is FULL when its last record is saturated.
+ *   sweep  start[c], the exact record at end s_c, for every c >= 1: the walk's record at index s_c - 1 when c = 1 or chunk c - 1
+ *          is not full, else join(start[c-1], C, the rows of chunk c-1's last record).  A run of full chunks is a chain of
+ *          dependent joins: one lane per run, the runs in parallel.
+ *   fix    one lane per end: a saturated record of a chunk c >= 1 becomes join(start[c], e - s_c, its own rows).  It reads
+ *          start[] and its own record only, so no lane waits for another.
+ * The join.  join((L, lo_s, hi_s), y, [lo, hi)) takes the exact state at s and the rows of Y = P[s .. e), |Y| = y, and needs the
+ * suffix array and its inverse beside the LCP array.  For a row r in [lo, hi) let q(r) = isa[sa[r] - y], and q(r) = n when
+ * sa[r] <= y (item 0, whose key is INF alone).  The rows of Y share reverse(Y) and then order by the key of the item before Y, so q
+ * is strictly increasing over them.
+ *   if L == 0: the result is (y, lo, hi)
+ *   a = the first r with q(r) >= lo_s, b = the first r with q(r) >= hi_s (binary searches)
+ *   if a < b:  the result is (y + L, a, b)
+ *   else:      lp = min lcp[q(a-1)+1 .. lo_s] when a > lo, else 0;  ls = min lcp[hi_s .. q(a)] when a < hi, else 0 (lcp[n] is 0)
+ *              l = max(lp, ls);  if l == 0 the result is (y, lo, hi)
+ *              u = the greatest p <= lo_s with lcp[p] < l;  v = the least p >= hi_s with lcp[p] < l, or n   (the parent move above)
+ *              the result is (y + l, the first r with q(r) >= u, the first r with q(r) >= v)
+ * The two range minima use the hierarchy of the attached LCP array: at most 2 (F - 1) entries per level each, and the two
+ * searches at most 2 (2 F - 1) per level as above.
+ * Example: "banana" (sa 2 4 6 1 3 5, isa[1..6] = 3 0 4 1 5 2, lcp 0 1 3 0 0 2), the text "nanan" and C = 2.  The walk gives
+ * (1,4,6) (2,1,3) | (1,4,6) (2,1,3) | (1,4,6): every record saturated, three full chunks.  start[1] = (2,1,3).  start[2] =
+ * join((2,1,3), 2, [1,3)): q = 0 1, a = 2 < b = 3: (4,2,3), "nana".  The fix: e = 3 is join((2,1,3), 1, [4,6)): q = 0 1, a = 5 <
+ * b = 6: (3,5,6); e = 4 is start[2]; e = 5 is join((4,2,3), 1, [4,6)): q = 0 1, a = b = 6; lp = min lcp[2 .. 2] = 3, ls = 0, l = 3;
+ * u = 1, v = 3; the rows with q in [1, 3) are [5, 6): (4,5,6), "anan".  The records are (1,4,6) (2,1,3) (3,5,6) (4,2,3) (4,5,6).
+ * Worst case: a text that occurs entire in the block (the block itself) makes every chunk full: the sweep is one chain of
+ * ceil(m / C) - 2 dependent joins on one lane, and the fix joins every end after the first chunk.
+ * Memory: the suffix array is one more device allocation of the handle, sa[n] and isa[n + 1]: 4 n + 4 (n + 1) bytes.  isa is preset
+ * to n and scattered from sa by one kernel.  archon_hip_fm_destroy frees it; handles without it behave exactly as before.  A call
+ * takes 12 m bytes of records plus the chunks' words from the calling thread's context arena, the host forms the text besides.
+ * A handle serves one thread at a time (as above). */
+/* sa[n] on the host: copied into the handle, isa made behind it.  Replaces an earlier attachment.  A value outside 1 .. n is
+ * ARCHON_E_CORRUPT and leaves an earlier attachment in place.  A value that occurs twice returns ARCHON_OK and gives
+ * unspecified records, every access inside the buffers. */
+int  archon_hip_fm_attach_sa(archon_hip_fm *f, const uint32_t *sa);
+/* the same from a device array; on `stream` (NULL = the context's own), complete on return */
+int  archon_hip_fm_attach_sa_dev(archon_hip_fm *f, const uint32_t *d_sa, void *stream);
+/* device to device from the resident block; preconditions and ARCHON_E_ARG cases are those of archon_hip_block_fm_attach_lcp.
+ * The block's LCP step reads the resident suffix array and leaves it as it is: the two attachments may come in either order. */
+int  archon_hip_block_fm_attach_sa(archon_hip_block *b, archon_hip_fm *f);
+/* host text[m] and len[m], lo[m], hi[m]: the record of end e at index e - 1.  lo_or_null and hi_or_null are both given or both
+ * NULL (lengths only); one without the other is ARCHON_E_ARG.  m = 0 writes nothing; a text longer than the block is searched
+ * like any other.  A handle without an LCP array or without a suffix array is ARCHON_E_ARG.  Four launches and one host wait. */
+int  archon_hip_fm_ms_text(archon_hip_fm *f, const uint8_t *text, uint32_t m, uint32_t *len, uint32_t *lo_or_null, uint32_t *hi_or_null);
+/* device text and records; on `stream` (NULL = the context's own), complete on return: one host wait */
+int  archon_hip_fm_ms_text_dev(archon_hip_fm *f, const uint8_t *d_text, uint32_t m, uint32_t *d_len, uint32_t *d_lo_or_null,
+                               uint32_t *d_hi_or_null, void *stream);
+/* The relative Lempel-Ziv parse of the text against the block.  One kernel turns the records into archon_hip_lpf_rec {len,
+ * src = sa[lo], or 0 when len is 0} and the parse of archon_hip_lz_parse makes the phrases over the m items: a phrase (end, len,
+ * src) says P[end-len .. end) = x[src-len .. src), len 0 is the literal P[end-1].  Output order is chain order from m; the cap
+ * rule is that of archon_hip_lz_parse (*total always written; out NULL: counting only; cap < *total: ARCHON_E_ARG, out untouched).
+ * The parse is greedy from the RIGHT: the longest phrase that ends at m, then the longest that ends where it starts.  Reversing
+ * both texts gives the greedy parse from the left, as the LZ77 parse above does with dir 1.  m = 0 gives *total = 0. */
+int  archon_hip_fm_rlz(archon_hip_fm *f, const uint8_t *text, uint32_t m, archon_hip_phrase *out_or_null, uint64_t cap, uint64_t *total);
+/* device text and phrases; on `stream`, complete on return */
+int  archon_hip_fm_rlz_dev(archon_hip_fm *f, const uint8_t *d_text, uint32_t m, archon_hip_phrase *d_out_or_null, uint64_t cap, uint64_t *total,
+                           void *stream);
+/* the CALLING THREAD's last attach_sa, ms_text or rlz call on `dev`; these calls leave every other statistics record alone
+ * (archon_hip_fm_ms_stats and archon_hip_lz_stats included).  saturated, full_chunks, runs and longest_run follow from x, P and C
+ * alone. */
+typedef struct archon_hip_fm_text_stats {
+    uint32_t n;                 /* block size of the index */
+    uint32_t m;                 /* bytes of the text (0 for an attach) */
+    uint32_t chunk;             /* C */
+    uint32_t chunks;            /* ceil(m / C) */
+    uint32_t fan;               /* F of the hierarchy of the handle's attached LCP array (0 without one) */
+    uint32_t levels;            /* its levels */
+    uint64_t saturated;         /* records the fix rewrote: the saturated records of chunks 1 .. */
+    uint32_t full_chunks;       /* chunks whose last record is saturated */
+    uint32_t runs;              /* runs of full chunks the sweep joined along */
+    uint32_t longest_run;       /* the dependent joins of the sweep's longest chain */
+    uint64_t sa_probes;         /* evaluations of q */
+    uint64_t lcp_probes;        /* entries of lcp and the hierarchy the joins read */
+    uint64_t matched;           /* the sum of all len */
+    uint32_t longest;           /* the largest len */
+    uint64_t phrases;           /* rlz: *total */
+    uint64_t sa_bytes;          /* device bytes of the attached sa and isa */
+    uint32_t kernel_launches;   /* launches issued by the call */
+    uint32_t host_syncs;        /* times the host waited for the stream inside the call */
+    float ms_walk;              /* device time of the offsets and the walk (HIP events) */
+    float ms_sweep;             /* of the sweep */
+    float ms_fix;               /* of the fix */
+    float ms_parse;             /* rlz: of the record kernel and the parse */
+} archon_hip_fm_text_stats;
+int  archon_hip_get_fm_text_stats(int dev, archon_hip_fm_text_stats *out);
 
 /* ---- measurement ------------------------------------------------------------- */
 

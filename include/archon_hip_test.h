@@ -34,6 +34,8 @@
  *   LZ_FAN         2..64 / 0      LZ: fan-out of the two hierarchies of the LPF pass, a power of two (0: 16).  It changes no result
  *   LZ_TILE        2..4096 / 0    LZ: items of a tile of the parse, a power of two (0: 256).  It changes no result: at 2, blocks of
  *                                 seven bytes cross three parse levels
+ *   MS_CHUNK       1.. / 0        text matching statistics: bytes of a chunk of the walk, any C >= 1 (0: 1024).  It changes no
+ *                                 record: at 1 every end after the first is a join
  *   NO_ALIGNED NO_BREAK_ROUND NO_CHAINS NO_DEEP_HINT NO_PACK NO_PACK_STREAM NO_PAIR_CHAINS NO_PERIOD_HINT NO_PERIOD_PROBE
  *   NO_PERIOD_STREAM NO_PROBE NO_RANK_WRITER NO_TEXT_ROUNDS NO_MID NO_SHALLOW NO_CLOSED_FORM NO_REL_RECORDS      nonzero switches the named step off
  * Returns 0, or ARCHON_E_ARG for an unknown name / a value out of range.  Process-wide; not thread-safe against
