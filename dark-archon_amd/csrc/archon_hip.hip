@@ -87,6 +87,7 @@ static thread_local LastStats<archon_hip_lcp_stats> t_lcp_stats;        // LCP c
 static thread_local LastStats<archon_hip_fm_stats> t_fm_stats;          // FM calls: they leave both of the others alone
 static thread_local LastStats<archon_hip_fm_walk_stats> t_fmw_stats;    // sampled-index calls: sample, block_fm_index, locate, extract
 static thread_local LastStats<archon_hip_fm_approx_stats> t_fma_stats;  // approximate calls: approx, locate_hits
+static thread_local LastStats<archon_hip_fm_edit_stats> t_fme_stats;    // edit-distance calls: edit, edit_dev, block_fm_edit
 static thread_local LastStats<archon_hip_fm_mem_stats> t_fmm_stats;     // SMEM calls: mirror, smems, locate_mems
 static thread_local LastStats<archon_hip_fm_ms_stats> t_fms_stats;      // matching-statistics calls: attach_lcp, ms
 static thread_local LastStats<archon_hip_fm_text_stats> t_fmt_stats;    // text calls: attach_sa, ms_text, rlz
@@ -2041,6 +2042,45 @@ int archon_hip_get_fm_approx_stats(int dev, archon_hip_fm_approx_stats *out)
     return t_fma_stats.get(dev, out, "approximate FM call");
 }
 
+// ---- edit-distance search
+int archon_hip_fm_edit(archon_hip_fm *f, const uint8_t *patterns, const uint32_t *offsets, uint32_t k, uint32_t max_errors, uint32_t *nhits,
+                       archon_hip_fm_edit_hit *hits_or_null, uint64_t cap, uint64_t *total)
+{
+    if (!f || !patterns || !offsets || !nhits || !total) { set_error("null pointer"); return ARCHON_E_ARG; }
+    ARCHON_TRY(fme_check_k(max_errors));
+    ARCHON_TRY(fme_check_patterns(offsets, k, max_errors));
+    ARCHON_TRY(fm_check_sampled(f));
+    *total = 0;
+    if (!k) return ARCHON_OK;
+    return with_ctx(f->dev, nullptr, [&](Ctx *c, hipStream_t s) -> int {
+        KeepStats<archon_hip_fm_edit_stats> keep(t_fme_stats, f->dev);
+        fme_call_stats(&keep.st, f->n, k, max_errors);
+        return fme_host(c, s, f, nullptr, nullptr, patterns, offsets, k, max_errors, nhits, hits_or_null, cap, total, &keep.st);
+    });
+}
+
+int archon_hip_fm_edit_dev(archon_hip_fm *f, const uint8_t *d_patterns, const uint32_t *d_offsets, uint32_t k, uint32_t max_errors, uint32_t *d_nhits,
+                           archon_hip_fm_edit_hit *d_hits_or_null, uint64_t cap, uint64_t *total, void *stream)
+{
+    if (!f || !d_patterns || !d_offsets || !d_nhits || !total) { set_error("null pointer"); return ARCHON_E_ARG; }
+    ARCHON_TRY(fme_check_k(max_errors));
+    ARCHON_TRY(fme_check_count(k));
+    ARCHON_TRY(fm_check_sampled(f));
+    *total = 0;
+    if (!k) return ARCHON_OK;
+    return with_ctx(f->dev, stream, [&](Ctx *c, hipStream_t s) -> int {
+        KeepStats<archon_hip_fm_edit_stats> keep(t_fme_stats, f->dev);
+        fme_call_stats(&keep.st, f->n, k, max_errors);
+        return fme_dev(c, s, f, d_patterns, d_offsets, k, max_errors, d_nhits, d_hits_or_null, cap, total, &keep.st);
+    });
+}
+
+int archon_hip_get_fm_edit_stats(int dev, archon_hip_fm_edit_stats *out)
+{
+    if (!out) { set_error("null pointer"); return ARCHON_E_ARG; }
+    return t_fme_stats.get(dev, out, "edit-distance FM call");
+}
+
 // ---- the mirror and the SMEM search
 int archon_hip_fm_mirror(archon_hip_fm *f)
 {
@@ -2556,6 +2596,29 @@ int archon_hip_block_fm_locate_hits(archon_hip_block *b, const uint32_t *offsets
         KeepStats<archon_hip_fm_approx_stats> keep(t_fma_stats, b->dev);
         fma_call_stats(&keep.st, b->n, k, 0);
         return fma_locate(c, s, nullptr, b->d_sa, offsets, k, hits, nhits, pos, cap, total, &keep.st);
+    });
+}
+
+int archon_hip_block_fm_edit(archon_hip_block *b, const uint8_t *patterns, const uint32_t *offsets, uint32_t k, uint32_t max_errors, uint32_t *nhits,
+                             archon_hip_fm_edit_hit *hits_or_null, uint64_t cap, uint64_t *total)
+{
+    if (!b || !patterns || !offsets || !nhits || !total) { set_error("null pointer"); return ARCHON_E_ARG; }
+    ARCHON_TRY(fme_check_k(max_errors));
+    ARCHON_TRY(fme_check_patterns(offsets, k, max_errors));
+    std::lock_guard<std::mutex> lkb(b->mu);
+    ARCHON_TRY(block_check(b, true));
+    *total = 0;
+    if (!k) return ARCHON_OK;
+    return with_ctx(b->dev, nullptr, [&](Ctx *c, hipStream_t s) -> int {
+        KeepStats<archon_hip_fm_edit_stats> keep(t_fme_stats, b->dev);
+        fme_call_stats(&keep.st, b->n, k, max_errors);
+        // a table built here is this call's work: into its own record, while fm_stats stays as it was
+        archon_hip_fm_stats fst = {};
+        ARCHON_TRY(block_fm_table(c, s, b, &fst));
+        keep.st.built = fst.built;
+        keep.st.ms_build = fst.ms_build;
+        keep.st.kernel_launches += fst.kernel_launches;
+        return fme_host(c, s, b->fm, b->d_sa, b->d_x, patterns, offsets, k, max_errors, nhits, hits_or_null, cap, total, &keep.st);
     });
 }
 
@@ -3305,6 +3368,16 @@ int archon_hip_test_route(const char *name, long value)
     if (!strcmp(name, "MS_CHUNK")) {
         if (value < 0 || value > 0xFFFFFFFFl) { set_error("MS_CHUNK=%ld: not a chunk of 1 .. 2^32 - 1 bytes (0: the default)", value); return ARCHON_E_ARG; }
         g_route.ms_chunk = value;
+        return ARCHON_OK;
+    }
+    if (!strcmp(name, "EDIT_TILE")) {
+        if (value < 0 || value > 64) { set_error("EDIT_TILE=%ld: not a tile of 1 .. 64 ends (0: the default)", value); return ARCHON_E_ARG; }
+        g_route.edit_tile = (int)value;
+        return ARCHON_OK;
+    }
+    if (!strcmp(name, "EDIT_BATCH")) {
+        if (value < 0 || value > 0x7FFFFFFFl) { set_error("EDIT_BATCH=%ld: not a batch of 1 .. 2^31 - 1 patterns (0: the budget's own)", value); return ARCHON_E_ARG; }
+        g_route.edit_batch = (int)value;
         return ARCHON_OK;
     }
     if (!strcmp(name, "FM_SAMPLE_WALK")) { g_route.fm_sample_walk = value ? 1 : 0; return ARCHON_OK; }

@@ -39,6 +39,7 @@ SYMBOLS = [
     "archon_hip_fm_extract_dev", "archon_hip_get_fm_walk_stats",
     "archon_hip_fm_approx", "archon_hip_fm_approx_dev", "archon_hip_block_fm_approx", "archon_hip_fm_locate_hits",
     "archon_hip_block_fm_locate_hits", "archon_hip_get_fm_approx_stats",
+    "archon_hip_fm_edit", "archon_hip_fm_edit_dev", "archon_hip_block_fm_edit", "archon_hip_get_fm_edit_stats",
     "archon_hip_fm_mirror", "archon_hip_fm_mirror_dev", "archon_hip_block_fm_mirror", "archon_hip_fm_read_mirror", "archon_hip_fm_smems",
     "archon_hip_fm_smems_dev", "archon_hip_fm_locate_mems", "archon_hip_block_fm_locate_mems", "archon_hip_get_fm_mem_stats",
     "archon_hip_fm_attach_lcp", "archon_hip_fm_attach_lcp_dev", "archon_hip_block_fm_attach_lcp", "archon_hip_fm_ms", "archon_hip_fm_ms_dev",
@@ -51,6 +52,8 @@ SYMBOLS = [
 
 # archon_hip_fm_hit: one distinct string within the distance of a pattern (FmIndex.approx, Block.fm_approx)
 FM_HIT = np.dtype([("lo", "<u4"), ("hi", "<u4"), ("mismatches", "<u4"), ("pattern", "<u4")])
+# archon_hip_fm_edit_hit: one match of a pattern within the edit distance (FmIndex.edit, Block.fm_edit): x[start .. end)
+FM_EDIT = np.dtype([("start", "<u4"), ("end", "<u4"), ("distance", "<u4"), ("pattern", "<u4")])
 # archon_hip_fm_mem: one super-maximal exact match of a pattern (FmIndex.smems): rows [lo, hi) of the piece [start, end)
 FM_MEM = np.dtype([("lo", "<u4"), ("hi", "<u4"), ("start", "<u4"), ("end", "<u4"), ("pattern", "<u4"), ("reserved0", "<u4")])
 # archon_hip_repeat: one repeat of a block (repeats, Block.repeats): rows [lo, hi) of a string of len bytes, its representative row
@@ -130,6 +133,21 @@ class FmApproxStats(ctypes.Structure):
         ("pattern_bytes", ctypes.c_uint64), ("expansions", ctypes.c_uint64), ("steps", ctypes.c_uint64), ("hits", ctypes.c_uint64),
         ("occurrences", ctypes.c_uint64), ("lf_steps", ctypes.c_uint64), ("kernel_launches", ctypes.c_uint32), ("host_syncs", ctypes.c_uint32),
         ("ms_build", ctypes.c_float), ("ms_count", ctypes.c_float), ("ms_emit", ctypes.c_float), ("ms_locate", ctypes.c_float),
+    ]
+
+    def asdict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
+class FmEditStats(ctypes.Structure):
+    """archon_hip_fm_edit_stats: the calling thread's last edit-distance call (edit, edit_dev, fm_edit) on a device"""
+    _fields_ = [
+        ("n", ctypes.c_uint32), ("patterns", ctypes.c_uint32), ("max_errors", ctypes.c_uint32), ("tile", ctypes.c_uint32),
+        ("batches", ctypes.c_uint32), ("built", ctypes.c_uint32),
+        ("pattern_bytes", ctypes.c_uint64), ("seed_rows", ctypes.c_uint64), ("tiles", ctypes.c_uint64), ("rows", ctypes.c_uint64),
+        ("hits", ctypes.c_uint64), ("lf_steps", ctypes.c_uint64), ("kernel_launches", ctypes.c_uint32), ("host_syncs", ctypes.c_uint32),
+        ("ms_build", ctypes.c_float), ("ms_seed", ctypes.c_float), ("ms_extract", ctypes.c_float), ("ms_count", ctypes.c_float),
+        ("ms_emit", ctypes.c_float),
     ]
 
     def asdict(self):
@@ -290,6 +308,10 @@ def load():
         "archon_hip_fm_locate_hits": [vp, vp, u32, vp, ctypes.c_uint64, vp, ctypes.c_uint64, vp],
         "archon_hip_block_fm_locate_hits": [vp, vp, u32, vp, ctypes.c_uint64, vp, ctypes.c_uint64, vp],
         "archon_hip_get_fm_approx_stats": [i32, ctypes.POINTER(FmApproxStats)],
+        "archon_hip_fm_edit": [vp, vp, vp, u32, u32, vp, vp, ctypes.c_uint64, vp],
+        "archon_hip_fm_edit_dev": [vp, vp, vp, u32, u32, vp, vp, ctypes.c_uint64, vp, vp],
+        "archon_hip_block_fm_edit": [vp, vp, vp, u32, u32, vp, vp, ctypes.c_uint64, vp],
+        "archon_hip_get_fm_edit_stats": [i32, ctypes.POINTER(FmEditStats)],
         "archon_hip_fm_mirror": [vp],
         "archon_hip_fm_mirror_dev": [vp, vp, vp],
         "archon_hip_block_fm_mirror": [vp, vp],
@@ -346,7 +368,8 @@ _routes_seen = None
 _ROUTE_NAMES = ("FORCE_PATH", "SMALL_BLOCK", "PASS_RANGES", "INV_ROWS", "INV_SLAB", "INV_SBITS", "INV_WALK_WGS", "NO_ALIGNED", "NO_CHAINS", "NO_DEEP_HINT",
                 "NO_PACK", "NO_PACK_STREAM", "NO_PAIR_CHAINS", "NO_PERIOD_HINT", "NO_BREAK_ROUND", "NO_PERIOD_PROBE", "NO_PERIOD_STREAM", "NO_PROBE",
                 "NO_RANK_WRITER", "NO_TEXT_ROUNDS", "NO_MID", "NO_SHALLOW", "NO_CLOSED_FORM", "NO_REL_RECORDS", "ALIGNED_MIN", "REL_MIN_SEG", "KEY_BYTES",
-                "LCP_CAP", "LCP_WINDOW", "FM_SUB_ROWS", "FM_SUPER_ROWS", "FM_SAMPLE_WALK", "REP_FAN", "LZ_FAN", "LZ_TILE", "MS_CHUNK")
+                "LCP_CAP", "LCP_WINDOW", "FM_SUB_ROWS", "FM_SUPER_ROWS", "FM_SAMPLE_WALK", "REP_FAN", "LZ_FAN", "LZ_TILE", "MS_CHUNK",
+                "EDIT_TILE", "EDIT_BATCH")
 
 
 def _sync_routes(L):
@@ -477,6 +500,13 @@ def fm_approx_stats(dev=0):
     """FmApproxStats of the calling thread's last approximate call (approx, locate_hits) on dev"""
     s = FmApproxStats()
     _check(lib().archon_hip_get_fm_approx_stats(dev, ctypes.byref(s)))
+    return s
+
+
+def fm_edit_stats(dev=0):
+    """FmEditStats of the calling thread's last edit-distance call (edit, edit_dev, fm_edit) on dev"""
+    s = FmEditStats()
+    _check(lib().archon_hip_get_fm_edit_stats(dev, ctypes.byref(s)))
     return s
 
 
@@ -677,6 +707,25 @@ def _approx(fn, h, patterns, k, hits):
     return nhits, nocc, out[:total.value]
 
 
+def _edit(fn, h, patterns, k, emit):
+    """(nhits, hits or None) of an edit-distance call: the hits into an array of a first guess, then of the size the call gave"""
+    packed, offsets = _pack_patterns(patterns)
+    npat = offsets.size - 1
+    nhits = np.zeros(npat, np.uint32)
+    total = ctypes.c_uint64(0)
+    tp = ctypes.cast(ctypes.byref(total), ctypes.c_void_p)
+    if not emit:
+        _check(fn(h, _p(packed), _p(offsets), npat, int(k), _p(nhits), None, 0, tp))
+        return nhits, None
+    out = np.zeros(max(8 * npat, 1), FM_EDIT)
+    rc = fn(h, _p(packed), _p(offsets), npat, int(k), _p(nhits), _p(out), out.size, tp)
+    if rc == E_ARG and total.value > out.size:
+        out = np.zeros(total.value, FM_EDIT)
+        rc = fn(h, _p(packed), _p(offsets), npat, int(k), _p(nhits), _p(out), out.size, tp)
+    _check(rc)
+    return nhits, out[:total.value]
+
+
 def _locate_hits(fn, h, patterns, hits):
     """the starts of every hit's occurrences: a list of uint32 arrays, one per hit, each in row order"""
     _, offsets = _pack_patterns(patterns)
@@ -786,6 +835,21 @@ class FmIndex:
     def locate_hits(self, patterns, hits):
         """the starts of every hit's occurrences from the samples (a list of uint32 arrays, one per hit, in the shape of locate)"""
         return _locate_hits(lib().archon_hip_fm_locate_hits, self.h, patterns, hits)
+
+    def edit(self, patterns, k, emit=True):
+        """every end in the block where a pattern matches with at most k substituted, inserted or deleted bytes: (nhits, hits),
+        hits an FM_EDIT array, pattern by pattern and by ascending end (None with emit=False: counting only); needs samples"""
+        return _edit(lib().archon_hip_fm_edit, self.h, patterns, k, emit)
+
+    def edit_dev(self, patterns_t, offsets_t, k, nhits_t, hits_t=None):
+        """torch tensors on the device: patterns uint8, offsets int32[n + 1], nhits int32[n] (written), hits an int32 tensor of
+        4 words per hit or None; current stream.  Returns the number of hits"""
+        total = ctypes.c_uint64(0)
+        cap = hits_t.numel() // 4 if hits_t is not None else 0
+        _check(lib().archon_hip_fm_edit_dev(self.h, ctypes.c_void_p(patterns_t.data_ptr()), ctypes.c_void_p(offsets_t.data_ptr()), nhits_t.numel(), int(k),
+                                            ctypes.c_void_p(nhits_t.data_ptr()), ctypes.c_void_p(hits_t.data_ptr()) if hits_t is not None else None, cap,
+                                            ctypes.cast(ctypes.byref(total), ctypes.c_void_p), _stream_ptr()))
+        return total.value
 
     def mirror(self, text=None):
         """builds the mirror (the index of the reversed block) that smems() needs: from the handle's own BWT, or from the
@@ -1091,6 +1155,10 @@ class Block:
     def fm_approx(self, patterns, k, hits=True):
         """FmIndex.approx on the resident block's BWT (its FM index built on the first FM call after a forward)"""
         return _approx(lib().archon_hip_block_fm_approx, self.h, patterns, k, hits)
+
+    def fm_edit(self, patterns, k, emit=True):
+        """FmIndex.edit on the resident block: its text and the suffix array of its last forward (want_sa=True)"""
+        return _edit(lib().archon_hip_block_fm_edit, self.h, patterns, k, emit)
 
     def fm_locate_hits(self, patterns, hits):
         """the starts of every hit's occurrences from the resident SA (needs forward(want_sa=True)): a list of uint32 arrays"""

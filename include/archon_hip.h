@@ -17,6 +17,7 @@
  *   archon_hip_fm_*         nothing: counting and locating patterns by backward search on the BWT (an FM index), below;
  *                           with a sampled SA and ISA it locates and extracts without the block's suffix array, and it
  *                           finds patterns with up to K substituted bytes (archon_hip_fm_approx)
+ *                           and with up to K substituted, inserted or deleted bytes (archon_hip_fm_edit)
  *   archon_hip_fm_smems     nothing: the super-maximal exact matches of patterns, with a mirror index (archon_hip_fm_mirror)
  *   archon_hip_fm_ms        nothing: the matching statistics of patterns -- for every position the longest piece ending there
  *                           that occurs, and its rows -- with the block's LCP array beside the index (archon_hip_fm_attach_lcp)
@@ -446,6 +447,76 @@ typedef struct archon_hip_fm_approx_stats {
     float ms_locate;            /* device time of locate_hits' kernel */
 } archon_hip_fm_approx_stats;
 int  archon_hip_get_fm_approx_stats(int dev, archon_hip_fm_approx_stats *out);
+
+/* ---- edit-distance search: patterns with up to K substituted, inserted or deleted bytes -----------------------------------
+ * x is the block (n bytes), P a pattern of m bytes, K the allowed errors: an error is a substitution, an insertion or a
+ * deletion of one byte, ed the Levenshtein distance.  For an end position e in [0, n] let
+ *   D(e) = min over 0 <= s <= e of ed(P, x[s .. e)).
+ * A MATCH is an e with D(e) <= K; its record is (start, end, distance, pattern), where start is the LARGEST s with
+ * ed(P, x[s .. e)) = D(e): the shortest best occurrence that ends at e.  Matches come pattern by pattern, each pattern's
+ * matches by ascending end.  Ends next to a good end match too, at a higher distance: that is the definition, as Sellers'
+ * algorithm and agrep use it, and a caller who wants one occurrence per place keeps the local minima of the distance.
+ * The same as a recurrence over cells (i, j), 0 <= i <= m, 0 <= j <= n, a cell being a pair (d, s):
+ *   (0, j) = (0, j);  (i, 0) = (i, 0);  otherwise d is the least of diag.d + [P[i-1] != x[j-1]], up.d + 1 and left.d + 1,
+ *   and s the largest s among the candidates that reach it.  The matches are the j with (m, j).d <= K.
+ * Example, x = "banana": "bnan" at K = 1 gives (start 0, end 3, 1) and (2, 5, 1); "nab" at K = 1 gives (2, 4, 1), (2, 5, 1)
+ * and (4, 6, 1).
+ * Limits: 0 <= K <= 8, and every pattern has K < m <= 4096 (at m <= K every position would match; a long text belongs to
+ * archon_hip_fm_ms_text).  A call that breaks one is ARCHON_E_ARG and writes nothing; the device form finds a bad pattern on
+ * the device and emits nothing.  With n < m - K a pattern has no matches and does no work.  k = 0 writes *total = 0 and
+ * nothing else.
+ * The search is a filter with a dense check, and its work counters follow from x, P, K and the tile width W (32) alone:
+ *   pieces    piece i (0 <= i <= K) is P[o_i .. o_{i+1}), o_i = floor(i m / (K + 1)): nonempty, and a pattern with at most K
+ *             errors holds one of them unchanged.  They are searched where they lie in the pattern buffer
+ *   seeds     the rows of piece i are its archon_hip_fm_count range; a row r gives the piece's start p = sa[r] - its length,
+ *             as locate does, and the diagonal g = p - o_i (signed).  seed_rows = the sum of the ranges
+ *   tiles     with u = e - (m - K) for a match end e (0 <= u <= n - m + K), tile t of a pattern owns the ends with
+ *             floor(u / W) = t.  A seed marks the tiles of u in [max(g, 0), min(g + 2K, n - m + K)] (none when that is empty):
+ *             every match lies in a marked tile, and a marked tile reports ALL of its matches however it came to be marked, so
+ *             the output does not depend on the seeds.  tiles = the distinct marked (pattern, tile) pairs, rows = the sum
+ *             over them of m, hits = the matches
+ * Device work: a wave per marked pair, its lanes the W + 2K diagonals around the tile, a loop over the pattern's bytes. */
+typedef struct archon_hip_fm_edit_hit {
+    uint32_t start, end;        /* the occurrence x[start .. end) */
+    uint32_t distance;          /* ed(P, x[start .. end)) = D(end) */
+    uint32_t pattern;           /* j: the pattern it belongs to */
+} archon_hip_fm_edit_hit;
+/* A handle with samples (archon_hip_fm_sample / archon_hip_block_fm_index; else ARCHON_E_ARG): the seeds are located by the
+ * LF walk, the text around the marked tiles is extracted.  nhits[k] and *total (the sum of nhits) always written.
+ * hits_or_null NULL: counting only.  cap < *total with hits given: ARCHON_E_ARG, counts and *total written, hits untouched.
+ * Patterns and offsets as for archon_hip_fm_count.  ARCHON_E_NOMEM names a single pattern whose seeds exceed the scratch of
+ * a batch (256 MiB). */
+int  archon_hip_fm_edit(archon_hip_fm *f, const uint8_t *patterns, const uint32_t *offsets, uint32_t k, uint32_t max_errors, uint32_t *nhits,
+                        archon_hip_fm_edit_hit *hits_or_null, uint64_t cap, uint64_t *total);
+/* device patterns, offsets, nhits and hits, *total a host pointer; on `stream` (NULL = the context's own), complete on return */
+int  archon_hip_fm_edit_dev(archon_hip_fm *f, const uint8_t *d_patterns, const uint32_t *d_offsets, uint32_t k, uint32_t max_errors,
+                            uint32_t *d_nhits, archon_hip_fm_edit_hit *d_hits_or_null, uint64_t cap, uint64_t *total, void *stream);
+/* the resident block: its text and the suffix array of its last forward (ARCHON_E_ARG when that kept none); its table is
+ * built on the first FM call after a forward, as for archon_hip_block_fm_count */
+int  archon_hip_block_fm_edit(archon_hip_block *b, const uint8_t *patterns, const uint32_t *offsets, uint32_t k, uint32_t max_errors,
+                              uint32_t *nhits, archon_hip_fm_edit_hit *hits_or_null, uint64_t cap, uint64_t *total);
+/* the CALLING THREAD's last edit call on `dev`; edit calls leave every other record alone */
+typedef struct archon_hip_fm_edit_stats {
+    uint32_t n;                 /* block size of the index */
+    uint32_t patterns;          /* k of the call */
+    uint32_t max_errors;        /* K */
+    uint32_t tile;              /* W */
+    uint32_t batches;           /* batches of patterns the scratch budget cut the call into */
+    uint32_t built;             /* 1 when the call built the block's table */
+    uint64_t pattern_bytes;     /* bytes of the patterns */
+    uint64_t seed_rows;         /* rows of all pieces */
+    uint64_t tiles;             /* distinct marked (pattern, tile) pairs */
+    uint64_t rows;              /* pattern bytes summed over them */
+    uint64_t hits;              /* matches */
+    uint64_t lf_steps;          /* a handle: LF steps of the seeds' walks and of the extracted text */
+    uint32_t kernel_launches;   /* launches issued by the call */
+    uint32_t host_syncs;        /* times the host waited for the stream inside the call */
+    float ms_build;             /* device time of the table build, 0 without one */
+    float ms_seed;              /* pieces, their count and locate, the marks and the sweep */
+    float ms_extract;           /* a handle: the text of the marked tiles */
+    float ms_count, ms_emit;    /* the count and the emit pass of the banded check (HIP events) */
+} archon_hip_fm_edit_stats;
+int  archon_hip_get_fm_edit_stats(int dev, archon_hip_fm_edit_stats *out);
 
 /* ---- super-maximal exact matches: which pieces of a pattern occur, with a mirror index ------------------------------------
  * Keys, R and occ' are those of the search rule above.  An SMEM of a pattern P of length m is a pair (b, e), 0 <= b < e <= m,

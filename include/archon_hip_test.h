@@ -36,6 +36,10 @@
  *                                 seven bytes cross three parse levels
  *   MS_CHUNK       1.. / 0        text matching statistics: bytes of a chunk of the walk, any C >= 1 (0: 1024).  It changes no
  *                                 record: at 1 every end after the first is a join
+ *   EDIT_TILE      1..64 / 0      edit-distance search: ends a tile owns, W (0: 32).  A call whose K makes W + 2K > 64 is ARCHON_E_ARG.
+ *                                 It changes no match: at 1 every end is a tile of its own
+ *   EDIT_BATCH     1.. / 0        edit-distance search: patterns of a batch at most (0: what the scratch budget holds).  It changes
+ *                                 no match: at 1 every pattern is marked, swept and checked alone
  *   NO_ALIGNED NO_BREAK_ROUND NO_CHAINS NO_DEEP_HINT NO_PACK NO_PACK_STREAM NO_PAIR_CHAINS NO_PERIOD_HINT NO_PERIOD_PROBE
  *   NO_PERIOD_STREAM NO_PROBE NO_RANK_WRITER NO_TEXT_ROUNDS NO_MID NO_SHALLOW NO_CLOSED_FORM NO_REL_RECORDS      nonzero switches the named step off
  * Returns 0, or ARCHON_E_ARG for an unknown name / a value out of range.  Process-wide; not thread-safe against
