@@ -18,6 +18,7 @@
 #include "fm_mem.hiph"
 #include "fm_ms.hiph"
 #include "fm_text.hiph"
+#include "fm_doc.hiph"
 #include "fm_host.hiph"
 #include "repeats.hiph"
 #include "lz.hiph"
@@ -91,6 +92,7 @@ static thread_local LastStats<archon_hip_fm_edit_stats> t_fme_stats;    // edit-
 static thread_local LastStats<archon_hip_fm_mem_stats> t_fmm_stats;     // SMEM calls: mirror, smems, locate_mems
 static thread_local LastStats<archon_hip_fm_ms_stats> t_fms_stats;      // matching-statistics calls: attach_lcp, ms
 static thread_local LastStats<archon_hip_fm_text_stats> t_fmt_stats;    // text calls: attach_sa, ms_text, rlz
+static thread_local LastStats<archon_hip_fm_doc_stats> t_fmd_stats;     // documents calls: attach_docs, docs, docs_ranges, doc_of
 static thread_local LastStats<archon_hip_repeat_stats> t_rep_stats;     // repeats calls
 static thread_local LastStats<archon_hip_lz_stats> t_lz_stats;          // LZ calls: lpf, lz_parse, block_lz
 
@@ -2305,6 +2307,139 @@ int archon_hip_get_fm_text_stats(int dev, archon_hip_fm_text_stats *out)
     return t_fmt_stats.get(dev, out, "text call");
 }
 
+// ---- documents
+// what an attach asks of host bounds before the handle is read, then with it
+static int fmd_attach_check(const archon_hip_fm *f, const uint32_t *bounds, uint32_t ndocs)
+{
+    ARCHON_TRY(fmd_check_bounds(bounds, ndocs));
+    if (!f->tsa) { set_error("FM attach docs: the handle has no suffix array (archon_hip_fm_attach_sa)"); return ARCHON_E_ARG; }
+    return fmd_check_fit(f->n, bounds, ndocs);
+}
+
+int archon_hip_fm_attach_docs(archon_hip_fm *f, const uint32_t *bounds, uint32_t ndocs)
+{
+    if (!f || !bounds) { set_error("null pointer"); return ARCHON_E_ARG; }
+    ARCHON_TRY(fmd_attach_check(f, bounds, ndocs));
+    return with_ctx(f->dev, nullptr, [&](Ctx *c, hipStream_t s) -> int {
+        KeepStats<archon_hip_fm_doc_stats> keep(t_fmd_stats, f->dev);
+        fmd_call_stats(&keep.st, f, 0);
+        return fmd_attach_run(c, s, f, f->tsa, bounds, nullptr, ndocs, &keep.st);
+    });
+}
+
+int archon_hip_fm_attach_docs_dev(archon_hip_fm *f, const uint32_t *d_bounds, uint32_t ndocs, void *stream)
+{
+    if (!f || !d_bounds) { set_error("null pointer"); return ARCHON_E_ARG; }
+    if (!ndocs) { set_error("FM attach docs: no documents"); return ARCHON_E_ARG; }
+    if (!f->tsa) { set_error("FM attach docs: the handle has no suffix array (archon_hip_fm_attach_sa)"); return ARCHON_E_ARG; }
+    ARCHON_TRY(fmd_check_fit(f->n, nullptr, ndocs));
+    return with_ctx(f->dev, stream, [&](Ctx *c, hipStream_t s) -> int {
+        KeepStats<archon_hip_fm_doc_stats> keep(t_fmd_stats, f->dev);
+        fmd_call_stats(&keep.st, f, 0);
+        return fmd_attach_run(c, s, f, f->tsa, nullptr, d_bounds, ndocs, &keep.st);
+    });
+}
+
+// *total is written whenever it is given: 0 before any refusal
+static int fmd_check(const archon_hip_fm *f, const void *a, const void *b, const void *ndocs, uint64_t *total)
+{
+    if (total) *total = 0;
+    if (!f || !a || !b || !ndocs || !total) { set_error("null pointer"); return ARCHON_E_ARG; }
+    return ARCHON_OK;
+}
+
+int archon_hip_fm_docs(archon_hip_fm *f, const uint8_t *patterns, const uint32_t *offsets, uint32_t k, uint32_t *ndocs, archon_hip_fm_doc *docs_or_null,
+                       uint64_t cap, uint64_t *total)
+{
+    ARCHON_TRY(fmd_check(f, patterns, offsets, ndocs, total));
+    ARCHON_TRY(fm_check_offsets(offsets, k));
+    ARCHON_TRY(fmd_check_attached(f));
+    if (!k) return ARCHON_OK;
+    return with_ctx(f->dev, nullptr, [&](Ctx *c, hipStream_t s) -> int {
+        KeepStats<archon_hip_fm_doc_stats> keep(t_fmd_stats, f->dev);
+        fmd_call_stats(&keep.st, f, k);
+        return fmd_host(c, s, f, patterns, offsets, k, ndocs, docs_or_null, cap, total, &keep.st);
+    });
+}
+
+int archon_hip_fm_docs_dev(archon_hip_fm *f, const uint8_t *d_patterns, const uint32_t *d_offsets, uint32_t k, uint32_t *d_ndocs,
+                           archon_hip_fm_doc *d_docs_or_null, uint64_t cap, uint64_t *total, void *stream)
+{
+    ARCHON_TRY(fmd_check(f, d_patterns, d_offsets, d_ndocs, total));
+    ARCHON_TRY(fmd_check_attached(f));
+    if (!k) return ARCHON_OK;
+    return with_ctx(f->dev, stream, [&](Ctx *c, hipStream_t s) -> int {
+        KeepStats<archon_hip_fm_doc_stats> keep(t_fmd_stats, f->dev);
+        fmd_call_stats(&keep.st, f, k);
+        return fmd_dev(c, s, f, d_patterns, d_offsets, k, d_ndocs, d_docs_or_null, cap, total, &keep.st);
+    });
+}
+
+int archon_hip_fm_docs_ranges(archon_hip_fm *f, const uint32_t *lo, const uint32_t *hi, uint32_t k, uint32_t *ndocs, archon_hip_fm_doc *docs_or_null,
+                              uint64_t cap, uint64_t *total)
+{
+    ARCHON_TRY(fmd_check(f, lo, hi, ndocs, total));
+    ARCHON_TRY(fmd_check_attached(f));
+    for (uint32_t j = 0; j < k; ++j)
+        if (lo[j] > hi[j] || hi[j] > f->n) { set_error("FM docs: range %u, rows [%u, %u), is not lo <= hi <= %u", j, lo[j], hi[j], f->n); return ARCHON_E_ARG; }
+    if (!k) return ARCHON_OK;
+    return with_ctx(f->dev, nullptr, [&](Ctx *c, hipStream_t s) -> int {
+        KeepStats<archon_hip_fm_doc_stats> keep(t_fmd_stats, f->dev);
+        fmd_call_stats(&keep.st, f, k);
+        return fmd_ranges_host<true>(c, s, f, lo, hi, k, ndocs, docs_or_null, cap, total, &keep.st);
+    });
+}
+
+int archon_hip_fm_docs_ranges_dev(archon_hip_fm *f, const uint32_t *d_lo, const uint32_t *d_hi, uint32_t k, uint32_t *d_ndocs,
+                                  archon_hip_fm_doc *d_docs_or_null, uint64_t cap, uint64_t *total, void *stream)
+{
+    ARCHON_TRY(fmd_check(f, d_lo, d_hi, d_ndocs, total));
+    ARCHON_TRY(fmd_check_attached(f));
+    if (!k) return ARCHON_OK;
+    return with_ctx(f->dev, stream, [&](Ctx *c, hipStream_t s) -> int {
+        KeepStats<archon_hip_fm_doc_stats> keep(t_fmd_stats, f->dev);
+        fmd_call_stats(&keep.st, f, k);
+        return fmd_ranges_dev(c, s, f, d_lo, d_hi, k, d_ndocs, d_docs_or_null, cap, total, &keep.st);
+    });
+}
+
+static int fmd_doc_of_check(const archon_hip_fm *f, const void *items, uint64_t count, const void *doc)
+{
+    if (!f || (!items && count) || (!doc && count)) { set_error("null pointer"); return ARCHON_E_ARG; }
+    if (count >> 32) { set_error("FM doc of: %llu items in one call", (unsigned long long)count); return ARCHON_E_ARG; }
+    return fmd_check_attached(f);
+}
+
+int archon_hip_fm_doc_of(archon_hip_fm *f, const uint32_t *items, uint64_t count, uint32_t *doc, uint32_t *off_or_null)
+{
+    ARCHON_TRY(fmd_doc_of_check(f, items, count, doc));
+    for (uint64_t i = 0; i < count; ++i)
+        if (items[i] - 1 >= f->n) { set_error("FM doc of: item %llu is %u, outside 1 .. %u", (unsigned long long)i, items[i], f->n); return ARCHON_E_ARG; }
+    if (!count) return ARCHON_OK;
+    return with_ctx(f->dev, nullptr, [&](Ctx *c, hipStream_t s) -> int {
+        KeepStats<archon_hip_fm_doc_stats> keep(t_fmd_stats, f->dev);
+        fmd_call_stats(&keep.st, f, 0);
+        return fmd_doc_of(c, s, f, items, nullptr, count, doc, off_or_null, &keep.st);
+    });
+}
+
+int archon_hip_fm_doc_of_dev(archon_hip_fm *f, const uint32_t *d_items, uint64_t count, uint32_t *d_doc, uint32_t *d_off_or_null, void *stream)
+{
+    ARCHON_TRY(fmd_doc_of_check(f, d_items, count, d_doc));
+    if (!count) return ARCHON_OK;
+    return with_ctx(f->dev, stream, [&](Ctx *c, hipStream_t s) -> int {
+        KeepStats<archon_hip_fm_doc_stats> keep(t_fmd_stats, f->dev);
+        fmd_call_stats(&keep.st, f, 0);
+        return fmd_doc_of(c, s, f, nullptr, d_items, count, d_doc, d_off_or_null, &keep.st);
+    });
+}
+
+int archon_hip_get_fm_doc_stats(int dev, archon_hip_fm_doc_stats *out)
+{
+    if (!out) { set_error("null pointer"); return ARCHON_E_ARG; }
+    return t_fmd_stats.get(dev, out, "documents call");
+}
+
 // ---- resident blocks ---------------------------------------------------------------------------------------------------
 // What a block-coder object keeps on the device between enCompute, validate and enWrite (bwt/a7/src/main.cpp:39-46): the
 // block, its suffix array and its BWT, in buffers of its own.  The state belongs to the HANDLE -- any number of objects on
@@ -2676,6 +2811,25 @@ int archon_hip_block_fm_attach_sa(archon_hip_block *b, archon_hip_fm *f)
         KeepStats<archon_hip_fm_text_stats> keep(t_fmt_stats, b->dev);
         fmt_call_stats(&keep.st, f, 0);
         return fmt_attach_run(c, s, f, nullptr, b->d_sa, &keep.st);
+    });
+}
+
+// the resident suffix array read where it is, device to device: the handle needs no attached suffix array of its own
+int archon_hip_block_fm_attach_docs(archon_hip_block *b, archon_hip_fm *f, const uint32_t *bounds, uint32_t ndocs)
+{
+    if (!b || !f || !bounds) { set_error("null pointer"); return ARCHON_E_ARG; }
+    ARCHON_TRY(fmd_check_bounds(bounds, ndocs));
+    std::lock_guard<std::mutex> lkb(b->mu);
+    ARCHON_TRY(block_check(b, true));
+    if (f->dev != b->dev || f->n != b->n || f->base != b->base) {
+        set_error("FM attach docs: the handle (%u bytes, primary row %u) is not of this block (%u bytes, primary row %u)", f->n, f->base, b->n, b->base);
+        return ARCHON_E_ARG;
+    }
+    ARCHON_TRY(fmd_check_fit(f->n, bounds, ndocs));
+    return with_ctx(b->dev, nullptr, [&](Ctx *c, hipStream_t s) -> int {
+        KeepStats<archon_hip_fm_doc_stats> keep(t_fmd_stats, b->dev);
+        fmd_call_stats(&keep.st, f, 0);
+        return fmd_attach_run(c, s, f, b->d_sa, bounds, nullptr, ndocs, &keep.st);
     });
 }
 
@@ -3378,6 +3532,14 @@ int archon_hip_test_route(const char *name, long value)
     if (!strcmp(name, "EDIT_BATCH")) {
         if (value < 0 || value > 0x7FFFFFFFl) { set_error("EDIT_BATCH=%ld: not a batch of 1 .. 2^31 - 1 patterns (0: the budget's own)", value); return ARCHON_E_ARG; }
         g_route.edit_batch = (int)value;
+        return ARCHON_OK;
+    }
+    if (!strcmp(name, "DOC_TILE")) {
+        if (value && (value < (long)fmd::kMinTile || value > (long)fmd::kMaxTile || value % 64)) {
+            set_error("DOC_TILE=%ld: not a tile of 64 .. 2^20 rows, a multiple of 64 (0: the default)", value);
+            return ARCHON_E_ARG;
+        }
+        g_route.doc_tile = (int)value;
         return ARCHON_OK;
     }
     if (!strcmp(name, "FM_SAMPLE_WALK")) { g_route.fm_sample_walk = value ? 1 : 0; return ARCHON_OK; }

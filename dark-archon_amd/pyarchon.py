@@ -46,6 +46,8 @@ SYMBOLS = [
     "archon_hip_get_fm_ms_stats",
     "archon_hip_fm_attach_sa", "archon_hip_fm_attach_sa_dev", "archon_hip_block_fm_attach_sa", "archon_hip_fm_ms_text", "archon_hip_fm_ms_text_dev",
     "archon_hip_fm_rlz", "archon_hip_fm_rlz_dev", "archon_hip_get_fm_text_stats",
+    "archon_hip_fm_attach_docs", "archon_hip_fm_attach_docs_dev", "archon_hip_block_fm_attach_docs", "archon_hip_fm_docs", "archon_hip_fm_docs_dev",
+    "archon_hip_fm_docs_ranges", "archon_hip_fm_docs_ranges_dev", "archon_hip_fm_doc_of", "archon_hip_fm_doc_of_dev", "archon_hip_get_fm_doc_stats",
     "archon_hip_repeats", "archon_hip_repeats_dev", "archon_hip_block_repeats", "archon_hip_get_repeat_stats",
     "archon_hip_lpf", "archon_hip_lpf_dev", "archon_hip_lz_parse", "archon_hip_lz_parse_dev", "archon_hip_block_lz", "archon_hip_get_lz_stats",
 ]
@@ -56,6 +58,8 @@ FM_HIT = np.dtype([("lo", "<u4"), ("hi", "<u4"), ("mismatches", "<u4"), ("patter
 FM_EDIT = np.dtype([("start", "<u4"), ("end", "<u4"), ("distance", "<u4"), ("pattern", "<u4")])
 # archon_hip_fm_mem: one super-maximal exact match of a pattern (FmIndex.smems): rows [lo, hi) of the piece [start, end)
 FM_MEM = np.dtype([("lo", "<u4"), ("hi", "<u4"), ("start", "<u4"), ("end", "<u4"), ("pattern", "<u4"), ("reserved0", "<u4")])
+# archon_hip_fm_doc: one document of a pattern or a row range (FmIndex.docs, docs_ranges): tf rows of the range lie in it, the first is `row`
+FM_DOC = np.dtype([("doc", "<u4"), ("tf", "<u4"), ("row", "<u4"), ("range", "<u4")])
 # archon_hip_repeat: one repeat of a block (repeats, Block.repeats): rows [lo, hi) of a string of len bytes, its representative row
 REPEAT = np.dtype([("lo", "<u4"), ("hi", "<u4"), ("len", "<u4"), ("row", "<u4")])
 # struct archon_hip_lpf: the longest previous factor that ends at an item and the item where a copy of it ends (lpf, Block.lz)
@@ -190,6 +194,20 @@ class FmTextStats(ctypes.Structure):
         ("longest", ctypes.c_uint32), ("phrases", ctypes.c_uint64), ("sa_bytes", ctypes.c_uint64), ("kernel_launches", ctypes.c_uint32),
         ("host_syncs", ctypes.c_uint32), ("ms_walk", ctypes.c_float), ("ms_sweep", ctypes.c_float), ("ms_fix", ctypes.c_float),
         ("ms_parse", ctypes.c_float),
+    ]
+
+    def asdict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
+class FmDocStats(ctypes.Structure):
+    """archon_hip_fm_doc_stats: the calling thread's last documents call (attach_docs, docs, docs_ranges, doc_of) on a device"""
+    _fields_ = [
+        ("n", ctypes.c_uint32), ("docs", ctypes.c_uint32), ("ranges", ctypes.c_uint32), ("tile", ctypes.c_uint32), ("attached", ctypes.c_uint32),
+        ("sort_passes", ctypes.c_uint32), ("longest_tf", ctypes.c_uint32), ("reserved0", ctypes.c_uint32),
+        ("pattern_bytes", ctypes.c_uint64), ("rows", ctypes.c_uint64), ("tiles", ctypes.c_uint64), ("listed", ctypes.c_uint64),
+        ("probes", ctypes.c_uint64), ("doc_bytes", ctypes.c_uint64), ("kernel_launches", ctypes.c_uint32), ("host_syncs", ctypes.c_uint32),
+        ("ms_attach", ctypes.c_float), ("ms_search", ctypes.c_float), ("ms_count", ctypes.c_float), ("ms_emit", ctypes.c_float),
     ]
 
     def asdict(self):
@@ -335,6 +353,16 @@ def load():
         "archon_hip_fm_rlz": [vp, vp, u32, vp, ctypes.c_uint64, vp],
         "archon_hip_fm_rlz_dev": [vp, vp, u32, vp, ctypes.c_uint64, vp, vp],
         "archon_hip_get_fm_text_stats": [i32, ctypes.POINTER(FmTextStats)],
+        "archon_hip_fm_attach_docs": [vp, vp, u32],
+        "archon_hip_fm_attach_docs_dev": [vp, vp, u32, vp],
+        "archon_hip_block_fm_attach_docs": [vp, vp, vp, u32],
+        "archon_hip_fm_docs": [vp, vp, vp, u32, vp, vp, ctypes.c_uint64, vp],
+        "archon_hip_fm_docs_dev": [vp, vp, vp, u32, vp, vp, ctypes.c_uint64, vp, vp],
+        "archon_hip_fm_docs_ranges": [vp, vp, vp, u32, vp, vp, ctypes.c_uint64, vp],
+        "archon_hip_fm_docs_ranges_dev": [vp, vp, vp, u32, vp, vp, ctypes.c_uint64, vp, vp],
+        "archon_hip_fm_doc_of": [vp, vp, ctypes.c_uint64, vp, vp],
+        "archon_hip_fm_doc_of_dev": [vp, vp, ctypes.c_uint64, vp, vp, vp],
+        "archon_hip_get_fm_doc_stats": [i32, ctypes.POINTER(FmDocStats)],
         "archon_hip_repeats": [vp, vp, u32, u32, u32, u32, u32, vp, ctypes.c_uint64, vp, i32],
         "archon_hip_repeats_dev": [vp, vp, u32, u32, u32, u32, u32, vp, ctypes.c_uint64, vp, i32, vp],
         "archon_hip_block_repeats": [vp, u32, u32, u32, vp, ctypes.c_uint64, vp],
@@ -369,7 +397,7 @@ _ROUTE_NAMES = ("FORCE_PATH", "SMALL_BLOCK", "PASS_RANGES", "INV_ROWS", "INV_SLA
                 "NO_PACK", "NO_PACK_STREAM", "NO_PAIR_CHAINS", "NO_PERIOD_HINT", "NO_BREAK_ROUND", "NO_PERIOD_PROBE", "NO_PERIOD_STREAM", "NO_PROBE",
                 "NO_RANK_WRITER", "NO_TEXT_ROUNDS", "NO_MID", "NO_SHALLOW", "NO_CLOSED_FORM", "NO_REL_RECORDS", "ALIGNED_MIN", "REL_MIN_SEG", "KEY_BYTES",
                 "LCP_CAP", "LCP_WINDOW", "FM_SUB_ROWS", "FM_SUPER_ROWS", "FM_SAMPLE_WALK", "REP_FAN", "LZ_FAN", "LZ_TILE", "MS_CHUNK",
-                "EDIT_TILE", "EDIT_BATCH")
+                "EDIT_TILE", "EDIT_BATCH", "DOC_TILE")
 
 
 def _sync_routes(L):
@@ -528,6 +556,13 @@ def fm_text_stats(dev=0):
     """FmTextStats of the calling thread's last attach_sa, ms_text or rlz call on dev"""
     s = FmTextStats()
     _check(lib().archon_hip_get_fm_text_stats(dev, ctypes.byref(s)))
+    return s
+
+
+def fm_doc_stats(dev=0):
+    """FmDocStats of the calling thread's last documents call (attach_docs, docs, docs_ranges, doc_of) on dev"""
+    s = FmDocStats()
+    _check(lib().archon_hip_get_fm_doc_stats(dev, ctypes.byref(s)))
     return s
 
 
@@ -724,6 +759,31 @@ def _edit(fn, h, patterns, k, emit):
         rc = fn(h, _p(packed), _p(offsets), npat, int(k), _p(nhits), _p(out), out.size, tp)
     _check(rc)
     return nhits, out[:total.value]
+
+
+def _docs(call, k, emit):
+    """(ndocs, records or None) of a documents call(ndocs, out, cap, total): the records into an array of a first guess, then of
+    the size the call gave"""
+    ndocs = np.zeros(max(k, 1), np.uint32)
+    total = ctypes.c_uint64(0)
+    tp = ctypes.cast(ctypes.byref(total), ctypes.c_void_p)
+    if not emit:
+        _check(call(_p(ndocs), None, 0, tp))
+        return ndocs[:k], None
+    out = np.zeros(max(4 * k, 1), FM_DOC)
+    rc = call(_p(ndocs), _p(out), out.size, tp)
+    if rc == E_ARG and total.value > out.size:
+        out = np.zeros(total.value, FM_DOC)
+        rc = call(_p(ndocs), _p(out), out.size, tp)
+    _check(rc)
+    return ndocs[:k], out[:total.value]
+
+
+def _bounds(bounds):
+    bounds = np.ascontiguousarray(bounds, dtype=np.uint32).ravel()
+    if bounds.size < 1:
+        raise ValueError("bounds: at least bounds[0]")
+    return bounds
 
 
 def _locate_hits(fn, h, patterns, hits):
@@ -1005,6 +1065,70 @@ class FmIndex:
                                            ctypes.cast(ctypes.byref(total), ctypes.c_void_p), _stream_ptr()))
         return total.value
 
+    def attach_docs(self, bounds):
+        """cuts the block into documents (uint32 bounds[D + 1], 0 = bounds[0] < ... < bounds[D] = n) for docs(), docs_ranges()
+        and doc_of(): 12 n + 4 (D + 1) bytes on the device.  Needs attach_sa(); replaces an earlier one; returns self"""
+        bounds = _bounds(bounds)
+        _check(lib().archon_hip_fm_attach_docs(self.h, _p(bounds), bounds.size - 1))
+        return self
+
+    def attach_docs_dev(self, bounds_t, stream=None):
+        """the same from a torch int32 tensor of D + 1 words on the device, on `stream` (a raw HIP stream; None: the current torch
+        stream); returns self"""
+        _check(lib().archon_hip_fm_attach_docs_dev(self.h, ctypes.c_void_p(bounds_t.data_ptr()), bounds_t.numel() - 1,
+                                                   _stream_ptr() if stream is None else ctypes.c_void_p(stream)))
+        return self
+
+    def docs(self, patterns, emit=True):
+        """the documents that hold each pattern: (ndocs, records), ndocs[j] the distinct documents of pattern j, records an FM_DOC
+        array pattern by pattern and by ascending first row (None with emit=False: document frequencies only).  An occurrence
+        belongs to the document of its LAST byte.  Needs attach_docs()"""
+        packed, offsets = _pack_patterns(patterns)
+        k = offsets.size - 1
+        fn = lib().archon_hip_fm_docs
+        return _docs(lambda nd, out, cap, tp: fn(self.h, _p(packed), _p(offsets), k, nd, out, cap, tp), k, emit)
+
+    def docs_dev(self, patterns_t, offsets_t, ndocs_t, docs_t=None):
+        """torch tensors on the device: patterns uint8, offsets int32[k + 1], ndocs int32[k] (written), docs an int32 tensor of
+        4 words per record or None; current stream.  Returns the number of records"""
+        total = ctypes.c_uint64(0)
+        cap = docs_t.numel() // 4 if docs_t is not None else 0
+        _check(lib().archon_hip_fm_docs_dev(self.h, ctypes.c_void_p(patterns_t.data_ptr()), ctypes.c_void_p(offsets_t.data_ptr()), ndocs_t.numel(),
+                                            ctypes.c_void_p(ndocs_t.data_ptr()), ctypes.c_void_p(docs_t.data_ptr()) if docs_t is not None else None, cap,
+                                            ctypes.cast(ctypes.byref(total), ctypes.c_void_p), _stream_ptr()))
+        return total.value
+
+    def docs_ranges(self, lo, hi, emit=True):
+        """the documents of the row ranges [lo[j], hi[j]) -- a count's, or the lo and hi of SMEMs, hits or repeats: (ndocs, records)
+        as docs()"""
+        lo = np.ascontiguousarray(lo, dtype=np.uint32).ravel()
+        hi = np.ascontiguousarray(hi, dtype=np.uint32).ravel()
+        if lo.size != hi.size:
+            raise ValueError("docs_ranges: %d lo and %d hi" % (lo.size, hi.size))
+        k = lo.size
+        lo_, hi_ = (lo, hi) if k else (np.zeros(1, np.uint32), np.zeros(1, np.uint32))
+        fn = lib().archon_hip_fm_docs_ranges
+        return _docs(lambda nd, out, cap, tp: fn(self.h, _p(lo_), _p(hi_), k, nd, out, cap, tp), k, emit)
+
+    def docs_ranges_dev(self, lo_t, hi_t, ndocs_t, docs_t=None):
+        """torch int32 tensors on the device: lo and hi [k], ndocs [k] (written), docs 4 words per record or None; current stream.
+        Returns the number of records"""
+        total = ctypes.c_uint64(0)
+        cap = docs_t.numel() // 4 if docs_t is not None else 0
+        _check(lib().archon_hip_fm_docs_ranges_dev(self.h, ctypes.c_void_p(lo_t.data_ptr()), ctypes.c_void_p(hi_t.data_ptr()), lo_t.numel(),
+                                                   ctypes.c_void_p(ndocs_t.data_ptr()), ctypes.c_void_p(docs_t.data_ptr()) if docs_t is not None else None,
+                                                   cap, ctypes.cast(ctypes.byref(total), ctypes.c_void_p), _stream_ptr()))
+        return total.value
+
+    def doc_of(self, items, offsets=True):
+        """(doc, off) of items in 1 .. n -- what locate() returns plus the pattern's length, or a start p as p + 1: the document
+        that holds byte items - 1 and the byte's offset in it (off None with offsets=False)"""
+        items = np.ascontiguousarray(items, dtype=np.uint32).ravel()
+        doc = np.zeros(max(items.size, 1), np.uint32)
+        off = np.zeros(max(items.size, 1), np.uint32) if offsets else None
+        _check(lib().archon_hip_fm_doc_of(self.h, _p(items) if items.size else None, items.size, _p(doc), _p(off) if offsets else None))
+        return doc[:items.size], (off[:items.size] if offsets else None)
+
     def locate_mems(self, mems):
         """the starts of every SMEM's occurrences from the samples (a list of uint32 arrays, one per SMEM, each in row order)"""
         return _locate_mems(lib().archon_hip_fm_locate_mems, self.h, mems)
@@ -1188,11 +1312,12 @@ class Block:
         got = _phrases(lambda out, cap, tp: fn(self.h, int(dir), _p(rec) if rec is not None and out is None else None, out, cap, tp), count_only)
         return (rec, got) if want_lpf else got
 
-    def fm_index(self, rate, mirror=False, sa=False, lcp=False):
+    def fm_index(self, rate, mirror=False, sa=False, docs=None, lcp=False):
         """a standalone sampled FmIndex of the last forward's BWT (samples from the SA when that forward kept one, else by the
         LF walk); it outlives later forwards and close().  mirror=True: with its mirror, built from the resident block.
         lcp=True: with the block's LCP array attached (needs forward(want_sa=True)); the array is made on the device.
-        sa=True: with the block's suffix array attached, device to device (needs forward(want_sa=True))"""
+        sa=True: with the block's suffix array attached, device to device (needs forward(want_sa=True)).
+        docs=bounds: cut into documents (FmIndex.attach_docs) from the resident suffix array (needs forward(want_sa=True))"""
         h = ctypes.c_void_p(None)
         _check(lib().archon_hip_block_fm_index(self.h, int(rate), ctypes.byref(h)))
         f = FmIndex(_handle=h)
@@ -1204,6 +1329,9 @@ class Block:
             _check(lib().archon_hip_block_fm_attach_lcp(self.h, f.h))
         if sa:
             _check(lib().archon_hip_block_fm_attach_sa(self.h, f.h))
+        if docs is not None:
+            bounds = _bounds(docs)
+            _check(lib().archon_hip_block_fm_attach_docs(self.h, f.h, _p(bounds), bounds.size - 1))
         return f
 
     def stats(self):

@@ -958,6 +958,101 @@ typedef struct archon_hip_fm_text_stats {
 } archon_hip_fm_text_stats;
 int  archon_hip_get_fm_text_stats(int dev, archon_hip_fm_text_stats *out);
 
+/* ---- document listing: which documents of a block hold each pattern, and how often ------------------------------------------------
+ * A block is often a collection: the files of an archive, a read set, the versions of a record.  Every other query above answers
+ * with rows or block offsets; these calls answer with documents.
+ * Documents.  bounds[0 .. D] with bounds[0] = 0 < bounds[1] < ... < bounds[D] = n and 1 <= D <= n; document d is
+ * x[bounds[d] .. bounds[d+1]).  Anything else is ARCHON_E_ARG: a decreasing or equal pair, bounds[0] != 0, bounds[D] != n, D = 0,
+ * D > n.  A refused attach leaves an earlier attachment in place.
+ * Document of an item.  Item s in 1 .. n belongs to the d with bounds[d] < s <= bounds[d+1]: the document that holds byte x[s-1].
+ * Document of a row.  Row r belongs to the document of sa[r].
+ * Document of an occurrence.  An occurrence of a pattern of m bytes at row r is x[sa[r]-m .. sa[r]).  It belongs to the document
+ * that holds its LAST byte -- also when it starts before that document's first byte.  A caller who wants no occurrence across a
+ * boundary ends every document with a byte the patterns do not hold (a newline, a 0), as collections are commonly stored; these
+ * calls do not filter such occurrences out.
+ * Listing of a row range [lo, hi), valid when lo <= hi <= n (else ARCHON_E_ARG): every distinct document among its rows gives one
+ * record with its term frequency tf (the rows of the range in that document) and its first row (the least row of the range in that
+ * document).  Records come range by range, by ascending j, and within a range by ascending row.  The tf of a range sum to
+ * hi - lo.  An empty range lists nothing.  SMEMs, approximate hits and repeats are row ranges too: their lo and hi list the same way.
+ * Example: "banana", sa = 2 4 6 1 3 5, bounds = 0 3 6: the documents are "ban" and "ana", the rows' documents 0 1 1 0 0 1.
+ *   "an"  rows [4, 6)  records (doc, tf, row) = (0, 1, 4) (1, 1, 5)
+ *   "a"   rows [0, 3)  (0, 1, 0) (1, 2, 1)
+ *   "na"  rows [1, 3)  (1, 2, 1): the occurrence x[2 .. 4) starts in document 0 and ends in document 1, so it counts for 1.
+ * Memory: the documents are one more device allocation of the handle, bounds (D + 1 words) | pv[n] | pos[n] | L[n]:
+ * 12 n + 4 (D + 1) bytes plus padding.  L holds the rows sorted by (document, row), so document d's rows are
+ * L[bounds[d] .. bounds[d+1]), ascending; pos[r] is the index of row r in L; pv[r] is 1 + the greatest row < r of the same
+ * document, 0 when there is none.  One kernel makes the pairs (document of sa[r], r), a stable LSB radix sort orders them on the
+ * bytes of D - 1 that can differ (none at D = 1), one kernel writes L, pos and pv.  The scratch, 24 n bytes, is the calling
+ * thread's context arena.  archon_hip_fm_destroy frees the allocation; handles without documents behave exactly as before and
+ * refuse these calls.
+ * Method of a listing.  Row r starts a document of [lo, hi) exactly when pv[r] <= lo.  Every nonempty range is cut into tiles of T
+ * rows (4096) counted from its own lo, one wave per tile; the count pass reads pv alone; a scan gives every tile its place; the emit
+ * pass, run only when records are asked for and fit, walks the same tiles 64 rows at a time.  Only a first row does more: it reads
+ * p = pos[r], finds d = upper_bound(bounds, p) - 1 and tf = lower_bound(L[p .. bounds[d+1]), hi) - p.  A call lists at most
+ * 2^32 - 1 rows (ARCHON_E_ARG above that), and its tile words fit 256 MiB of arena (ARCHON_E_NOMEM above that).
+ * A handle serves one thread at a time (as above). */
+typedef struct archon_hip_fm_doc {
+    uint32_t doc;      /* the document */
+    uint32_t tf;       /* rows of the range in it */
+    uint32_t row;      /* the first of them: sa[row] - m is one start (archon_hip_fm_locate_mems gives all) */
+    uint32_t range;    /* j: the pattern or range it belongs to */
+} archon_hip_fm_doc;
+/* bounds[ndocs + 1] on the host: copied into the handle, L, pos and pv made behind it from the handle's attached suffix array
+ * (archon_hip_fm_attach_sa; a handle without one is ARCHON_E_ARG).  Replaces an earlier attachment; the suffix array may be
+ * attached again or not afterwards, the documents keep what they made. */
+int  archon_hip_fm_attach_docs(archon_hip_fm *f, const uint32_t *bounds, uint32_t ndocs);
+/* the same from a device array, whose entries a kernel checks; on `stream` (NULL = the context's own), complete on return */
+int  archon_hip_fm_attach_docs_dev(archon_hip_fm *f, const uint32_t *d_bounds, uint32_t ndocs, void *stream);
+/* f a handle from archon_hip_block_fm_index of this block's last forward, which kept its suffix array: reads the resident array
+ * device to device and needs no archon_hip_fm_attach_sa; preconditions and ARCHON_E_ARG cases of archon_hip_block_fm_attach_sa */
+int  archon_hip_block_fm_attach_docs(archon_hip_block *b, archon_hip_fm *f, const uint32_t *bounds, uint32_t ndocs);
+/* Host patterns (offsets[k + 1] as archon_hip_fm_count): the count, then the listing of its ranges; `range` of a record is the
+ * pattern.  The cap rule is that of archon_hip_fm_smems: ndocs[k] (the distinct documents of every pattern) and *total (their sum)
+ * are always written; docs_or_null NULL: document frequencies only, no emit pass; cap < *total with docs_or_null given is
+ * ARCHON_E_ARG with docs untouched; k = 0 writes *total = 0 and nothing else.  *total is 0 after any other refusal.  A handle
+ * without documents is ARCHON_E_ARG. */
+int  archon_hip_fm_docs(archon_hip_fm *f, const uint8_t *patterns, const uint32_t *offsets, uint32_t k, uint32_t *ndocs,
+                        archon_hip_fm_doc *docs_or_null, uint64_t cap, uint64_t *total);
+/* device patterns, offsets, counts and records, *total on the host; on `stream`, complete on return */
+int  archon_hip_fm_docs_dev(archon_hip_fm *f, const uint8_t *d_patterns, const uint32_t *d_offsets, uint32_t k, uint32_t *d_ndocs,
+                            archon_hip_fm_doc *d_docs_or_null, uint64_t cap, uint64_t *total, void *stream);
+/* the listing of k row ranges [lo[j], hi[j]) on the host; a range that is not lo <= hi <= n is ARCHON_E_ARG */
+int  archon_hip_fm_docs_ranges(archon_hip_fm *f, const uint32_t *lo, const uint32_t *hi, uint32_t k, uint32_t *ndocs,
+                               archon_hip_fm_doc *docs_or_null, uint64_t cap, uint64_t *total);
+/* device ranges, counts and records; a bad range is found on the device: ARCHON_E_ARG, nothing emitted */
+int  archon_hip_fm_docs_ranges_dev(archon_hip_fm *f, const uint32_t *d_lo, const uint32_t *d_hi, uint32_t k, uint32_t *d_ndocs,
+                                   archon_hip_fm_doc *d_docs_or_null, uint64_t cap, uint64_t *total, void *stream);
+/* The document of items.  Item s in 1 .. n -- what a locate returns plus m, or a start p passed as p + 1 -- gives doc[i] and, when
+ * off_or_null is given, its offset s - 1 - bounds[doc] in it.  An item outside 1 .. n is ARCHON_E_ARG, nothing written. */
+int  archon_hip_fm_doc_of(archon_hip_fm *f, const uint32_t *items, uint64_t count, uint32_t *doc, uint32_t *off_or_null);
+/* device arrays; on `stream`, complete on return */
+int  archon_hip_fm_doc_of_dev(archon_hip_fm *f, const uint32_t *d_items, uint64_t count, uint32_t *d_doc, uint32_t *d_off_or_null, void *stream);
+/* the CALLING THREAD's last documents call (attach, listing or doc_of) on `dev`; these calls leave every other statistics record
+ * alone.  rows, tiles and listed follow from x, bounds, the ranges and T alone. */
+typedef struct archon_hip_fm_doc_stats {
+    uint32_t n;                 /* block size of the index */
+    uint32_t docs;              /* D */
+    uint32_t ranges;            /* k */
+    uint32_t tile;              /* T */
+    uint32_t attached;          /* 1 when the call attached documents */
+    uint32_t sort_passes;       /* radix passes the attach ran: at most ceil(bits(D - 1) / 8) */
+    uint32_t longest_tf;        /* the largest tf emitted */
+    uint32_t reserved0;
+    uint64_t pattern_bytes;     /* bytes of the patterns (0 for ranges) */
+    uint64_t rows;              /* the sum of hi - lo */
+    uint64_t tiles;             /* the sum of ceil((hi - lo) / T) over the nonempty ranges */
+    uint64_t listed;            /* *total */
+    uint64_t probes;            /* entries of bounds and L the emit pass's two searches read: at most listed (ceil(log2(D+1)) + ceil(log2(n+1))) */
+    uint64_t doc_bytes;         /* device bytes of the attachment */
+    uint32_t kernel_launches;   /* launches issued by the call */
+    uint32_t host_syncs;        /* times the host waited for the stream inside the call */
+    float ms_attach;            /* device time of the attach (HIP events) */
+    float ms_search;            /* of the count of the patterns and the tiling of the ranges */
+    float ms_count;             /* of the count pass, its scan and the per-range counts */
+    float ms_emit;              /* of the emit pass */
+} archon_hip_fm_doc_stats;
+int  archon_hip_get_fm_doc_stats(int dev, archon_hip_fm_doc_stats *out);
+
 /* ---- measurement ------------------------------------------------------------- */
 
 /* Per-stage device times (HIP events on the stream the kernels ran on) and

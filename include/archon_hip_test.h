@@ -40,6 +40,8 @@
  *                                 It changes no match: at 1 every end is a tile of its own
  *   EDIT_BATCH     1.. / 0        edit-distance search: patterns of a batch at most (0: what the scratch budget holds).  It changes
  *                                 no match: at 1 every pattern is marked, swept and checked alone
+ *   DOC_TILE       64..2^20 / 0   document listing: rows of a tile, a multiple of 64 (0: 4096).  It changes no record: at 64 a range of
+ *                                 65 rows is two tiles
  *   NO_ALIGNED NO_BREAK_ROUND NO_CHAINS NO_DEEP_HINT NO_PACK NO_PACK_STREAM NO_PAIR_CHAINS NO_PERIOD_HINT NO_PERIOD_PROBE
  *   NO_PERIOD_STREAM NO_PROBE NO_RANK_WRITER NO_TEXT_ROUNDS NO_MID NO_SHALLOW NO_CLOSED_FORM NO_REL_RECORDS      nonzero switches the named step off
  * Returns 0, or ARCHON_E_ARG for an unknown name / a value out of range.  Process-wide; not thread-safe against
