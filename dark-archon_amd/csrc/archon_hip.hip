@@ -1935,10 +1935,10 @@ int archon_hip_fm_read_samples(archon_hip_fm *f, uint32_t *isa, uint32_t cap, ui
 {
     if (!f || !isa || !count) { set_error("null pointer"); return ARCHON_E_ARG; }
     ARCHON_TRY(fm_check_sampled(f));
-    *count = f->ns;
-    if (cap < f->ns) { set_error("FM samples: %u ISA entries, room for %u", f->ns, cap); return ARCHON_E_ARG; }
+    *count = f->smp.ns;
+    if (cap < f->smp.ns) { set_error("FM samples: %u ISA entries, room for %u", f->smp.ns, cap); return ARCHON_E_ARG; }
     ARCHON_HIP_TRY(hipSetDevice(f->dev));
-    ARCHON_HIP_TRY(hipMemcpy(isa, f->isa, (size_t)f->ns * 4, hipMemcpyDeviceToHost));
+    ARCHON_HIP_TRY(hipMemcpy(isa, f->smp.isa, (size_t)f->smp.ns * 4, hipMemcpyDeviceToHost));
     return ARCHON_OK;
 }
 
@@ -2006,7 +2006,7 @@ int archon_hip_fm_approx(archon_hip_fm *f, const uint8_t *patterns, const uint32
     return with_ctx(f->dev, nullptr, [&](Ctx *c, hipStream_t s) -> int {
         KeepStats<archon_hip_fm_approx_stats> keep(t_fma_stats, f->dev);
         fma_call_stats(&keep.st, f->n, k, max_mismatches);
-        return fma_host(c, s, f, patterns, offsets, k, max_mismatches, nhits, nocc, hits_or_null, cap, total, &keep.st);
+        return fm_search_host(c, s, FmaSearch{max_mismatches}, f, patterns, offsets, k, nhits, nocc, hits_or_null, cap, total, &keep.st);
     });
 }
 
@@ -2020,7 +2020,7 @@ int archon_hip_fm_approx_dev(archon_hip_fm *f, const uint8_t *d_patterns, const 
     return with_ctx(f->dev, stream, [&](Ctx *c, hipStream_t s) -> int {
         KeepStats<archon_hip_fm_approx_stats> keep(t_fma_stats, f->dev);
         fma_call_stats(&keep.st, f->n, k, max_mismatches);
-        return fma_dev(c, s, f, d_patterns, d_offsets, k, max_mismatches, d_nhits, d_nocc, d_hits_or_null, cap, total, &keep.st);
+        return fm_search_dev(c, s, FmaSearch{max_mismatches}, f, d_patterns, d_offsets, k, d_nhits, d_nocc, d_hits_or_null, cap, total, &keep.st);
     });
 }
 
@@ -2111,7 +2111,7 @@ int archon_hip_fm_read_mirror(archon_hip_fm *f, uint8_t *bwt, uint32_t cap, uint
     *base_id = f->mirror->base;
     if (cap < f->n) { set_error("FM mirror: %u bytes, room for %u", f->n, cap); return ARCHON_E_ARG; }
     ARCHON_HIP_TRY(hipSetDevice(f->dev));
-    ARCHON_HIP_TRY(hipMemcpy(bwt, f->mirror->bwt, f->n, hipMemcpyDeviceToHost));
+    ARCHON_HIP_TRY(hipMemcpy(bwt, f->mirror->tab.bwt, f->n, hipMemcpyDeviceToHost));
     return ARCHON_OK;
 }
 
@@ -2126,7 +2126,7 @@ int archon_hip_fm_smems(archon_hip_fm *f, const uint8_t *patterns, const uint32_
     return with_ctx(f->dev, nullptr, [&](Ctx *c, hipStream_t s) -> int {
         KeepStats<archon_hip_fm_mem_stats> keep(t_fmm_stats, f->dev);
         fmm_call_stats(&keep.st, f, f->n, k, min_len);
-        return fmm_host(c, s, f, patterns, offsets, k, min_len, nmems, nocc, mems_or_null, cap, total, &keep.st);
+        return fm_search_host(c, s, FmmSearch{min_len}, f, patterns, offsets, k, nmems, nocc, mems_or_null, cap, total, &keep.st);
     });
 }
 
@@ -2140,7 +2140,7 @@ int archon_hip_fm_smems_dev(archon_hip_fm *f, const uint8_t *d_patterns, const u
     return with_ctx(f->dev, stream, [&](Ctx *c, hipStream_t s) -> int {
         KeepStats<archon_hip_fm_mem_stats> keep(t_fmm_stats, f->dev);
         fmm_call_stats(&keep.st, f, f->n, k, min_len);
-        return fmm_dev(c, s, f, d_patterns, d_offsets, k, min_len, d_nmems, d_nocc, d_mems_or_null, cap, total, &keep.st);
+        return fm_search_dev(c, s, FmmSearch{min_len}, f, d_patterns, d_offsets, k, d_nmems, d_nocc, d_mems_or_null, cap, total, &keep.st);
     });
 }
 
@@ -2312,7 +2312,7 @@ int archon_hip_get_fm_text_stats(int dev, archon_hip_fm_text_stats *out)
 static int fmd_attach_check(const archon_hip_fm *f, const uint32_t *bounds, uint32_t ndocs)
 {
     ARCHON_TRY(fmd_check_bounds(bounds, ndocs));
-    if (!f->tsa) { set_error("FM attach docs: the handle has no suffix array (archon_hip_fm_attach_sa)"); return ARCHON_E_ARG; }
+    if (!f->sa.mem) { set_error("FM attach docs: the handle has no suffix array (archon_hip_fm_attach_sa)"); return ARCHON_E_ARG; }
     return fmd_check_fit(f->n, bounds, ndocs);
 }
 
@@ -2323,7 +2323,7 @@ int archon_hip_fm_attach_docs(archon_hip_fm *f, const uint32_t *bounds, uint32_t
     return with_ctx(f->dev, nullptr, [&](Ctx *c, hipStream_t s) -> int {
         KeepStats<archon_hip_fm_doc_stats> keep(t_fmd_stats, f->dev);
         fmd_call_stats(&keep.st, f, 0);
-        return fmd_attach_run(c, s, f, f->tsa, bounds, nullptr, ndocs, &keep.st);
+        return fmd_attach_run(c, s, f, f->sa.sa, bounds, nullptr, ndocs, &keep.st);
     });
 }
 
@@ -2331,12 +2331,12 @@ int archon_hip_fm_attach_docs_dev(archon_hip_fm *f, const uint32_t *d_bounds, ui
 {
     if (!f || !d_bounds) { set_error("null pointer"); return ARCHON_E_ARG; }
     if (!ndocs) { set_error("FM attach docs: no documents"); return ARCHON_E_ARG; }
-    if (!f->tsa) { set_error("FM attach docs: the handle has no suffix array (archon_hip_fm_attach_sa)"); return ARCHON_E_ARG; }
+    if (!f->sa.mem) { set_error("FM attach docs: the handle has no suffix array (archon_hip_fm_attach_sa)"); return ARCHON_E_ARG; }
     ARCHON_TRY(fmd_check_fit(f->n, nullptr, ndocs));
     return with_ctx(f->dev, stream, [&](Ctx *c, hipStream_t s) -> int {
         KeepStats<archon_hip_fm_doc_stats> keep(t_fmd_stats, f->dev);
         fmd_call_stats(&keep.st, f, 0);
-        return fmd_attach_run(c, s, f, f->tsa, nullptr, d_bounds, ndocs, &keep.st);
+        return fmd_attach_run(c, s, f, f->sa.sa, nullptr, d_bounds, ndocs, &keep.st);
     });
 }
 
@@ -2643,6 +2643,31 @@ static int block_fm_table(Ctx *c, hipStream_t s, archon_hip_block *b, archon_hip
     return b->fm ? ARCHON_OK : fm_build(c, s, nullptr, b->d_bwt, false, b->n, b->base, &b->fm, st);
 }
 
+// the same for a call that keeps another record: a table built here is this call's work, into its own record, while fm_stats
+// stays as it was
+extern "C++" {
+template <class Stats>
+static int block_fm_table_own(Ctx *c, hipStream_t s, archon_hip_block *b, Stats *st)
+{
+    archon_hip_fm_stats fst = {};
+    ARCHON_TRY(block_fm_table(c, s, b, &fst));
+    st->built = fst.built;
+    st->ms_build = fst.ms_build;
+    st->kernel_launches += fst.kernel_launches;
+    return ARCHON_OK;
+}
+}   // extern "C++"
+
+// a handle given beside a block is one of that block's BWT, on its device
+static int block_check_handle(const archon_hip_block *b, const archon_hip_fm *f, const char *what)
+{
+    if (f->dev != b->dev || f->n != b->n || f->base != b->base) {
+        set_error("%s: the handle (%u bytes, primary row %u) is not of this block (%u bytes, primary row %u)", what, f->n, f->base, b->n, b->base);
+        return ARCHON_E_ARG;
+    }
+    return ARCHON_OK;
+}
+
 int archon_hip_block_fm_count(archon_hip_block *b, const uint8_t *patterns, const uint32_t *offsets, uint32_t k, uint32_t *lo, uint32_t *hi)
 {
     if (!b || !patterns || !offsets || !lo || !hi) { set_error("null pointer"); return ARCHON_E_ARG; }
@@ -2709,13 +2734,8 @@ int archon_hip_block_fm_approx(archon_hip_block *b, const uint8_t *patterns, con
     return with_ctx(b->dev, nullptr, [&](Ctx *c, hipStream_t s) -> int {
         KeepStats<archon_hip_fm_approx_stats> keep(t_fma_stats, b->dev);
         fma_call_stats(&keep.st, b->n, k, max_mismatches);
-        // a table built here is this call's work: into its own record, while fm_stats stays as it was
-        archon_hip_fm_stats fst = {};
-        ARCHON_TRY(block_fm_table(c, s, b, &fst));
-        keep.st.built = fst.built;
-        keep.st.ms_build = fst.ms_build;
-        keep.st.kernel_launches += fst.kernel_launches;
-        return fma_host(c, s, b->fm, patterns, offsets, k, max_mismatches, nhits, nocc, hits_or_null, cap, total, &keep.st);
+        ARCHON_TRY(block_fm_table_own(c, s, b, &keep.st));
+        return fm_search_host(c, s, FmaSearch{max_mismatches}, b->fm, patterns, offsets, k, nhits, nocc, hits_or_null, cap, total, &keep.st);
     });
 }
 
@@ -2747,12 +2767,7 @@ int archon_hip_block_fm_edit(archon_hip_block *b, const uint8_t *patterns, const
     return with_ctx(b->dev, nullptr, [&](Ctx *c, hipStream_t s) -> int {
         KeepStats<archon_hip_fm_edit_stats> keep(t_fme_stats, b->dev);
         fme_call_stats(&keep.st, b->n, k, max_errors);
-        // a table built here is this call's work: into its own record, while fm_stats stays as it was
-        archon_hip_fm_stats fst = {};
-        ARCHON_TRY(block_fm_table(c, s, b, &fst));
-        keep.st.built = fst.built;
-        keep.st.ms_build = fst.ms_build;
-        keep.st.kernel_launches += fst.kernel_launches;
+        ARCHON_TRY(block_fm_table_own(c, s, b, &keep.st));
         return fme_host(c, s, b->fm, b->d_sa, b->d_x, patterns, offsets, k, max_errors, nhits, hits_or_null, cap, total, &keep.st);
     });
 }
@@ -2762,10 +2777,7 @@ int archon_hip_block_fm_mirror(archon_hip_block *b, archon_hip_fm *f)
     if (!b || !f) { set_error("null pointer"); return ARCHON_E_ARG; }
     std::lock_guard<std::mutex> lkb(b->mu);
     ARCHON_TRY(block_check(b, false));
-    if (f->dev != b->dev || f->n != b->n || f->base != b->base) {
-        set_error("FM mirror: the handle (%u bytes, primary row %u) is not of this block (%u bytes, primary row %u)", f->n, f->base, b->n, b->base);
-        return ARCHON_E_ARG;
-    }
+    ARCHON_TRY(block_check_handle(b, f, "FM mirror"));
     return with_ctx(b->dev, nullptr, [&](Ctx *c, hipStream_t s) -> int {
         KeepStats<archon_hip_fm_mem_stats> keep(t_fmm_stats, b->dev);
         fmm_call_stats(&keep.st, f, f->n, 0, 0);
@@ -2779,10 +2791,7 @@ int archon_hip_block_fm_attach_lcp(archon_hip_block *b, archon_hip_fm *f)
     if (!b || !f) { set_error("null pointer"); return ARCHON_E_ARG; }
     std::lock_guard<std::mutex> lkb(b->mu);
     ARCHON_TRY(block_check(b, true));
-    if (f->dev != b->dev || f->n != b->n || f->base != b->base) {
-        set_error("FM attach lcp: the handle (%u bytes, primary row %u) is not of this block (%u bytes, primary row %u)", f->n, f->base, b->n, b->base);
-        return ARCHON_E_ARG;
-    }
+    ARCHON_TRY(block_check_handle(b, f, "FM attach lcp"));
     return with_ctx(b->dev, nullptr, [&](Ctx *c, hipStream_t s) -> int {
         KeepStats<archon_hip_fm_ms_stats> keep(t_fms_stats, b->dev);
         fms_call_stats(&keep.st, f, 0);
@@ -2803,10 +2812,7 @@ int archon_hip_block_fm_attach_sa(archon_hip_block *b, archon_hip_fm *f)
     if (!b || !f) { set_error("null pointer"); return ARCHON_E_ARG; }
     std::lock_guard<std::mutex> lkb(b->mu);
     ARCHON_TRY(block_check(b, true));
-    if (f->dev != b->dev || f->n != b->n || f->base != b->base) {
-        set_error("FM attach sa: the handle (%u bytes, primary row %u) is not of this block (%u bytes, primary row %u)", f->n, f->base, b->n, b->base);
-        return ARCHON_E_ARG;
-    }
+    ARCHON_TRY(block_check_handle(b, f, "FM attach sa"));
     return with_ctx(b->dev, nullptr, [&](Ctx *c, hipStream_t s) -> int {
         KeepStats<archon_hip_fm_text_stats> keep(t_fmt_stats, b->dev);
         fmt_call_stats(&keep.st, f, 0);
@@ -2821,10 +2827,7 @@ int archon_hip_block_fm_attach_docs(archon_hip_block *b, archon_hip_fm *f, const
     ARCHON_TRY(fmd_check_bounds(bounds, ndocs));
     std::lock_guard<std::mutex> lkb(b->mu);
     ARCHON_TRY(block_check(b, true));
-    if (f->dev != b->dev || f->n != b->n || f->base != b->base) {
-        set_error("FM attach docs: the handle (%u bytes, primary row %u) is not of this block (%u bytes, primary row %u)", f->n, f->base, b->n, b->base);
-        return ARCHON_E_ARG;
-    }
+    ARCHON_TRY(block_check_handle(b, f, "FM attach docs"));
     ARCHON_TRY(fmd_check_fit(f->n, bounds, ndocs));
     return with_ctx(b->dev, nullptr, [&](Ctx *c, hipStream_t s) -> int {
         KeepStats<archon_hip_fm_doc_stats> keep(t_fmd_stats, b->dev);

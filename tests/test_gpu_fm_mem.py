@@ -199,6 +199,19 @@ def test_mirror_refuses(archon):
         wrong.close()
         lo, hi = f.count([x[50:60].tobytes()])
         assert hi[0] > lo[0]
+        # a refused replacement leaves the earlier mirror answering
+        f.mirror()
+        pats = [x[200:260].tobytes(), x[1000:1020].tobytes() + x[5000:5030].tobytes(), b"abc"]
+        nm, no, mems = f.smems(pats)
+        mirror_bwt, mirror_base = f.read_mirror()
+        assert mems.size >= 2
+        with pytest.raises(archon.ArchonError) as e:
+            f.mirror(other)
+        assert e.value.code == archon.E_ARG
+        nm2, no2, mems2 = f.smems(pats)
+        assert (nm2 == nm).all() and (no2 == no).all() and (mems2 == mems).all()
+        again_bwt, again_base = f.read_mirror()
+        assert again_base == mirror_base and (again_bwt == mirror_bwt).all()
         f.close()
     finally:
         b.close()

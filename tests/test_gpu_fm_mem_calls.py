@@ -15,10 +15,10 @@ pytestmark = pytest.mark.gpu
 N = 256 << 10
 RATE = 32
 # The drivers, step by step (fm_host.hiph):
-#   fmm_count    the count pass: 1 launch; one wait for the counters, nmems and nocc
-#   fmm_emit     the emit pass: 1 launch; one wait for it
-#   fmm_host     fmm_count, then (SMEMs wanted and found, cap large enough) fmm_emit and one wait more for the SMEMs' copy
-#   fmm_dev      fmm_count, then fmm_emit: the SMEMs stay on the device
+#   fm_search_count   the count pass: 1 launch; one wait for the counters, nmems and nocc
+#   fm_search_emit    the emit pass: 1 launch; one wait for it
+#   fm_search_host    the count, then (SMEMs wanted and found, cap large enough) the emit and one wait more for the SMEMs' copy
+#   fm_search_dev     the count, then the emit: the SMEMs stay on the device
 #   fmm_locate   1 launch (the gather or the walks), one wait for the starts
 COUNT_ONLY = (1, 1)
 HOST_WITH_MEMS = (2, 3)
