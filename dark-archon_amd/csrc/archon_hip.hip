@@ -15,6 +15,7 @@
 #include "fm.hiph"
 #include "fm_walk.hiph"
 #include "fm_approx.hiph"
+#include "fm_class.hiph"
 #include "fm_mem.hiph"
 #include "fm_ms.hiph"
 #include "fm_text.hiph"
@@ -88,6 +89,7 @@ static thread_local LastStats<archon_hip_lcp_stats> t_lcp_stats;        // LCP c
 static thread_local LastStats<archon_hip_fm_stats> t_fm_stats;          // FM calls: they leave both of the others alone
 static thread_local LastStats<archon_hip_fm_walk_stats> t_fmw_stats;    // sampled-index calls: sample, block_fm_index, locate, extract
 static thread_local LastStats<archon_hip_fm_approx_stats> t_fma_stats;  // approximate calls: approx, locate_hits
+static thread_local LastStats<archon_hip_fm_class_stats> t_fmc_stats;   // class calls: classes, classes_dev, block_fm_classes
 static thread_local LastStats<archon_hip_fm_edit_stats> t_fme_stats;    // edit-distance calls: edit, edit_dev, block_fm_edit
 static thread_local LastStats<archon_hip_fm_mem_stats> t_fmm_stats;     // SMEM calls: mirror, smems, locate_mems
 static thread_local LastStats<archon_hip_fm_ms_stats> t_fms_stats;      // matching-statistics calls: attach_lcp, ms
@@ -2044,6 +2046,38 @@ int archon_hip_get_fm_approx_stats(int dev, archon_hip_fm_approx_stats *out)
     return t_fma_stats.get(dev, out, "approximate FM call");
 }
 
+// ---- class search
+int archon_hip_fm_classes(archon_hip_fm *f, const uint8_t *patterns, const uint32_t *offsets, uint32_t k, const uint32_t *classes, uint32_t *nhits,
+                          uint32_t *nocc, archon_hip_fm_hit *hits_or_null, uint64_t cap, uint64_t *total)
+{
+    if (!f || !patterns || !offsets || !classes || !nhits || !nocc || !total) { set_error("null pointer"); return ARCHON_E_ARG; }
+    ARCHON_TRY(fm_check_offsets(offsets, k));
+    if (!k) { *total = 0; return ARCHON_OK; }
+    return with_ctx(f->dev, nullptr, [&](Ctx *c, hipStream_t s) -> int {
+        KeepStats<archon_hip_fm_class_stats> keep(t_fmc_stats, f->dev);
+        fmc_call_stats(&keep.st, f->n, k);
+        return fm_search_host(c, s, FmcSearch{classes, nullptr}, f, patterns, offsets, k, nhits, nocc, hits_or_null, cap, total, &keep.st);
+    });
+}
+
+int archon_hip_fm_classes_dev(archon_hip_fm *f, const uint8_t *d_patterns, const uint32_t *d_offsets, uint32_t k, const uint32_t *d_classes,
+                              uint32_t *d_nhits, uint32_t *d_nocc, archon_hip_fm_hit *d_hits_or_null, uint64_t cap, uint64_t *total, void *stream)
+{
+    if (!f || !d_patterns || !d_offsets || !d_classes || !d_nhits || !d_nocc || !total) { set_error("null pointer"); return ARCHON_E_ARG; }
+    if (!k) { *total = 0; return ARCHON_OK; }
+    return with_ctx(f->dev, stream, [&](Ctx *c, hipStream_t s) -> int {
+        KeepStats<archon_hip_fm_class_stats> keep(t_fmc_stats, f->dev);
+        fmc_call_stats(&keep.st, f->n, k);
+        return fm_search_dev(c, s, FmcSearch{nullptr, d_classes}, f, d_patterns, d_offsets, k, d_nhits, d_nocc, d_hits_or_null, cap, total, &keep.st);
+    });
+}
+
+int archon_hip_get_fm_class_stats(int dev, archon_hip_fm_class_stats *out)
+{
+    if (!out) { set_error("null pointer"); return ARCHON_E_ARG; }
+    return t_fmc_stats.get(dev, out, "class FM call");
+}
+
 // ---- edit-distance search
 int archon_hip_fm_edit(archon_hip_fm *f, const uint8_t *patterns, const uint32_t *offsets, uint32_t k, uint32_t max_errors, uint32_t *nhits,
                        archon_hip_fm_edit_hit *hits_or_null, uint64_t cap, uint64_t *total)
@@ -2736,6 +2770,22 @@ int archon_hip_block_fm_approx(archon_hip_block *b, const uint8_t *patterns, con
         fma_call_stats(&keep.st, b->n, k, max_mismatches);
         ARCHON_TRY(block_fm_table_own(c, s, b, &keep.st));
         return fm_search_host(c, s, FmaSearch{max_mismatches}, b->fm, patterns, offsets, k, nhits, nocc, hits_or_null, cap, total, &keep.st);
+    });
+}
+
+int archon_hip_block_fm_classes(archon_hip_block *b, const uint8_t *patterns, const uint32_t *offsets, uint32_t k, const uint32_t *classes,
+                                uint32_t *nhits, uint32_t *nocc, archon_hip_fm_hit *hits_or_null, uint64_t cap, uint64_t *total)
+{
+    if (!b || !patterns || !offsets || !classes || !nhits || !nocc || !total) { set_error("null pointer"); return ARCHON_E_ARG; }
+    ARCHON_TRY(fm_check_offsets(offsets, k));
+    std::lock_guard<std::mutex> lkb(b->mu);
+    ARCHON_TRY(block_check(b, false));
+    if (!k) { *total = 0; return ARCHON_OK; }
+    return with_ctx(b->dev, nullptr, [&](Ctx *c, hipStream_t s) -> int {
+        KeepStats<archon_hip_fm_class_stats> keep(t_fmc_stats, b->dev);
+        fmc_call_stats(&keep.st, b->n, k);
+        ARCHON_TRY(block_fm_table_own(c, s, b, &keep.st));
+        return fm_search_host(c, s, FmcSearch{classes, nullptr}, b->fm, patterns, offsets, k, nhits, nocc, hits_or_null, cap, total, &keep.st);
     });
 }
 

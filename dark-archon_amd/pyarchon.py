@@ -39,6 +39,7 @@ SYMBOLS = [
     "archon_hip_fm_extract_dev", "archon_hip_get_fm_walk_stats",
     "archon_hip_fm_approx", "archon_hip_fm_approx_dev", "archon_hip_block_fm_approx", "archon_hip_fm_locate_hits",
     "archon_hip_block_fm_locate_hits", "archon_hip_get_fm_approx_stats",
+    "archon_hip_fm_classes", "archon_hip_fm_classes_dev", "archon_hip_block_fm_classes", "archon_hip_get_fm_class_stats",
     "archon_hip_fm_edit", "archon_hip_fm_edit_dev", "archon_hip_block_fm_edit", "archon_hip_get_fm_edit_stats",
     "archon_hip_fm_mirror", "archon_hip_fm_mirror_dev", "archon_hip_block_fm_mirror", "archon_hip_fm_read_mirror", "archon_hip_fm_smems",
     "archon_hip_fm_smems_dev", "archon_hip_fm_locate_mems", "archon_hip_block_fm_locate_mems", "archon_hip_get_fm_mem_stats",
@@ -137,6 +138,19 @@ class FmApproxStats(ctypes.Structure):
         ("pattern_bytes", ctypes.c_uint64), ("expansions", ctypes.c_uint64), ("steps", ctypes.c_uint64), ("hits", ctypes.c_uint64),
         ("occurrences", ctypes.c_uint64), ("lf_steps", ctypes.c_uint64), ("kernel_launches", ctypes.c_uint32), ("host_syncs", ctypes.c_uint32),
         ("ms_build", ctypes.c_float), ("ms_count", ctypes.c_float), ("ms_emit", ctypes.c_float), ("ms_locate", ctypes.c_float),
+    ]
+
+    def asdict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
+class FmClassStats(ctypes.Structure):
+    """archon_hip_fm_class_stats: the calling thread's last class call (classes, classes_dev, fm_classes) on a device"""
+    _fields_ = [
+        ("n", ctypes.c_uint32), ("patterns", ctypes.c_uint32), ("max_width", ctypes.c_uint32), ("built", ctypes.c_uint32),
+        ("pattern_bytes", ctypes.c_uint64), ("expansions", ctypes.c_uint64), ("steps", ctypes.c_uint64), ("hits", ctypes.c_uint64),
+        ("occurrences", ctypes.c_uint64), ("kernel_launches", ctypes.c_uint32), ("host_syncs", ctypes.c_uint32),
+        ("ms_build", ctypes.c_float), ("ms_width", ctypes.c_float), ("ms_count", ctypes.c_float), ("ms_emit", ctypes.c_float),
     ]
 
     def asdict(self):
@@ -326,6 +340,10 @@ def load():
         "archon_hip_fm_locate_hits": [vp, vp, u32, vp, ctypes.c_uint64, vp, ctypes.c_uint64, vp],
         "archon_hip_block_fm_locate_hits": [vp, vp, u32, vp, ctypes.c_uint64, vp, ctypes.c_uint64, vp],
         "archon_hip_get_fm_approx_stats": [i32, ctypes.POINTER(FmApproxStats)],
+        "archon_hip_fm_classes": [vp, vp, vp, u32, vp, vp, vp, vp, ctypes.c_uint64, vp],
+        "archon_hip_fm_classes_dev": [vp, vp, vp, u32, vp, vp, vp, vp, ctypes.c_uint64, vp, vp],
+        "archon_hip_block_fm_classes": [vp, vp, vp, u32, vp, vp, vp, vp, ctypes.c_uint64, vp],
+        "archon_hip_get_fm_class_stats": [i32, ctypes.POINTER(FmClassStats)],
         "archon_hip_fm_edit": [vp, vp, vp, u32, u32, vp, vp, ctypes.c_uint64, vp],
         "archon_hip_fm_edit_dev": [vp, vp, vp, u32, u32, vp, vp, ctypes.c_uint64, vp, vp],
         "archon_hip_block_fm_edit": [vp, vp, vp, u32, u32, vp, vp, ctypes.c_uint64, vp],
@@ -528,6 +546,13 @@ def fm_approx_stats(dev=0):
     """FmApproxStats of the calling thread's last approximate call (approx, locate_hits) on dev"""
     s = FmApproxStats()
     _check(lib().archon_hip_get_fm_approx_stats(dev, ctypes.byref(s)))
+    return s
+
+
+def fm_class_stats(dev=0):
+    """FmClassStats of the calling thread's last class call (classes, classes_dev, fm_classes) on dev"""
+    s = FmClassStats()
+    _check(lib().archon_hip_get_fm_class_stats(dev, ctypes.byref(s)))
     return s
 
 
@@ -742,6 +767,58 @@ def _approx(fn, h, patterns, k, hits):
     return nhits, nocc, out[:total.value]
 
 
+def classes_identity():
+    """the class table under which every byte accepts itself alone: a (256, 8) uint32 array, bit c of row b is word c >> 5,
+    bit c & 31 (archon_hip_fm_classes)"""
+    t = np.zeros((256, 8), np.uint32)
+    b = np.arange(256)
+    t[b, b >> 5] = np.uint32(1) << (b & 31).astype(np.uint32)
+    return t
+
+
+def classes_set(table, byte, accepted_bytes):
+    """the table with the class of `byte` set to exactly accepted_bytes (a new array)"""
+    t = np.array(table, np.uint32).reshape(256, 8)
+    b = byte[0] if isinstance(byte, (bytes, bytearray)) else int(byte)
+    t[b] = 0
+    for c in accepted_bytes:            # bytes, or any iterable of values below 256
+        t[b, int(c) >> 5] |= np.uint32(1 << (int(c) & 31))
+    return t
+
+
+def classes_fold_case():
+    """the identity with every ASCII letter accepting both of its cases"""
+    t = classes_identity()
+    for lower in range(ord("a"), ord("z") + 1):
+        both = bytes([lower, lower - 32])
+        t = classes_set(classes_set(t, lower, both), lower - 32, both)
+    return t
+
+
+IUPAC = {"R": "AG", "Y": "CT", "S": "CG", "W": "AT", "K": "GT", "M": "AC", "B": "CGT", "D": "AGT", "H": "ACT", "V": "ACG", "N": "ACGT"}
+
+
+def classes_iupac():
+    """the identity with the 11 IUPAC ambiguity codes (upper case) accepting their bases among ACGT and not themselves"""
+    t = classes_identity()
+    for code, bases in IUPAC.items():
+        t = classes_set(t, ord(code), bases.encode())
+    return t
+
+
+def _class_table(table):
+    t = np.ascontiguousarray(table, np.uint32)
+    if t.size != 256 * 8:
+        raise ValueError("class table: %d words, not 256 x 8" % t.size)
+    return t
+
+
+def _classes(fn, h, patterns, table, hits):
+    """(nhits, nocc, hits or None) of a class call, as _approx gives them"""
+    t = _class_table(table)
+    return _approx(lambda h_, pat, off, n, _k, *rest: fn(h_, pat, off, n, _p(t), *rest), h, patterns, 0, hits)
+
+
 def _edit(fn, h, patterns, k, emit):
     """(nhits, hits or None) of an edit-distance call: the hits into an array of a first guess, then of the size the call gave"""
     packed, offsets = _pack_patterns(patterns)
@@ -890,6 +967,23 @@ class FmIndex:
                                               int(k), ctypes.c_void_p(nhits_t.data_ptr()), ctypes.c_void_p(nocc_t.data_ptr()),
                                               ctypes.c_void_p(hits_t.data_ptr()) if hits_t is not None else None, cap,
                                               ctypes.cast(ctypes.byref(total), ctypes.c_void_p), _stream_ptr()))
+        return total.value
+
+    def classes(self, patterns, table, hits=True):
+        """every distinct string of the block that lies in each pattern's classes under a (256, 8) class table (classes_identity,
+        classes_fold_case, classes_iupac, classes_set): (nhits, nocc, hits), hits an FM_HIT array in ascending order of the
+        strings (None with hits=False: counting only)"""
+        return _classes(lib().archon_hip_fm_classes, self.h, patterns, table, hits)
+
+    def classes_dev(self, patterns_t, offsets_t, table_t, nhits_t, nocc_t, hits_t=None):
+        """torch tensors on the device: patterns uint8, offsets int32[n + 1], the table int32[256 * 8], nhits and nocc int32[n]
+        (written), hits an int32 tensor of 4 words per hit or None; current stream.  Returns the number of hits"""
+        total = ctypes.c_uint64(0)
+        cap = hits_t.numel() // 4 if hits_t is not None else 0
+        _check(lib().archon_hip_fm_classes_dev(self.h, ctypes.c_void_p(patterns_t.data_ptr()), ctypes.c_void_p(offsets_t.data_ptr()), nhits_t.numel(),
+                                               ctypes.c_void_p(table_t.data_ptr()), ctypes.c_void_p(nhits_t.data_ptr()),
+                                               ctypes.c_void_p(nocc_t.data_ptr()), ctypes.c_void_p(hits_t.data_ptr()) if hits_t is not None else None, cap,
+                                               ctypes.cast(ctypes.byref(total), ctypes.c_void_p), _stream_ptr()))
         return total.value
 
     def locate_hits(self, patterns, hits):
@@ -1279,6 +1373,10 @@ class Block:
     def fm_approx(self, patterns, k, hits=True):
         """FmIndex.approx on the resident block's BWT (its FM index built on the first FM call after a forward)"""
         return _approx(lib().archon_hip_block_fm_approx, self.h, patterns, k, hits)
+
+    def fm_classes(self, patterns, table, hits=True):
+        """FmIndex.classes on the resident block's BWT (its FM index built on the first FM call after a forward)"""
+        return _classes(lib().archon_hip_block_fm_classes, self.h, patterns, table, hits)
 
     def fm_edit(self, patterns, k, emit=True):
         """FmIndex.edit on the resident block: its text and the suffix array of its last forward (want_sa=True)"""

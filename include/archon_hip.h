@@ -17,7 +17,8 @@
  *   archon_hip_fm_*         nothing: counting and locating patterns by backward search on the BWT (an FM index), below;
  *                           with a sampled SA and ISA it locates and extracts without the block's suffix array, and it
  *                           finds patterns with up to K substituted bytes (archon_hip_fm_approx)
- *                           and with up to K substituted, inserted or deleted bytes (archon_hip_fm_edit)
+ *                           and with up to K substituted, inserted or deleted bytes (archon_hip_fm_edit), and patterns
+ *                           whose positions each accept a set of bytes (archon_hip_fm_classes)
  *   archon_hip_fm_smems     nothing: the super-maximal exact matches of patterns, with a mirror index (archon_hip_fm_mirror)
  *   archon_hip_fm_ms        nothing: the matching statistics of patterns -- for every position the longest piece ending there
  *                           that occurs, and its rows -- with the block's LCP array beside the index (archon_hip_fm_attach_lcp)
@@ -447,6 +448,77 @@ typedef struct archon_hip_fm_approx_stats {
     float ms_locate;            /* device time of locate_hits' kernel */
 } archon_hip_fm_approx_stats;
 int  archon_hip_get_fm_approx_stats(int dev, archon_hip_fm_approx_stats *out);
+
+/* ---- class search: patterns whose positions each accept a set of bytes ----------------------------------------------------
+ * Case folding, a wildcard at a known position, IUPAC codes: the pattern says WHERE the text may differ and INTO WHAT.
+ * A CLASS TABLE is uint32_t classes[256][8] (8 KiB): bit c of classes[b] is word c >> 5, bit c & 31; when it is set the text
+ * byte c is accepted where the pattern holds byte b.  Pattern bytes are class names: the identity table makes the call
+ * archon_hip_fm_count; classes['a'] = {a, A} folds case; a byte may name a class that does not hold the byte itself, as IUPAC
+ * N = {A, C, G, T} does.  One table serves all patterns of a call.
+ * Keys, R and occ' are those of the search rule above.  Sigma(x) is the set of bytes that occur in the block (the nonempty
+ * buckets, R[c] < R[c+1]); the EFFECTIVE CLASS of position t is M_t = classes[P[t]] cut to Sigma(x).
+ * A HIT of pattern P (length m) is a distinct string w of length m that occurs in x with w[t] in M_t for every t.  Its rows
+ * [lo, hi) are exactly what archon_hip_fm_count(w) returns, its `mismatches` the number of t with w[t] != P[t]; the record
+ * is archon_hip_fm_hit, and archon_hip_fm_locate_hits / archon_hip_block_fm_locate_hits locate these hits as they stand.
+ * The search and its output order are this depth-first procedure, frame(t, lo, hi, d) called first as frame(0, 0, n, 0):
+ *   loop:
+ *     if t == m: emit hit (lo, hi, d); return
+ *     if |M_t| == 1 (its symbol c):  one rank step, as archon_hip_fm_count takes it
+ *         (lo, hi) = the bucket of c if t == 0, else the rank step for c (t >= 1: counted in `steps`)
+ *         if lo >= hi: return
+ *         d += (c != P[t]); t += 1
+ *     else:                          an EXPANSION, as archon_hip_fm_approx takes it
+ *         child[c] = [R[c], R[c+1])                           if t == 0 (the buckets: no rank step, not counted)
+ *                  = [R[c] + occ'(c,lo), R[c] + occ'(c,hi))   if t >= 1 (counted in `expansions`)
+ *         for c in M_t ascending, child[c] nonempty: frame(t+1, child[c], d + (c != P[t]))
+ *         return
+ * So the hits of one pattern come in ascending byte order of their strings w, the patterns in ascending j, and the ranges
+ * of one pattern's hits are disjoint.  m = 0 gives the single hit (0, n, 0); m > n, or an empty M_t at any t, gives no hits
+ * and does no work.  The work counters follow from x, P and the table alone (Sub_t(x): the distinct substrings of length t):
+ *   expansions = sum over t = 1 .. m-1 with |M_t| >= 2 of |{u in Sub_t(x) : u[i] in M_i for all i < t}|
+ *   steps      = the same sum over the t with |M_t| == 1
+ * The WIDTH of a pattern is W = sum over t of (|M_t| - 1); it bounds the frames that can be pending at once (the frames
+ * pushed at position t are at most |M_t| - 1, and the pending ones lie beside one path).  Every call requires W <= 1024 for
+ * every pattern that is searched (a pattern that does no work -- m > n, or an empty M_t -- has no width), otherwise
+ * ARCHON_E_ARG and nothing written.  Because M_t is cut to Sigma(x), a wildcard costs 3 on DNA and 255 on random bytes.
+ * Example: "banana" (BWT nnbaaa, primary row 2, sa = 2 4 6 1 3 5), the identity table with classes['?'] = all bytes, the
+ * pattern "?a": Sigma(x) = {a, b, n}, W = 2; the buckets expand into three children at t = 0 (not counted) and each child
+ * takes one rank step with 'a': 0 expansions, 3 steps.  The child "a" dies at "aa"; the hits are (0, 1, 1) ("ba", start 0)
+ * and then (1, 3, 1) ("na", starts 2 and 4).
+ * Device work: one wave per pattern with a stack of 16-byte frames in LDS, sized by the widest pattern of the call; a pass
+ * over the patterns before the search finds the widths and the patterns with an empty class. */
+/* nhits[k] and nocc[k] (distinct hits, rows summed over them) and *total (the sum of nhits) written by every call that
+ * searches.  hits_or_null NULL: counting only (no emit pass).  cap < *total with hits given: ARCHON_E_ARG, counts and *total
+ * written, hits untouched.  Patterns and offsets as for archon_hip_fm_count; k = 0 writes *total = 0 and nothing else.
+ * NULL classes: ARCHON_E_ARG before the handle is read. */
+int  archon_hip_fm_classes(archon_hip_fm *f, const uint8_t *patterns, const uint32_t *offsets, uint32_t k, const uint32_t *classes,
+                           uint32_t *nhits, uint32_t *nocc, archon_hip_fm_hit *hits_or_null, uint64_t cap, uint64_t *total);
+/* device patterns, offsets, table, nhits, nocc and hits, *total a host pointer; on `stream` (NULL = the context's own),
+ * complete on return; decreasing offsets are found on the device (ARCHON_E_ARG, nothing written) */
+int  archon_hip_fm_classes_dev(archon_hip_fm *f, const uint8_t *d_patterns, const uint32_t *d_offsets, uint32_t k, const uint32_t *d_classes,
+                               uint32_t *d_nhits, uint32_t *d_nocc, archon_hip_fm_hit *d_hits_or_null, uint64_t cap, uint64_t *total,
+                               void *stream);
+/* the resident block's BWT; its table is built on the first FM call after a forward, as for archon_hip_block_fm_approx */
+int  archon_hip_block_fm_classes(archon_hip_block *b, const uint8_t *patterns, const uint32_t *offsets, uint32_t k, const uint32_t *classes,
+                                 uint32_t *nhits, uint32_t *nocc, archon_hip_fm_hit *hits_or_null, uint64_t cap, uint64_t *total);
+/* the CALLING THREAD's last class call on `dev`; class calls leave every other statistics record alone */
+typedef struct archon_hip_fm_class_stats {
+    uint32_t n;                 /* block size of the index */
+    uint32_t patterns;          /* k of the call */
+    uint32_t max_width;         /* the largest W of the call's searched patterns, saturating (above 1024: the call was refused) */
+    uint32_t built;             /* 1 when the call built the block's table */
+    uint64_t pattern_bytes;     /* bytes of the patterns */
+    uint64_t expansions;        /* expansions at t >= 1 (count pass) */
+    uint64_t steps;             /* single rank steps at t >= 1 (count pass) */
+    uint64_t hits;              /* hits found */
+    uint64_t occurrences;       /* rows summed over those hits */
+    uint32_t kernel_launches;   /* launches issued by the call */
+    uint32_t host_syncs;        /* times the host waited for the stream inside the call */
+    float ms_build;             /* device time of the table build, 0 without one */
+    float ms_width;             /* device time of the pass that finds the widths (HIP events) */
+    float ms_count, ms_emit;    /* device time of the count and the emit pass */
+} archon_hip_fm_class_stats;
+int  archon_hip_get_fm_class_stats(int dev, archon_hip_fm_class_stats *out);
 
 /* ---- edit-distance search: patterns with up to K substituted, inserted or deleted bytes -----------------------------------
  * x is the block (n bytes), P a pattern of m bytes, K the allowed errors: an error is a substitution, an insertion or a
