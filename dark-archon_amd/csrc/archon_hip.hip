@@ -164,55 +164,59 @@ int ctx_get(int dev, Ctx **out)
     std::lock_guard<std::mutex> lk(g_ctx_mu);
     ARCHON_HIP_TRY(hipSetDevice(dev));
     if (!g_ctx[dev][slot]) {
-        Ctx *c = new Ctx();
+        // published after its last allocation: one that fails frees what was made, on this device
+        std::unique_ptr<Ctx> c(new Ctx());
         c->dev = dev;
         memset(&c->stats, 0, sizeof c->stats);
         ARCHON_HIP_TRY(hipStreamCreateWithFlags(&c->own_stream, hipStreamNonBlocking));
         ARCHON_HIP_TRY(hipHostMalloc((void **)&c->h_mail, mail::kWords * sizeof(uint32_t), hipHostMallocDefault));
         memset(c->h_mail, 0, mail::kWords * sizeof(uint32_t));
         ARCHON_HIP_TRY(hipHostGetDevicePointer((void **)&c->h_mail_dev, c->h_mail, 0));      // (coherent: bs::k_mail writes the block's summary there)
-        ARCHON_HIP_TRY(hipMalloc((void **)&c->d_mail, mail::kDevWords * sizeof(uint32_t)));
-        g_ctx[dev][slot] = c;
+        ARCHON_TRY(c->mail_dev.alloc(mail::kDevWords * sizeof(uint32_t), "context mailbox"));
+        g_ctx[dev][slot] = c.release();
     }
     *out = g_ctx[dev][slot];
     return ARCHON_OK;
 }
 
-// Grows a buffer of a context (*p, *have bytes) to `want` bytes when it holds fewer than `need`: the device is idle before
-// the old buffer goes.  `fail` is the message of a failed allocation, given the bytes asked for.
-static int regrow(char **p, size_t *have, size_t need, size_t want, const char *fail)
+// what the DevBufs of a context do not own; the caller has set the device (ctx_get, archon_hip_release)
+Ctx::~Ctx()
 {
-    if (need <= *have) return ARCHON_OK;
+    if (h_mail) (void)hipHostFree(h_mail);
+    for (hipEvent_t e : ev_pool)
+        if (e) (void)hipEventDestroy(e);
+    if (own_stream) (void)hipStreamDestroy(own_stream);
+}
+
+// Grows a buffer of a context to `want` bytes when it holds fewer than `need`: the device is idle before the old buffer
+// goes.  `fail` is the message of a failed allocation, given the bytes asked for.
+static int regrow(DevBuf &b, size_t need, size_t want, const char *fail)
+{
+    if (need <= b.bytes) return ARCHON_OK;
     ARCHON_HIP_TRY(hipDeviceSynchronize());
-    if (*p) {
-        ARCHON_HIP_TRY(hipFree(*p));
-        *p = nullptr;
-        *have = 0;
-    }
-    if (hipMalloc((void **)p, want) != hipSuccess) {
-        (void)hipGetLastError();
+    ARCHON_HIP_TRY(b.release());
+    if (b.alloc(want, "context") != ARCHON_OK) {
         set_error(fail, want);
         return ARCHON_E_NOMEM;
     }
-    *have = want;
     return ARCHON_OK;
 }
 
 int ctx_ensure_arena(Ctx *c, size_t bytes)
 {
-    return regrow(&c->arena, &c->arena_bytes, bytes, bytes + (bytes >> 4) + (1u << 20), "device arena allocation of %zu bytes failed");
+    return regrow(c->arena, bytes, bytes + (bytes >> 4) + (1u << 20), "device arena allocation of %zu bytes failed");
 }
 
 // the second tier grows like the first; growing it never touches the first (a forward call asks for it in mid-flight)
 static int ctx_ensure_arena2(Ctx *c, size_t bytes)
 {
-    return regrow(&c->arena2, &c->arena2_bytes, bytes, bytes + (bytes >> 4) + (1u << 20), "device arena allocation of %zu bytes (general stage) failed");
+    return regrow(c->arena2, bytes, bytes + (bytes >> 4) + (1u << 20), "device arena allocation of %zu bytes (general stage) failed");
 }
 
 int ctx_io(Ctx *c, int slot, size_t bytes, void **out)
 {
-    ARCHON_TRY(regrow(&c->io[slot], &c->io_bytes[slot], bytes, bytes + 256, "device staging allocation of %zu bytes failed"));
-    *out = c->io[slot];
+    ARCHON_TRY(regrow(c->io[slot], bytes, bytes + 256, "device staging allocation of %zu bytes failed"));
+    *out = c->io[slot].p;
     return ARCHON_OK;
 }
 
@@ -942,7 +946,7 @@ int Fwd::general_buffers()
 {
     if (B.rank) return ARCHON_OK;
     { Carve count; ARCHON_TRY(ctx_ensure_arena2(c, fwd_tier2(count, B, n))); }
-    Carve a2{c->arena2, 0, c->arena2_bytes};
+    Carve a2{c->arena2.p, 0, c->arena2.bytes};
     fwd_tier2(a2, B, n);
     if (!a2.ok()) { set_error("arena exhausted (general stage)"); return ARCHON_E_NOMEM; }
     B.rwb.r1 = B.rwb.r2 = nullptr;
@@ -964,8 +968,8 @@ int Fwd::setup()
     c->stats.n = n;
 
     // tier 1 from the arena's bottom up to the closed-form tail, which lies at a fixed distance from the arena's end
-    tail_at = (c->arena_bytes - kClosedTail) & ~size_t(255);
-    Carve a1{c->arena, 0, tail_at};
+    tail_at = (c->arena.bytes - kClosedTail) & ~size_t(255);
+    Carve a1{c->arena.p, 0, tail_at};
     fwd_tier1(a1, B, n, c->dev, d_sa_user == nullptr);
     if (!a1.ok()) { set_error("arena exhausted (tier 1 of a %u-byte block reaches the closed-form tail)", n); return ARCHON_E_NOMEM; }
     tier1_bytes = arena_bytes = a1.off;
@@ -1287,7 +1291,7 @@ static int forward_run(Ctx *c, hipStream_t s, const uint8_t *d_x_in, uint32_t n,
 int Fwd::closed_form()
 {
     const uint32_t p = c->h_mail[mail::kProbe.at], m2 = 2u * p;
-    Carve t{c->arena + tail_at, 0, kClosedTail};
+    Carve t{c->arena.p + tail_at, 0, kClosedTail};
     uint32_t *sa2 = t.take<uint32_t>(m2);
     uint32_t *off = t.take<uint32_t>(m2 + 1);
     uint8_t *bwt2 = t.take<uint8_t>(m2);
@@ -1299,7 +1303,7 @@ int Fwd::closed_form()
     // the nested call asks for no more than the arena holds: it neither grows nor frees it, and its tier 1 ends below the tail
     FwdBuf nb{};
     Carve count;
-    if (fwd_tier1(count, nb, m2, c->dev, false) > c->arena_bytes) {
+    if (fwd_tier1(count, nb, m2, c->dev, false) > c->arena.bytes) {
         set_error("closed form: tier 1 of the %u-byte block of period %u does not fit below the tail", m2, p);
         return ARCHON_E_INTERNAL;
     }
@@ -1311,7 +1315,7 @@ int Fwd::closed_form()
     // Tier 1 again, for the expansion.  The nested call carved it from the bottom: of the aligned copy of the text (B.xa) only
     // the slot is kept, so that tile_lo lands behind it -- its first 2p + 64 bytes are still the text (the nested block read them
     // in place), the rest was overwritten, and k_expand reads nothing of x but x[0].
-    Carve a{c->arena, 0, tail_at};
+    Carve a{c->arena.p, 0, tail_at};
     if (x_in_arena) (void)a.take<uint8_t>((size_t)n + 64);
     const uint32_t ntiles = div_up(n, pf::kTile);
     uint32_t *tile_lo = a.take<uint32_t>((size_t)ntiles + 2);
@@ -1687,7 +1691,7 @@ int archon_hip_forward(const uint8_t *x, uint32_t n, uint32_t *sa_or_null, uint8
         ARCHON_TRY(ctx_io(c, 0, (size_t)n + 64, (void **)&d_x));
         ARCHON_TRY(ctx_io(c, 1, (size_t)n + 64, (void **)&d_bwt));
         if (sa_or_null) ARCHON_TRY(ctx_io(c, 2, (size_t)n * 4, (void **)&d_sa));
-        uint32_t *d_base = c->d_mail + mail::kDevBase.at;
+        uint32_t *d_base = c->d_mail() + mail::kDevBase.at;
         ARCHON_HIP_TRY(hipMemcpyAsync(d_x, x, n, hipMemcpyHostToDevice, s));
         ARCHON_TRY(keep_stats(c, forward_run(c, s, d_x, n, d_sa, d_bwt, d_base)));
         // BWT first (the block coder's enWrite can start on it), then the 4N bytes of the suffix array
@@ -2478,16 +2482,20 @@ int archon_hip_get_fm_doc_stats(int dev, archon_hip_fm_doc_stats *out)
 // What a block-coder object keeps on the device between enCompute, validate and enWrite (bwt/a7/src/main.cpp:39-46): the
 // block, its suffix array and its BWT, in buffers of its own.  The state belongs to the HANDLE -- any number of objects on
 // any number of threads; the compute arena is the calling thread's context, held only for the duration of a call.
-struct archon_hip_block {
+struct FmRelease {
+    void operator()(archon_hip_fm *f) const { fm_release(f); }
+};
+struct ARCHON_LOCAL archon_hip_block {
     int dev = 0;
     std::mutex mu;
-    uint8_t *d_x = nullptr, *d_bwt = nullptr;
-    uint32_t *d_sa = nullptr;
-    size_t cap_x = 0, cap_sa = 0;
+    DevBuf x, bwt, sa;                  // n + 64 bytes each (x and bwt: both or neither), 4 n + 64; freed by archon_hip_block_destroy
+    uint8_t *d_x() const { return reinterpret_cast<uint8_t *>(x.p); }
+    uint8_t *d_bwt() const { return reinterpret_cast<uint8_t *>(bwt.p); }
+    uint32_t *d_sa() const { return reinterpret_cast<uint32_t *>(sa.p); }
     uint32_t n = 0, base = 0;
     bool valid = false, has_sa = false;
     archon_hip_stats stats;
-    archon_hip_fm *fm = nullptr;        // the FM index over d_bwt, built by the first FM call after a forward
+    std::unique_ptr<archon_hip_fm, FmRelease> fm;   // the FM index over d_bwt, built by the first FM call after a forward
 };
 
 // what a call that reads the resident block (with_sa: and its suffix array) asks first, under the block's lock
@@ -2500,29 +2508,19 @@ static int block_check(const archon_hip_block *b, bool with_sa)
 
 static int block_reserve(archon_hip_block *b, uint32_t n, bool want_sa)
 {
-    const size_t need = (size_t)n + 64;
-    if (need > b->cap_x) {
-        if (b->d_x) (void)hipFree(b->d_x);
-        if (b->d_bwt) (void)hipFree(b->d_bwt);
-        b->d_x = b->d_bwt = nullptr;
-        b->cap_x = 0;
-        if (hipMalloc((void **)&b->d_x, need) != hipSuccess || hipMalloc((void **)&b->d_bwt, need) != hipSuccess) {
-            (void)hipGetLastError();
-            set_error("resident block: device allocation of 2 x %zu bytes failed", need);
+    // the old ones go before the new ones are made: at 1 GiB blocks the peak matters
+    const size_t need = (size_t)n + 64, need_sa = (size_t)n * 4 + 64;
+    if (need > b->x.bytes) {
+        (void)b->x.release();
+        (void)b->bwt.release();
+        if (b->x.alloc(need, "resident block") != ARCHON_OK || b->bwt.alloc(need, "resident block") != ARCHON_OK) {
+            (void)b->x.release();       // both or neither
             return ARCHON_E_NOMEM;
         }
-        b->cap_x = need;
     }
-    if (want_sa && (size_t)n * 4 > b->cap_sa) {
-        if (b->d_sa) (void)hipFree(b->d_sa);
-        b->d_sa = nullptr;
-        b->cap_sa = 0;
-        if (hipMalloc((void **)&b->d_sa, (size_t)n * 4 + 64) != hipSuccess) {
-            (void)hipGetLastError();
-            set_error("resident block: device allocation of %zu bytes failed", (size_t)n * 4 + 64);
-            return ARCHON_E_NOMEM;
-        }
-        b->cap_sa = (size_t)n * 4;
+    if (want_sa && need_sa > b->sa.bytes) {
+        (void)b->sa.release();
+        ARCHON_TRY(b->sa.alloc(need_sa, "resident block"));
     }
     return ARCHON_OK;
 }
@@ -2543,12 +2541,13 @@ void archon_hip_block_destroy(archon_hip_block *b)
     if (!b) return;
     {
         std::lock_guard<std::mutex> lk(b->mu);
-        fm_release(b->fm);
-        if (b->d_x || b->d_sa) {
+        b->fm.reset();
+        // an empty block (a thread's default block at thread exit) touches no device; bwt is there exactly when x is
+        if (b->x || b->sa) {
             (void)hipSetDevice(b->dev);
-            if (b->d_x) (void)hipFree(b->d_x);
-            if (b->d_bwt) (void)hipFree(b->d_bwt);
-            if (b->d_sa) (void)hipFree(b->d_sa);
+            (void)b->x.release();
+            (void)b->bwt.release();
+            (void)b->sa.release();
         }
     }
     delete b;
@@ -2560,14 +2559,13 @@ int archon_hip_block_forward(archon_hip_block *b, const uint8_t *x, uint32_t n, 
     ARCHON_TRY(check_n(n));
     std::lock_guard<std::mutex> lkb(b->mu);
     b->valid = false;
-    fm_release(b->fm);
-    b->fm = nullptr;
+    b->fm.reset();
     return with_ctx(b->dev, nullptr, [&](Ctx *c, hipStream_t s) -> int {
         ARCHON_TRY(block_reserve(b, n, sa_or_null != nullptr));
-        uint32_t *d_sa = sa_or_null ? b->d_sa : nullptr;
-        uint32_t *d_base = c->d_mail + mail::kDevBase.at;
-        ARCHON_HIP_TRY(hipMemcpyAsync(b->d_x, x, n, hipMemcpyHostToDevice, s));
-        ARCHON_TRY(forward_run(c, s, b->d_x, n, d_sa, b->d_bwt, d_base));
+        uint32_t *d_sa = sa_or_null ? b->d_sa() : nullptr;
+        uint32_t *d_base = c->d_mail() + mail::kDevBase.at;
+        ARCHON_HIP_TRY(hipMemcpyAsync(b->d_x(), x, n, hipMemcpyHostToDevice, s));
+        ARCHON_TRY(forward_run(c, s, b->d_x(), n, d_sa, b->d_bwt(), d_base));
         ARCHON_HIP_TRY(hipMemcpyAsync(base_id, d_base, 4, hipMemcpyDeviceToHost, s));
         if (sa_or_null) ARCHON_HIP_TRY(hipMemcpyAsync(sa_or_null, d_sa, (size_t)n * 4, hipMemcpyDeviceToHost, s));
         ARCHON_SYNC(s);
@@ -2587,7 +2585,7 @@ int archon_hip_block_read_bwt(archon_hip_block *b, uint32_t offset, uint32_t len
     std::lock_guard<std::mutex> lkb(b->mu);
     if (!b->valid || (uint64_t)offset + len > b->n) { set_error("no resident BWT for that range"); return ARCHON_E_ARG; }
     ARCHON_HIP_TRY(hipSetDevice(b->dev));
-    ARCHON_HIP_TRY(hipMemcpy(dst, b->d_bwt + offset, len, hipMemcpyDeviceToHost));
+    ARCHON_HIP_TRY(hipMemcpy(dst, b->d_bwt() + offset, len, hipMemcpyDeviceToHost));
     return ARCHON_OK;
 }
 
@@ -2596,7 +2594,19 @@ int archon_hip_block_validate(archon_hip_block *b)
     if (!b) { set_error("null pointer"); return ARCHON_E_ARG; }
     std::lock_guard<std::mutex> lkb(b->mu);
     ARCHON_TRY(block_check(b, true));
-    return with_ctx(b->dev, nullptr, [&](Ctx *c, hipStream_t s) -> int { return validate_resident_run(c, s, b->d_x, b->n, b->d_sa, b->d_bwt, b->base); });
+    return with_ctx(b->dev, nullptr, [&](Ctx *c, hipStream_t s) -> int { return validate_resident_run(c, s, b->d_x(), b->n, b->d_sa(), b->d_bwt(), b->base); });
+}
+
+// The resident LCP array into staging buffer 1, its record kept for the thread whether or not the run succeeded, its time
+// into *ms_lcp_or_null when it did
+static int block_lcp_step(Ctx *c, hipStream_t s, const archon_hip_block *b, uint32_t **d_lcp, float *ms_lcp_or_null)
+{
+    ARCHON_TRY(ctx_io(c, 1, (size_t)b->n * 4 + 64, (void **)d_lcp));
+    archon_hip_lcp_stats st = {};
+    const int rc = lcp_run(c, s, b->d_x(), b->n, b->d_sa(), b->d_bwt(), *d_lcp, &st);
+    t_lcp_stats.keep(b->dev, st);
+    if (rc == ARCHON_OK && ms_lcp_or_null) *ms_lcp_or_null = st.ms_total;
+    return rc;
 }
 
 // the result through a staging buffer
@@ -2607,11 +2617,7 @@ int archon_hip_block_lcp(archon_hip_block *b, uint32_t *lcp)
     ARCHON_TRY(block_check(b, true));
     return with_ctx(b->dev, nullptr, [&](Ctx *c, hipStream_t s) -> int {
         uint32_t *d_lcp = nullptr;
-        ARCHON_TRY(ctx_io(c, 1, (size_t)b->n * 4 + 64, (void **)&d_lcp));
-        archon_hip_lcp_stats st = {};
-        const int rc = lcp_run(c, s, b->d_x, b->n, b->d_sa, b->d_bwt, d_lcp, &st);
-        t_lcp_stats.keep(b->dev, st);
-        ARCHON_TRY(rc);
+        ARCHON_TRY(block_lcp_step(c, s, b, &d_lcp, nullptr));
         ARCHON_HIP_TRY(hipMemcpyAsync(lcp, d_lcp, (size_t)b->n * 4, hipMemcpyDeviceToHost, s));
         ARCHON_SYNC(s);
         return ARCHON_OK;
@@ -2631,13 +2637,8 @@ int archon_hip_block_repeats(archon_hip_block *b, uint32_t kind, uint32_t min_le
         KeepStats<archon_hip_repeat_stats> keep(t_rep_stats, b->dev);
         rep_call_stats(&keep.st, b->n, kind, min_len, min_occ);
         uint32_t *d_lcp = nullptr;
-        ARCHON_TRY(ctx_io(c, 1, (size_t)b->n * 4 + 64, (void **)&d_lcp));
-        archon_hip_lcp_stats st = {};
-        const int rc = lcp_run(c, s, b->d_x, b->n, b->d_sa, b->d_bwt, d_lcp, &st);
-        t_lcp_stats.keep(b->dev, st);
-        ARCHON_TRY(rc);
-        keep.st.ms_lcp = st.ms_total;
-        RepCall q = {d_lcp, b->d_bwt, b->n, b->base, kind, min_len, min_occ};
+        ARCHON_TRY(block_lcp_step(c, s, b, &d_lcp, &keep.st.ms_lcp));
+        RepCall q = {d_lcp, b->d_bwt(), b->n, b->base, kind, min_len, min_occ};
         return rep_to_host(c, s, q, out_or_null, cap, total, &keep.st);
     });
 }
@@ -2656,15 +2657,10 @@ int archon_hip_block_lz(archon_hip_block *b, uint32_t dir, archon_hip_lpf_rec *l
         lz_call_stats(&keep.st, b->n, dir);
         uint32_t *d_lcp = nullptr;
         archon_hip_lpf_rec *d_lpf = nullptr;
-        ARCHON_TRY(ctx_io(c, 1, (size_t)b->n * 4 + 64, (void **)&d_lcp));
-        ARCHON_TRY(ctx_io(c, 0, (size_t)b->n * 8 + 64, (void **)&d_lpf));
-        archon_hip_lcp_stats st = {};
-        const int rc = lcp_run(c, s, b->d_x, b->n, b->d_sa, b->d_bwt, d_lcp, &st);
-        t_lcp_stats.keep(b->dev, st);
-        ARCHON_TRY(rc);
-        keep.st.ms_lcp = st.ms_total;
+        ARCHON_TRY(ctx_io(c, 0, (size_t)b->n * 8 + 64, (void **)&d_lpf));       // (before the LCP runs: a refusal leaves no record of it)
+        ARCHON_TRY(block_lcp_step(c, s, b, &d_lcp, &keep.st.ms_lcp));
         StageTimer tm(c, 96, s);
-        ARCHON_TRY(lpf_run(c, s, tm, b->d_sa, d_lcp, b->n, dir, d_lpf, &keep.st));
+        ARCHON_TRY(lpf_run(c, s, tm, b->d_sa(), d_lcp, b->n, dir, d_lpf, &keep.st));
         if (lpf_or_null) ARCHON_HIP_TRY(hipMemcpyAsync(lpf_or_null, d_lpf, (size_t)b->n * 8, hipMemcpyDeviceToHost, s));
         ParseCall q = {reinterpret_cast<const uint32_t *>(d_lpf), b->n};
         return parse_to_host(c, s, tm, q, out_or_null, cap, total, &keep.st);     // (its count waits for the stream: the records have arrived)
@@ -2674,7 +2670,11 @@ int archon_hip_block_lz(archon_hip_block *b, uint32_t dir, archon_hip_lpf_rec *l
 // The block's FM handle over its own BWT, built by the first FM call after a forward: its build into *st, which then says built
 static int block_fm_table(Ctx *c, hipStream_t s, archon_hip_block *b, archon_hip_fm_stats *st)
 {
-    return b->fm ? ARCHON_OK : fm_build(c, s, nullptr, b->d_bwt, false, b->n, b->base, &b->fm, st);
+    if (b->fm) return ARCHON_OK;
+    archon_hip_fm *f = nullptr;
+    ARCHON_TRY(fm_build(c, s, nullptr, b->d_bwt(), false, b->n, b->base, &f, st));
+    b->fm.reset(f);
+    return ARCHON_OK;
 }
 
 // the same for a call that keeps another record: a table built here is this call's work, into its own record, while fm_stats
@@ -2712,7 +2712,7 @@ int archon_hip_block_fm_count(archon_hip_block *b, const uint8_t *patterns, cons
     return with_ctx(b->dev, nullptr, [&](Ctx *c, hipStream_t s) -> int {
         KeepStats<archon_hip_fm_stats> keep(t_fm_stats, b->dev);
         ARCHON_TRY(block_fm_table(c, s, b, &keep.st));
-        return fm_count_host(c, s, b->fm, patterns, offsets, k, lo, hi, &keep.st);
+        return fm_count_host(c, s, b->fm.get(), patterns, offsets, k, lo, hi, &keep.st);
     });
 }
 
@@ -2728,7 +2728,7 @@ int archon_hip_block_fm_locate(archon_hip_block *b, const uint8_t *patterns, con
     return with_ctx(b->dev, nullptr, [&](Ctx *c, hipStream_t s) -> int {
         KeepStats<archon_hip_fm_stats> keep(t_fm_stats, b->dev);
         ARCHON_TRY(block_fm_table(c, s, b, &keep.st));
-        return fm_locate_host(c, s, b->fm, b->d_sa, patterns, offsets, k, pos, cap, total, &keep.st, nullptr);
+        return fm_locate_host(c, s, b->fm.get(), b->d_sa(), patterns, offsets, k, pos, cap, total, &keep.st, nullptr);
     });
 }
 
@@ -2743,12 +2743,12 @@ int archon_hip_block_fm_index(archon_hip_block *b, uint32_t rate, archon_hip_fm 
         archon_hip_fm *f = nullptr;
         {
             KeepStats<archon_hip_fm_stats> keep(t_fm_stats, b->dev);
-            ARCHON_TRY(fm_build(c, s, nullptr, b->d_bwt, true, b->n, b->base, &f, &keep.st));
+            ARCHON_TRY(fm_build(c, s, nullptr, b->d_bwt(), true, b->n, b->base, &f, &keep.st));
         }
         // the samples' record is kept once there is a table to sample
         KeepStats<archon_hip_fm_walk_stats> keep(t_fmw_stats, b->dev);
         const bool from_sa = b->has_sa && !g_route.fm_sample_walk;
-        const int rc = fm_sample_run(c, s, f, rbits, from_sa ? b->d_sa : nullptr, &keep.st);
+        const int rc = fm_sample_run(c, s, f, rbits, from_sa ? b->d_sa() : nullptr, &keep.st);
         if (rc != ARCHON_OK) fm_release(f);
         else *out = f;
         return rc;
@@ -2769,7 +2769,7 @@ int archon_hip_block_fm_approx(archon_hip_block *b, const uint8_t *patterns, con
         KeepStats<archon_hip_fm_approx_stats> keep(t_fma_stats, b->dev);
         fma_call_stats(&keep.st, b->n, k, max_mismatches);
         ARCHON_TRY(block_fm_table_own(c, s, b, &keep.st));
-        return fm_search_host(c, s, FmaSearch{max_mismatches}, b->fm, patterns, offsets, k, nhits, nocc, hits_or_null, cap, total, &keep.st);
+        return fm_search_host(c, s, FmaSearch{max_mismatches}, b->fm.get(), patterns, offsets, k, nhits, nocc, hits_or_null, cap, total, &keep.st);
     });
 }
 
@@ -2785,7 +2785,7 @@ int archon_hip_block_fm_classes(archon_hip_block *b, const uint8_t *patterns, co
         KeepStats<archon_hip_fm_class_stats> keep(t_fmc_stats, b->dev);
         fmc_call_stats(&keep.st, b->n, k);
         ARCHON_TRY(block_fm_table_own(c, s, b, &keep.st));
-        return fm_search_host(c, s, FmcSearch{classes, nullptr}, b->fm, patterns, offsets, k, nhits, nocc, hits_or_null, cap, total, &keep.st);
+        return fm_search_host(c, s, FmcSearch{classes, nullptr}, b->fm.get(), patterns, offsets, k, nhits, nocc, hits_or_null, cap, total, &keep.st);
     });
 }
 
@@ -2800,7 +2800,7 @@ int archon_hip_block_fm_locate_hits(archon_hip_block *b, const uint32_t *offsets
     return with_ctx(b->dev, nullptr, [&](Ctx *c, hipStream_t s) -> int {
         KeepStats<archon_hip_fm_approx_stats> keep(t_fma_stats, b->dev);
         fma_call_stats(&keep.st, b->n, k, 0);
-        return fma_locate(c, s, nullptr, b->d_sa, offsets, k, hits, nhits, pos, cap, total, &keep.st);
+        return fma_locate(c, s, nullptr, b->d_sa(), offsets, k, hits, nhits, pos, cap, total, &keep.st);
     });
 }
 
@@ -2818,7 +2818,7 @@ int archon_hip_block_fm_edit(archon_hip_block *b, const uint8_t *patterns, const
         KeepStats<archon_hip_fm_edit_stats> keep(t_fme_stats, b->dev);
         fme_call_stats(&keep.st, b->n, k, max_errors);
         ARCHON_TRY(block_fm_table_own(c, s, b, &keep.st));
-        return fme_host(c, s, b->fm, b->d_sa, b->d_x, patterns, offsets, k, max_errors, nhits, hits_or_null, cap, total, &keep.st);
+        return fme_host(c, s, b->fm.get(), b->d_sa(), b->d_x(), patterns, offsets, k, max_errors, nhits, hits_or_null, cap, total, &keep.st);
     });
 }
 
@@ -2831,7 +2831,7 @@ int archon_hip_block_fm_mirror(archon_hip_block *b, archon_hip_fm *f)
     return with_ctx(b->dev, nullptr, [&](Ctx *c, hipStream_t s) -> int {
         KeepStats<archon_hip_fm_mem_stats> keep(t_fmm_stats, b->dev);
         fmm_call_stats(&keep.st, f, f->n, 0, 0);
-        return fmm_mirror_run(c, s, f, b->d_x, false, &keep.st);
+        return fmm_mirror_run(c, s, f, b->d_x(), false, &keep.st);
     });
 }
 
@@ -2846,17 +2846,12 @@ int archon_hip_block_fm_attach_lcp(archon_hip_block *b, archon_hip_fm *f)
         KeepStats<archon_hip_fm_ms_stats> keep(t_fms_stats, b->dev);
         fms_call_stats(&keep.st, f, 0);
         uint32_t *d_lcp = nullptr;
-        ARCHON_TRY(ctx_io(c, 1, (size_t)b->n * 4 + 64, (void **)&d_lcp));
-        archon_hip_lcp_stats st = {};
-        const int rc = lcp_run(c, s, b->d_x, b->n, b->d_sa, b->d_bwt, d_lcp, &st);
-        t_lcp_stats.keep(b->dev, st);
-        ARCHON_TRY(rc);
-        keep.st.ms_lcp = st.ms_total;
+        ARCHON_TRY(block_lcp_step(c, s, b, &d_lcp, &keep.st.ms_lcp));
         return fms_attach_run(c, s, f, nullptr, d_lcp, &keep.st);
     });
 }
 
-// the resident suffix array into the handle, device to device (the LCP step reads b->d_sa and leaves it as it is)
+// the resident suffix array into the handle, device to device (the LCP step reads b->d_sa() and leaves it as it is)
 int archon_hip_block_fm_attach_sa(archon_hip_block *b, archon_hip_fm *f)
 {
     if (!b || !f) { set_error("null pointer"); return ARCHON_E_ARG; }
@@ -2866,7 +2861,7 @@ int archon_hip_block_fm_attach_sa(archon_hip_block *b, archon_hip_fm *f)
     return with_ctx(b->dev, nullptr, [&](Ctx *c, hipStream_t s) -> int {
         KeepStats<archon_hip_fm_text_stats> keep(t_fmt_stats, b->dev);
         fmt_call_stats(&keep.st, f, 0);
-        return fmt_attach_run(c, s, f, nullptr, b->d_sa, &keep.st);
+        return fmt_attach_run(c, s, f, nullptr, b->d_sa(), &keep.st);
     });
 }
 
@@ -2882,7 +2877,7 @@ int archon_hip_block_fm_attach_docs(archon_hip_block *b, archon_hip_fm *f, const
     return with_ctx(b->dev, nullptr, [&](Ctx *c, hipStream_t s) -> int {
         KeepStats<archon_hip_fm_doc_stats> keep(t_fmd_stats, b->dev);
         fmd_call_stats(&keep.st, f, 0);
-        return fmd_attach_run(c, s, f, b->d_sa, bounds, nullptr, ndocs, &keep.st);
+        return fmd_attach_run(c, s, f, b->d_sa(), bounds, nullptr, ndocs, &keep.st);
     });
 }
 
@@ -2896,7 +2891,7 @@ int archon_hip_block_fm_locate_mems(archon_hip_block *b, const archon_hip_fm_mem
     return with_ctx(b->dev, nullptr, [&](Ctx *c, hipStream_t s) -> int {
         KeepStats<archon_hip_fm_mem_stats> keep(t_fmm_stats, b->dev);
         fmm_call_stats(&keep.st, nullptr, b->n, 0, 0);
-        return fmm_locate(c, s, nullptr, b->d_sa, mems, nmems, pos, cap, total, &keep.st);
+        return fmm_locate(c, s, nullptr, b->d_sa(), mems, nmems, pos, cap, total, &keep.st);
     });
 }
 
@@ -3042,17 +3037,14 @@ int archon_hip_hist256(const uint8_t *x, size_t n, uint32_t out[256], int dev)
 {
     if (!x || !out) { set_error("null pointer"); return ARCHON_E_ARG; }
     return with_ctx(dev, nullptr, [&](Ctx *c, hipStream_t s) -> int {
-        uint8_t *d_x = nullptr;
-        ARCHON_HIP_TRY(hipMalloc((void **)&d_x, n + 64));
-        hipError_t e = hipMemcpyAsync(d_x, x, n, hipMemcpyHostToDevice, s);
-        int rc = ARCHON_OK;
-        uint32_t *d_counts = c->d_mail + mail::kDevCounts.at;
-        if (e == hipSuccess) rc = launch_hist256(s, d_x, n, d_counts, n);
-        if (e == hipSuccess && rc == ARCHON_OK) e = hipMemcpyAsync(out, d_counts, 256 * 4, hipMemcpyDeviceToHost, s);
-        if (e == hipSuccess) e = hipStreamSynchronize(s);
-        (void)hipFree(d_x);
-        if (e != hipSuccess) { set_error("HIP call failed: %s", hipGetErrorString(e)); return ARCHON_E_HIP; }
-        return rc;
+        DevBuf buf;         // freed when the stream has been waited for (a step that fails leaves it to hipFree, which waits)
+        ARCHON_TRY(buf.alloc(n + 64, "hist256"));
+        uint32_t *d_counts = c->d_mail() + mail::kDevCounts.at;
+        ARCHON_HIP_TRY(hipMemcpyAsync(buf.p, x, n, hipMemcpyHostToDevice, s));
+        ARCHON_TRY(launch_hist256(s, reinterpret_cast<const uint8_t *>(buf.p), n, d_counts, n));
+        ARCHON_HIP_TRY(hipMemcpyAsync(out, d_counts, 256 * 4, hipMemcpyDeviceToHost, s));
+        ARCHON_HIP_TRY(hipStreamSynchronize(s));
+        return ARCHON_OK;
     });
 }
 
@@ -3088,7 +3080,7 @@ int archon_hip_validate(const uint8_t *x, uint32_t n, const uint32_t *sa, int de
 static int sa_to_bwt_run(Ctx *c, hipStream_t s, const uint8_t *d_x, uint32_t n, const uint32_t *d_sa, uint8_t *d_bwt,
                          uint32_t *d_base_out)
 {
-    uint32_t *res = c->d_mail + mail::kDevSaRes.at;      // [0] bad value seen, [1] rows holding n, [2] the primary index
+    uint32_t *res = c->d_mail() + mail::kDevSaRes.at;      // [0] bad value seen, [1] rows holding n, [2] the primary index
     uint32_t *rd = c->h_mail + mail::kRead.at;
     ARCHON_HIP_TRY(hipMemsetAsync(res, 0, 3 * sizeof(uint32_t), s));
     hipLaunchKernelGGL(fwd::k_sa_to_bwt, dim3(div_up(div_up(n, 4), 256)), dim3(256), 0, s, d_x, d_sa, n, d_bwt, res + 2, res);
@@ -3124,9 +3116,9 @@ int archon_hip_sa_to_bwt(const uint8_t *x, uint32_t n, const uint32_t *sa, uint8
         ARCHON_TRY(ctx_io(c, 2, (size_t)n * 4 + 64, (void **)&d_sa));
         ARCHON_HIP_TRY(hipMemcpyAsync(d_x, x, n, hipMemcpyHostToDevice, s));
         ARCHON_HIP_TRY(hipMemcpyAsync(d_sa, sa, (size_t)n * 4, hipMemcpyHostToDevice, s));
-        ARCHON_TRY(sa_to_bwt_run(c, s, d_x, n, d_sa, d_bwt, c->d_mail + mail::kDevSaBase.at));
+        ARCHON_TRY(sa_to_bwt_run(c, s, d_x, n, d_sa, d_bwt, c->d_mail() + mail::kDevSaBase.at));
         ARCHON_HIP_TRY(hipMemcpyAsync(bwt, d_bwt, n, hipMemcpyDeviceToHost, s));
-        ARCHON_HIP_TRY(hipMemcpyAsync(base_id, c->d_mail + mail::kDevSaBase.at, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+        ARCHON_HIP_TRY(hipMemcpyAsync(base_id, c->d_mail() + mail::kDevSaBase.at, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
         ARCHON_SYNC(s);
         return ARCHON_OK;
     });
@@ -3149,7 +3141,7 @@ static int post_run(Ctx *c, hipStream_t s, const uint8_t *d_bwt, uint32_t n, uin
         sizes = a.take<uint32_t>(np);
         return a.off;
     }));
-    unsigned long long *d_total = reinterpret_cast<unsigned long long *>(c->d_mail + mail::kDevPostTotal.at);
+    unsigned long long *d_total = reinterpret_cast<unsigned long long *>(c->d_mail() + mail::kDevPostTotal.at);
     hipLaunchKernelGGL(post::k_post_piece, dim3(np), dim3(post::kLanes), 0, s, d_bwt, n, slots, sizes);
     hipLaunchKernelGGL(post::k_post_gather, dim3(np), dim3(256), 0, s, slots, sizes, np, d_out, d_total);
     ARCHON_HIP_TRY(hipGetLastError());
@@ -3169,7 +3161,7 @@ static int post_decode_run(Ctx *c, hipStream_t s, const uint8_t *d_in, size_t in
     const size_t np_max = (size_t)cap / post::kPiece + 2;
     unsigned long long *off;
     ARCHON_TRY(ctx_carve(c, [&](Carve &a) { off = a.take<unsigned long long>(np_max + 2); return a.off; }));
-    uint32_t *meta = c->d_mail + mail::kDevPostMeta.at;      // [0] n, [1] pieces, [2] bad
+    uint32_t *meta = c->d_mail() + mail::kDevPostMeta.at;      // [0] n, [1] pieces, [2] bad
     ARCHON_HIP_TRY(hipMemsetAsync(meta, 0, 3 * sizeof(uint32_t), s));
     hipLaunchKernelGGL(post::k_post_offsets, dim3(1), dim3(1024), 0, s, d_in, (unsigned long long)in_bytes, cap, off, meta, meta + 2);
     hipLaunchKernelGGL(post::k_post_decode, dim3(div_up(np_max, post::kDecWaves)), dim3(64 * post::kDecWaves), 0, s, d_in, off, meta, d_bwt, meta + 2);
@@ -3232,7 +3224,7 @@ int archon_hip_forward_post(const uint8_t *x, uint32_t n, uint8_t *out, size_t c
         ARCHON_TRY(ctx_io(c, 0, (size_t)n + 64, (void **)&d_x));
         ARCHON_TRY(ctx_io(c, 1, (size_t)n + 64, (void **)&d_bwt));
         ARCHON_TRY(ctx_io(c, 2, post::block_bound(n) + 64, (void **)&d_pk));
-        uint32_t *d_base = c->d_mail + mail::kDevBase.at;
+        uint32_t *d_base = c->d_mail() + mail::kDevBase.at;
         ARCHON_HIP_TRY(hipMemcpyAsync(d_x, x, n, hipMemcpyHostToDevice, s));
         ARCHON_TRY(keep_stats(c, forward_run(c, s, d_x, n, nullptr, d_bwt, d_base)));
         ARCHON_TRY(post_run(c, s, d_bwt, n, d_pk, out_bytes));
@@ -3311,8 +3303,8 @@ int archon_hip_lms_select(const uint8_t *x, uint32_t n, uint32_t count[256], uin
         ARCHON_TRY(ctx_io(c, 0, (size_t)n + 64, (void **)&d_x));
         ARCHON_TRY(ctx_io(c, 2, ((size_t)n / 2 + 8) * 4, (void **)&d_items));
         ARCHON_HIP_TRY(hipMemcpyAsync(d_x, x, n, hipMemcpyHostToDevice, s));
-        ARCHON_TRY(lms_select_run(c, s, d_x, n, c->d_mail + mail::kDevLmsCount.at, d_items, n1));
-        ARCHON_HIP_TRY(hipMemcpyAsync(count, c->d_mail + mail::kDevLmsCount.at, 256 * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+        ARCHON_TRY(lms_select_run(c, s, d_x, n, c->d_mail() + mail::kDevLmsCount.at, d_items, n1));
+        ARCHON_HIP_TRY(hipMemcpyAsync(count, c->d_mail() + mail::kDevLmsCount.at, 256 * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
         if (*n1) ARCHON_HIP_TRY(hipMemcpyAsync(items, d_items, (size_t)*n1 * 4, hipMemcpyDeviceToHost, s));
         ARCHON_SYNC(s);
         return ARCHON_OK;
@@ -3323,7 +3315,7 @@ int archon_hip_radix_scatter_dev(const uint8_t *d_src, size_t n, uint8_t *d_dst,
 {
     if (!d_src || !d_dst) { set_error("null pointer"); return ARCHON_E_ARG; }
     return with_ctx(dev, stream, [&](Ctx *c, hipStream_t s) -> int {
-        uint32_t *d_counts = c->d_mail + mail::kDevCounts.at, *d_starts = c->d_mail + mail::kDevStarts.at;
+        uint32_t *d_counts = c->d_mail() + mail::kDevCounts.at, *d_starts = c->d_mail() + mail::kDevStarts.at;
         ARCHON_TRY(launch_hist256(s, d_src, n, d_counts, n));
         hipLaunchKernelGGL(k_scan257, dim3(1), dim3(64), 0, s, d_counts, d_starts);
         uint32_t grid = div_up(n, 256 * 16);
@@ -3340,19 +3332,17 @@ int archon_hip_radix_scatter(const uint8_t *src, size_t n, uint8_t *dst, int dev
 {
     if (!src || !dst) { set_error("null pointer"); return ARCHON_E_ARG; }
     if (n >= 0xFFFFFFFFull) { set_error("n too large"); return ARCHON_E_ARG; }
-    uint8_t *d_a = nullptr, *d_b = nullptr;
+    DevBuf a, b;        // (freed on the device the calls below leave current: dev)
     // the context only for the allocations and the upload: the _dev call takes it again
     ARCHON_TRY(with_ctx(dev, nullptr, [&](Ctx *, hipStream_t) -> int {
-        ARCHON_HIP_TRY(hipMalloc((void **)&d_a, n + 64));
-        if (hipMalloc((void **)&d_b, n + 64) != hipSuccess) { (void)hipFree(d_a); set_error("alloc"); return ARCHON_E_NOMEM; }
-        if (hipMemcpy(d_a, src, n, hipMemcpyHostToDevice) != hipSuccess) { (void)hipFree(d_a); (void)hipFree(d_b); set_error("copy"); return ARCHON_E_HIP; }
+        ARCHON_TRY(a.alloc(n + 64, "radix scatter"));
+        ARCHON_TRY(b.alloc(n + 64, "radix scatter"));
+        ARCHON_HIP_TRY(hipMemcpy(a.p, src, n, hipMemcpyHostToDevice));
         return ARCHON_OK;
     }));
-    int rc = archon_hip_radix_scatter_dev(d_a, n, d_b, dev, nullptr);
-    if (rc == ARCHON_OK && hipMemcpy(dst, d_b, n, hipMemcpyDeviceToHost) != hipSuccess) { set_error("copy"); rc = ARCHON_E_HIP; }
-    (void)hipFree(d_a);
-    (void)hipFree(d_b);
-    return rc;
+    ARCHON_TRY(archon_hip_radix_scatter_dev(reinterpret_cast<const uint8_t *>(a.p), n, reinterpret_cast<uint8_t *>(b.p), dev, nullptr));   // (waits for its stream)
+    ARCHON_HIP_TRY(hipMemcpy(dst, b.p, n, hipMemcpyDeviceToHost));
+    return ARCHON_OK;
 }
 
 // ---- several small blocks per call ---------------------------------------------------------------------------------------
@@ -3443,7 +3433,7 @@ int archon_hip_reserve(uint32_t n, int dev, size_t *bytes_or_null)
         if (inv > need) need = inv;
         ARCHON_TRY(ctx_ensure_arena(c, need));
         ARCHON_TRY(ctx_ensure_arena2(c, fwd_tier2(f2, B, n)));
-        if (bytes_or_null) *bytes_or_null = c->arena_bytes + c->arena2_bytes;
+        if (bytes_or_null) *bytes_or_null = c->arena.bytes + c->arena2.bytes;
         return ARCHON_OK;
     });
 }
@@ -3459,17 +3449,8 @@ int archon_hip_release(int dev)
             std::lock_guard<std::mutex> lk2(c->mu);
             (void)hipSetDevice(dev);
             (void)hipDeviceSynchronize();
-            if (c->arena) (void)hipFree(c->arena);
-            if (c->arena2) (void)hipFree(c->arena2);
-            for (int i = 0; i < Ctx::kIo; ++i)
-                if (c->io[i]) (void)hipFree(c->io[i]);
-            if (c->d_mail) (void)hipFree(c->d_mail);
-            if (c->h_mail) (void)hipHostFree(c->h_mail);
-            for (int i = 0; i < Ctx::kEvents; ++i)
-                if (c->ev_pool[i]) (void)hipEventDestroy(c->ev_pool[i]);
-            if (c->own_stream) (void)hipStreamDestroy(c->own_stream);
         }
-        delete c;
+        delete c;       // (~Ctx and its DevBufs, on the device set above; its lock is free again: a locked mutex is not destroyed)
         g_ctx[dev][slot] = nullptr;
     }
     return ARCHON_OK;
