@@ -1,0 +1,674 @@
+"""A plain numpy model of the streaming first stage (dark-archon_amd/csrc/bucket_sort.hiph: k_local_sort<1|3|9>,
+k_resolve_ties, k_unpack_big, behind the two passes of passes.hiph), and the table of inputs and routes its GPU tests run.
+
+What the stage computes, restated.  Item s in 1..n of a text x has the key bytes b_d = x[s - d] (d = 1, 2, ...), 0xFF where
+s < d ("bytes before x[0] read as 0xFF"); its two-byte bucket is b1 || b2, its 24-bit key b3 || b4 || b5, its 13-bit bin
+key >> 11, the other 11 bits its remainder.  One workgroup sorts a bucket of nb rows:
+  nb == 0 / 1          nothing / one row written by one lane
+  nb >  LS_CAP (4608)  the rows stay as they came: ONE group tied at depth 2, nb - 1 rows counted in tie_items (a periodic block's
+                       buckets beyond BIG_ROWS rows are written by k_unpack_big, in chunks of UNPACK_CHUNK rows, instead)
+  else                 a counting sort on the bin; inside a bin of m rows: m == 1 nothing, 2..4 one lane, 5..64 the wave
+                       (a size of 63 and more is looked up again: the field that carries it saturates), m > LS_MAX_BIN (64)
+                       the rows stay as they came: ONE group tied at depth 3, m - 1 rows in tie_items.  Rows of equal
+                       remainders -- equal on five key bytes -- are one GROUP, listed for k_resolve_ties (tie_groups += 1,
+                       tie_items += len - 1).
+k_resolve_ties takes a listed group of at most TIE_GROUP_MAX (32) rows and sorts it by comparing the items in the text from
+symbol 5q + 1 up to and including symbol 69q (1-based, as b_d above; the kernel's 0-based 5q .. 5q + 64q - 1).  An item that
+runs out of text (s < d) sorts behind one that has not, of two that have the shorter one sorts later.  A pair still equal
+behind symbol 69q leaves its whole group tied for the general stage, and so does a group of more than 32 rows.  When more than
+LIST_CAP (2^20) groups were listed only TIE_SAMPLE of them -- whichever came first -- are compared and all others stay tied.
+The general stage's entry sweep (forward.hiph, k_first_groups) counts EVERY row of a group that is still tied, its head row
+included ("row kept" = not a group of one): `rows_left` is that count, and the library reports it as unresolved_initial.
+
+Compacted alphabets (q = 2, 4, 8 symbols per key byte; k_build_y): with bits = 8 / q and code(c) = the rank of byte c among
+the bytes that occur, the key text is y[i] = code(x[i]) << (8 - bits) | code(x[i-1]) << (8 - 2 bits) | ... | code(x[i-q+1]),
+positions before x[0] taking the all-ones code; item s = i + 1 then has the key bytes y[i], y[i - q], y[i - 2q], ..., 0xFF
+before y[0].  Buckets, bins and groups are those of y; k_resolve_ties compares symbols of x itself from symbol 5q + 1 on.
+
+`census(x, q)` returns all of it for one text; EDGES names the conditions the tests are written for as predicates over a
+census; CASES is the ONE table of (id, builder, routes, edges).  tests/test_bucket_model.py proves on the CPU that every edge
+a row lists occurs in its input, tests/test_gpu_bucket_sort.py runs the rows on the GPU and holds the library's counters
+against the census.  Expected counters always come from the census of the whole text, never from what a builder meant to put
+in: a random filler has accidental five-byte ties of its own.
+
+No GPU and nothing of the oracle in here.
+"""
+import collections
+import itertools
+
+import numpy as np
+
+LS_BLOCK = 512                 # rows per round of k_local_sort
+LS_CAP = 4608                  # kLsCap
+LS_MAX_BIN = 64                # kLsMaxBin
+TIE_GROUP_MAX = 32             # kTieGroupMax
+BIG_ROWS = 32768               # kBigRows
+UNPACK_CHUNK = 4096            # kUnpackChunk
+LIST_CAP = 1 << 20             # kTieListCap (archon_hip.hip)
+TIE_SAMPLE = 1 << 16           # kTieSample
+KEY_BYTES = 5                  # key bytes the stage sorts on
+RESOLVE_BYTES = 64             # further key bytes k_resolve_ties compares
+
+
+# ---------------------------------------------------------------- the key text
+def build_y(x, q):
+    """the key text of k_build_y (see the module docstring); q = 1 is the text itself"""
+    x = np.ascontiguousarray(x, np.uint8)
+    if q == 1:
+        return x
+    bits = 8 // q
+    lut = np.zeros(256, np.int64)
+    present = np.unique(x)
+    assert present.size <= (1 << bits)
+    lut[present] = np.arange(present.size)
+    code = np.concatenate([np.full(q - 1, (1 << bits) - 1, np.int64), lut[x]])          # code of x[i - (q - 1)] .. x[i]
+    n = x.size
+    y = np.zeros(n, np.int64)
+    for t in range(q):
+        y |= code[q - 1 - t: q - 1 - t + n] << (8 - bits * (t + 1))
+    return y.astype(np.uint8)
+
+
+def key_bytes(y, q, depth=KEY_BYTES):
+    """[depth][n] : key byte d = 1..depth of item s = 1..n (column s - 1)"""
+    n = y.size
+    pad = np.concatenate([np.full(depth * q, 0xFF, np.uint8), y])
+    return [pad[depth * q - (d - 1) * q: depth * q - (d - 1) * q + n].astype(np.int64) for d in range(1, depth + 1)]
+
+
+def codes(x, q=1):
+    """bucket << 24 | key of the items 1..n (index s - 1): what the stage sorts on"""
+    b = key_bytes(build_y(x, q), q)
+    return (((b[0] << 8) | b[1]) << 24) | (b[2] << 16) | (b[3] << 8) | b[4]
+
+
+# ---------------------------------------------------------------- the census
+Census = collections.namedtuple("Census", [
+    "n", "q", "hot",
+    "sizes", "starts", "max_bucket", "big_items", "instance",           # [65536] rows per bucket, [65537] starts; rounds of the instance
+    "rows",                                                             # items in (bucket, key) order, arrival order by item inside a key
+    "bin_bucket", "bin_size",                                           # every non-empty bin of the buckets sorted in LDS
+    "g_start", "g_len", "g_bucket", "g_bin_size",                       # every group of >= 2 rows equal on five key bytes: place in rows[]
+    "g_listed", "g_depth", "g_one_exhausted", "g_both_exhausted", "g_left",
+    "tie_groups", "tie_items", "overflow", "rows_left", "rows_left_max", "min_depth",
+    "chunk_kinds", "item_n"])
+
+
+def instance_of(n, max_bucket, hot=False):
+    """rounds of the k_local_sort instance that runs (Fwd::streaming and the kernel's first lines): the short instance queued
+    from n >> 16 where the count's largest bucket fits it, else the general one"""
+    avg = n >> 16
+    short = 0 if hot else 1 if avg <= 400 else 3 if avg <= 1350 else 0
+    return short if short and max_bucket <= short * LS_BLOCK else 9
+
+
+def _part_depths(x, q, items, gid, ngroups):
+    """For rows (items, their group ids) tied on five key bytes: per group the 1-based symbol depth at which its last two rows
+    part (0: some rows are still equal behind symbol 69q), whether an exhausted item met one that was not at the symbol that
+    parted them, and whether two exhausted items met."""
+    depth = np.zeros(ngroups, np.int64)
+    one = np.zeros(ngroups, bool)
+    both = np.zeros(ngroups, bool)
+    undecided = np.ones(ngroups, bool)
+    glen = np.bincount(gid, minlength=ngroups)
+    first, last = KEY_BYTES * q + 1, (KEY_BYTES + RESOLVE_BYTES) * q
+    # pairs, vectorised: (a, b) with a < b
+    pg = np.flatnonzero(glen == 2)
+    if pg.size:
+        sel = np.flatnonzero(np.isin(gid, pg))
+        o = sel[np.lexsort((items[sel], gid[sel]))]
+        a, b, g = items[o[0::2]], items[o[1::2]], gid[o[0::2]]
+        alive = np.arange(a.size)
+        for d in range(first, last + 1):
+            if not alive.size:
+                break
+            aa, bb = a[alive], b[alive]
+            ea, eb = aa < d, bb < d
+            ca = x[np.maximum(aa - d, 0)]
+            cb = x[np.maximum(bb - d, 0)]
+            parted = ea | eb | (ca != cb)
+            gp = g[alive[parted]]
+            depth[gp] = d
+            one[gp] = (ea ^ eb)[parted]
+            both[gp] = (ea & eb)[parted]
+            undecided[gp] = False
+            alive = alive[~parted]
+        undecided[g[alive]] = False          # equal through the window: depth stays 0
+    # longer groups: refine the classes symbol by symbol; a row alone in its class drops out
+    sel = np.flatnonzero(glen[gid] > 2)
+    if sel.size:
+        s, cls = items[sel], gid[sel].astype(np.int64)
+        owner = gid[sel]
+        for d in range(first, last + 1):
+            if not s.size:
+                break
+            ex = s < d
+            sym = np.where(ex, 256 + s, x[np.maximum(s - d, 0)].astype(np.int64))       # an exhausted item equals nobody
+            # classes that hold exhausted rows: two of them met, or one met a row that still has text
+            nex = np.bincount(cls, weights=ex, minlength=int(cls.max()) + 1)
+            ntot = np.bincount(cls, minlength=int(cls.max()) + 1)
+            both[owner[(nex[cls] >= 2)]] = True
+            one[owner[(nex[cls] >= 1) & (ntot[cls] > nex[cls])]] = True
+            _, cls = np.unique(cls * (1 << 32) + sym, return_inverse=True)
+            keep = np.bincount(cls)[cls] > 1
+            depth[owner] = d                                  # the last symbol at which rows of the group were still together
+            s, cls, owner = s[keep], cls[keep], owner[keep]
+        g_un = np.unique(owner)
+        depth[g_un] = 0
+        undecided[np.flatnonzero(glen > 2)] = False
+    assert not undecided[glen >= 2].any()
+    return depth, one, both
+
+
+def census(x, q=1, hot=False):
+    """Everything the stage does with text x at q symbols per key byte.  hot: the periodic route (buckets beyond BIG_ROWS rows
+    are deferred to k_unpack_big; the general instance of the sort)."""
+    x = np.ascontiguousarray(x, np.uint8)
+    n = x.size
+    code = codes(x, q)
+    bucket = code >> 24
+    rows = np.argsort(code, kind="stable")                   # inside equal codes: by item, the order the two stable passes leave
+    sc = code[rows]
+    rows = rows + 1                                           # items
+    sizes = np.bincount(bucket, minlength=65536)
+    starts = np.zeros(65537, np.int64)
+    np.cumsum(sizes, out=starts[1:])
+    max_bucket = int(sizes.max())
+    big_items = int(sizes[sizes > LS_CAP].sum())
+    # bins of the buckets that are sorted in LDS
+    in_lds = (sizes > 1) & (sizes <= LS_CAP)
+    bcode = sc >> 11
+    edge = np.flatnonzero(np.concatenate([[True], bcode[1:] != bcode[:-1]]))
+    bsize = np.diff(np.concatenate([edge, [n]]))
+    bbucket = bcode[edge] >> 13
+    keep = in_lds[bbucket]
+    bin_bucket, bin_size = bbucket[keep], bsize[keep]
+    row_bin_size = np.repeat(bsize, bsize)
+    # groups of rows equal on five key bytes
+    edge = np.flatnonzero(np.concatenate([[True], sc[1:] != sc[:-1]]))
+    glen = np.diff(np.concatenate([edge, [n]]))
+    multi = glen >= 2
+    g_start, g_len = edge[multi], glen[multi]
+    g_bucket = sc[g_start] >> 24
+    g_bin_size = row_bin_size[g_start]
+    g_listed = in_lds[g_bucket] & (g_bin_size <= LS_MAX_BIN)
+    ng = g_start.size
+    g_depth = np.zeros(ng, np.int64)
+    g_one = np.zeros(ng, bool)
+    g_both = np.zeros(ng, bool)
+    cmp_g = np.flatnonzero(g_listed & (g_len <= TIE_GROUP_MAX))
+    if cmp_g.size:
+        lens = g_len[cmp_g]
+        idx = np.repeat(g_start[cmp_g], lens) + (np.arange(lens.sum()) - np.repeat(np.cumsum(lens) - lens, lens))
+        d, o1, o2 = _part_depths(x, q, rows[idx], np.repeat(np.arange(cmp_g.size), lens), cmp_g.size)
+        g_depth[cmp_g], g_one[cmp_g], g_both[cmp_g] = d, o1, o2
+    g_left = g_listed & ((g_len > TIE_GROUP_MAX) | (g_depth == 0))
+    tie_groups = int(g_listed.sum())
+    over_bins = bin_size[bin_size > LS_MAX_BIN]
+    over_buckets = sizes[sizes > LS_CAP]
+    tie_items = int((over_buckets - 1).sum() + (over_bins - 1).sum() + (g_len[g_listed] - 1).sum())
+    overflow = tie_groups > LIST_CAP
+    fixed = int(over_buckets.sum() + over_bins.sum())
+    rows_left = fixed + int(g_len[g_left].sum())
+    # a list that overflowed: which groups are compared is not the model's to say -- between "those that settle were all
+    # compared" (rows_left) and "none of them was"
+    rows_left_max = fixed + int(g_len[g_listed].sum()) if overflow else rows_left
+    min_depth = 2 if over_buckets.size else 3 if over_bins.size else 5
+    # k_unpack_big's chunks (periodic route): inside ONE bucket that is deferred / that is not, or over several
+    kinds = []
+    if hot:
+        for i0 in range(0, n, UNPACK_CHUNK):
+            i1 = min(i0 + UNPACK_CHUNK, n) - 1
+            b0, b1 = np.searchsorted(starts, [i0, i1], side="right") - 1
+            if b0 == b1:
+                kinds.append("deferred" if sizes[b0] > BIG_ROWS else "plain")
+            else:
+                d = sizes[b0:b1 + 1][sizes[b0:b1 + 1] > 0] > BIG_ROWS
+                kinds.append("straddle_both" if d.any() and not d.all() else "straddle_deferred" if d.all() else "straddle_plain")
+    # where item n lies
+    at = int(np.flatnonzero(rows == n)[0])
+    nb = int(sizes[bucket[n - 1]])
+    gi = np.searchsorted(g_start, at, side="right") - 1
+    in_group = gi >= 0 and g_start[gi] <= at < g_start[gi] + g_len[gi]
+    if nb == 1:
+        where = "one_row_bucket"
+    elif nb > LS_CAP:
+        where = "oversized_bucket"
+    elif row_bin_size[at] > LS_MAX_BIN:
+        where = "long_bin"
+    elif in_group:
+        where = "left_group" if g_left[gi] else "resolved_group"
+    else:
+        where = "alone"
+    return Census(n, q, hot, sizes, starts, max_bucket, big_items, instance_of(n, max_bucket, hot), rows, bin_bucket, bin_size,
+                  g_start, g_len, g_bucket, g_bin_size, g_listed, g_depth, g_one, g_both, g_left,
+                  tie_groups, tie_items, overflow, rows_left, rows_left_max, min_depth, tuple(kinds), where)
+
+
+def group_items(c, g):
+    """the items of group g of a census, ascending"""
+    return c.rows[c.g_start[g]: c.g_start[g] + c.g_len[g]]
+
+
+def bin_signatures(c, x, bucket):
+    """per bin of `bucket` (q = 1): (rows, lengths of its groups of equal remainders in ascending order of the remainder)"""
+    lo, hi = c.starts[bucket], c.starts[bucket + 1]
+    s = c.rows[lo:hi]
+    pad = np.concatenate([np.full(KEY_BYTES, 0xFF, np.uint8), x]).astype(np.int64)
+    key = (pad[s + 2] << 16) | (pad[s + 1] << 8) | pad[s]            # x[s-3], x[s-4], x[s-5]
+    out = []
+    for bin_ in np.unique(key >> 11):
+        rem = np.sort(key[key >> 11 == bin_] & 0x7FF)
+        _, cnt = np.unique(rem, return_counts=True)
+        out.append((rem.size, tuple(int(v) for v in cnt)))
+    return out
+
+
+# ---------------------------------------------------------------- builders
+# A "word" [... c5 c4 c3 Q P] in a random filler: P and Q are reserved bytes that occur nowhere else, so the item behind P lies
+# in bucket (P, Q) with the key c3 || c4 || c5 -- exact control of the bucket's size, of the bin (c3 and the top five bits of c4)
+# and of the remainder; the bytes in front of the word are key bytes 6, 7, ... and set the depth at which two equal keys part.
+FILL = 240                     # filler bytes are 0 .. FILL - 1
+Q_BYTE = 250                   # the reserved second byte; first bytes P are 240 .. 249
+_SAFE = np.arange(FILL)          # key bytes of the random words: no reserved byte, so no stray bucket between those of two P
+
+
+class _Text:
+    def __init__(self, seed):
+        self.rng = np.random.default_rng(seed)
+        self.parts = []
+
+    def fill(self, k):
+        return self.rng.integers(0, FILL, size=int(k), dtype=np.uint8)
+
+    def word(self, P, key, prefix=()):
+        """the bytes of one word: prefix (text order: its LAST byte is key byte 6), then c5 c4 c3 Q P"""
+        c3, c4, c5 = key >> 16, (key >> 8) & 0xFF, key & 0xFF
+        assert c3 < FILL and c4 != Q_BYTE and c5 != Q_BYTE and 240 <= P < Q_BYTE
+        return np.concatenate([np.asarray(prefix, np.uint8), np.array([c5, c4, c3, Q_BYTE, P], np.uint8)])
+
+    def add(self, *words):
+        """one part: words that stay together, in this order"""
+        self.parts.append(np.concatenate([np.concatenate([self.fill(1), w]) for w in words]))
+
+    def random_keys(self, k):
+        """k distinct keys free of the reserved bytes, in bins from 100 << 5 on (the builders' own bins lie below)"""
+        out = set()
+        while len(out) < k:
+            out.add((int(self.rng.integers(100, FILL)) << 16) | (int(self.rng.choice(_SAFE)) << 8) | int(self.rng.choice(_SAFE)))
+        return sorted(out)
+
+    def bucket(self, P, k):
+        for key in self.random_keys(k):
+            self.add(self.word(P, key, self.fill(1)))
+
+    def build(self, head=(), gap=3, last=None, min_n=70000):
+        """head, the parts in random order between gaps of filler, filler up to min_n bytes (ALIGNED_MIN=65536 lets pass B
+        consider bucket mode from 65 536 bytes on), and `last`: the word behind which item n lies"""
+        order = self.rng.permutation(len(self.parts))
+        out = [np.asarray(head, np.uint8), self.fill(8)]
+        for i in order:
+            out += [self.parts[i], self.fill(self.rng.integers(1, gap + 1))]
+        out.append(self.fill(max(0, min_n - sum(p.size for p in out))))
+        if last is not None:
+            out.append(last)
+        return np.ascontiguousarray(np.concatenate(out))
+
+
+def bucket_id(P):
+    return (P << 8) | Q_BYTE
+
+
+def _key(bin_, rem):
+    """bin (13 bits) and remainder (11 bits) -> key; the caller keeps c3 < FILL and the reserved bytes out"""
+    return (bin_ << 11) | rem
+
+
+def _rems(k, rng=None):
+    """k distinct remainders whose low byte is no reserved byte, ascending"""
+    vals = [r for r in range(2048) if (r & 0xFF) not in (Q_BYTE, 0xFF)]
+    if rng is not None:
+        vals = sorted(rng.choice(vals, size=k, replace=False).tolist())
+    return vals[:k]
+
+
+def build_sizes_short(plus1=False):
+    t = _Text(101 + plus1)
+    for P, k in zip(range(240, 250), [1, 2, 3, 4, 5, 511, 512] + ([513] if plus1 else [])):
+        t.bucket(P, k)
+    # 330 000 bytes: the 1538 words' second byte stays within a quarter of the mean, so ALIGNED_MIN=65536 does run bucket mode
+    return t.build(min_n=330000)
+
+
+def build_sizes_cap():
+    # the buckets follow each other in the order of P with nothing between them: with these sizes (3, 1, 1, 1, 0, 0 mod 4) both the
+    # starts and the ends take all four values mod 4 wherever the first one starts
+    t = _Text(103)
+    for P, k in zip(range(240, 250), [4607, 1025, 4097, 4609, 1024, 4608]):
+        t.bucket(P, k)
+    return t.build(gap=2)
+
+
+def build_pairs_full():
+    t = _Text(105)
+    bins = t.rng.choice(np.arange(8 << 5, 230 << 5), size=LS_CAP // 2, replace=False)
+    for bin_ in bins:
+        while True:
+            key = _key(int(bin_), int(t.rng.integers(0, 2048)))
+            if (key >> 8) & 0xFF not in (Q_BYTE, 0xFF) and key & 0xFF not in (Q_BYTE, 0xFF):
+                break
+        u, v = t.rng.choice(FILL, size=2, replace=False)
+        t.add(t.word(240, key, [u]))
+        t.add(t.word(240, key, [v]))
+    return t.build()
+
+
+def compositions(m):
+    """every way to write m as an ordered sum: the group lengths of a bin in ascending order of the remainder"""
+    if m == 0:
+        return [()]
+    return [(k,) + rest for k in range(1, m + 1) for rest in compositions(m - k)]
+
+
+def set_partitions(m):
+    """every partition of range(m) into blocks (2, 5, 15 of them for m = 2, 3, 4)"""
+    if m == 0:
+        return [[]]
+    out = []
+    for p in set_partitions(m - 1):
+        out += [p[:i] + [p[i] + [m - 1]] + p[i + 1:] for i in range(len(p))] + [p + [[m - 1]]]
+    return out
+
+
+def build_small_bins():
+    """every set partition of a bin of 2, 3 and 4 rows by equality of remainders, its distinct remainders in every relative
+    order; the rows of a bin follow each other in the text in the partition's own numbering (what order they ARRIVE in is the
+    LDS atomics' choice)"""
+    t = _Text(107)
+    bin_ = 8 << 5
+    for m in (2, 3, 4):
+        for part in set_partitions(m):
+            for order in itertools.permutations(range(len(part))):
+                rem = _rems(len(part), t.rng)
+                words = [None] * m
+                for blk, rank in zip(part, order):
+                    for row in blk:
+                        words[row] = t.word(240, _key(bin_, rem[rank]), [10 + row])        # equal keys part at key byte 6
+                t.add(*words)
+                bin_ += 1
+    t.bucket(240, 900)
+    return t.build()
+
+
+def build_long_bins():
+    t = _Text(109)
+    bin_ = [8 << 5]
+
+    def a_bin(groups):
+        """one bin whose rows fall into groups of these lengths (1 = a remainder of its own)"""
+        rem = _rems(len(groups), t.rng)
+        for r, k in zip(rem, groups):
+            for j in range(k):
+                t.add(t.word(240, _key(bin_[0], r), [20 + j]))
+        bin_[0] += 1
+
+    for m in (5, 6, 62, 63, 64, 65, 66, 200):
+        a_bin([1] * m)
+    a_bin([2, 3])
+    a_bin([64])
+    a_bin([32, 32])
+    a_bin([33, 31])
+    a_bin([2] + [1] * 61)
+    t.bucket(240, 500)
+    return t.build()
+
+
+def build_bins_settled():
+    """the wave-wide ranking at its last sizes -- 62, 63 (the size field saturates) and 64 rows, with and without equal rows --
+    in a block the streaming stage settles alone: what the sort writes IS the answer, no later round can repair it"""
+    t = _Text(117)
+    bin_ = [8 << 5]
+
+    def a_bin(groups):
+        for r, k in zip(_rems(len(groups), t.rng), groups):
+            for j in range(k):
+                t.add(t.word(240, _key(bin_[0], r), [20 + j]))
+        bin_[0] += 1
+
+    for groups in ([1] * 5, [1] * 62, [1] * 63, [1] * 64, [2] + [1] * 61, [32, 32], [31] + [1] * 33):
+        a_bin(groups)
+    t.bucket(240, 700)
+    return t.build()
+
+
+RESOLVE_DEPTHS = (6, 7, 68, 69, 70, 200)
+
+
+def build_resolve_depths(variant):
+    """pairs that part at the key bytes RESOLVE_DEPTHS, exhausted items, a group of 32 in reverse order, an oversized bucket and
+    a long bin; variant: where the text's LAST word -- item n -- lies"""
+    t = _Text(111)
+    bin0 = 8 << 5
+    for j, depth in enumerate(RESOLVE_DEPTHS):
+        shared = t.fill(depth - 6)                                    # key bytes 6 .. depth - 1
+        u, v = t.rng.choice(FILL, size=2, replace=False)
+        key = _key(bin0 + j, 5)
+        t.add(t.word(240, key, np.concatenate([[u], shared])))
+        t.add(t.word(240, key, np.concatenate([[v], shared])))
+    # 32 rows of one key whose key byte 6 falls as the items rise: the order they arrive in is the reverse of the one they leave in
+    key = _key(bin0 + 10, 7)
+    t.add(*[t.word(240, key, [100 - j]) for j in range(32)])
+    # a bin of 70 rows, a bucket past the sort's capacity, and rows to take bucket 240 past 1024
+    for r in _rems(69 if variant == "long_bin" else 70):
+        t.add(t.word(240, _key(bin0 + 11, r), t.fill(1)))
+    t.bucket(240, 1000)
+    t.bucket(241, LS_CAP + 50)
+    # the text opens with 0xFF 0xFF and ten bytes that recur behind another 0xFF 0xFF: items 1 and 2 are both exhausted where the
+    # comparison starts, item 12 runs out against its twin; a run of six 0xFF elsewhere joins the group of items 1 and 2
+    opening = np.concatenate([[0xFF, 0xFF], t.fill(10)])
+    t.parts.append(np.concatenate([t.fill(3), opening, t.fill(2)]))
+    t.parts.append(np.concatenate([t.fill(3), np.full(6, 0xFF, np.uint8), t.fill(2)]))
+    pair = _key(bin0 + 12, 9)
+    t.add(t.word(240, pair, [1]))
+    last = {"one_row_bucket": t.word(249, _key(bin0, 1), t.fill(2)),
+            "resolved_group": t.word(240, pair, [2]),
+            "oversized_bucket": t.word(241, _key(bin0 + 13, 3), t.fill(2)),
+            "long_bin": t.word(240, _key(bin0 + 11, _rems(70)[69]), t.fill(2))}[variant]
+    if variant != "resolved_group":
+        t.add(t.word(240, pair, [2]))
+    return t.build(head=opening, last=last)
+
+
+def build_list_overflow():
+    """a random block written twice, and its first bytes a third time: every group holds a pair that agrees far beyond the
+    compared window, so every listed group is left whichever of them the sample takes"""
+    r = np.random.default_rng(113).integers(0, 256, size=1_150_000, dtype=np.uint8)
+    return np.concatenate([r, r, r[:160]])
+
+
+HOT_MOTIF = b"acegikmo"
+
+
+def build_hot_unpack():
+    """eight distinct bigrams; n = 8 * 32768 + 9 gives every one of them 32769 rows, and the defect takes one row from two of them"""
+    n = 8 * BIG_ROWS + 9
+    x = np.tile(np.frombuffer(HOT_MOTIF, np.uint8), n // 8 + 1)[:n].copy()
+    x[100003] = ord("z")
+    return x
+
+
+def build_dna_depths():
+    """four symbols, four to a key byte: pairs that part at symbol 5q + 1, 69q and 69q + 1 (the first and the last symbol
+    k_resolve_ties compares, and the first it does not), and two passages repeated 64 and 65 times that differ in the fifth
+    key byte's low bits only: bins of 64 and 65 rows on the packed key text"""
+    q = 4
+    rng = np.random.default_rng(115)
+    acgt = np.frombuffer(b"ACGT", np.uint8)
+    sym = lambda k: rng.integers(0, 4, size=int(k))
+    parts = []
+    for depth in (5 * q + 1, 69 * q, 69 * q + 1):
+        shared = sym(depth - 1)                                    # symbols 1 .. depth - 1 of the item behind it (text order)
+        for c in rng.choice(4, size=2, replace=False):
+            parts.append(np.concatenate([sym(8), [c], shared, sym(3)]))
+    # a bin = the top 13 of 24 key bits = symbols 9 .. 14 and the high bit of symbol 15 of an item (two bits a symbol); with
+    # symbols 1 .. 14 fixed and the rest free, the items behind the passage share a bucket and a bin
+    for count in (64, 65):
+        fixed = sym(14)
+        for _ in range(count):
+            parts.append(np.concatenate([sym(11), rng.integers(0, 2, size=1), fixed[::-1], sym(2)]))       # symbol 15: A or C
+    out = [sym(20)]
+    for i in rng.permutation(len(parts)):
+        out += [parts[i], sym(rng.integers(1500, 2500))]
+    return acgt[np.concatenate(out)]
+
+
+# ---------------------------------------------------------------- the edges
+def _bucket_sizes(*ks):
+    return lambda c, x: all((c.sizes == k).any() for k in ks)
+
+
+def _bins(*ms):
+    return lambda c, x: all((c.bin_size == m).any() for m in ms)
+
+
+def _groups(length, left, distinct_bin=None):
+    """a listed group of this length that is left / resolved (distinct_bin: in a bin of that many rows)"""
+    return lambda c, x: bool((c.g_listed & (c.g_len == length) & (c.g_left == left) &
+                              (True if distinct_bin is None else c.g_bin_size == distinct_bin)).any())
+
+
+def _pair_depth(d, left):
+    return lambda c, x: bool((c.g_listed & (c.g_len == 2) & (c.g_left == left) & (c.g_depth == (0 if left else d))).any()) and \
+        (not left or _parts_at(c, x, d))
+
+
+def _parts_at(c, x, d):
+    """some left pair's items first differ at symbol d exactly (1-based)"""
+    for g in np.flatnonzero(c.g_listed & (c.g_len == 2) & c.g_left):
+        a, b = (int(v) for v in group_items(c, g))
+        if a > d and (x[a - d + 1: a] == x[b - d + 1: b]).all() and x[a - d] != x[b - d]:
+            return True
+    return False
+
+
+def _small_bin_patterns(c, x):
+    seen = set(bin_signatures(c, x, bucket_id(240)))
+    return all((m, comp) in seen for m in (2, 3, 4) for comp in compositions(m))
+
+
+def _reversed_32(c, x):
+    for g in np.flatnonzero(c.g_listed & (c.g_len == 32) & ~c.g_left & (c.g_depth == 6)):
+        s = group_items(c, g)
+        if (np.diff(x[s - 6].astype(np.int64)) < 0).all():
+            return True
+    return False
+
+
+EDGES = {
+    # ---- buckets
+    "buckets_1_to_5": _bucket_sizes(1, 2, 3, 4, 5),
+    "buckets_511_512": _bucket_sizes(511, 512),
+    "max_bucket_512": lambda c, x: c.max_bucket == 512,
+    "bucket_513": lambda c, x: c.max_bucket == 513,
+    "instance_1": lambda c, x: c.instance == 1,
+    "instance_9": lambda c, x: c.instance == 9,
+    "buckets_around_1024": _bucket_sizes(1024, 1025),
+    "buckets_around_cap": _bucket_sizes(4097, 4607, 4608, 4609),
+    "oversized_bucket": lambda c, x: bool((c.sizes > LS_CAP).any()) and c.min_depth == 2,
+    "starts_cover_lo_mod_4": lambda c, x: {int(v) & 3 for v in c.starts[:-1][c.sizes >= 1024]} == {0, 1, 2, 3},
+    "ends_cover_hi_mod_4": lambda c, x: {int(v) & 3 for v in c.starts[1:][c.sizes >= 1024]} == {0, 1, 2, 3},
+    "bucket_4608": _bucket_sizes(4608),
+    "bucket_over_1024": lambda c, x: LS_CAP >= c.sizes[bucket_id(240)] > 1024,
+    # ---- the lists in LDS
+    "bin_list_full": lambda c, x: int(((c.bin_bucket == bucket_id(240)) & (c.bin_size >= 2) & (c.bin_size <= 4)).sum()) == LS_CAP // 2,
+    "tie_list_full": lambda c, x: int((c.g_listed & (c.g_bucket == bucket_id(240))).sum()) == LS_CAP // 2,
+    "all_pairs_part_at_6": lambda c, x: bool((c.g_depth[c.g_listed & (c.g_bucket == bucket_id(240))] == 6).all()),
+    "nothing_left": lambda c, x: c.rows_left == 0,
+    # ---- bins
+    "small_bin_patterns": _small_bin_patterns,
+    "bins_5_6": _bins(5, 6),
+    "bins_62_63_64": _bins(62, 63, 64),
+    "bins_65_66_200": lambda c, x: _bins(65, 66, 200)(c, x) and c.min_depth == 3,
+    "bin_70": _bins(70),
+    "bin_5_groups_2_3": lambda c, x: _groups(2, False, 5)(c, x) and _groups(3, False, 5)(c, x),
+    "bin_64_one_group": _groups(64, True, 64),
+    "bin_64_groups_32_32": lambda c, x: int((c.g_listed & (c.g_len == 32) & ~c.g_left & (c.g_bin_size == 64)).sum()) >= 2,
+    "bin_64_groups_33_31": lambda c, x: _groups(33, True, 64)(c, x) and _groups(31, False, 64)(c, x),
+    "bin_63_with_pair": _groups(2, False, 63),
+    # ---- k_resolve_ties
+    "pair_parts_at_6": _pair_depth(6, False), "pair_parts_at_7": _pair_depth(7, False),
+    "pair_parts_at_68": _pair_depth(68, False), "pair_parts_at_69": _pair_depth(69, False),
+    "pair_parts_at_70_left": _pair_depth(70, True), "pair_parts_at_200_left": _pair_depth(200, True),
+    "one_exhausted": lambda c, x: bool((c.g_listed & ~c.g_left & (c.g_len == 2) & c.g_one_exhausted).any()),
+    "both_exhausted": lambda c, x: bool((c.g_listed & ~c.g_left & (c.g_len <= TIE_GROUP_MAX) & c.g_both_exhausted).any()),
+    "group_32_reversed": _reversed_32,
+    "item_n_one_row_bucket": lambda c, x: c.item_n == "one_row_bucket",
+    "item_n_resolved_group": lambda c, x: c.item_n == "resolved_group",
+    "item_n_oversized_bucket": lambda c, x: c.item_n == "oversized_bucket",
+    "item_n_long_bin": lambda c, x: c.item_n == "long_bin",
+    "list_overflows": lambda c, x: c.overflow and c.tie_groups > LIST_CAP,
+    "every_listed_group_left": lambda c, x: c.rows_left == c.rows_left_max and c.rows_left > 0,
+    # ---- k_unpack_big
+    "buckets_32768_32769": _bucket_sizes(BIG_ROWS, BIG_ROWS + 1),
+    "chunks_of_all_kinds": lambda c, x: {"deferred", "plain", "straddle_both"} <= set(c.chunk_kinds),
+    # ---- packed keys (q = 4)
+    "dna_pair_parts_at_5q_plus_1": _pair_depth(21, False), "dna_pair_parts_at_69q": _pair_depth(276, False),
+    "dna_pair_parts_at_69q_plus_1_left": _pair_depth(277, True),
+    "bins_64_65": _bins(64, 65),
+}
+
+# ---------------------------------------------------------------- routes
+# what a row runs under (ARCHON_<NAME>, handed on by pyarchon); FORCE_PATH=1 keeps a row on the streaming stage whatever its buckets
+_FORCE = {"ARCHON_FORCE_PATH": "1"}
+_MODES = {
+    "plain": {},
+    "no_aligned": {"ARCHON_NO_ALIGNED": "1"},
+    "rel_records": {"ARCHON_ALIGNED_MIN": "65536", "ARCHON_REL_MIN_SEG": "1"},
+    "plain_records": {"ARCHON_ALIGNED_MIN": "65536", "ARCHON_NO_REL_RECORDS": "1"},
+}
+ROUTES_FORCED = {k: dict(_FORCE, **v) for k, v in _MODES.items()}
+ROUTES_UNFORCED = {k: dict(v) for k, v in _MODES.items() if k != "plain"}
+
+Case = collections.namedtuple("Case", "id builder args q hot routes edges")
+CASES = []
+
+
+def _case(id, builder, args, edges, q=1, hot=False, routes=None):
+    assert edges and all(e in EDGES for e in edges), [e for e in edges if e not in EDGES]
+    CASES.append(Case(id, builder, args, q, hot, ROUTES_FORCED if routes is None else routes, tuple(edges)))
+
+
+_case("sizes_short", build_sizes_short, (False,), ("buckets_1_to_5", "buckets_511_512", "max_bucket_512", "instance_1"))
+_case("sizes_short_plus1", build_sizes_short, (True,), ("buckets_1_to_5", "buckets_511_512", "bucket_513", "instance_9"))
+_case("sizes_cap", build_sizes_cap, (), ("buckets_around_1024", "buckets_around_cap", "oversized_bucket", "starts_cover_lo_mod_4",
+                                         "ends_cover_hi_mod_4", "instance_9"))
+_case("pairs_full", build_pairs_full, (), ("bucket_4608", "bin_list_full", "tie_list_full", "all_pairs_part_at_6", "nothing_left"))
+_case("small_bins", build_small_bins, (), ("bucket_over_1024", "small_bin_patterns"))
+_case("long_bins", build_long_bins, (), ("bucket_over_1024", "bins_5_6", "bins_62_63_64", "bins_65_66_200", "bin_5_groups_2_3", "bin_64_one_group",
+                                         "bin_64_groups_32_32", "bin_64_groups_33_31", "bin_63_with_pair"))
+_case("bins_settled", build_bins_settled, (), ("bucket_over_1024", "bins_62_63_64", "bin_63_with_pair", "bin_64_groups_32_32", "nothing_left"))
+for _v in ("one_row_bucket", "resolved_group", "oversized_bucket", "long_bin"):
+    _case("resolve_depths_" + _v, build_resolve_depths, (_v,),
+          ("pair_parts_at_6", "pair_parts_at_7", "pair_parts_at_68", "pair_parts_at_69", "pair_parts_at_70_left", "pair_parts_at_200_left",
+           "one_exhausted", "both_exhausted", "group_32_reversed", "oversized_bucket", "bin_70", "item_n_" + _v))
+_case("list_overflow", build_list_overflow, (), ("list_overflows", "every_listed_group_left"))
+# the period probe has to see the block: no FORCE_PATH
+_case("hot_unpack", build_hot_unpack, (), ("buckets_32768_32769", "chunks_of_all_kinds"), hot=True, routes=ROUTES_UNFORCED)
+# <= 4 distinct bytes: the driver recodes the block by itself (FORCE_PATH would keep it on byte keys)
+_case("dna_depths", build_dna_depths, (), ("dna_pair_parts_at_5q_plus_1", "dna_pair_parts_at_69q", "dna_pair_parts_at_69q_plus_1_left", "bins_64_65"),
+      q=4, routes={"default": {}, **ROUTES_UNFORCED})
+
+_built = {}
+
+
+def gen_input(case):
+    """the text of a row (built once per process; callers must not write to it)"""
+    if case.id not in _built:
+        x = case.builder(*case.args)
+        x.setflags(write=False)
+        _built[case.id] = x
+    return _built[case.id]
+
+
+def case(id):
+    return next(c for c in CASES if c.id == id)
