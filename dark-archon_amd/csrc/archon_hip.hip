@@ -267,11 +267,13 @@ constexpr uint32_t kSettled = 604;  // rows the run shortcut settled
 constexpr uint32_t kLastBrk = 606;  // [2] the period's last real break, how many breaks
 constexpr uint32_t kProbe = 610;    // [pf::kCleanWords] the period probe: period, votes, breaks, whole text compared
 constexpr uint32_t kCtl = 640;      // bs::TieCtl
-constexpr uint32_t kFu = 700;       // [6] counters of the rounds (general_stage)
+constexpr uint32_t kFu = 700;       // [6] counters of the rounds (general_stage), the words of Cnt
+enum Cnt : uint32_t { kCntS = 0, kCntLog = 1, kCntB = 2, kCntGroups = 3, kCntPairs = 4, kCntSeen = 5, kCntWords = 6 };      // entries appended to the next S list, rank log
+                                    // entries, entries of the next B list, its groups, pairs listed, pairs seen
 constexpr uint32_t kLut = 900;      // [64] the packed keys' recode table (256 bytes)
 constexpr uint32_t kWords = 1024;
 static_assert(kCounts + 256 <= kTotal && kLastBrk + 2 <= kProbe && kProbe + pf::kCleanWords <= kCtl &&
-              kCtl + sizeof(bs::TieCtl) / 4 <= kFu && kFu + 6 <= kLut && kLut + 64 <= kWords, "forward scratch words overlap");
+              kCtl + sizeof(bs::TieCtl) / 4 <= kFu && kFu + kCntWords <= kLut && kLut + 64 <= kWords, "forward scratch words overlap");
 }
 
 struct FwdBuf {
@@ -416,6 +418,412 @@ struct Fwd {
     int count16(int form, const uint8_t *src, bool force_stream, bool alpha_probe), streaming(int form, const uint8_t *key_text);
     int seven_pass(), first_groups(int mode, const uint64_t *keys, const uint32_t *items, uint32_t shift);
     void queue_probe(bool clean), probe_arrived(), take_byte_hist(bool exact), stamp(int i);
+    // what the steps of the general stage (General, Rounds) share: the readback words (mail::GeneralRead), the rounds' counters
+    // (fwd_small::Cnt), the look-back words of the list kernels, and the launches that more than one step makes
+    uint32_t *rd() const { return c->h_mail + mail::kRead.at; }
+    uint32_t *cnt() const { return B.small + fwd_small::kFu; }
+    unsigned long long *fg_status() const { return reinterpret_cast<unsigned long long *>(B.sc.d_status); }
+    int reset_lookback(uint32_t tiles), recount_tied(), writer_regions(uint64_t *r1);
+};
+
+// Calls fn(std::integral_constant<int, V>{}) for the first V of the list that equals v, for the last one when none does: the
+// driver's runtime choices (symbols per key byte, a mode, a flag) as the template arguments of the kernel that matches.
+template <int V, int... Vs, class Fn>
+static void with_const(int v, Fn &&fn)
+{
+    if constexpr (sizeof...(Vs) == 0) fn(std::integral_constant<int, V>{});
+    else if (v == V) fn(std::integral_constant<int, V>{});
+    else with_const<Vs...>(v, fn);
+}
+
+// ---- the general stage (Fwd::general_stage): its tracer, the refinement rounds (Rounds), its steps (General)
+
+// What more than one step queues.  The look-back words of a list kernel that sweeps `tiles` tiles:
+int Fwd::reset_lookback(uint32_t tiles)
+{
+    ARCHON_HIP_TRY(hipMemsetAsync(fg_status(), 0, (size_t)tiles * sizeof(unsigned long long), s));
+    ARCHON_HIP_TRY(hipMemsetAsync(B.sc.d_ticket, 0, sizeof(uint32_t), s));
+    return ARCHON_OK;
+}
+
+// the tied set as it is now: flags in B.keep, their places in B.dst, their number in fwd_small::kTotal
+int Fwd::recount_tied()
+{
+    hipLaunchKernelGGL(fwd::k_keep_flags, dim3(div_up(n, 256)), dim3(256), 0, s, B.v, n, B.keep);
+    ARCHON_TRY(launch_scan<0>(s, B.keep, B.dst, n, B.scan_tmp, B.small + fwd_small::kTotal));
+    c->launches += 3;
+    return ARCHON_OK;
+}
+
+// the rank writer's record regions (rank_writer.hiph): r1 in a key buffer that is idle, r2 in the value block, the counts cleared
+int Fwd::writer_regions(uint64_t *r1)
+{
+    B.rwb.r1 = reinterpret_cast<uint2 *>(r1);
+    B.rwb.r2 = reinterpret_cast<uint2 *>(B.valA);
+    ARCHON_HIP_TRY(hipMemsetAsync(B.rwb.cnt1, 0, (rw::kMaxCoarse + rw::fine_buckets(n)) * sizeof(uint32_t), s));
+    return ARCHON_OK;
+}
+
+struct Rounds;
+// Times of the steps and of the rounds, for the experiments library alone (ARCHON_TRACE_ROUNDS; with ARCHON_TRACE_STAMPS the
+// stamps of the S kernel's slowest workgroup): the product compiles every call to nothing.
+struct RoundTrace {
+#ifdef ARCHON_EXPERIMENTS
+    using Clock = std::chrono::steady_clock;
+    hipStream_t s;
+    bool on = getenv("ARCHON_TRACE_ROUNDS") != nullptr;
+    Clock::time_point t_last = Clock::now(), t0;
+    uint32_t ms0 = 0, mb0 = 0, mm0 = 0;          // the lists when the round began
+    explicit RoundTrace(hipStream_t stream) : s(stream) {}
+    static double ms_since(Clock::time_point t) { return std::chrono::duration<double, std::milli>(Clock::now() - t).count(); }
+    void step(const char *what)
+    {
+        if (!on) return;
+        (void)hipStreamSynchronize(s);
+        fprintf(stderr, "  general_stage: %-28s %.3f ms\n", what, ms_since(t_last));
+        t_last = Clock::now();
+    }
+    int begin(const Rounds &R);
+    void break_round(bool distance, uint32_t p, uint32_t h, const Rounds &R) const;
+    void doubling_round(uint32_t h, const Rounds &R) const;
+#else
+    explicit RoundTrace(hipStream_t) {}
+    void step(const char *) {}
+    int begin(const Rounds &) { return ARCHON_OK; }
+    void break_round(bool, uint32_t, uint32_t, const Rounds &) const {}
+    void doubling_round(uint32_t, const Rounds &) const {}
+#endif
+};
+
+// The lists of the refinement rounds and one round over them (rounds.hiph, mid_rounds.hiph).
+struct Rounds {
+    Fwd &f;
+    int cur = 0, cs = 0;                         // the buffers that hold the B list and the S list
+    uint32_t ms = 0, mb = 0, bgroups = 1;        // entries of the S list and of the B list, groups of the B list
+    uint32_t mm = 0, mdS = 0, mdL = 0;           // the mid lists (mid_rounds.hiph): entries / groups of the two classes in the CURRENT list (buffer `cur`)
+    uint64_t *kT = f.B.keyA, *kS = f.B.keyB;     // the B sort's (group | key, item) pairs and the buffers it sorts them into
+    uint32_t *vT = f.B.valA, *vS = f.B.valB;
+    // pair chains (rounds.hiph, k_pair_*): {smaller item, distance} records, their {row, flag} words, sort buffers, run heads
+    // (the list itself lives through the round; the chain pass behind the round's rank updates borrows the key / value
+    //  buffers of the B sort, which are idle by then)
+    uint64_t *pk = reinterpret_cast<uint64_t *>(f.B.keep), *pk2 = f.B.keyA;       // n/2 records of 8 bytes each
+    uint32_t *pv = f.B.pairw, *pv2 = f.B.valA, *pair_v = f.B.valA + (f.n / 2 + 8), *pair_code = f.B.valA + 2 * ((size_t)f.n / 2 + 8);
+    // (deep_ties: the streaming stage compared every tied group 64 symbols deep and they still agree -- long duplicates: no
+    //  text rounds, and the first doubling round already lists its pairs)
+    bool chain_next = f.deep_ties;               // list the pairs of the coming round and settle them by passage
+    uint32_t chain_cool = 0;
+    const bool chain_ok = f.n >= 4 && !route_off(kRtNoPairChains);
+    const bool writer_ok = f.n >= (1u << 22) && !route_off(kRtNoRankWriter);
+    const uint32_t kWriterMinLog = f.n >= (1u << 26) ? (24u << 20) : f.n / 4;       // (small blocks keep exercising the writer in the tests)
+
+    // one round: what it was asked for, and what each step decides for the steps behind it
+    struct Plan {
+        int mode;
+        uint32_t hh;
+        bool b_only;
+        const uint8_t *cert;
+        const uint32_t *okey;
+        uint32_t chain;                          // the S kernel lists the round's pairs
+        uint2 *s_next;                           // the S list the round appends to
+        bool mid;                                // the round deals the B list out by group length
+        int nxt;                                 // the buffer of the next B list
+        uint32_t nS, nL, nbig, nbig_groups;      // groups of the two mid classes; entries / groups that take the global sort
+        uint32_t mid_from_b = 0;
+        bool split = false;                      // the B list was dealt out: its big groups go to the global sort compacted
+        bool writer = false;                     // k_b_finish logs its rank updates by position for the rank writer
+        uint32_t shift = 32, nbytes = 0;         // bits of a key, bytes of a (group | key) word
+        uint2 *b_log = nullptr;
+        uint32_t nlog = 0;                       // entries of the rank log
+    };
+
+    explicit Rounds(Fwd &fwd) : f(fwd) {}
+    uint32_t tied() const { return ms + mb + mm; }
+    int round(int mode, uint32_t hh, bool b_only = false, const uint8_t *cert = nullptr, const uint32_t *okey = nullptr);
+    int plan_b(Plan &r), b_keys(const Plan &r), mid_class(const Plan &r, int lanes, const uint4 *dir, uint32_t groups), s_round(const Plan &r), b_sort(Plan &r);
+    int fetch_counters(Plan &r), apply_ranks(const Plan &r), next_lists(const Plan &r), pair_chain(uint32_t np);
+};
+
+#ifdef ARCHON_EXPERIMENTS
+int RoundTrace::begin(const Rounds &R)
+{
+    ARCHON_SYNC(s);
+    t0 = Clock::now();
+    ms0 = R.ms, mb0 = R.mb, mm0 = R.mm;
+    return ARCHON_OK;
+}
+
+void RoundTrace::break_round(bool distance, uint32_t p, uint32_t h, const Rounds &R) const
+{
+    if (!getenv("ARCHON_TRACE_ROUNDS")) return;
+    fprintf(stderr, "break round (%s) p=%u (h=%u) S=%u B=%u %.3f ms -> S=%u B=%u\n", distance ? "distance" : "continuation", p, h, ms0, mb0, ms_since(t0), R.ms, R.mb);
+}
+
+void RoundTrace::doubling_round(uint32_t h, const Rounds &R) const
+{
+    if (!getenv("ARCHON_TRACE_ROUNDS")) return;
+    fprintf(stderr, "round h=%u S=%u B=%u M=%u %.3f ms -> S=%u B=%u M=%u (%u + %u groups)\n", h, ms0, mb0, mm0, ms_since(t0), R.ms, R.mb, R.mm, R.mdS, R.mdL);
+    unsigned long long v[24];
+    if (!ms0 || !getenv("ARCHON_TRACE_STAMPS") || hipMemcpyFromSymbol(v, HIP_SYMBOL(fwd::g_fu_stamps), sizeof v) != hipSuccess) return;
+    fprintf(stderr, "   fused wg: longest %llu owned %llu surv/log 0x%llx cycles:", v[11], v[12], v[13]);
+    for (int i = 2; i <= 10; ++i) fprintf(stderr, " %llu", v[i] - v[i - 1]);
+    fprintf(stderr, " (load, own, gather-issue, heads, ends, sort, newgroups, counts+atomic, stores)\n");
+}
+#endif
+
+// One round over both lists: mode 0 keys on rank[s-h], mode 1 on the next four text bytes, modes 2 and 3 (hh = the period)
+// on the distance to the last period defect and on the rank of the item the key continues as behind it (rounds.hiph,
+// break_key / cont_key; rank table kept as in mode 0).
+// The rank table is read by every key gather of the round (S: k_round_fused, B: k_b_keys) before anything writes it
+// (S: the log, applied at the end; B: k_b_finish): the steps below are ordered accordingly.
+// b_only (modes 2, 3 with certified groups, `cert` = the marks of k_zone_certify): the S list sits the round out;
+// groups of the B list that have become short are appended to it where it is.
+int Rounds::round(int mode, uint32_t hh, bool b_only, const uint8_t *cert, const uint32_t *okey)
+{
+    Plan r{mode, hh, b_only, cert, okey};
+    const uint32_t ms_kept = b_only ? ms : 0u;
+    if (b_only) ms = 0;
+    r.chain = (chain_next && chain_ok && mode == 0 && ms) ? 1u : 0u;
+    const uint32_t m_before = tied();
+    // the round's counters start at zero; the kept entries are written behind that clear: k_b_finish appends behind them
+    ARCHON_HIP_TRY(hipMemsetAsync(f.cnt(), 0, fwd_small::kCntWords * sizeof(uint32_t), f.s));
+    if (ms_kept) ARCHON_HIP_TRY(hipMemsetD32Async((hipDeviceptr_t)(f.cnt() + fwd_small::kCntS), (int)ms_kept, 1, f.s));
+    r.s_next = b_only ? f.B.slist[cs] : f.B.slist[cs ^ 1];
+    // Mid groups (mid_rounds.hiph): the B list is dealt out by group length -- groups of at most 16 Ki entries are sorted by
+    // ONE workgroup each, in LDS (with the groups the mid kernels made last round); only the longer ones take the global
+    // sort.  (Text rounds keep round 3's path: they run on small sets.)
+    r.mid = mode != 1 && !route_off(kRtNoMid);
+    r.nxt = cur ^ 1;
+    ARCHON_TRY(plan_b(r));
+    // B: keys (the gather) now, global sort on (group, key) behind the S kernel -- which so runs while the host waits for
+    // the sort's digit counts
+    ARCHON_TRY(b_keys(r));
+    if (r.mid && r.nL) ARCHON_TRY(mid_class(r, fwd::kMidLargeLanes, f.B.dirL[cur], r.nL));
+    if (r.mid && r.nS) ARCHON_TRY(mid_class(r, fwd::kMidSmallLanes, f.B.dirS[cur], r.nS));
+    ARCHON_TRY(s_round(r));
+    ARCHON_TRY(b_sort(r));
+    // The round's counters come to the host BEFORE its rank updates are applied: how the S and mid lists' updates (the log) are
+    // written depends on how many there are, and the host has to wait for these counters anyway.
+    ARCHON_TRY(fetch_counters(r));
+    ARCHON_TRY(apply_ranks(r));
+    ARCHON_TRY(next_lists(r));
+    const uint32_t *rd = f.rd() + mail::kRdCnt;
+    const uint32_t np = r.chain ? rd[fwd_small::kCntPairs] : 0u;
+    const uint32_t pairs_seen = r.chain ? np : rd[fwd_small::kCntSeen];
+    if (np) ARCHON_TRY(pair_chain(np));
+    // 9. The next round lists its pairs when this one got nowhere and pairs are most of what is left.
+    if (chain_cool) --chain_cool;
+    chain_next = chain_ok && !chain_cool && (uint64_t)tied() * 4 >= (uint64_t)m_before * 3 && (uint64_t)pairs_seen * 4 >= ms && ms;
+    return ARCHON_OK;
+}
+
+// 1. What of the B list takes the global sort: all of it, or -- dealt out (k_b_dir, k_b_plan, one wait) -- its big groups; the
+// width of the sort's words.
+int Rounds::plan_b(Plan &r)
+{
+    FwdBuf &B = f.B;
+    const uint32_t n = f.n;
+    const uint32_t *h_mc = f.c->h_mail + mail::kRounds.at;       // the mid lists' counters (fwd::kMc*)
+    r.nS = mdS, r.nL = mdL, r.nbig = mb, r.nbig_groups = bgroups;
+    if (r.mid) {
+        // the next list starts empty: no groups, its items from the top of the buffer downwards
+        // (fills, not copies out of the mailbox: mail::kRounds receives this round's counters further down)
+        ARCHON_HIP_TRY(hipMemsetD32Async((hipDeviceptr_t)(B.mc + fwd::kMcSmall + r.nxt), 0, 1, f.s));
+        ARCHON_HIP_TRY(hipMemsetD32Async((hipDeviceptr_t)(B.mc + fwd::kMcLarge + r.nxt), 0, 1, f.s));
+        ARCHON_HIP_TRY(hipMemsetD32Async((hipDeviceptr_t)(B.mc + fwd::kMcTop + r.nxt), (int)n, 1, f.s));
+        // (a B list whose groups average twice the largest mid group -- a periodic block with defects: one group per phase of
+        //  the period -- goes to the global sort as it is: the two sweeps that would deal it out find nothing to hand over)
+        if (mb && (uint64_t)bgroups * (2u * fwd::kMidLargeCap) > mb) {
+            const uint32_t tiles = div_up(mb, fwd::kBfTile);
+            ARCHON_TRY(f.reset_lookback(tiles));
+            r.split = true;
+            hipLaunchKernelGGL(fwd::k_b_dir, dim3(tiles), dim3(256), 0, f.s, B.upos[cur], B.ug[cur], mb, B.gdir_off, B.gdir_row, f.fg_status(), B.sc.d_ticket, B.sc.d_err, B.mc, (uint32_t)mid_dir_cap(n), B.tile_g0);
+            hipLaunchKernelGGL(fwd::k_b_plan, dim3(1), dim3(1024), 0, f.s, B.gdir_off, B.gdir_row, mb, B.gcls, B.gbig, B.dirS[cur], B.dirL[cur], B.mc, (uint32_t)cur,
+                               (uint32_t)fwd::kMidSmallCap, (uint32_t)fwd::kMidLargeCap, (uint32_t)mid_dir_cap(n), B.sc.d_err, B.tile_big);
+            ARCHON_HIP_TRY(hipGetLastError());
+            ARCHON_HIP_TRY(hipMemcpyAsync(f.c->h_mail + mail::kRounds.at, B.mc, fwd::kMcWords * sizeof(uint32_t), hipMemcpyDeviceToHost, f.s));
+            ARCHON_SYNC(f.s);
+            f.c->launches += 2;
+            if (h_mc[fwd::kMcGroups] > mid_dir_cap(n)) { set_error("B list of %u entries holds %u groups (directory: %zu)", mb, h_mc[fwd::kMcGroups], mid_dir_cap(n)); return ARCHON_E_INTERNAL; }
+            r.nS = h_mc[fwd::kMcSmall + cur];
+            r.nL = h_mc[fwd::kMcLarge + cur];
+            r.nbig = h_mc[fwd::kMcBigEntries];
+            r.nbig_groups = h_mc[fwd::kMcBigGroups];
+            r.mid_from_b = h_mc[fwd::kMcMidEntries];
+            if (r.nbig + r.mid_from_b != mb) { set_error("plan of the B list lost entries (%u + %u of %u)", r.nbig, r.mid_from_b, mb); return ARCHON_E_INTERNAL; }
+        }
+    }
+    f.c->stats.mid_items += r.mid ? mm + r.mid_from_b : 0u;
+    // a long B list logs its rank updates by position for the rank writer (apply_ranks) instead of storing them one by one
+    r.writer = r.mode != 1 && writer_ok && r.nbig >= (8u << 20);
+    uint32_t gbits = 1;
+    if (r.mode != 1) { r.shift = 1; while ((2ull * n + (r.mode == 2 ? 2u : 0u)) >> r.shift) ++r.shift; }    // bits of a key k < 2n (mode 2: 2n + 2)
+    while ((uint64_t)r.nbig_groups >> gbits) ++gbits;                           // bits of a group number of the (big) B list
+    r.nbytes = (r.shift + gbits + 7) / 8;
+    return ARCHON_OK;
+}
+
+// 2. The keys of the B list's big groups, as (group | key, item) pairs for the global sort, and the sort's first digit counts.
+int Rounds::b_keys(const Plan &r)
+{
+    if (!r.nbig) return ARCHON_OK;
+    FwdBuf &B = f.B;
+    f.c->stats.seg_big_items += r.nbig;
+    const uint32_t tiles = div_up(mb, fwd::kBfTile);
+    ARCHON_TRY(f.reset_lookback(tiles));
+    ARCHON_HIP_TRY(hipMemsetAsync(B.sc.d_ghist, 0, 8 * 256 * sizeof(uint32_t), f.s));
+    if (r.split)
+        with_const<0, 2, 3>(r.mode, [&](auto M) {
+            hipLaunchKernelGGL(HIP_KERNEL_NAME(fwd::k_b_keys_split<decltype(M)::value>), dim3(tiles), dim3(256), 0, f.s, B.upos[cur], B.ug[cur], B.uitem[cur], B.rank, f.d_x, r.hh, f.n,
+                               r.shift, mb, kT, vT, f.fg_status(), B.sc.d_ticket, B.sc.d_err, B.sc.d_ghist, r.nbytes, B.brk, r.cert, r.okey,
+                               B.gdir_off, B.gcls, B.gbig, B.upos[r.nxt], B.ug[r.nxt], B.tile_g0, B.tile_big);
+        });
+    else
+        with_const<0, 1, 2, 3>(r.mode, [&](auto M) {
+            hipLaunchKernelGGL(HIP_KERNEL_NAME(fwd::k_b_keys<decltype(M)::value>), dim3(tiles), dim3(256), 0, f.s, B.upos[cur], B.ug[cur], B.uitem[cur], B.rank, f.d_x, r.hh, f.n,
+                               r.shift, mb, kT, vT, f.fg_status(), B.sc.d_ticket, B.sc.d_err, B.sc.d_ghist, r.nbytes, B.brk, r.cert, r.okey);
+        });
+    ++f.c->launches;
+    return ARCHON_OK;
+}
+
+// 3. The groups of one mid class (the large one first, then the small one), one workgroup each.
+int Rounds::mid_class(const Plan &r, int lanes, const uint4 *dir, uint32_t groups)
+{
+    FwdBuf &B = f.B;
+    with_const<0, 2, 3>(r.mode, [&](auto M) {
+        with_const<(int)fwd::kMidLargeLanes, (int)fwd::kMidSmallLanes>(lanes, [&](auto LN) {
+            hipLaunchKernelGGL(HIP_KERNEL_NAME(fwd::k_mid_round<decltype(M)::value, decltype(LN)::value>), dim3(groups), dim3(decltype(LN)::value), 0, f.s, dir, B.uitem[cur], B.rank, f.d_x, r.hh, f.n,
+                               f.sa, r.s_next, B.rlog, f.cnt(), B.uitem[r.nxt], B.dirS[r.nxt], B.dirL[r.nxt], (uint32_t)mid_dir_cap(f.n), B.mc, (uint32_t)r.nxt, f.d_bwt, f.d_base, B.brk, r.cert,
+                               r.okey, B.sc.d_err);
+        });
+    });
+    ARCHON_HIP_TRY(hipGetLastError());
+    ++f.c->launches;
+    return ARCHON_OK;
+}
+
+// 4. The S list, in one kernel: behind the B keys (both read the rank table the round found) and before the B sort, whose
+// host waits it fills.
+int Rounds::s_round(const Plan &r)
+{
+    if (!ms) return ARCHON_OK;
+    FwdBuf &B = f.B;
+    with_const<0, 1, 2, 3>(r.mode, [&](auto M) {
+        hipLaunchKernelGGL(HIP_KERNEL_NAME(fwd::k_round_fused<decltype(M)::value>), dim3(div_up(ms, fwd::kFuT)), dim3(fwd::kFuLanes), 0, f.s, B.slist[cs], ms, B.rank, f.d_x, r.hh, f.sa, B.v,
+                           B.slist[cs ^ 1], B.rlog, f.cnt(), B.sc.d_err, f.d_bwt, f.d_base, f.n, r.chain, pk, pv, B.brk);
+    });
+    ARCHON_HIP_TRY(hipGetLastError());
+    ++f.c->launches;
+    return ARCHON_OK;
+}
+
+// 5. The global sort of the big groups' pairs, and k_b_finish: new groups, ranks (stored, or logged for the writer), the next lists.
+int Rounds::b_sort(Plan &r)
+{
+    if (!r.nbig) return ARCHON_OK;
+    FwdBuf &B = f.B;
+    uint32_t passes = 0;
+    bool b_in_b = false;
+    ARCHON_TRY(rs::sort_pairs(f.s, B.sc, kT, vT, kS, vS, r.nbig, (1u << r.nbytes) - 1u, &b_in_b, &passes, &f.c->launches, nullptr, nullptr, nullptr, true));
+    const uint32_t tiles = div_up(r.nbig, fwd::kBfTile);
+    ARCHON_TRY(f.reset_lookback(tiles));
+    const uint64_t *ks = b_in_b ? kS : kT;
+    const uint32_t *vs = b_in_b ? vS : vT;
+    r.b_log = r.writer ? reinterpret_cast<uint2 *>(b_in_b ? kT : kS) : nullptr;        // the sort's other key buffer is free now
+    // (split: the big groups' rows and old group starts lie compacted in the NEXT list's buffers, which k_b_finish then
+    //  overwrites in place -- a tile writes at or below its own positions, and only once every tile before it has
+    //  published its totals, which it does after loading its entries)
+    const int src = r.split ? r.nxt : cur;
+    // (a text round has no rank table yet: its new group starts go to B.v)
+    with_const<0, 1>(r.mode == 1, [&](auto T) {
+        hipLaunchKernelGGL(HIP_KERNEL_NAME(fwd::k_b_finish<decltype(T)::value>), dim3(tiles), dim3(256), 0, f.s, ks, vs, B.upos[src], B.ug[src], r.nbig, f.sa, decltype(T)::value ? B.v : B.rank, r.s_next,
+                           f.cnt(), B.upos[r.nxt], B.ug[r.nxt], B.uitem[r.nxt], f.fg_status(), B.sc.d_ticket, B.sc.d_err, f.d_x, f.d_bwt, f.d_base, f.n, r.b_log);
+    });
+    ARCHON_HIP_TRY(hipGetLastError());
+    ++f.c->launches;
+    return ARCHON_OK;
+}
+
+// 6. The round's counters (and the mid lists'), with the round's one unconditional wait.
+int Rounds::fetch_counters(Plan &r)
+{
+    if (r.mid) ARCHON_HIP_TRY(hipMemcpyAsync(f.c->h_mail + mail::kRounds.at, f.B.mc, fwd::kMcWords * sizeof(uint32_t), hipMemcpyDeviceToHost, f.s));
+    ARCHON_HIP_TRY(hipMemcpyAsync(f.rd() + mail::kRdCnt, f.cnt(), fwd_small::kCntWords * sizeof(uint32_t), hipMemcpyDeviceToHost, f.s));
+    ARCHON_SYNC(f.s);
+    r.nlog = r.mode != 1 ? f.rd()[mail::kRdCnt + fwd_small::kCntLog] : 0u;
+    return ARCHON_OK;
+}
+
+// 7. Rank updates, now that every key of the round has been read.  Dealt by item into windows of the table (rank_writer.hiph:
+// two partition sweeps + one window write, 0.6 ms whatever the number + 11 ps per update) they beat one random store each
+// (32 ps) from about 28 M updates on; the B list's updates are logged by position whenever that list is long (b_log).
+int Rounds::apply_ranks(const Plan &r)
+{
+    FwdBuf &B = f.B;
+    if (r.b_log || (writer_ok && r.mode != 1 && r.nlog >= kWriterMinLog)) {
+        ARCHON_TRY(f.writer_regions(r.b_log == reinterpret_cast<uint2 *>(kT) ? kS : kT));       // the key buffer that is not the B log
+        if (r.nlog) hipLaunchKernelGGL(HIP_KERNEL_NAME(rw::k_part<1, 0>), dim3(div_up(r.nlog, rw::kTile)), dim3(rw::kLanes), 0, f.s, B.rlog, nullptr, r.nlog, nullptr, nullptr, nullptr, B.rwb.r1, B.rwb.cnt1);
+        if (r.b_log) hipLaunchKernelGGL(HIP_KERNEL_NAME(rw::k_part<1, 0>), dim3(div_up(r.nbig, rw::kTile)), dim3(rw::kLanes), 0, f.s, r.b_log, nullptr, r.nbig, nullptr, nullptr, nullptr, B.rwb.r1, B.rwb.cnt1);
+        ARCHON_TRY(rw::write_back(f.s, B.rwb, f.n, B.rank, &f.c->launches));
+        f.c->launches += 2;
+    } else if (r.nlog) {
+        hipLaunchKernelGGL(fwd::k_rank_apply, dim3(div_up(r.nlog, 256)), dim3(256), 0, f.s, B.rlog, f.cnt() + fwd_small::kCntLog, B.rank);
+        ++f.c->launches;
+    }
+    return ARCHON_OK;
+}
+
+// the lists the round left, from its counters
+int Rounds::next_lists(const Plan &r)
+{
+    const uint32_t *rd = f.rd() + mail::kRdCnt, *h_mc = f.c->h_mail + mail::kRounds.at;
+    const bool flip = r.mid || mb != 0;         // (short groups that straddle a tile of k_b_finish's sweep stay in B for another round)
+    ms = rd[fwd_small::kCntS];
+    mb = r.nbig ? rd[fwd_small::kCntB] : 0u;
+    bgroups = rd[fwd_small::kCntGroups];
+    if (r.mid) {
+        mdS = h_mc[fwd::kMcSmall + r.nxt];
+        mdL = h_mc[fwd::kMcLarge + r.nxt];
+        mm = f.n - h_mc[fwd::kMcTop + r.nxt];
+        if (mdS > mid_dir_cap(f.n) || mdL > mid_dir_cap(f.n)) { set_error("mid directory overflow (%u / %u groups)", mdS, mdL); return ARCHON_E_INTERNAL; }
+    }
+    if (flip) cur ^= 1;
+    if (!r.b_only) cs ^= 1;
+    return ARCHON_OK;
+}
+
+// 8. The round's pairs by passage: sort the records by their smaller item, one look-up per run, spread, apply; one wait for
+// the entries the pass hands back to the S list.
+int Rounds::pair_chain(uint32_t np)
+{
+    FwdBuf &B = f.B;
+    bool in2 = false;
+    uint32_t passes = 0;
+    ARCHON_TRY(rs::sort_pairs(f.s, B.sc, pk, pv, pk2, pv2, np, 0xF0u, &in2, &passes, &f.c->launches));
+    const uint64_t *k2 = in2 ? pk2 : pk;
+    const uint32_t *v2 = in2 ? pv2 : pv;
+    hipLaunchKernelGGL(fwd::k_pair_heads, dim3(div_up(np, 256)), dim3(256), 0, f.s, k2, np, B.rank, pair_v, pair_code);
+    ARCHON_TRY(launch_scan<1>(f.s, pair_v, pair_v, np, B.scan_tmp, nullptr));
+    hipLaunchKernelGGL(fwd::k_pair_apply, dim3(div_up(np, 256)), dim3(256), 0, f.s, k2, v2, pair_v, pair_code, np, f.sa, B.rank, f.d_x, f.d_bwt, f.d_base, f.n,
+                       B.slist[cs], f.cnt());
+    ARCHON_HIP_TRY(hipGetLastError());
+    f.c->launches += 4;
+    uint32_t *rd = f.rd() + mail::kRdCnt;
+    ARCHON_HIP_TRY(hipMemcpyAsync(rd, f.cnt(), sizeof(uint32_t), hipMemcpyDeviceToHost, f.s));
+    ARCHON_SYNC(f.s);
+    const uint32_t back = rd[fwd_small::kCntS] - ms;         // entries the pass could not settle (two per pair)
+    ms = rd[fwd_small::kCntS];
+    f.c->stats.chain_pairs += np - back / 2u;
+    if ((uint64_t)back > np) chain_cool = 3;         // fewer than half of the pairs settled: give the rounds some time
+    return ARCHON_OK;
+}
+
+// The period-defect rounds (modes 2 and 3 of Rounds::round) and what they go by.
+struct PeriodDefects {
+    uint32_t period = 0;         // period of the break table in B.brk while its rounds can still settle something
+    uint32_t fail = 0;           // continuation rounds in a row that settled nothing
+    uint32_t breaks = 0;         // positions where the text stops repeating at that distance
+    bool first = true;           // the next of its rounds is the distance round
 };
 
 // A5 + A7 for whatever the first stage left tied.  On entry (k_first_groups): sa[] holds the items in first-stage order,
@@ -424,492 +832,295 @@ struct Fwd {
 // (row, group start, item) triples in buffer 0 (fwd_small::kTotal counts them, fwd_small::kFu + 3 their groups).  Runs the run
 // shortcut for periodic blocks, text rounds, the rank table, doubling rounds with the pair chains.  Rows take their
 // BWT symbol when they become final.
+struct General {
+    Fwd &f;
+    archon_hip_stats &st = f.c->stats;
+    RoundTrace tr{f.s};
+    Rounds R{f};
+    PeriodDefects z;
+    uint32_t m = 0, h = f.h0;                    // tied rows; symbols every tied group agrees on
+    uint32_t ms_first = 0, mb_first = 0, groups_first = 0;      // the lists of k_first_groups
+    bool lists_ready = f.ws_ready;               // the lists of k_first_groups still describe the tied set
+    bool keep_ready = false;                     // B.keep / B.dst describe the current tied set
+
+    explicit General(Fwd &fwd) : f(fwd) {}
+    int entry_counts(), run_shortcut(), settle_runs(uint32_t p), build_lists(), text_rounds(), fill_rank_table(), certified_break_rounds(), break_rounds(), rounds_to_the_end();
+};
+
 int Fwd::general_stage()
 {
-    archon_hip_stats &st = c->stats;
-    const uint32_t p_hint = period_hint, p_breaks = period_breaks;
-    const uint32_t g256 = div_up(n, 256);
-#ifdef ARCHON_EXPERIMENTS
-    const bool tracing = getenv("ARCHON_TRACE_ROUNDS") != nullptr;
-    auto t_last = std::chrono::steady_clock::now();
-    auto trace = [&](const char *what) {
-        if (!tracing) return;
-        (void)hipStreamSynchronize(s);
-        const auto t = std::chrono::steady_clock::now();
-        fprintf(stderr, "  general_stage: %-28s %.3f ms\n", what, std::chrono::duration<double, std::milli>(t - t_last).count());
-        t_last = t;
-    };
-#else
-    auto trace = [](const char *) {};
-#endif
-    trace("enter");
-    uint32_t *rd = c->h_mail + mail::kRead.at;   // readback words
-    const uint32_t *h_mc = c->h_mail + mail::kRounds.at;     // the mid lists' counters (fwd::kMc*) after a round
-    uint32_t *d_total = B.small + fwd_small::kTotal;
-    uint32_t *d_fu = B.small + fwd_small::kFu;              // [0] entries appended to the next S list, [1] rank log entries, [2] the next B list, [3] its groups, [4] pairs listed, [5] pairs seen
-    ARCHON_HIP_TRY(hipMemcpyAsync(rd, d_total, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
-    ARCHON_HIP_TRY(hipMemcpyAsync(rd + 4, d_fu, 4 * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
-    ARCHON_SYNC(s);
-    const uint32_t ms_first = ws_ready ? rd[4] : 0u, mb_first = rd[0], groups_first = rd[7];
-    uint32_t m = ms_first + mb_first;
+    General g(*this);
+    ARCHON_TRY(g.entry_counts());
+    ARCHON_TRY(g.run_shortcut());
+    ARCHON_TRY(g.build_lists());
+    ARCHON_TRY(g.text_rounds());
+    ARCHON_TRY(g.fill_rank_table());
+    ARCHON_TRY(g.certified_break_rounds());
+    ARCHON_TRY(g.rounds_to_the_end());
+    g.tr.step("rounds done");
+    return ARCHON_OK;
+}
+
+// How many rows the first stage left tied, and in which lists.
+int General::entry_counts()
+{
+    tr.step("enter");
+    uint32_t *rd = f.rd();
+    ARCHON_HIP_TRY(hipMemcpyAsync(rd + mail::kRdTotal, f.B.small + fwd_small::kTotal, sizeof(uint32_t), hipMemcpyDeviceToHost, f.s));
+    ARCHON_HIP_TRY(hipMemcpyAsync(rd + mail::kRdEntryCnt, f.cnt(), 4 * sizeof(uint32_t), hipMemcpyDeviceToHost, f.s));
+    ARCHON_SYNC(f.s);
+    ms_first = f.ws_ready ? rd[mail::kRdEntryCnt + fwd_small::kCntS] : 0u;
+    mb_first = rd[mail::kRdTotal];
+    groups_first = rd[mail::kRdEntryCnt + fwd_small::kCntGroups];
+    m = ms_first + mb_first;
     st.unresolved_initial = m;
-    uint32_t z_period = 0;                       // period of the break table in B.brk while its rounds (do_round modes 2, 3) can still settle something
-    uint32_t z_fail = 0;                         // continuation rounds in a row that settled nothing
-    uint32_t z_breaks = 0;                       // positions where the text stops repeating at that distance
-    bool z_first = true;
-    bool lists_ready = ws_ready;                 // the lists of k_first_groups still describe the tied set
-    bool keep_ready = false;                     // B.keep / B.dst describe the current tied set
-    // long-repeat defence: when much of the block is tied and one neighbour gap dominates the tied groups,
-    // settle the periodic runs directly (forward.hiph, k_chain_*) before any doubling round
-    // (long duplicates without a period -- deep_ties and no period probe -- are pairs: the pair chains of the rounds settle
-    //  them with less per-group work than this shortcut spends on millions of two-row groups)
-    if (brk_ready && p_breaks && m) {
+    return ARCHON_OK;
+}
+
+// Long-repeat defence: when much of the block is tied and one neighbour gap dominates the tied groups,
+// settle the periodic runs directly (forward.hiph, k_chain_*) before any doubling round
+// (long duplicates without a period -- deep_ties and no period probe -- are pairs: the pair chains of the rounds settle
+//  them with less per-group work than this shortcut spends on millions of two-row groups)
+int General::run_shortcut()
+{
+    const uint32_t p_hint = f.period_hint, p_breaks = f.period_breaks;
+    if (f.brk_ready && p_breaks && m) {
         // the period is known and the text breaks it somewhere: the tied groups straddle the defects, none of them is one clean
-        // run -- the run shortcut would look at every row and settle nothing; the period-defect rounds below take all of it
-        z_period = p_hint;
-        z_breaks = p_breaks;
+        // run -- the run shortcut would look at every row and settle nothing; the period-defect rounds take all of it
+        z.period = p_hint;
+        z.breaks = p_breaks;
         st.period = p_hint;
-    } else if (m >= n / 16 && !(deep_ties && p_hint == 0) && !route_off(kRtNoChains)) {
-        uint32_t p = p_hint;
-        bool dominant = p_hint != 0;        // the driver's period probe already named the period (and the groups may be unordered)
-        if (!dominant) {
-            uint32_t *tab = B.hist16;                       // 2 * kGapSlots words (32 KiB) of the two-byte count's table, idle by now (256 KiB whatever n is:
-                                                            // a list buffer of a small block is shorter than the table)
-            ARCHON_HIP_TRY(hipMemsetAsync(tab, 0, 2 * fwd::kGapSlots * sizeof(uint32_t), s));
-            hipLaunchKernelGGL(fwd::k_gap_sample, dim3(div_up(div_up(n, fwd::kGapStride), 256)), dim3(256), 0, s, sa, B.v, n, tab);
-            const uint32_t *h_tab = c->h_mail + mail::kGapTable.at;
-            ARCHON_HIP_TRY(hipMemcpyAsync(c->h_mail + mail::kGapTable.at, tab, 2 * fwd::kGapSlots * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
-            ARCHON_SYNC(s);
-            c->launches += 1;
-            uint64_t total = 0;
-            uint32_t best = 0;
-            for (uint32_t i = 0; i < fwd::kGapSlots; ++i) {
-                total += h_tab[i];
-                if (h_tab[i] > h_tab[best]) best = i;
-            }
-            p = h_tab[fwd::kGapSlots + best];
-            dominant = (uint64_t)h_tab[best] * 4 >= total;
-        }
-        if (p >= 1 && p < n && dominant) {
-            uint32_t *brk = B.brk, *ginfo = B.dst, *gend = B.keep, *settled = B.small + fwd_small::kSettled;
-            uint32_t *gmin = B.ug[1], *gmax = B.uitem[1];       // the second triple buffers are idle
-            uint32_t *d_lastbrk = B.small + fwd_small::kLastBrk;
-            if (!(brk_ready && p == p_hint)) {
-                ARCHON_HIP_TRY(hipMemsetAsync(d_lastbrk, 0, 2 * sizeof(uint32_t), s));  // [0] last real break, [1] how many
-                hipLaunchKernelGGL(fwd::k_period_breaks, dim3(div_up(div_up(n, 4), 256)), dim3(256), 0, s, d_x, n, p, brk, d_lastbrk);
-                ARCHON_TRY(launch_scan<1>(s, brk, brk, n, B.scan_tmp, nullptr));
-            }
-            hipLaunchKernelGGL(fwd::k_chain_init, dim3(g256), dim3(256), 0, s, B.v, n, gmin, gmax, ginfo);
-            ARCHON_HIP_TRY(hipMemsetAsync(settled, 0, sizeof(uint32_t), s));
-            trace("breaks + scan + memsets");
-            hipLaunchKernelGGL(fwd::k_chain_minmax, dim3(div_up(n, fwd::kChainRows)), dim3(256), 0, s, sa, B.v, n, gmin, gmax);
-            trace("chain_minmax");
-            hipLaunchKernelGGL(fwd::k_chain_probe, dim3(div_up(n, fwd::kChainRows)), dim3(256), 0, s, d_x, sa, B.v, brk, n, p, gmin, gmax, d_lastbrk, ginfo, gend);
-            trace("chain_probe");
-            hipLaunchKernelGGL(fwd::k_chain_apply, dim3(div_up(n, fwd::kChainRows)), dim3(256), 0, s, sa, B.v, ginfo, gend, gmin, gmax, brk, d_lastbrk, d_x, n, p, d_bwt, d_base, settled);
-            trace("chain_apply");
-            ARCHON_HIP_TRY(hipMemcpyAsync(rd + 1, settled, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
-            ARCHON_HIP_TRY(hipMemcpyAsync(rd + 2, d_lastbrk + 1, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
-            ARCHON_SYNC(s);
-            z_breaks = rd[2];
-            c->launches += 8;
-            if (rd[1] >= m) {
-                m = 0;                          // every tied row was settled: nothing to count or compact
-            } else if (rd[1] != 0 || !lists_ready) {
-                lists_ready = false;
-                keep_ready = true;
-                // the tied set again, without the settled groups
-                hipLaunchKernelGGL(fwd::k_keep_flags, dim3(g256), dim3(256), 0, s, B.v, n, B.keep);
-                ARCHON_TRY(launch_scan<0>(s, B.keep, B.dst, n, B.scan_tmp, d_total));
-                ARCHON_HIP_TRY(hipMemcpyAsync(rd, d_total, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
-                ARCHON_SYNC(s);
-                c->launches += 3;
-                m = rd[0];
-            }
-            trace("keep + scan again");
-            st.period = p;
-            st.chain_items = rd[1];
-            if (m) z_period = p;                // what is left straddles defects of the period: one break-distance round once h >= p
-        }
-    }
-    int cur = 0;                                 // buffer that holds the B list
-    uint64_t *kT = B.keyA, *kS = B.keyB;
-    uint32_t *vT = B.valA, *vS = B.valB;
-    uint32_t h = h0;
-    uint32_t ms = 0, mb = 0, bgroups = 1;
-    // the mid lists (mid_rounds.hiph): entries / groups of the two classes in the CURRENT list (buffer `cur`)
-    uint32_t mm = 0, mdS = 0, mdL = 0;
-    {
-        uint32_t init[fwd::kMcWords] = {};
-        init[fwd::kMcTop] = init[fwd::kMcTop + 1] = n;
-        memcpy(c->h_mail + mail::kRoundsInit.at, init, sizeof init);     // (words of their own: mail::kRounds takes the rounds' counters)
-        ARCHON_HIP_TRY(hipMemcpyAsync(B.mc, c->h_mail + mail::kRoundsInit.at, sizeof init, hipMemcpyHostToDevice, s));
-    }
-    int cs = 0;
-    unsigned long long *fg_status = reinterpret_cast<unsigned long long *>(B.sc.d_status);
-    if (m && lists_ready) {
-        ms = ms_first;
-        mb = mb_first;
-        bgroups = groups_first;
-    } else if (m) {
-        // the run shortcut changed the tied set (or the set was only counted): all of it as triples, then split into the
-        // lists (k_classify: short groups to S, the others stay in row order)
-        if (!keep_ready) {
-            hipLaunchKernelGGL(fwd::k_keep_flags, dim3(g256), dim3(256), 0, s, B.v, n, B.keep);
-            ARCHON_TRY(launch_scan<0>(s, B.keep, B.dst, n, B.scan_tmp, d_total));
-            c->launches += 3;
-        }
-        hipLaunchKernelGGL(fwd::k_compact_first, dim3(g256), dim3(256), 0, s, B.keep, B.dst, B.v, sa, n, B.upos[0], B.ug[0], B.uitem[0]);
-        const uint32_t tiles = div_up(m, fwd::kClT);
-        ARCHON_HIP_TRY(hipMemsetAsync(d_fu, 0, 4 * sizeof(uint32_t), s));
-        ARCHON_HIP_TRY(hipMemsetAsync(fg_status, 0, (size_t)tiles * sizeof(unsigned long long), s));
-        ARCHON_HIP_TRY(hipMemsetAsync(B.sc.d_ticket, 0, sizeof(uint32_t), s));
-        hipLaunchKernelGGL(fwd::k_classify, dim3(tiles), dim3(fwd::kFuLanes), 0, s, B.upos[0], B.ug[0], B.uitem[0], m, B.slist[cs], d_fu,
-                           B.upos[1], B.ug[1], B.uitem[1], d_fu + 2, fg_status, B.sc.d_ticket, B.sc.d_err);
-        ARCHON_HIP_TRY(hipGetLastError());
-        c->launches += 2;
-        ARCHON_HIP_TRY(hipMemcpyAsync(rd, d_fu, 3 * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
-        ARCHON_SYNC(s);
-        ms = rd[0];
-        mb = rd[2];
-        bgroups = mb / (fwd::kFuMax + 1u) + 2u;          // every group left in B is longer than kFuMax
-        cur = 1;
-        if (ms + mb != m) { set_error("classification lost entries (%u + %u of %u)", ms, mb, m); return ARCHON_E_INTERNAL; }
-        trace("classify");
-    }
-    // pair chains (rounds.hiph, k_pair_*): {smaller item, distance} records, their {row, flag} words, sort buffers, run heads
-    // (the list itself lives through the round; the chain pass behind the round's rank updates borrows the key / value
-    //  buffers of the B sort, which are idle by then)
-    uint64_t *pk = reinterpret_cast<uint64_t *>(B.keep), *pk2 = B.keyA;       // n/2 records of 8 bytes each
-    uint32_t *pv = B.pairw, *pv2 = B.valA, *pair_v = B.valA + (n / 2 + 8), *pair_code = B.valA + 2 * ((size_t)n / 2 + 8);
-    // (deep_ties: the streaming stage compared every tied group 64 symbols deep and they still agree -- long duplicates: no
-    //  text rounds, and the first doubling round already lists its pairs)
-    bool chain_next = deep_ties;                 // list the pairs of the coming round and settle them by passage
-    uint32_t chain_cool = 0;
-    const bool chain_ok = n >= 4 && !route_off(kRtNoPairChains);
-    const bool writer_ok = n >= (1u << 22) && !route_off(kRtNoRankWriter);
-    const uint32_t kWriterMinLog = n >= (1u << 26) ? (24u << 20) : n / 4;       // (small blocks keep exercising the writer in the tests)
-    // One round over both lists: mode 0 keys on rank[s-h], mode 1 on the next four text bytes, modes 2 and 3 (hh = the period)
-    // on the distance to the last period defect and on the rank of the item the key continues as behind it (rounds.hiph,
-    // break_key / cont_key; rank table kept as in mode 0).
-    // The rank table is read by every key gather of the round (S: k_round_fused, B: k_b_keys) before anything writes it
-    // (S: the log, applied at the end; B: k_b_finish): the launches below are ordered accordingly.
-    // b_only (modes 2, 3 with certified groups, `cert` = the marks of k_zone_certify): the S list sits the round out;
-    // groups of the B list that have become short are appended to it where it is.
-    auto do_round = [&](int mode, uint32_t hh, bool b_only = false, const uint8_t *cert = nullptr, const uint32_t *okey = nullptr) -> int {
-        const uint32_t ms_kept = b_only ? ms : 0u;
-        if (b_only) ms = 0;
-        const uint32_t chain = (chain_next && chain_ok && mode == 0 && ms) ? 1u : 0u;
-        const uint32_t m_before = ms + mb + mm;
-        ARCHON_HIP_TRY(hipMemsetAsync(d_fu, 0, 6 * sizeof(uint32_t), s));
-        if (ms_kept) ARCHON_HIP_TRY(hipMemsetD32Async((hipDeviceptr_t)d_fu, (int)ms_kept, 1, s));      // k_b_finish appends behind the kept entries
-        uint2 *s_next = b_only ? B.slist[cs] : B.slist[cs ^ 1];
-        // Mid groups (mid_rounds.hiph): the B list is dealt out by group length -- groups of at most 16 Ki entries are sorted by
-        // ONE workgroup each, in LDS (with the groups the mid kernels made last round); only the longer ones take the global
-        // sort below.  (Text rounds keep round 3's path: they run on small sets.)
-        const bool mid = mode != 1 && !route_off(kRtNoMid);
-        uint32_t nS = mdS, nL = mdL, nbig = mb, nbig_groups = bgroups, mid_from_b = 0;
-        bool split = false;                         // the B list was dealt out: its big groups go to the global sort compacted
-        const int nxt = cur ^ 1;
-        if (mid) {
-            // the next list starts empty: no groups, its items from the top of the buffer downwards
-            // (fills, not copies out of the mailbox: mail::kRounds receives this round's counters further down)
-            ARCHON_HIP_TRY(hipMemsetD32Async((hipDeviceptr_t)(B.mc + fwd::kMcSmall + nxt), 0, 1, s));
-            ARCHON_HIP_TRY(hipMemsetD32Async((hipDeviceptr_t)(B.mc + fwd::kMcLarge + nxt), 0, 1, s));
-            ARCHON_HIP_TRY(hipMemsetD32Async((hipDeviceptr_t)(B.mc + fwd::kMcTop + nxt), (int)n, 1, s));
-            // (a B list whose groups average twice the largest mid group -- a periodic block with defects: one group per phase of
-            //  the period -- goes to the global sort as it is: the two sweeps that would deal it out find nothing to hand over)
-            if (mb && (uint64_t)bgroups * (2u * fwd::kMidLargeCap) > mb) {
-                const uint32_t tiles = div_up(mb, fwd::kBfTile);
-                ARCHON_HIP_TRY(hipMemsetAsync(fg_status, 0, (size_t)tiles * sizeof(unsigned long long), s));
-                ARCHON_HIP_TRY(hipMemsetAsync(B.sc.d_ticket, 0, sizeof(uint32_t), s));
-                split = true;
-                hipLaunchKernelGGL(fwd::k_b_dir, dim3(tiles), dim3(256), 0, s, B.upos[cur], B.ug[cur], mb, B.gdir_off, B.gdir_row, fg_status, B.sc.d_ticket, B.sc.d_err, B.mc, (uint32_t)mid_dir_cap(n), B.tile_g0);
-                hipLaunchKernelGGL(fwd::k_b_plan, dim3(1), dim3(1024), 0, s, B.gdir_off, B.gdir_row, mb, B.gcls, B.gbig, B.dirS[cur], B.dirL[cur], B.mc, (uint32_t)cur,
-                                   (uint32_t)fwd::kMidSmallCap, (uint32_t)fwd::kMidLargeCap, (uint32_t)mid_dir_cap(n), B.sc.d_err, B.tile_big);
-                ARCHON_HIP_TRY(hipGetLastError());
-                ARCHON_HIP_TRY(hipMemcpyAsync(c->h_mail + mail::kRounds.at, B.mc, fwd::kMcWords * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
-                ARCHON_SYNC(s);
-                c->launches += 2;
-                if (h_mc[fwd::kMcGroups] > mid_dir_cap(n)) { set_error("B list of %u entries holds %u groups (directory: %zu)", mb, h_mc[fwd::kMcGroups], mid_dir_cap(n)); return ARCHON_E_INTERNAL; }
-                nS = h_mc[fwd::kMcSmall + cur];
-                nL = h_mc[fwd::kMcLarge + cur];
-                nbig = h_mc[fwd::kMcBigEntries];
-                nbig_groups = h_mc[fwd::kMcBigGroups];
-                mid_from_b = h_mc[fwd::kMcMidEntries];
-                if (nbig + mid_from_b != mb) { set_error("plan of the B list lost entries (%u + %u of %u)", nbig, mid_from_b, mb); return ARCHON_E_INTERNAL; }
-            }
-        }
-        const uint32_t mid_entries = mid ? mm + mid_from_b : 0u;
-        st.mid_items += mid_entries;
-        // a long B list logs its rank updates by position for the rank writer (below) instead of storing them one by one
-        const bool writer = mode != 1 && writer_ok && nbig >= (8u << 20);
-        // B: keys (the gather) now, global sort on (group, key) behind the S kernel -- which so runs while the host waits for
-        // the sort's digit counts
-        uint32_t shift = 32, gbits = 1;
-        if (mode != 1) { shift = 1; while ((2ull * n + (mode == 2 ? 2u : 0u)) >> shift) ++shift; }    // bits of a key k < 2n (mode 2: 2n + 2)
-        while ((uint64_t)nbig_groups >> gbits) ++gbits;                             // bits of a group number of the (big) B list
-        const uint32_t nbytes = (shift + gbits + 7) / 8;
-        const uint32_t mb_round = nbig;
-        if (nbig) {
-            st.seg_big_items += nbig;
-            const uint32_t tiles = div_up(mb, fwd::kBfTile);
-            ARCHON_HIP_TRY(hipMemsetAsync(fg_status, 0, (size_t)tiles * sizeof(unsigned long long), s));
-            ARCHON_HIP_TRY(hipMemsetAsync(B.sc.d_ticket, 0, sizeof(uint32_t), s));
-            ARCHON_HIP_TRY(hipMemsetAsync(B.sc.d_ghist, 0, 8 * 256 * sizeof(uint32_t), s));
-#define ARCHON_B_KEYS(M) hipLaunchKernelGGL(HIP_KERNEL_NAME(fwd::k_b_keys<M>), dim3(tiles), dim3(256), 0, s, B.upos[cur], B.ug[cur], B.uitem[cur], B.rank, d_x, hh, n, \
-                                            shift, mb, kT, vT, fg_status, B.sc.d_ticket, B.sc.d_err, B.sc.d_ghist, nbytes, B.brk, cert, okey)
-#define ARCHON_B_KEYS_SPLIT(M) hipLaunchKernelGGL(HIP_KERNEL_NAME(fwd::k_b_keys_split<M>), dim3(tiles), dim3(256), 0, s, B.upos[cur], B.ug[cur], B.uitem[cur], B.rank, d_x, hh, n, \
-                                            shift, mb, kT, vT, fg_status, B.sc.d_ticket, B.sc.d_err, B.sc.d_ghist, nbytes, B.brk, cert, okey, \
-                                            B.gdir_off, B.gcls, B.gbig, B.upos[nxt], B.ug[nxt], B.tile_g0, B.tile_big)
-            if (split) {
-                if (mode == 0) ARCHON_B_KEYS_SPLIT(0);
-                else if (mode == 2) ARCHON_B_KEYS_SPLIT(2);
-                else ARCHON_B_KEYS_SPLIT(3);
-            } else if (mode == 0) ARCHON_B_KEYS(0);
-            else if (mode == 1) ARCHON_B_KEYS(1);
-            else if (mode == 2) ARCHON_B_KEYS(2);
-            else ARCHON_B_KEYS(3);
-#undef ARCHON_B_KEYS
-#undef ARCHON_B_KEYS_SPLIT
-            ++c->launches;
-        }
-        if (mid && (nS || nL)) {
-#define ARCHON_MID(M, LN, DIRP, CNT) hipLaunchKernelGGL(HIP_KERNEL_NAME(fwd::k_mid_round<M, LN>), dim3(CNT), dim3(LN), 0, s, DIRP, B.uitem[cur], B.rank, d_x, hh, n, sa, s_next, \
-                                                        B.rlog, d_fu, B.uitem[nxt], B.dirS[nxt], B.dirL[nxt], (uint32_t)mid_dir_cap(n), B.mc, (uint32_t)nxt, d_bwt, d_base, B.brk, cert, okey, B.sc.d_err)
-            if (nL) {
-                if (mode == 0) ARCHON_MID(0, fwd::kMidLargeLanes, B.dirL[cur], nL);
-                else if (mode == 2) ARCHON_MID(2, fwd::kMidLargeLanes, B.dirL[cur], nL);
-                else ARCHON_MID(3, fwd::kMidLargeLanes, B.dirL[cur], nL);
-                ++c->launches;
-            }
-            if (nS) {
-                if (mode == 0) ARCHON_MID(0, fwd::kMidSmallLanes, B.dirS[cur], nS);
-                else if (mode == 2) ARCHON_MID(2, fwd::kMidSmallLanes, B.dirS[cur], nS);
-                else ARCHON_MID(3, fwd::kMidSmallLanes, B.dirS[cur], nS);
-                ++c->launches;
-            }
-#undef ARCHON_MID
-            ARCHON_HIP_TRY(hipGetLastError());
-        }
-        if (ms) {
-            const dim3 grid(div_up(ms, fwd::kFuT)), block(fwd::kFuLanes);
-#define ARCHON_S_ROUND(M) hipLaunchKernelGGL(HIP_KERNEL_NAME(fwd::k_round_fused<M>), grid, block, 0, s, B.slist[cs], ms, B.rank, d_x, hh, sa, B.v, B.slist[cs ^ 1], B.rlog, \
-                                             d_fu, B.sc.d_err, d_bwt, d_base, n, chain, pk, pv, B.brk)
-            if (mode == 0) ARCHON_S_ROUND(0);
-            else if (mode == 1) ARCHON_S_ROUND(1);
-            else if (mode == 2) ARCHON_S_ROUND(2);
-            else ARCHON_S_ROUND(3);
-#undef ARCHON_S_ROUND
-            ARCHON_HIP_TRY(hipGetLastError());
-            ++c->launches;
-        }
-        uint2 *b_log = nullptr;
-        if (nbig) {
-            uint32_t passes = 0;
-            bool b_in_b = false;
-            ARCHON_TRY(rs::sort_pairs(s, B.sc, kT, vT, kS, vS, nbig, (1u << nbytes) - 1u, &b_in_b, &passes, &c->launches, nullptr, nullptr, nullptr, true));
-            const uint32_t tiles = div_up(nbig, fwd::kBfTile);
-            ARCHON_HIP_TRY(hipMemsetAsync(fg_status, 0, (size_t)tiles * sizeof(unsigned long long), s));
-            ARCHON_HIP_TRY(hipMemsetAsync(B.sc.d_ticket, 0, sizeof(uint32_t), s));
-            const uint64_t *ks = b_in_b ? kS : kT;
-            const uint32_t *vs = b_in_b ? vS : vT;
-            b_log = writer ? reinterpret_cast<uint2 *>(b_in_b ? kT : kS) : nullptr;        // the sort's other key buffer is free now
-            // (split: the big groups' rows and old group starts lie compacted in the NEXT list's buffers, which k_b_finish then
-            //  overwrites in place -- a tile writes at or below its own positions, and only once every tile before it has
-            //  published its totals, which it does after loading its entries)
-            const int src = split ? nxt : cur;
-            if (mode != 1)
-                hipLaunchKernelGGL(HIP_KERNEL_NAME(fwd::k_b_finish<0>), dim3(tiles), dim3(256), 0, s, ks, vs, B.upos[src], B.ug[src], nbig, sa, B.rank, s_next, d_fu,
-                                   B.upos[nxt], B.ug[nxt], B.uitem[nxt], fg_status, B.sc.d_ticket, B.sc.d_err, d_x, d_bwt, d_base, n, b_log);
-            else
-                hipLaunchKernelGGL(HIP_KERNEL_NAME(fwd::k_b_finish<1>), dim3(tiles), dim3(256), 0, s, ks, vs, B.upos[src], B.ug[src], nbig, sa, B.v, s_next, d_fu,
-                                   B.upos[nxt], B.ug[nxt], B.uitem[nxt], fg_status, B.sc.d_ticket, B.sc.d_err, d_x, d_bwt, d_base, n, b_log);
-            ARCHON_HIP_TRY(hipGetLastError());
-            ++c->launches;
-        }
-        const bool flip = mid || mb != 0;           // (short groups that straddle a tile of k_b_finish's sweep stay in B for another round)
-        // The round's counters come to the host BEFORE its rank updates are applied: how the S and mid lists' updates (the log) are
-        // written depends on how many there are, and the host has to wait for these counters anyway.
-        if (mid) ARCHON_HIP_TRY(hipMemcpyAsync(c->h_mail + mail::kRounds.at, B.mc, fwd::kMcWords * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
-        ARCHON_HIP_TRY(hipMemcpyAsync(rd, d_fu, 6 * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
-        ARCHON_SYNC(s);
-        const uint32_t nlog = mode != 1 ? rd[1] : 0u;
-        // Rank updates, now that every key of the round has been read.  Dealt by item into windows of the table (rank_writer.hiph:
-        // two partition sweeps + one window write, 0.6 ms whatever the number + 11 ps per update) they beat one random store each
-        // (32 ps) from about 28 M updates on; the B list's updates are logged by position whenever that list is long (b_log).
-        if (b_log || (writer_ok && mode != 1 && nlog >= kWriterMinLog)) {
-            B.rwb.r1 = reinterpret_cast<uint2 *>(b_log == reinterpret_cast<uint2 *>(kT) ? kS : kT);       // the key buffer that is not the B log
-            B.rwb.r2 = reinterpret_cast<uint2 *>(B.valA);
-            ARCHON_HIP_TRY(hipMemsetAsync(B.rwb.cnt1, 0, (rw::kMaxCoarse + rw::fine_buckets(n)) * sizeof(uint32_t), s));
-            if (nlog) hipLaunchKernelGGL(HIP_KERNEL_NAME(rw::k_part<1, 0>), dim3(div_up(nlog, rw::kTile)), dim3(rw::kLanes), 0, s, B.rlog, nullptr, nlog, nullptr, nullptr, nullptr, B.rwb.r1, B.rwb.cnt1);
-            if (b_log) hipLaunchKernelGGL(HIP_KERNEL_NAME(rw::k_part<1, 0>), dim3(div_up(mb_round, rw::kTile)), dim3(rw::kLanes), 0, s, b_log, nullptr, mb_round, nullptr, nullptr, nullptr, B.rwb.r1, B.rwb.cnt1);
-            ARCHON_TRY(rw::write_back(s, B.rwb, n, B.rank, &c->launches));
-            c->launches += 2;
-        } else if (nlog) {
-            hipLaunchKernelGGL(fwd::k_rank_apply, dim3(div_up(nlog, 256)), dim3(256), 0, s, B.rlog, d_fu + 1, B.rank);
-            ++c->launches;
-        }
-        ms = rd[0];
-        mb = mb_round ? rd[2] : 0u;
-        bgroups = rd[3];
-        if (mid) {
-            mdS = h_mc[fwd::kMcSmall + nxt];
-            mdL = h_mc[fwd::kMcLarge + nxt];
-            mm = n - h_mc[fwd::kMcTop + nxt];
-            if (mdS > mid_dir_cap(n) || mdL > mid_dir_cap(n)) { set_error("mid directory overflow (%u / %u groups)", mdS, mdL); return ARCHON_E_INTERNAL; }
-        }
-        if (flip) cur ^= 1;
-        if (!b_only) cs ^= 1;
-        uint32_t np = chain ? rd[4] : 0u;
-        const uint32_t pairs_seen = chain ? np : rd[5];
-        if (np) {
-            // the round's pairs by passage: sort the records by their smaller item, one look-up per run, spread, apply
-            bool in2 = false;
-            uint32_t passes = 0;
-            ARCHON_TRY(rs::sort_pairs(s, B.sc, pk, pv, pk2, pv2, np, 0xF0u, &in2, &passes, &c->launches));
-            const uint64_t *k2 = in2 ? pk2 : pk;
-            const uint32_t *v2 = in2 ? pv2 : pv;
-            hipLaunchKernelGGL(fwd::k_pair_heads, dim3(div_up(np, 256)), dim3(256), 0, s, k2, np, B.rank, pair_v, pair_code);
-            ARCHON_TRY(launch_scan<1>(s, pair_v, pair_v, np, B.scan_tmp, nullptr));
-            hipLaunchKernelGGL(fwd::k_pair_apply, dim3(div_up(np, 256)), dim3(256), 0, s, k2, v2, pair_v, pair_code, np, sa, B.rank, d_x, d_bwt, d_base, n,
-                               B.slist[cs], d_fu);
-            ARCHON_HIP_TRY(hipGetLastError());
-            c->launches += 4;
-            ARCHON_HIP_TRY(hipMemcpyAsync(rd, d_fu, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
-            ARCHON_SYNC(s);
-            const uint32_t back = rd[0] - ms;         // entries the pass could not settle (two per pair)
-            ms = rd[0];
-            st.chain_pairs += np - back / 2u;
-            if ((uint64_t)back > np) chain_cool = 3;         // fewer than half of the pairs settled: give the rounds some time
-        }
-        // the next round lists its pairs when this one got nowhere and pairs are most of what is left
-        if (chain_cool) --chain_cool;
-        const uint32_t m_after = ms + mb + mm;
-        chain_next = chain_ok && !chain_cool && (uint64_t)m_after * 4 >= (uint64_t)m_before * 3 && (uint64_t)pairs_seen * 4 >= ms && ms;
         return ARCHON_OK;
-    };
-    // Text rounds: while few items are tied, key them on the next four bytes of the text instead of on ranks -- no
-    // inverse suffix array yet (filling it costs more than a whole round on a small set).  They stop as soon as a round
-    // fails to halve the set (long repeats: doubling is what resolves those).
-    while (m && !route_off(kRtNoTextRounds) && !deep_ties && (uint64_t)m * 4 <= n && st.text_rounds < 4 && h < n) {
+    }
+    if (!(m >= f.n / 16 && !(f.deep_ties && p_hint == 0) && !route_off(kRtNoChains))) return ARCHON_OK;
+    uint32_t p = p_hint;
+    bool dominant = p_hint != 0;        // the driver's period probe already named the period (and the groups may be unordered)
+    if (!dominant) {
+        // ... or a sample of the neighbour gaps inside the tied groups does: the most frequent gap, when it is a quarter of the sample
+        uint32_t *tab = f.B.hist16;                     // 2 * kGapSlots words (32 KiB) of the two-byte count's table, idle by now (256 KiB whatever n is:
+                                                        // a list buffer of a small block is shorter than the table)
+        ARCHON_HIP_TRY(hipMemsetAsync(tab, 0, 2 * fwd::kGapSlots * sizeof(uint32_t), f.s));
+        hipLaunchKernelGGL(fwd::k_gap_sample, dim3(div_up(div_up(f.n, fwd::kGapStride), 256)), dim3(256), 0, f.s, f.sa, f.B.v, f.n, tab);
+        const uint32_t *h_tab = f.c->h_mail + mail::kGapTable.at;
+        ARCHON_HIP_TRY(hipMemcpyAsync(f.c->h_mail + mail::kGapTable.at, tab, 2 * fwd::kGapSlots * sizeof(uint32_t), hipMemcpyDeviceToHost, f.s));
+        ARCHON_SYNC(f.s);
+        f.c->launches += 1;
+        uint64_t total = 0;
+        uint32_t best = 0;
+        for (uint32_t i = 0; i < fwd::kGapSlots; ++i) {
+            total += h_tab[i];
+            if (h_tab[i] > h_tab[best]) best = i;
+        }
+        p = h_tab[fwd::kGapSlots + best];
+        dominant = (uint64_t)h_tab[best] * 4 >= total;
+    }
+    if (p >= 1 && p < f.n && dominant) ARCHON_TRY(settle_runs(p));
+    return ARCHON_OK;
+}
+
+// The runs of period p settled directly: the break table (unless the period stage left it), the chain kernels, and -- when
+// they settled some rows but not all -- the tied set counted again.
+int General::settle_runs(uint32_t p)
+{
+    FwdBuf &B = f.B;
+    hipStream_t s = f.s;
+    const uint32_t n = f.n;
+    uint32_t *rd = f.rd();
+    uint32_t *brk = B.brk, *ginfo = B.dst, *gend = B.keep, *settled = B.small + fwd_small::kSettled;
+    uint32_t *gmin = B.ug[1], *gmax = B.uitem[1];       // the second triple buffers are idle
+    uint32_t *d_lastbrk = B.small + fwd_small::kLastBrk;
+    if (!(f.brk_ready && p == f.period_hint)) {
+        ARCHON_HIP_TRY(hipMemsetAsync(d_lastbrk, 0, 2 * sizeof(uint32_t), s));  // [0] last real break, [1] how many
+        hipLaunchKernelGGL(fwd::k_period_breaks, dim3(div_up(div_up(n, 4), 256)), dim3(256), 0, s, f.d_x, n, p, brk, d_lastbrk);
+        ARCHON_TRY(launch_scan<1>(s, brk, brk, n, B.scan_tmp, nullptr));
+    }
+    hipLaunchKernelGGL(fwd::k_chain_init, dim3(div_up(n, 256)), dim3(256), 0, s, B.v, n, gmin, gmax, ginfo);
+    ARCHON_HIP_TRY(hipMemsetAsync(settled, 0, sizeof(uint32_t), s));
+    tr.step("breaks + scan + memsets");
+    hipLaunchKernelGGL(fwd::k_chain_minmax, dim3(div_up(n, fwd::kChainRows)), dim3(256), 0, s, f.sa, B.v, n, gmin, gmax);
+    tr.step("chain_minmax");
+    hipLaunchKernelGGL(fwd::k_chain_probe, dim3(div_up(n, fwd::kChainRows)), dim3(256), 0, s, f.d_x, f.sa, B.v, brk, n, p, gmin, gmax, d_lastbrk, ginfo, gend);
+    tr.step("chain_probe");
+    hipLaunchKernelGGL(fwd::k_chain_apply, dim3(div_up(n, fwd::kChainRows)), dim3(256), 0, s, f.sa, B.v, ginfo, gend, gmin, gmax, brk, d_lastbrk, f.d_x, n, p, f.d_bwt, f.d_base, settled);
+    tr.step("chain_apply");
+    ARCHON_HIP_TRY(hipMemcpyAsync(rd + mail::kRdSettled, settled, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+    ARCHON_HIP_TRY(hipMemcpyAsync(rd + mail::kRdBreaks, d_lastbrk + 1, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+    ARCHON_SYNC(s);
+    z.breaks = rd[mail::kRdBreaks];
+    f.c->launches += 8;
+    const uint32_t done = rd[mail::kRdSettled];
+    if (done >= m) {
+        m = 0;                          // every tied row was settled: nothing to count or compact
+    } else if (done != 0 || !lists_ready) {
+        lists_ready = false;
+        keep_ready = true;
+        // the tied set again, without the settled groups
+        ARCHON_TRY(f.recount_tied());
+        ARCHON_HIP_TRY(hipMemcpyAsync(rd + mail::kRdTotal, B.small + fwd_small::kTotal, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+        ARCHON_SYNC(s);
+        m = rd[mail::kRdTotal];
+    }
+    tr.step("keep + scan again");
+    st.period = p;
+    st.chain_items = done;
+    if (m) z.period = p;                // what is left straddles defects of the period: one break-distance round once h >= p
+    return ARCHON_OK;
+}
+
+// The lists of the rounds: those of k_first_groups while they still describe the tied set; otherwise -- the run shortcut
+// changed the set, or the set was only counted -- all of it as triples, then split into the lists (k_classify: short groups
+// to S, the others stay in row order).
+int General::build_lists()
+{
+    FwdBuf &B = f.B;
+    hipStream_t s = f.s;
+    uint32_t init[fwd::kMcWords] = {};          // the mid lists start empty, their items from the top of the buffers downwards
+    init[fwd::kMcTop] = init[fwd::kMcTop + 1] = f.n;
+    memcpy(f.c->h_mail + mail::kRoundsInit.at, init, sizeof init);     // (words of their own: mail::kRounds takes the rounds' counters)
+    ARCHON_HIP_TRY(hipMemcpyAsync(B.mc, f.c->h_mail + mail::kRoundsInit.at, sizeof init, hipMemcpyHostToDevice, s));
+    if (!m) return ARCHON_OK;
+    if (lists_ready) {
+        R.ms = ms_first;
+        R.mb = mb_first;
+        R.bgroups = groups_first;
+        return ARCHON_OK;
+    }
+    if (!keep_ready) ARCHON_TRY(f.recount_tied());
+    hipLaunchKernelGGL(fwd::k_compact_first, dim3(div_up(f.n, 256)), dim3(256), 0, s, B.keep, B.dst, B.v, f.sa, f.n, B.upos[0], B.ug[0], B.uitem[0]);
+    const uint32_t tiles = div_up(m, fwd::kClT);
+    uint32_t *d_cnt = f.cnt(), *rd = f.rd() + mail::kRdCnt;
+    ARCHON_HIP_TRY(hipMemsetAsync(d_cnt, 0, 4 * sizeof(uint32_t), s));
+    ARCHON_TRY(f.reset_lookback(tiles));
+    hipLaunchKernelGGL(fwd::k_classify, dim3(tiles), dim3(fwd::kFuLanes), 0, s, B.upos[0], B.ug[0], B.uitem[0], m, B.slist[R.cs], d_cnt + fwd_small::kCntS,
+                       B.upos[1], B.ug[1], B.uitem[1], d_cnt + fwd_small::kCntB, f.fg_status(), B.sc.d_ticket, B.sc.d_err);
+    ARCHON_HIP_TRY(hipGetLastError());
+    f.c->launches += 2;
+    ARCHON_HIP_TRY(hipMemcpyAsync(rd, d_cnt, 3 * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+    ARCHON_SYNC(s);
+    R.ms = rd[fwd_small::kCntS];
+    R.mb = rd[fwd_small::kCntB];
+    R.bgroups = R.mb / (fwd::kFuMax + 1u) + 2u;          // every group left in B is longer than kFuMax
+    R.cur = 1;
+    if (R.ms + R.mb != m) { set_error("classification lost entries (%u + %u of %u)", R.ms, R.mb, m); return ARCHON_E_INTERNAL; }
+    tr.step("classify");
+    return ARCHON_OK;
+}
+
+// Text rounds: while few items are tied, key them on the next four bytes of the text instead of on ranks -- no
+// inverse suffix array yet (filling it costs more than a whole round on a small set).  They stop as soon as a round
+// fails to halve the set (long repeats: doubling is what resolves those).
+int General::text_rounds()
+{
+    while (m && !route_off(kRtNoTextRounds) && !f.deep_ties && (uint64_t)m * 4 <= f.n && st.text_rounds < 4 && h < f.n) {
         st.unresolved_total += m;
         ++st.text_rounds;
-        trace("before text round");
-        ARCHON_TRY(do_round(1, h));
-        trace("text round");
+        tr.step("before text round");
+        ARCHON_TRY(R.round(1, h));
+        tr.step("text round");
         h += 4;
-        const uint32_t m2 = ms + mb + mm;
+        const uint32_t m2 = R.tied();
         const bool productive = (uint64_t)m2 * 2 <= m;
         m = m2;
         if (!productive) break;
     }
-    if (m) {
-        // ranks are needed only now: rank[sa[i]] = first row of the group of row i, for every row
-        trace("before scatter_rank");
-        if (writer_ok) {
-            // ... dealt by item into windows of the table (rank_writer.hiph) instead of n random stores
-            B.rwb.r1 = reinterpret_cast<uint2 *>(B.keyA);           // (the first stage's pairs / records are dead)
-            B.rwb.r2 = reinterpret_cast<uint2 *>(B.valA);
-            ARCHON_HIP_TRY(hipMemsetAsync(B.rwb.cnt1, 0, (rw::kMaxCoarse + rw::fine_buckets(n)) * sizeof(uint32_t), s));
-            hipLaunchKernelGGL(HIP_KERNEL_NAME(rw::k_part<1, 1>), dim3(div_up(n, rw::kTile)), dim3(rw::kLanes), 0, s, nullptr, nullptr, n, sa, B.v, nullptr, B.rwb.r1, B.rwb.cnt1);
-            ARCHON_TRY(rw::write_back(s, B.rwb, n, B.rank, &c->launches));
-        } else {
-            hipLaunchKernelGGL(fwd::k_scatter_rank, dim3(g256), dim3(256), 0, s, sa, B.v, n, B.rank);
-        }
-        ++c->launches;
-        trace("scatter_rank");
+    return ARCHON_OK;
+}
+
+// Ranks are needed only now: rank[sa[i]] = first row of the group of row i, for every row -- dealt by item into windows of
+// the table (rank_writer.hiph) instead of n random stores when the block is large enough for the writer.
+int General::fill_rank_table()
+{
+    if (!m) return ARCHON_OK;
+    FwdBuf &B = f.B;
+    tr.step("before scatter_rank");
+    if (R.writer_ok) {
+        ARCHON_TRY(f.writer_regions(B.keyA));           // (the first stage's pairs / records are dead)
+        hipLaunchKernelGGL(HIP_KERNEL_NAME(rw::k_part<1, 1>), dim3(div_up(f.n, rw::kTile)), dim3(rw::kLanes), 0, f.s, nullptr, nullptr, f.n, f.sa, B.v, nullptr, B.rwb.r1, B.rwb.cnt1);
+        ARCHON_TRY(rw::write_back(f.s, B.rwb, f.n, B.rank, &f.c->launches));
+    } else {
+        hipLaunchKernelGGL(fwd::k_scatter_rank, dim3(div_up(f.n, 256)), dim3(256), 0, f.s, f.sa, B.v, f.n, B.rank);
     }
-    // Period defects, long groups, before the groups are tied over a whole period (a periodic block enters with h = 3):
-    // certify the groups whose members share a whole period (k_zone_certify) and run the break rounds on those alone --
-    // unless the defects are so many that the byte-by-byte comparisons of the certification would cost more than the rounds.
-    if (m && mb && z_period && h < z_period && (uint64_t)z_breaks * z_period * z_period <= 8ull * n && !route_off(kRtNoBreakRound)) {
-        uint8_t *cert = reinterpret_cast<uint8_t *>(B.pairw);                // (2n bytes, idle until a doubling round lists pairs; the rank log takes the mid kernels' updates)
-        uint32_t *okey = B.keep;                                             // (idle until a doubling round lists pairs)
-        ARCHON_HIP_TRY(hipMemsetAsync(cert, 0, n, s));
-        ARCHON_HIP_TRY(hipMemsetAsync(okey, 0, (size_t)n * sizeof(uint32_t), s));
-        hipLaunchKernelGGL(fwd::k_zone_certify, dim3(g256), dim3(256), 0, s, B.rank, sa, B.brk, d_x, n, z_period, cert, okey);
-        ARCHON_HIP_TRY(hipGetLastError());
-        ++c->launches;
-        trace("zone certify");
-        for (bool distance = true;; distance = false) {
-            st.unresolved_total += mb + mm;
-            ++st.break_rounds;
-            const uint32_t before = ms + mb + mm;
-            ARCHON_TRY(do_round(distance ? 2 : 3, z_period, true, cert, okey));
-            const uint32_t settled = before - (ms + mb + mm);
-            st.break_settled += settled;
-            m = ms + mb + mm;
-            trace(distance ? "break round on certified groups (distance)" : "break round on certified groups (continuation)");
-            if (!(mb + mm) || (!distance && !settled)) break;
+    ++f.c->launches;
+    tr.step("scatter_rank");
+    return ARCHON_OK;
+}
+
+// Period defects, long groups, before the groups are tied over a whole period (a periodic block enters with h = 3):
+// certify the groups whose members share a whole period (k_zone_certify) and run the break rounds on those alone --
+// unless the defects are so many that the byte-by-byte comparisons of the certification would cost more than the rounds.
+int General::certified_break_rounds()
+{
+    if (!(m && R.mb && z.period && h < z.period && (uint64_t)z.breaks * z.period * z.period <= 8ull * f.n && !route_off(kRtNoBreakRound))) return ARCHON_OK;
+    FwdBuf &B = f.B;
+    uint8_t *cert = reinterpret_cast<uint8_t *>(B.pairw);                // (2n bytes, idle until a doubling round lists pairs; the rank log takes the mid kernels' updates)
+    uint32_t *okey = B.keep;                                             // (idle until a doubling round lists pairs)
+    ARCHON_HIP_TRY(hipMemsetAsync(cert, 0, f.n, f.s));
+    ARCHON_HIP_TRY(hipMemsetAsync(okey, 0, (size_t)f.n * sizeof(uint32_t), f.s));
+    hipLaunchKernelGGL(fwd::k_zone_certify, dim3(div_up(f.n, 256)), dim3(256), 0, f.s, B.rank, f.sa, B.brk, f.d_x, f.n, z.period, cert, okey);
+    ARCHON_HIP_TRY(hipGetLastError());
+    ++f.c->launches;
+    tr.step("zone certify");
+    for (bool distance = true;; distance = false) {
+        st.unresolved_total += R.mb + R.mm;
+        ++st.break_rounds;
+        const uint32_t before = R.tied();
+        ARCHON_TRY(R.round(distance ? 2 : 3, z.period, true, cert, okey));
+        const uint32_t settled = before - R.tied();
+        st.break_settled += settled;
+        m = R.tied();
+        tr.step(distance ? "break round on certified groups (distance)" : "break round on certified groups (continuation)");
+        if (!(R.mb + R.mm) || (!distance && !settled)) break;
+    }
+    return ARCHON_OK;
+}
+
+// Groups that straddle defects of the period: once every group is tied over a whole period, one round keyed on the
+// distance to the last defect settles them, bar the items that share that distance and the side they leave on; those
+// follow from the rank of the item their key continues as -- a round that is repeated while it settles something
+// (the continuation items may have been settled by the round before) and tried again behind every doubling round
+// until it has failed twice in a row.  h stays: what these rounds leave tied is still tied over h symbols.
+int General::break_rounds()
+{
+    for (;;) {
+        st.unresolved_total += m;
+        ++st.break_rounds;
+        const bool distance = z.first;
+        ARCHON_TRY(tr.begin(R));
+        ARCHON_TRY(R.round(distance ? 2 : 3, z.period));
+        tr.break_round(distance, z.period, h, R);
+        const uint32_t settled = m - R.tied();
+        st.break_settled += settled;
+        m = R.tied();
+        z.first = false;
+        if (!m) break;
+        if (!distance) {
+            if (settled) z.fail = 0;
+            else { ++z.fail; break; }
         }
     }
+    return ARCHON_OK;
+}
+
+// Doubling rounds until nothing is tied, the period-defect rounds in front of each while they are worth trying.
+int General::rounds_to_the_end()
+{
     while (m) {
-        // Groups that straddle defects of the period: once every group is tied over a whole period, one round keyed on the
-        // distance to the last defect settles them, bar the items that share that distance and the side they leave on; those
-        // follow from the rank of the item their key continues as -- a round that is repeated while it settles something
-        // (the continuation items may have been settled by the round before) and tried again behind every doubling round
-        // until it has failed twice in a row.  h stays: what these rounds leave tied is still tied over h symbols.
-        if (z_period && h >= z_period && z_fail < 2 && !route_off(kRtNoBreakRound)) {
-            for (;;) {
-                st.unresolved_total += m;
-                ++st.break_rounds;
-                const bool distance = z_first;
-#ifdef ARCHON_EXPERIMENTS
-                ARCHON_SYNC(s);
-                const auto t0 = std::chrono::steady_clock::now();
-                const uint32_t ms0 = ms, mb0 = mb;
-#endif
-                ARCHON_TRY(do_round(distance ? 2 : 3, z_period));
-#ifdef ARCHON_EXPERIMENTS
-                if (getenv("ARCHON_TRACE_ROUNDS")) {
-                    const auto t1 = std::chrono::steady_clock::now();
-                    fprintf(stderr, "break round (%s) p=%u (h=%u) S=%u B=%u %.3f ms -> S=%u B=%u\n", distance ? "distance" : "continuation", z_period, h, ms0, mb0,
-                            std::chrono::duration<double, std::milli>(t1 - t0).count(), ms, mb);
-                }
-#endif
-                const uint32_t settled = m - (ms + mb + mm);
-                st.break_settled += settled;
-                m = ms + mb + mm;
-                z_first = false;
-                if (!m) break;
-                if (!distance) {
-                    if (settled) z_fail = 0;
-                    else { ++z_fail; break; }
-                }
-            }
+        if (z.period && h >= z.period && z.fail < 2 && !route_off(kRtNoBreakRound)) {
+            ARCHON_TRY(break_rounds());
             if (!m) break;
         }
         st.unresolved_total += m;
         ++st.doubling_rounds;
-#ifdef ARCHON_EXPERIMENTS
-        ARCHON_SYNC(s);
-        const auto t0 = std::chrono::steady_clock::now();
-        const uint32_t ms0 = ms, mb0 = mb, mm0 = mm;
-#endif
-        ARCHON_TRY(do_round(0, h));
-#ifdef ARCHON_EXPERIMENTS
-        if (getenv("ARCHON_TRACE_ROUNDS")) {
-            const auto t1 = std::chrono::steady_clock::now();
-            fprintf(stderr, "round h=%u S=%u B=%u M=%u %.3f ms -> S=%u B=%u M=%u (%u + %u groups)\n", h, ms0, mb0, mm0, std::chrono::duration<double, std::milli>(t1 - t0).count(), ms, mb, mm, mdS, mdL);
-            if (ms0 && getenv("ARCHON_TRACE_STAMPS")) {
-                unsigned long long v[24];
-                if (hipMemcpyFromSymbol(v, HIP_SYMBOL(fwd::g_fu_stamps), sizeof v) == hipSuccess) {
-                    fprintf(stderr, "   fused wg: longest %llu owned %llu surv/log 0x%llx cycles:", v[11], v[12], v[13]);
-                    for (int i = 2; i <= 10; ++i) fprintf(stderr, " %llu", v[i] - v[i - 1]);
-                    fprintf(stderr, " (load, own, gather-issue, heads, ends, sort, newgroups, counts+atomic, stores)\n");
-                }
-            }
-        }
-#endif
-        m = ms + mb + mm;
-        if (h > n && m) {   // h >= n resolves everything; reaching here means an internal fault
+        ARCHON_TRY(tr.begin(R));
+        ARCHON_TRY(R.round(0, h));
+        tr.doubling_round(h, R);
+        m = R.tied();
+        if (h > f.n && m) {   // h >= n resolves everything; reaching here means an internal fault
             set_error("doubling did not converge (m=%u at h=%u)", m, h);
             return ARCHON_E_INTERNAL;
         }
         h = h > 0x40000000u ? 0x80000000u : h * 2;
     }
-    trace("rounds done");
     return ARCHON_OK;
 }
 
@@ -923,15 +1134,6 @@ void Fwd::stamp(int i) { if (trace_host) t_host[i] = std::chrono::steady_clock::
 void Fwd::stamp(int) {}
 #endif
 
-// Calls fn(std::integral_constant<int, V>{}) for the first V of the list that equals v, for the last one when none does: the
-// driver's runtime choices (symbols per key byte, a mode, a flag) as the template arguments of the kernel that matches.
-template <int V, int... Vs, class Fn>
-static void with_const(int v, Fn &&fn)
-{
-    if constexpr (sizeof...(Vs) == 0) fn(std::integral_constant<int, V>{});
-    else if (v == V) fn(std::integral_constant<int, V>{});
-    else with_const<Vs...>(v, fn);
-}
 // The key forms of the streaming stage: Q symbols per key byte (1 = plain bytes; 2 / 4 / 8 = a compacted alphabet), or
 // kHotForm -- plain bytes, ranked wave-aggregated for periodic blocks (measured on a^N: passes 0.98 + 1.12 ms against 1.48 + 1.46).
 constexpr int kHotForm = 0;

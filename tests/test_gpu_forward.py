@@ -5,6 +5,7 @@ import numpy as np
 import pytest
 
 import archon_synth as S
+from forward_cases import _class_limit_block, _defect_cases, _dup_cases, _repeat_cases, _seg_cases, _word_soup
 
 pytestmark = pytest.mark.gpu
 
@@ -227,31 +228,6 @@ def test_alphabet_compaction(archon, oracle):
         assert (sa1 == P).all() and (sa2 == P).all() and (bwt1 == B).all() and b1 == b0 == b2
 
 
-def _repeat_cases():
-    rng = np.random.default_rng(31)
-    motif = rng.integers(0, 256, size=1000, dtype=np.uint8)
-    short = np.frombuffer(b"abcabd", np.uint8)
-    a = lambda k, c=97: np.full(k, c, np.uint8)
-    r = lambda k: rng.integers(0, 256, size=k, dtype=np.uint8)
-    lit = lambda s: np.frombuffer(s, np.uint8)
-    return {
-        "a": a(300000),
-        "ab": np.tile(lit(b"ab"), 150000),
-        "ba_odd": np.tile(lit(b"ba"), 150000)[:-1],
-        "motif1000": np.tile(motif, 300),
-        "motif1000_ragged": np.tile(motif, 300)[137:-451],
-        "motif6": np.tile(short, 50000),
-        "ff": a(200000, 255),
-        "feff": np.tile(np.array([254, 255], np.uint8), 100000),
-        "three_runs": np.concatenate([a(100000), lit(b"b"), a(100000), lit(b"c"), a(70000), lit(b"\x00"), a(30000)]),
-        "run_inside_random": np.concatenate([r(5000), np.tile(motif, 250), r(5000)]),
-        "two_periods": np.concatenate([np.tile(lit(b"ab"), 80000), np.tile(lit(b"abc"), 60000)]),
-        "run_signs": np.concatenate([lit(b"z"), a(60000), lit(b"A"), a(60000), lit(b"z"), a(60001), lit(b"a"), a(5)]),
-        "motif_with_glitches": np.concatenate([np.tile(motif, 100), motif[:500], lit(b"!"), np.tile(motif, 100), motif[:3]]),
-        "nested": np.tile(np.concatenate([a(500), lit(b"b")]), 400),
-    }
-
-
 @pytest.mark.parametrize("closed", ["closed_form", "shortcut"])
 @pytest.mark.parametrize("name", sorted(_repeat_cases()))
 def test_long_repeats(archon, oracle, name, closed, monkeypatch):
@@ -371,33 +347,6 @@ def test_closed_form_without_sa_and_unaligned(archon, oracle):
         assert (sa_t.cpu().numpy().astype(np.uint32) == P).all() and (bwt_t.cpu().numpy() == B).all() and int(base_t.item()) == b0
 
 
-def _defect_cases():
-    """a motif repeated with point defects: groups that straddle the defects (never ONE clean run of the period)"""
-    rng = np.random.default_rng(4099)
-    out = {}
-    for p, n, flips in ((1, 300000, 3), (2, 400001, 4), (3, 299999, 2), (7, 500000, 5), (100, 600000, 3), (1000, 1200000, 3),
-                        (4099, 2000000, 3), (257, 700000, 12)):
-        motif = rng.integers(0, 256, size=p, dtype=np.uint8)
-        x = np.tile(motif, n // p + 1)[:n].copy()
-        for q in rng.integers(0, n, size=flips):
-            x[q] ^= np.uint8(1 + rng.integers(0, 255))
-        out["p%d_%dflips" % (p, flips)] = x
-    motif = rng.integers(0, 256, size=50, dtype=np.uint8)
-    x = np.tile(motif, 8000)
-    x[100000] = 0; x[200000] = 255; x[300000] = 0          # same phase, leaving below / above / below the periodic continuation
-    out["same_phase_signs"] = x.copy()
-    x = np.tile(motif, 8000)
-    x[120025] ^= 1; x[240025] ^= 1                          # the same defect twice: items at equal distances behind them stay tied for the rounds
-    out["twin_defects"] = x.copy()
-    x = np.tile(motif, 8000)
-    x[5] ^= 7; x[399990] ^= 9; x[200000:200003] ^= 3        # defects inside the first and the last period, and three in a row
-    out["edges_and_burst"] = x.copy()
-    x = np.concatenate([np.tile(motif, 4000), np.tile(rng.integers(0, 256, size=50, dtype=np.uint8), 4000)])   # two motifs of one period
-    x[77777] ^= 1
-    out["two_motifs"] = x
-    return out
-
-
 @pytest.mark.parametrize("name", sorted(_defect_cases()))
 def test_period_defects(archon, oracle, name, monkeypatch):
     """N3 beyond exact periods (a4's anchors / tandem test, direct.c:90-161,198-221): groups that straddle defects of the
@@ -418,22 +367,6 @@ def test_period_defects(archon, oracle, name, monkeypatch):
     assert st2["break_rounds"] == 0
     if st["break_rounds"]:
         assert st["doubling_rounds"] < st2["doubling_rounds"], (st, st2)
-
-
-def _seg_cases():
-    rng = np.random.default_rng(77)
-    r = lambda k, hi=256: rng.integers(0, hi, size=k, dtype=np.uint8)
-    R = r(200000)
-    words = [bytes(r(int(k), 26) + 97) for k in rng.integers(2, 9, size=300)]
-    prose = np.frombuffer(b" ".join(words[i] for i in rng.integers(0, 300, size=120000)), np.uint8)
-    runs = np.concatenate([np.concatenate([np.full(int(k), 32, np.uint8), r(40, 26) + 97]) for k in rng.integers(1, 400, size=2500)])
-    return {
-        "duplicated_block": np.concatenate([R, r(7), R, r(3), R[:150000]]),                 # pairs and triples, deep repeats
-        "prose": prose,                                                                     # skewed groups of every size
-        "prose_twice": np.concatenate([prose[:300000], prose[:300000]]),
-        "space_runs": runs,                                                                 # long groups next to short ones
-        "dups_and_runs": np.concatenate([R[:60000], runs[:200000], R[:60000], np.full(5000, 7, np.uint8), R[:999]]),
-    }
 
 
 @pytest.mark.parametrize("name", sorted(_seg_cases()))
@@ -530,18 +463,6 @@ def test_workspace_follows_the_block(archon, oracle):
     assert st2["arena_bytes"] > 60 * y.size
 
 
-def _word_soup(n, vocab, word_len, seed, skew=1.3, alphabet=12):
-    """tokens drawn (Zipf-like) from a small vocabulary of fixed-length words over a small alphabet: after the first stage the
-    tied groups are the (word, offset) classes -- thousands to tens of thousands of rows each -- and every doubling round
-    splits them by the words in front: groups of every size class, each handing groups down to the smaller ones"""
-    rng = np.random.default_rng(seed)
-    words = rng.integers(97, 97 + alphabet, size=(vocab, word_len)).astype(np.uint8)
-    pr = 1.0 / np.arange(1, vocab + 1) ** skew
-    pr /= pr.sum()
-    toks = rng.choice(vocab, size=n // word_len + 1, p=pr)
-    return words[toks].reshape(-1)[:n].copy()
-
-
 @pytest.mark.parametrize("n,vocab,wl", [(3 << 20, 24, 16), ((5 << 20) + 12345, 7, 24), (1 << 21, 150, 9)])
 def test_mid_groups(archon, oracle, monkeypatch, n, vocab, wl):
     """mid_rounds.hiph: groups of 1025 .. 16384 rows sorted by one workgroup in LDS, longer ones through the global sort,
@@ -572,12 +493,7 @@ def test_mid_groups_at_the_class_limits(archon, oracle, monkeypatch):
     exactly that often, in random order -- the rows of a word's offsets 7 .. 15 are tied in groups of the word's count after the
     first stage, on the boundaries between the S list, the two mid classes (a full LDS image: the end mark of the group falls
     behind the last bitmap word) and the global path"""
-    rng = np.random.default_rng(16384)
-    counts = [16384, 16385, 16383, 4096, 4097, 4095, 1025, 1024, 1023, 513, 512, 511, 8192, 2048, 2, 3, 1, 40000]
-    words = rng.integers(0, 256, size=(len(counts), 16)).astype(np.uint8)
-    toks = np.repeat(np.arange(len(counts)), counts)
-    rng.shuffle(toks)
-    x = words[toks].reshape(-1).copy()
+    x = _class_limit_block()
     P, B, b0 = oracle.forward(x)
     for env in ({}, {"ARCHON_FORCE_PATH": "0"}, {"ARCHON_NO_TEXT_ROUNDS": "1"}, {"ARCHON_FORCE_PATH": "0", "ARCHON_NO_TEXT_ROUNDS": "1", "ARCHON_NO_RANK_WRITER": "1"}):
         for k, v in env.items():
@@ -893,24 +809,6 @@ def test_tie_heavy_block_full_size(archon):
     out_t = torch.empty(n, dtype=torch.uint8, device="cuda")
     archon.inverse_dev(bwt_t, int(base_t.item()), out_t)
     assert torch.equal(out_t, x_t)
-
-
-def _dup_cases():
-    rng = np.random.default_rng(91)
-    r = lambda k, hi=256: rng.integers(0, hi, size=k, dtype=np.uint8)
-    R = r(1 << 20)
-    words = [bytes(r(int(k), 26) + 97) for k in rng.integers(2, 9, size=400)]
-    prose = np.frombuffer(b" ".join(words[i] for i in rng.integers(0, 400, size=200000)), np.uint8)
-    return {
-        # random block with one long duplicate: every tied group is a pair {s, s + d} of ONE passage
-        "one_duplicate": np.concatenate([R, r(11), R[100000:900000], r(5)]),
-        # three copies of a passage (groups of three at first, pairs once the copies' left contexts differ), nested copies
-        "three_copies": np.concatenate([R[:300000], r(3), R[:300000], r(7), R[:200000], R[50000:250000]]),
-        # text with copied passages next to many short repeats: pairs are listed while longer groups keep doubling
-        "prose_with_copies": np.concatenate([prose[:400000], prose[100000:350000], prose[400000:600000], prose[120000:300000]]),
-        # a duplicate whose predecessors sit in a LONGER group (the run's head cannot be settled at first): 0-runs in front of the copies
-        "duplicate_behind_runs": np.concatenate([np.zeros(5000, np.uint8), R[:200000], np.zeros(5000, np.uint8), R[:200000], np.zeros(4000, np.uint8), R[:100000]]),
-    }
 
 
 @pytest.mark.parametrize("name", sorted(_dup_cases()))
