@@ -46,7 +46,7 @@ void set_error(const char *fmt, ...)
 }
 
 Route g_route;
-thread_local uint32_t t_sync_count = 0;
+thread_local uint32_t t_sync_count = 0, t_launch_count = 0;
 
 // ------------------------------------------------------------------ contexts
 // Compute contexts of a device (arena, staging buffers, stream, mailbox each), created when first used: a host thread is
@@ -99,17 +99,20 @@ static thread_local LastStats<archon_hip_repeat_stats> t_rep_stats;     // repea
 static thread_local LastStats<archon_hip_lz_stats> t_lz_stats;          // LZ calls: lpf, lz_parse, block_lz
 
 // The record of one FM call: kept for the calling thread when the scope ends, on whichever path the call leaves it, with the
-// host waits since the scope began.
+// host waits and the kernel launches since the scope began.  A record that covers less than its call takes its launches
+// where that part runs (`whole_call` false).
 template <class T>
 struct KeepStats {
     LastStats<T> &last;
     int dev;
-    uint32_t syncs0 = t_sync_count;
+    bool whole_call;
+    uint32_t syncs0 = t_sync_count, launches0 = t_launch_count;
     T st = {};
-    KeepStats(LastStats<T> &l, int d) : last(l), dev(d) {}
+    KeepStats(LastStats<T> &l, int d, bool whole = true) : last(l), dev(d), whole_call(whole) {}
     ~KeepStats()
     {
         st.host_syncs = t_sync_count - syncs0;
+        if (whole_call) st.kernel_launches = t_launch_count - launches0;
         last.keep(dev, st);
     }
 };
@@ -411,6 +414,7 @@ struct Fwd {
     int e_start = -1, e_count = -1, e_sorted = -1, e_local = -1, e_first = -1, e_general = -1, e_end = -1;
     int iA0 = -1, iA1 = -1, iB0 = -1, iB1 = -1;
     bool trace_host = false;     // (experiments library, ARCHON_TRACE_HOST)
+    uint32_t launches0 = 0, syncs0 = 0;             // the thread's counters when the call started (setup): finish subtracts
 
     // the steps of forward_run, in its order, and what they share
     int setup(), first_look(), closed_form(), alphabet(), period(), recode(), first_stage(), tied_rows(), general_stage(), finish();
@@ -449,9 +453,9 @@ int Fwd::reset_lookback(uint32_t tiles)
 // the tied set as it is now: flags in B.keep, their places in B.dst, their number in fwd_small::kTotal
 int Fwd::recount_tied()
 {
-    hipLaunchKernelGGL(fwd::k_keep_flags, dim3(div_up(n, 256)), dim3(256), 0, s, B.v, n, B.keep);
+    ARCHON_LAUNCH(fwd::k_keep_flags, dim3(div_up(n, 256)), dim3(256), 0, s, B.v, n, B.keep);
     ARCHON_TRY(launch_scan<0>(s, B.keep, B.dst, n, B.scan_tmp, B.small + fwd_small::kTotal));
-    c->launches += 3;
+    launches_miscounted(-1);        // four launches, k_keep_flags and the scan's three, were counted as three
     return ARCHON_OK;
 }
 
@@ -636,13 +640,12 @@ int Rounds::plan_b(Plan &r)
             const uint32_t tiles = div_up(mb, fwd::kBfTile);
             ARCHON_TRY(f.reset_lookback(tiles));
             r.split = true;
-            hipLaunchKernelGGL(fwd::k_b_dir, dim3(tiles), dim3(256), 0, f.s, B.upos[cur], B.ug[cur], mb, B.gdir_off, B.gdir_row, f.fg_status(), B.sc.d_ticket, B.sc.d_err, B.mc, (uint32_t)mid_dir_cap(n), B.tile_g0);
-            hipLaunchKernelGGL(fwd::k_b_plan, dim3(1), dim3(1024), 0, f.s, B.gdir_off, B.gdir_row, mb, B.gcls, B.gbig, B.dirS[cur], B.dirL[cur], B.mc, (uint32_t)cur,
-                               (uint32_t)fwd::kMidSmallCap, (uint32_t)fwd::kMidLargeCap, (uint32_t)mid_dir_cap(n), B.sc.d_err, B.tile_big);
+            ARCHON_LAUNCH(fwd::k_b_dir, dim3(tiles), dim3(256), 0, f.s, B.upos[cur], B.ug[cur], mb, B.gdir_off, B.gdir_row, f.fg_status(), B.sc.d_ticket, B.sc.d_err, B.mc, (uint32_t)mid_dir_cap(n), B.tile_g0);
+            ARCHON_LAUNCH(fwd::k_b_plan, dim3(1), dim3(1024), 0, f.s, B.gdir_off, B.gdir_row, mb, B.gcls, B.gbig, B.dirS[cur], B.dirL[cur], B.mc, (uint32_t)cur,
+                           (uint32_t)fwd::kMidSmallCap, (uint32_t)fwd::kMidLargeCap, (uint32_t)mid_dir_cap(n), B.sc.d_err, B.tile_big);
             ARCHON_HIP_TRY(hipGetLastError());
             ARCHON_HIP_TRY(hipMemcpyAsync(f.c->h_mail + mail::kRounds.at, B.mc, fwd::kMcWords * sizeof(uint32_t), hipMemcpyDeviceToHost, f.s));
             ARCHON_SYNC(f.s);
-            f.c->launches += 2;
             if (h_mc[fwd::kMcGroups] > mid_dir_cap(n)) { set_error("B list of %u entries holds %u groups (directory: %zu)", mb, h_mc[fwd::kMcGroups], mid_dir_cap(n)); return ARCHON_E_INTERNAL; }
             r.nS = h_mc[fwd::kMcSmall + cur];
             r.nL = h_mc[fwd::kMcLarge + cur];
@@ -673,16 +676,15 @@ int Rounds::b_keys(const Plan &r)
     ARCHON_HIP_TRY(hipMemsetAsync(B.sc.d_ghist, 0, 8 * 256 * sizeof(uint32_t), f.s));
     if (r.split)
         with_const<0, 2, 3>(r.mode, [&](auto M) {
-            hipLaunchKernelGGL(HIP_KERNEL_NAME(fwd::k_b_keys_split<decltype(M)::value>), dim3(tiles), dim3(256), 0, f.s, B.upos[cur], B.ug[cur], B.uitem[cur], B.rank, f.d_x, r.hh, f.n,
-                               r.shift, mb, kT, vT, f.fg_status(), B.sc.d_ticket, B.sc.d_err, B.sc.d_ghist, r.nbytes, B.brk, r.cert, r.okey,
-                               B.gdir_off, B.gcls, B.gbig, B.upos[r.nxt], B.ug[r.nxt], B.tile_g0, B.tile_big);
+            ARCHON_LAUNCH(HIP_KERNEL_NAME(fwd::k_b_keys_split<decltype(M)::value>), dim3(tiles), dim3(256), 0, f.s, B.upos[cur], B.ug[cur], B.uitem[cur], B.rank, f.d_x, r.hh, f.n,
+                           r.shift, mb, kT, vT, f.fg_status(), B.sc.d_ticket, B.sc.d_err, B.sc.d_ghist, r.nbytes, B.brk, r.cert, r.okey,
+                           B.gdir_off, B.gcls, B.gbig, B.upos[r.nxt], B.ug[r.nxt], B.tile_g0, B.tile_big);
         });
     else
         with_const<0, 1, 2, 3>(r.mode, [&](auto M) {
-            hipLaunchKernelGGL(HIP_KERNEL_NAME(fwd::k_b_keys<decltype(M)::value>), dim3(tiles), dim3(256), 0, f.s, B.upos[cur], B.ug[cur], B.uitem[cur], B.rank, f.d_x, r.hh, f.n,
-                               r.shift, mb, kT, vT, f.fg_status(), B.sc.d_ticket, B.sc.d_err, B.sc.d_ghist, r.nbytes, B.brk, r.cert, r.okey);
+            ARCHON_LAUNCH(HIP_KERNEL_NAME(fwd::k_b_keys<decltype(M)::value>), dim3(tiles), dim3(256), 0, f.s, B.upos[cur], B.ug[cur], B.uitem[cur], B.rank, f.d_x, r.hh, f.n,
+                           r.shift, mb, kT, vT, f.fg_status(), B.sc.d_ticket, B.sc.d_err, B.sc.d_ghist, r.nbytes, B.brk, r.cert, r.okey);
         });
-    ++f.c->launches;
     return ARCHON_OK;
 }
 
@@ -692,13 +694,12 @@ int Rounds::mid_class(const Plan &r, int lanes, const uint4 *dir, uint32_t group
     FwdBuf &B = f.B;
     with_const<0, 2, 3>(r.mode, [&](auto M) {
         with_const<(int)fwd::kMidLargeLanes, (int)fwd::kMidSmallLanes>(lanes, [&](auto LN) {
-            hipLaunchKernelGGL(HIP_KERNEL_NAME(fwd::k_mid_round<decltype(M)::value, decltype(LN)::value>), dim3(groups), dim3(decltype(LN)::value), 0, f.s, dir, B.uitem[cur], B.rank, f.d_x, r.hh, f.n,
-                               f.sa, r.s_next, B.rlog, f.cnt(), B.uitem[r.nxt], B.dirS[r.nxt], B.dirL[r.nxt], (uint32_t)mid_dir_cap(f.n), B.mc, (uint32_t)r.nxt, f.d_bwt, f.d_base, B.brk, r.cert,
-                               r.okey, B.sc.d_err);
+            ARCHON_LAUNCH(HIP_KERNEL_NAME(fwd::k_mid_round<decltype(M)::value, decltype(LN)::value>), dim3(groups), dim3(decltype(LN)::value), 0, f.s, dir, B.uitem[cur], B.rank, f.d_x, r.hh, f.n,
+                           f.sa, r.s_next, B.rlog, f.cnt(), B.uitem[r.nxt], B.dirS[r.nxt], B.dirL[r.nxt], (uint32_t)mid_dir_cap(f.n), B.mc, (uint32_t)r.nxt, f.d_bwt, f.d_base, B.brk, r.cert,
+                           r.okey, B.sc.d_err);
         });
     });
     ARCHON_HIP_TRY(hipGetLastError());
-    ++f.c->launches;
     return ARCHON_OK;
 }
 
@@ -709,11 +710,10 @@ int Rounds::s_round(const Plan &r)
     if (!ms) return ARCHON_OK;
     FwdBuf &B = f.B;
     with_const<0, 1, 2, 3>(r.mode, [&](auto M) {
-        hipLaunchKernelGGL(HIP_KERNEL_NAME(fwd::k_round_fused<decltype(M)::value>), dim3(div_up(ms, fwd::kFuT)), dim3(fwd::kFuLanes), 0, f.s, B.slist[cs], ms, B.rank, f.d_x, r.hh, f.sa, B.v,
-                           B.slist[cs ^ 1], B.rlog, f.cnt(), B.sc.d_err, f.d_bwt, f.d_base, f.n, r.chain, pk, pv, B.brk);
+        ARCHON_LAUNCH(HIP_KERNEL_NAME(fwd::k_round_fused<decltype(M)::value>), dim3(div_up(ms, fwd::kFuT)), dim3(fwd::kFuLanes), 0, f.s, B.slist[cs], ms, B.rank, f.d_x, r.hh, f.sa, B.v,
+                       B.slist[cs ^ 1], B.rlog, f.cnt(), B.sc.d_err, f.d_bwt, f.d_base, f.n, r.chain, pk, pv, B.brk);
     });
     ARCHON_HIP_TRY(hipGetLastError());
-    ++f.c->launches;
     return ARCHON_OK;
 }
 
@@ -724,7 +724,7 @@ int Rounds::b_sort(Plan &r)
     FwdBuf &B = f.B;
     uint32_t passes = 0;
     bool b_in_b = false;
-    ARCHON_TRY(rs::sort_pairs(f.s, B.sc, kT, vT, kS, vS, r.nbig, (1u << r.nbytes) - 1u, &b_in_b, &passes, &f.c->launches, nullptr, nullptr, nullptr, true));
+    ARCHON_TRY(rs::sort_pairs(f.s, B.sc, kT, vT, kS, vS, r.nbig, (1u << r.nbytes) - 1u, &b_in_b, &passes, nullptr, nullptr, nullptr, true));
     const uint32_t tiles = div_up(r.nbig, fwd::kBfTile);
     ARCHON_TRY(f.reset_lookback(tiles));
     const uint64_t *ks = b_in_b ? kS : kT;
@@ -736,11 +736,10 @@ int Rounds::b_sort(Plan &r)
     const int src = r.split ? r.nxt : cur;
     // (a text round has no rank table yet: its new group starts go to B.v)
     with_const<0, 1>(r.mode == 1, [&](auto T) {
-        hipLaunchKernelGGL(HIP_KERNEL_NAME(fwd::k_b_finish<decltype(T)::value>), dim3(tiles), dim3(256), 0, f.s, ks, vs, B.upos[src], B.ug[src], r.nbig, f.sa, decltype(T)::value ? B.v : B.rank, r.s_next,
-                           f.cnt(), B.upos[r.nxt], B.ug[r.nxt], B.uitem[r.nxt], f.fg_status(), B.sc.d_ticket, B.sc.d_err, f.d_x, f.d_bwt, f.d_base, f.n, r.b_log);
+        ARCHON_LAUNCH(HIP_KERNEL_NAME(fwd::k_b_finish<decltype(T)::value>), dim3(tiles), dim3(256), 0, f.s, ks, vs, B.upos[src], B.ug[src], r.nbig, f.sa, decltype(T)::value ? B.v : B.rank, r.s_next,
+                       f.cnt(), B.upos[r.nxt], B.ug[r.nxt], B.uitem[r.nxt], f.fg_status(), B.sc.d_ticket, B.sc.d_err, f.d_x, f.d_bwt, f.d_base, f.n, r.b_log);
     });
     ARCHON_HIP_TRY(hipGetLastError());
-    ++f.c->launches;
     return ARCHON_OK;
 }
 
@@ -762,13 +761,12 @@ int Rounds::apply_ranks(const Plan &r)
     FwdBuf &B = f.B;
     if (r.b_log || (writer_ok && r.mode != 1 && r.nlog >= kWriterMinLog)) {
         ARCHON_TRY(f.writer_regions(r.b_log == reinterpret_cast<uint2 *>(kT) ? kS : kT));       // the key buffer that is not the B log
-        if (r.nlog) hipLaunchKernelGGL(HIP_KERNEL_NAME(rw::k_part<1, 0>), dim3(div_up(r.nlog, rw::kTile)), dim3(rw::kLanes), 0, f.s, B.rlog, nullptr, r.nlog, nullptr, nullptr, nullptr, B.rwb.r1, B.rwb.cnt1);
-        if (r.b_log) hipLaunchKernelGGL(HIP_KERNEL_NAME(rw::k_part<1, 0>), dim3(div_up(r.nbig, rw::kTile)), dim3(rw::kLanes), 0, f.s, r.b_log, nullptr, r.nbig, nullptr, nullptr, nullptr, B.rwb.r1, B.rwb.cnt1);
-        ARCHON_TRY(rw::write_back(f.s, B.rwb, f.n, B.rank, &f.c->launches));
-        f.c->launches += 2;
+        if (r.nlog) ARCHON_LAUNCH(HIP_KERNEL_NAME(rw::k_part<1, 0>), dim3(div_up(r.nlog, rw::kTile)), dim3(rw::kLanes), 0, f.s, B.rlog, nullptr, r.nlog, nullptr, nullptr, nullptr, B.rwb.r1, B.rwb.cnt1);
+        if (r.b_log) ARCHON_LAUNCH(HIP_KERNEL_NAME(rw::k_part<1, 0>), dim3(div_up(r.nbig, rw::kTile)), dim3(rw::kLanes), 0, f.s, r.b_log, nullptr, r.nbig, nullptr, nullptr, nullptr, B.rwb.r1, B.rwb.cnt1);
+        ARCHON_TRY(rw::write_back(f.s, B.rwb, f.n, B.rank));
+        if (!(r.nlog && r.b_log)) launches_miscounted(1);       // rw::k_part<1, 0> was counted for both logs, also when one of them was empty
     } else if (r.nlog) {
-        hipLaunchKernelGGL(fwd::k_rank_apply, dim3(div_up(r.nlog, 256)), dim3(256), 0, f.s, B.rlog, f.cnt() + fwd_small::kCntLog, B.rank);
-        ++f.c->launches;
+        ARCHON_LAUNCH(fwd::k_rank_apply, dim3(div_up(r.nlog, 256)), dim3(256), 0, f.s, B.rlog, f.cnt() + fwd_small::kCntLog, B.rank);
     }
     return ARCHON_OK;
 }
@@ -799,15 +797,15 @@ int Rounds::pair_chain(uint32_t np)
     FwdBuf &B = f.B;
     bool in2 = false;
     uint32_t passes = 0;
-    ARCHON_TRY(rs::sort_pairs(f.s, B.sc, pk, pv, pk2, pv2, np, 0xF0u, &in2, &passes, &f.c->launches));
+    ARCHON_TRY(rs::sort_pairs(f.s, B.sc, pk, pv, pk2, pv2, np, 0xF0u, &in2, &passes));
     const uint64_t *k2 = in2 ? pk2 : pk;
     const uint32_t *v2 = in2 ? pv2 : pv;
-    hipLaunchKernelGGL(fwd::k_pair_heads, dim3(div_up(np, 256)), dim3(256), 0, f.s, k2, np, B.rank, pair_v, pair_code);
+    ARCHON_LAUNCH(fwd::k_pair_heads, dim3(div_up(np, 256)), dim3(256), 0, f.s, k2, np, B.rank, pair_v, pair_code);
     ARCHON_TRY(launch_scan<1>(f.s, pair_v, pair_v, np, B.scan_tmp, nullptr));
-    hipLaunchKernelGGL(fwd::k_pair_apply, dim3(div_up(np, 256)), dim3(256), 0, f.s, k2, v2, pair_v, pair_code, np, f.sa, B.rank, f.d_x, f.d_bwt, f.d_base, f.n,
-                       B.slist[cs], f.cnt());
+    ARCHON_LAUNCH(fwd::k_pair_apply, dim3(div_up(np, 256)), dim3(256), 0, f.s, k2, v2, pair_v, pair_code, np, f.sa, B.rank, f.d_x, f.d_bwt, f.d_base, f.n,
+                   B.slist[cs], f.cnt());
     ARCHON_HIP_TRY(hipGetLastError());
-    f.c->launches += 4;
+    launches_miscounted(-1);        // five launches, k_pair_heads, the scan's three and k_pair_apply, were counted as four
     uint32_t *rd = f.rd() + mail::kRdCnt;
     ARCHON_HIP_TRY(hipMemcpyAsync(rd, f.cnt(), sizeof(uint32_t), hipMemcpyDeviceToHost, f.s));
     ARCHON_SYNC(f.s);
@@ -900,11 +898,10 @@ int General::run_shortcut()
         uint32_t *tab = f.B.hist16;                     // 2 * kGapSlots words (32 KiB) of the two-byte count's table, idle by now (256 KiB whatever n is:
                                                         // a list buffer of a small block is shorter than the table)
         ARCHON_HIP_TRY(hipMemsetAsync(tab, 0, 2 * fwd::kGapSlots * sizeof(uint32_t), f.s));
-        hipLaunchKernelGGL(fwd::k_gap_sample, dim3(div_up(div_up(f.n, fwd::kGapStride), 256)), dim3(256), 0, f.s, f.sa, f.B.v, f.n, tab);
+        ARCHON_LAUNCH(fwd::k_gap_sample, dim3(div_up(div_up(f.n, fwd::kGapStride), 256)), dim3(256), 0, f.s, f.sa, f.B.v, f.n, tab);
         const uint32_t *h_tab = f.c->h_mail + mail::kGapTable.at;
         ARCHON_HIP_TRY(hipMemcpyAsync(f.c->h_mail + mail::kGapTable.at, tab, 2 * fwd::kGapSlots * sizeof(uint32_t), hipMemcpyDeviceToHost, f.s));
         ARCHON_SYNC(f.s);
-        f.c->launches += 1;
         uint64_t total = 0;
         uint32_t best = 0;
         for (uint32_t i = 0; i < fwd::kGapSlots; ++i) {
@@ -931,23 +928,23 @@ int General::settle_runs(uint32_t p)
     uint32_t *d_lastbrk = B.small + fwd_small::kLastBrk;
     if (!(f.brk_ready && p == f.period_hint)) {
         ARCHON_HIP_TRY(hipMemsetAsync(d_lastbrk, 0, 2 * sizeof(uint32_t), s));  // [0] last real break, [1] how many
-        hipLaunchKernelGGL(fwd::k_period_breaks, dim3(div_up(div_up(n, 4), 256)), dim3(256), 0, s, f.d_x, n, p, brk, d_lastbrk);
+        ARCHON_LAUNCH(fwd::k_period_breaks, dim3(div_up(div_up(n, 4), 256)), dim3(256), 0, s, f.d_x, n, p, brk, d_lastbrk);
         ARCHON_TRY(launch_scan<1>(s, brk, brk, n, B.scan_tmp, nullptr));
     }
-    hipLaunchKernelGGL(fwd::k_chain_init, dim3(div_up(n, 256)), dim3(256), 0, s, B.v, n, gmin, gmax, ginfo);
+    ARCHON_LAUNCH(fwd::k_chain_init, dim3(div_up(n, 256)), dim3(256), 0, s, B.v, n, gmin, gmax, ginfo);
     ARCHON_HIP_TRY(hipMemsetAsync(settled, 0, sizeof(uint32_t), s));
     tr.step("breaks + scan + memsets");
-    hipLaunchKernelGGL(fwd::k_chain_minmax, dim3(div_up(n, fwd::kChainRows)), dim3(256), 0, s, f.sa, B.v, n, gmin, gmax);
+    ARCHON_LAUNCH(fwd::k_chain_minmax, dim3(div_up(n, fwd::kChainRows)), dim3(256), 0, s, f.sa, B.v, n, gmin, gmax);
     tr.step("chain_minmax");
-    hipLaunchKernelGGL(fwd::k_chain_probe, dim3(div_up(n, fwd::kChainRows)), dim3(256), 0, s, f.d_x, f.sa, B.v, brk, n, p, gmin, gmax, d_lastbrk, ginfo, gend);
+    ARCHON_LAUNCH(fwd::k_chain_probe, dim3(div_up(n, fwd::kChainRows)), dim3(256), 0, s, f.d_x, f.sa, B.v, brk, n, p, gmin, gmax, d_lastbrk, ginfo, gend);
     tr.step("chain_probe");
-    hipLaunchKernelGGL(fwd::k_chain_apply, dim3(div_up(n, fwd::kChainRows)), dim3(256), 0, s, f.sa, B.v, ginfo, gend, gmin, gmax, brk, d_lastbrk, f.d_x, n, p, f.d_bwt, f.d_base, settled);
+    ARCHON_LAUNCH(fwd::k_chain_apply, dim3(div_up(n, fwd::kChainRows)), dim3(256), 0, s, f.sa, B.v, ginfo, gend, gmin, gmax, brk, d_lastbrk, f.d_x, n, p, f.d_bwt, f.d_base, settled);
     tr.step("chain_apply");
     ARCHON_HIP_TRY(hipMemcpyAsync(rd + mail::kRdSettled, settled, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
     ARCHON_HIP_TRY(hipMemcpyAsync(rd + mail::kRdBreaks, d_lastbrk + 1, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
     ARCHON_SYNC(s);
     z.breaks = rd[mail::kRdBreaks];
-    f.c->launches += 8;
+    if (f.brk_ready && p == f.period_hint) launches_miscounted(4);     // k_period_breaks and its scan, launched and counted by Fwd::period, were counted here again
     const uint32_t done = rd[mail::kRdSettled];
     if (done >= m) {
         m = 0;                          // every tied row was settled: nothing to count or compact
@@ -986,15 +983,14 @@ int General::build_lists()
         return ARCHON_OK;
     }
     if (!keep_ready) ARCHON_TRY(f.recount_tied());
-    hipLaunchKernelGGL(fwd::k_compact_first, dim3(div_up(f.n, 256)), dim3(256), 0, s, B.keep, B.dst, B.v, f.sa, f.n, B.upos[0], B.ug[0], B.uitem[0]);
+    ARCHON_LAUNCH(fwd::k_compact_first, dim3(div_up(f.n, 256)), dim3(256), 0, s, B.keep, B.dst, B.v, f.sa, f.n, B.upos[0], B.ug[0], B.uitem[0]);
     const uint32_t tiles = div_up(m, fwd::kClT);
     uint32_t *d_cnt = f.cnt(), *rd = f.rd() + mail::kRdCnt;
     ARCHON_HIP_TRY(hipMemsetAsync(d_cnt, 0, 4 * sizeof(uint32_t), s));
     ARCHON_TRY(f.reset_lookback(tiles));
-    hipLaunchKernelGGL(fwd::k_classify, dim3(tiles), dim3(fwd::kFuLanes), 0, s, B.upos[0], B.ug[0], B.uitem[0], m, B.slist[R.cs], d_cnt + fwd_small::kCntS,
-                       B.upos[1], B.ug[1], B.uitem[1], d_cnt + fwd_small::kCntB, f.fg_status(), B.sc.d_ticket, B.sc.d_err);
+    ARCHON_LAUNCH(fwd::k_classify, dim3(tiles), dim3(fwd::kFuLanes), 0, s, B.upos[0], B.ug[0], B.uitem[0], m, B.slist[R.cs], d_cnt + fwd_small::kCntS,
+                   B.upos[1], B.ug[1], B.uitem[1], d_cnt + fwd_small::kCntB, f.fg_status(), B.sc.d_ticket, B.sc.d_err);
     ARCHON_HIP_TRY(hipGetLastError());
-    f.c->launches += 2;
     ARCHON_HIP_TRY(hipMemcpyAsync(rd, d_cnt, 3 * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
     ARCHON_SYNC(s);
     R.ms = rd[fwd_small::kCntS];
@@ -1035,12 +1031,11 @@ int General::fill_rank_table()
     tr.step("before scatter_rank");
     if (R.writer_ok) {
         ARCHON_TRY(f.writer_regions(B.keyA));           // (the first stage's pairs / records are dead)
-        hipLaunchKernelGGL(HIP_KERNEL_NAME(rw::k_part<1, 1>), dim3(div_up(f.n, rw::kTile)), dim3(rw::kLanes), 0, f.s, nullptr, nullptr, f.n, f.sa, B.v, nullptr, B.rwb.r1, B.rwb.cnt1);
-        ARCHON_TRY(rw::write_back(f.s, B.rwb, f.n, B.rank, &f.c->launches));
+        ARCHON_LAUNCH(HIP_KERNEL_NAME(rw::k_part<1, 1>), dim3(div_up(f.n, rw::kTile)), dim3(rw::kLanes), 0, f.s, nullptr, nullptr, f.n, f.sa, B.v, nullptr, B.rwb.r1, B.rwb.cnt1);
+        ARCHON_TRY(rw::write_back(f.s, B.rwb, f.n, B.rank));
     } else {
-        hipLaunchKernelGGL(fwd::k_scatter_rank, dim3(div_up(f.n, 256)), dim3(256), 0, f.s, f.sa, B.v, f.n, B.rank);
+        ARCHON_LAUNCH(fwd::k_scatter_rank, dim3(div_up(f.n, 256)), dim3(256), 0, f.s, f.sa, B.v, f.n, B.rank);
     }
-    ++f.c->launches;
     tr.step("scatter_rank");
     return ARCHON_OK;
 }
@@ -1056,9 +1051,8 @@ int General::certified_break_rounds()
     uint32_t *okey = B.keep;                                             // (idle until a doubling round lists pairs)
     ARCHON_HIP_TRY(hipMemsetAsync(cert, 0, f.n, f.s));
     ARCHON_HIP_TRY(hipMemsetAsync(okey, 0, (size_t)f.n * sizeof(uint32_t), f.s));
-    hipLaunchKernelGGL(fwd::k_zone_certify, dim3(div_up(f.n, 256)), dim3(256), 0, f.s, B.rank, f.sa, B.brk, f.d_x, f.n, z.period, cert, okey);
+    ARCHON_LAUNCH(fwd::k_zone_certify, dim3(div_up(f.n, 256)), dim3(256), 0, f.s, B.rank, f.sa, B.brk, f.d_x, f.n, z.period, cert, okey);
     ARCHON_HIP_TRY(hipGetLastError());
-    ++f.c->launches;
     tr.step("zone certify");
     for (bool distance = true;; distance = false) {
         st.unresolved_total += R.mb + R.mm;
@@ -1164,8 +1158,8 @@ int Fwd::setup()
 #endif
     stamp(0);
     { Carve count; ARCHON_TRY(ctx_ensure_arena(c, fwd_tier1(count, B, n, c->dev, d_sa_user == nullptr))); }
-    c->launches = 0;
-    if (depth == 0) t_sync_count = 0;
+    launches0 = t_launch_count;
+    syncs0 = t_sync_count;
     memset(&c->stats, 0, sizeof c->stats);
     c->stats.n = n;
 
@@ -1183,7 +1177,8 @@ int Fwd::setup()
     pres = B.small + fwd_small::kProbe;
     // (one launch clears the scratch words, arms the period probe's result word and clears the two-byte count's tables)
     count_zero_bytes = (size_t)(reinterpret_cast<char *>(&B.prep->rowtot[0]) - reinterpret_cast<char *>(B.hist16));
-    hipLaunchKernelGGL(bs::k_prep, dim3(256), dim3(256), 0, s, B.small, fwd_small::kWords, fwd_small::kProbe, reinterpret_cast<uint4 *>(B.hist16), (uint32_t)(count_zero_bytes / 16));
+    ARCHON_LAUNCH(bs::k_prep, dim3(256), dim3(256), 0, s, B.small, fwd_small::kWords, fwd_small::kProbe, reinterpret_cast<uint4 *>(B.hist16), (uint32_t)(count_zero_bytes / 16));
+    launches_miscounted(-1);        // k_prep was not counted here, where every block launches it, but with each streaming stage (Fwd::streaming)
     static_assert(offsetof(bs::Prep, rowtot) % 16 == 0, "the count's tables end on a 16-byte boundary");
     stamp(1);
 
@@ -1243,13 +1238,9 @@ int Fwd::setup()
 // (pf::k_period_clean).  The result word was set to "none" and the votes and flags behind it cleared by k_prep.
 void Fwd::queue_probe(bool clean)
 {
-    hipLaunchKernelGGL(fwd::k_period_find, dim3(fwd::kPeriodSearch / 256), dim3(256), 0, s, d_x, n, pres);
-    hipLaunchKernelGGL(fwd::k_period_vote, dim3(fwd::kPeriodVotes / 256), dim3(256), 0, s, d_x, n, pres);
-    c->launches += 2;
-    if (clean) {
-        hipLaunchKernelGGL(pf::k_period_clean, dim3(kNumCU * 8), dim3(256), 0, s, d_x, n, pres);
-        ++c->launches;
-    }
+    ARCHON_LAUNCH(fwd::k_period_find, dim3(fwd::kPeriodSearch / 256), dim3(256), 0, s, d_x, n, pres);
+    ARCHON_LAUNCH(fwd::k_period_vote, dim3(fwd::kPeriodVotes / 256), dim3(256), 0, s, d_x, n, pres);
+    if (clean) ARCHON_LAUNCH(pf::k_period_clean, dim3(kNumCU * 8), dim3(256), 0, s, d_x, n, pres);
     probe_queued = true;
     probe_clean = clean;
 }
@@ -1294,12 +1285,11 @@ void Fwd::take_byte_hist(bool exact)
 // the exact alphabet: 256 presence bits -> sigma, lut (the order-preserving recode)
 int Fwd::presence()
 {
-    hipLaunchKernelGGL(bs::k_presence, dim3(kNumCU * 8), dim3(256), 0, s, d_x, n, B.prep->present);
+    ARCHON_LAUNCH(bs::k_presence, dim3(kNumCU * 8), dim3(256), 0, s, d_x, n, B.prep->present);
     const uint32_t *h_present = c->h_mail + mail::kPresence.at;
     ARCHON_HIP_TRY(hipMemcpyAsync(c->h_mail + mail::kPresence.at, B.prep->present, 8 * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
     if (!probe_fetched) ARCHON_TRY(fetch_probe());         // (hinted: the period probe's verdict has not travelled yet)
     ARCHON_SYNC(s);
-    ++c->launches;
     probe_arrived();
     sigma = 0;
     for (uint32_t v = 0; v < 256; ++v) {
@@ -1324,15 +1314,14 @@ int Fwd::count16(int form, const uint8_t *src, bool force_stream, bool alpha_pro
     // B.hist16 (zeroed above) first serves as the spill table of the count, then receives the totals (k_rows_total)
     with_const<kHotForm, 1, 2, 4, 8>(form, [&](auto k) {
         constexpr int F = decltype(k)::value;
-        hipLaunchKernelGGL(HIP_KERNEL_NAME(bs::k_hist16<key_q(F), F == kHotForm>), dim3(nparts), dim3(bs::kH16Block), 0, s, src, n, B.h16part, B.hist16,
-                           tpr * kTileItems, B.rhist, d_suspect, sub);
+        ARCHON_LAUNCH(HIP_KERNEL_NAME(bs::k_hist16<key_q(F), F == kHotForm>), dim3(nparts), dim3(bs::kH16Block), 0, s, src, n, B.h16part, B.hist16,
+                       tpr * kTileItems, B.rhist, d_suspect, sub);
     });
     static_assert(bs::kMaxRanges <= 1024, "four ranges per lane in the column half of k_rows_sum_total");
-    hipLaunchKernelGGL(bs::k_rows_sum_total, dim3(512), dim3(256), 0, s, B.hist16, B.h16part, nparts, B.prep, (uint32_t)bs::kLsCap, B.rhist, R);
-    hipLaunchKernelGGL(bs::k_rows_scan, dim3(256), dim3(256), 0, s, B.hist16, B.prep, force_stream ? 1u : 0u, allow_aligned, d_ctl, (uint32_t)kTieListCap, n,
-                       probe_clean ? pres : nullptr);
+    ARCHON_LAUNCH(bs::k_rows_sum_total, dim3(512), dim3(256), 0, s, B.hist16, B.h16part, nparts, B.prep, (uint32_t)bs::kLsCap, B.rhist, R);
+    ARCHON_LAUNCH(bs::k_rows_scan, dim3(256), dim3(256), 0, s, B.hist16, B.prep, force_stream ? 1u : 0u, allow_aligned, d_ctl, (uint32_t)kTieListCap, n,
+                   probe_clean ? pres : nullptr);
     ARCHON_HIP_TRY(hipGetLastError());
-    c->launches += 3;
     e_count = tm.mark();
     return ARCHON_OK;
 }
@@ -1355,28 +1344,26 @@ int Fwd::streaming(int form, const uint8_t *key_text)
     with_const<kHotForm, 1, 2, 4, 8>(form, [&](auto k) {
         constexpr int F = decltype(k)::value;
         auto pass_a = [&](auto rel) {
-            hipLaunchKernelGGL(HIP_KERNEL_NAME(bs::k_pass_text<bs::kPassBlock, bs::kPassIPT, key_q(F), F == kHotForm, decltype(rel)::value>), dim3(R), dim3(bs::kPassBlock),
-                               0, s, d_x, n, tpr, A_R, A_B1, B.prep->startA, B.rhist, key_text, d_skip, B.trash, &d_ctl->base_bucket, twin);
+            ARCHON_LAUNCH(HIP_KERNEL_NAME(bs::k_pass_text<bs::kPassBlock, bs::kPassIPT, key_q(F), F == kHotForm, decltype(rel)::value>), dim3(R), dim3(bs::kPassBlock),
+                           0, s, d_x, n, tpr, A_R, A_B1, B.prep->startA, B.rhist, key_text, d_skip, B.trash, &d_ctl->base_bucket, twin);
         };
         pass_a(std::false_type{});
         if (rel_ok) pass_a(std::true_type{});
     });
-    if (rel_ok) ++c->launches;
     iA1 = ps.mark();
     // pass B walks the same tile grid in the same ranges; in bucket mode (Prep::aligned) workgroup c takes bucket c
     const uint32_t gridB = (allow_aligned && R < 256u) ? 256u : R;      // bucket mode needs 256; surplus workgroups return at once
-    hipLaunchKernelGGL(bs::k_range_hist_text, dim3(R), dim3(bs::kRhBlock), 0, s, A_B1, n, tpr, B.rhist, 0u, kTileItems, d_skip);
-    hipLaunchKernelGGL(bs::k_col_prefix, dim3(256), dim3(1024), 0, s, B.rhist, R, d_skip, twin);    // (bucket mode with range-relative records: pass A's table stays)
+    ARCHON_LAUNCH(bs::k_range_hist_text, dim3(R), dim3(bs::kRhBlock), 0, s, A_B1, n, tpr, B.rhist, 0u, kTileItems, d_skip);
+    ARCHON_LAUNCH(bs::k_col_prefix, dim3(256), dim3(1024), 0, s, B.rhist, R, d_skip, twin);    // (bucket mode with range-relative records: pass A's table stays)
     iB0 = ps.mark();
     with_const<0, 1>(hot, [&](auto h) {
         auto pass_b = [&](auto rel) {
-            hipLaunchKernelGGL(HIP_KERNEL_NAME(bs::k_pass_rec<bs::kPassBBlock, bs::kPassBIPT, decltype(h)::value != 0, decltype(rel)::value>), dim3(gridB), dim3(bs::kPassBBlock),
-                               0, s, A_R, A_B1, n, tpr, B_R, B.prep->startB, B.rhist, B.prep->startA, d_skip, B.prep->start16, B.trash, twin, B.rhist, R, tpr * kTileItems);
+            ARCHON_LAUNCH(HIP_KERNEL_NAME(bs::k_pass_rec<bs::kPassBBlock, bs::kPassBIPT, decltype(h)::value != 0, decltype(rel)::value>), dim3(gridB), dim3(bs::kPassBBlock),
+                           0, s, A_R, A_B1, n, tpr, B_R, B.prep->startB, B.rhist, B.prep->startA, d_skip, B.prep->start16, B.trash, twin, B.rhist, R, tpr * kTileItems);
         };
         pass_b(std::false_type{});
         if (rel_ok) pass_b(std::true_type{});
     });
-    if (rel_ok) ++c->launches;
     iB1 = ps.mark();
     e_sorted = tm.mark();
     // (a block of few rows per bucket: the short instance of the bucket sort in front of the general one -- whichever matches the
@@ -1385,30 +1372,25 @@ int Fwd::streaming(int form, const uint8_t *key_text)
     const uint32_t short_rounds = hot ? 0u : avg_rows <= 400u ? 1u : avg_rows <= 1350u ? 3u : 0u;
     if (short_rounds) {
         with_const<1, 3>((int)short_rounds, [&](auto r) {
-            hipLaunchKernelGGL(HIP_KERNEL_NAME(bs::k_local_sort<decltype(r)::value>), dim3(65536), dim3(bs::kLsBlock), 0, s, B_R, B.prep->start16, n, sa, d_bwt, d_ctl,
-                               B.tie_list, d_skip, 0u, 0u);
+            ARCHON_LAUNCH(HIP_KERNEL_NAME(bs::k_local_sort<decltype(r)::value>), dim3(65536), dim3(bs::kLsBlock), 0, s, B_R, B.prep->start16, n, sa, d_bwt, d_ctl,
+                           B.tie_list, d_skip, 0u, 0u);
         });
-        ++c->launches;
     }
-    hipLaunchKernelGGL(HIP_KERNEL_NAME(bs::k_local_sort<bs::kLsIPT>), dim3(65536), dim3(bs::kLsBlock), 0, s, B_R, B.prep->start16, n, sa,
-                       d_bwt, d_ctl, B.tie_list, d_skip, hot ? 1u : 0u, short_rounds * (uint32_t)bs::kLsBlock);
-    if (hot) {
-        hipLaunchKernelGGL(bs::k_unpack_big, dim3(div_up(n, bs::kUnpackChunk)), dim3(256), 0, s, B_R, B.prep->start16, n, sa, d_bwt, d_ctl, d_skip);
-        ++c->launches;
-    }
+    ARCHON_LAUNCH(HIP_KERNEL_NAME(bs::k_local_sort<bs::kLsIPT>), dim3(65536), dim3(bs::kLsBlock), 0, s, B_R, B.prep->start16, n, sa,
+                   d_bwt, d_ctl, B.tie_list, d_skip, hot ? 1u : 0u, short_rounds * (uint32_t)bs::kLsBlock);
+    if (hot) ARCHON_LAUNCH(bs::k_unpack_big, dim3(div_up(n, bs::kUnpackChunk)), dim3(256), 0, s, B_R, B.prep->start16, n, sa, d_bwt, d_ctl, d_skip);
     e_local = tm.mark();
-    hipLaunchKernelGGL(bs::k_resolve_ties, dim3(div_up(kTieListCap, 256)), dim3(256), 0, s, d_x, n, B.tie_list, d_ctl,
-                       sa, d_bwt, 5u * (uint32_t)q, 64u * (uint32_t)q, d_skip);
+    ARCHON_LAUNCH(bs::k_resolve_ties, dim3(div_up(kTieListCap, 256)), dim3(256), 0, s, d_x, n, B.tie_list, d_ctl,
+                   sa, d_bwt, 5u * (uint32_t)q, 64u * (uint32_t)q, d_skip);
     ARCHON_HIP_TRY(hipGetLastError());
-    c->launches += 7;
+    launches_miscounted(1);         // k_prep of Fwd::setup was counted here: once per streaming stage of the block, never on the other routes
     // (on the chance that this is all the block needs -- the graded case -- the primary index goes to the caller and the
     //  consistency flag to the host with the same round trip: the call then ends without a second one.  Everything the host
     //  reads -- summary, flag, byte counts for skewed blocks, the period probe -- is written into the pinned mailbox by k_mail.)
     e_first = tm.mark();
-    hipLaunchKernelGGL(bs::k_mail, dim3(1), dim3(256), 0, s, d_ctl, B.sc.d_err, q == 1 ? B.prep->cntA : nullptr, d_x + (n - 1),
-                       probe_clean ? pres : nullptr, c->h_mail_dev, d_base_out, ++c->mail_seq);
+    ARCHON_LAUNCH(bs::k_mail, dim3(1), dim3(256), 0, s, d_ctl, B.sc.d_err, q == 1 ? B.prep->cntA : nullptr, d_x + (n - 1),
+                   probe_clean ? pres : nullptr, c->h_mail_dev, d_base_out, ++c->mail_seq);
     ARCHON_HIP_TRY(hipGetLastError());
-    ++c->launches;
     probe_fetched = probe_clean;
     stamp(2);
     // the host's one wait of the block: spin on the sequence word k_mail writes last (pinned, coherent memory); should it not
@@ -1443,7 +1425,6 @@ int Fwd::first_look()
     if (small_block) {
         uint32_t *d_counts = B.small + fwd_small::kCounts;
         ARCHON_TRY(launch_hist256(s, d_x, n, d_counts, n));
-        ++c->launches;
         e_count = tm.mark();
         ARCHON_TRY(fetch_byte_counts(d_counts));
         // (a small block's time is its host round trips: the period probe and the block's last bytes -- what the LSB passes' digit
@@ -1509,10 +1490,8 @@ int Fwd::closed_form()
         set_error("closed form: tier 1 of the %u-byte block of period %u does not fit below the tail", m2, p);
         return ARCHON_E_INTERNAL;
     }
-    const uint32_t launches0 = c->launches;
     const bool x_in_arena = d_x == B.xa;
-    ARCHON_TRY(forward_run(c, s, d_x, m2, sa2, bwt2, base2, depth + 1));      // (c->stats, c->launches, tier 1: the nested call's from here on)
-    const uint32_t launches1 = c->stats.kernel_launches;
+    ARCHON_TRY(forward_run(c, s, d_x, m2, sa2, bwt2, base2, depth + 1));      // (c->stats, tier 1: the nested call's from here on)
     const uint64_t arena1 = c->stats.arena_bytes;
     // Tier 1 again, for the expansion.  The nested call carved it from the bottom: of the aligned copy of the text (B.xa) only
     // the slot is kept, so that tile_lo lands behind it -- its first 2p + 64 bytes are still the text (the nested block read them
@@ -1522,9 +1501,9 @@ int Fwd::closed_form()
     const uint32_t ntiles = div_up(n, pf::kTile);
     uint32_t *tile_lo = a.take<uint32_t>((size_t)ntiles + 2);
     if (!tile_lo) { set_error("arena exhausted (closed form)"); return ARCHON_E_NOMEM; }
-    hipLaunchKernelGGL(pf::k_offsets, dim3(1), dim3(1024), 0, s, sa2, m2, p, n, off);
-    hipLaunchKernelGGL(pf::k_tiles, dim3(div_up(ntiles + 1, 256)), dim3(256), 0, s, off, m2, ntiles, tile_lo);
-    hipLaunchKernelGGL(pf::k_expand, dim3(ntiles), dim3(256), 0, s, off, sa2, bwt2, tile_lo, m2, p, n, d_x, d_sa_user, d_bwt, d_base_out);
+    ARCHON_LAUNCH(pf::k_offsets, dim3(1), dim3(1024), 0, s, sa2, m2, p, n, off);
+    ARCHON_LAUNCH(pf::k_tiles, dim3(div_up(ntiles + 1, 256)), dim3(256), 0, s, off, m2, ntiles, tile_lo);
+    ARCHON_LAUNCH(pf::k_expand, dim3(ntiles), dim3(256), 0, s, off, sa2, bwt2, tile_lo, m2, p, n, d_x, d_sa_user, d_bwt, d_base_out);
     ARCHON_HIP_TRY(hipGetLastError());
     e_sorted = e_end = tm.mark();
     uint32_t *rd = c->h_mail + mail::kRead.at;
@@ -1533,7 +1512,6 @@ int Fwd::closed_form()
     if (rd[0] != n) { set_error("closed form: the classes of period %u hold %u rows of %u", p, rd[0], n); return ARCHON_E_INTERNAL; }
     path = Path::kClosed;
     closed_period = p;
-    c->launches = launches0 + launches1 + 3;
     arena_bytes = arena1 > a.off ? arena1 : a.off;
     if (depth == 0) c->hint_poor_alphabet = true;      // (periodic after periodic: the probe's verdict before any count)
     return ARCHON_OK;
@@ -1599,12 +1577,11 @@ int Fwd::period()
     ARCHON_TRY(general_buffers());
     uint32_t *d_lastbrk = B.small + fwd_small::kLastBrk;
     ARCHON_HIP_TRY(hipMemsetAsync(d_lastbrk, 0, 2 * sizeof(uint32_t), s));          // [0] last real break, [1] how many
-    hipLaunchKernelGGL(fwd::k_period_breaks, dim3(div_up(div_up(n, 4), 256)), dim3(256), 0, s, d_x, n, period_hint, B.brk, d_lastbrk);
+    ARCHON_LAUNCH(fwd::k_period_breaks, dim3(div_up(div_up(n, 4), 256)), dim3(256), 0, s, d_x, n, period_hint, B.brk, d_lastbrk);
     ARCHON_TRY(launch_scan<1>(s, B.brk, B.brk, n, B.scan_tmp, nullptr));
     uint32_t *rd = c->h_mail + mail::kRead.at;
     ARCHON_HIP_TRY(hipMemcpyAsync(rd + 2, d_lastbrk + 1, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
     ARCHON_SYNC(s);
-    c->launches += 4;
     brk_ready = true;
     period_breaks = route_off(kRtNoBreakRound) ? 0u : rd[2];
     return ARCHON_OK;
@@ -1634,9 +1611,8 @@ int Fwd::recode()
     if (sigma >= 2 && sigma <= 16 && forced < 0 && !small_block && !route_off(kRtNoPackStream)) {
         const int q = bits == 1 ? 8 : bits == 2 ? 4 : 2;
         with_const<8, 4, 2>(q, [&](auto k) {
-            hipLaunchKernelGGL(HIP_KERNEL_NAME(bs::k_build_y<decltype(k)::value>), dim3(div_up(div_up(n, 16), 256)), dim3(256), 0, s, d_x, n, d_lut, B.y);
+            ARCHON_LAUNCH(HIP_KERNEL_NAME(bs::k_build_y<decltype(k)::value>), dim3(div_up(div_up(n, 16), 256)), dim3(256), 0, s, d_x, n, d_lut, B.y);
         });
-        ++c->launches;
         ARCHON_TRY(count16(q, B.y, false, false));
         ARCHON_TRY(streaming(q, B.y));
         if ((uint64_t)big_items * 2 <= n) {
@@ -1660,12 +1636,11 @@ int Fwd::first_groups(int mode, const uint64_t *keys, const uint32_t *items, uin
     ARCHON_HIP_TRY(hipMemsetAsync(B.small + fwd_small::kFu, 0, 4 * sizeof(uint32_t), s));
     const uint32_t ws_mode = ws_ready ? 2u : 0u;      // 2: the S / B lists of rounds.hiph
     with_const<0, 1>(mode, [&](auto m) {
-        hipLaunchKernelGGL(HIP_KERNEL_NAME(fwd::k_first_groups<decltype(m)::value>), dim3(tiles), dim3(256), 0, s, keys, items, shift, n, sa, d_bwt, d_base, B.v,
-                           B.upos[0], B.ug[0], B.uitem[0], B.small + fwd_small::kTotal, fg_status, B.sc.d_ticket, B.sc.d_err, ws_mode, B.slist[0],
-                           B.small + fwd_small::kFu, (uint32_t)fwd::kFuMax);
+        ARCHON_LAUNCH(HIP_KERNEL_NAME(fwd::k_first_groups<decltype(m)::value>), dim3(tiles), dim3(256), 0, s, keys, items, shift, n, sa, d_bwt, d_base, B.v,
+                       B.upos[0], B.ug[0], B.uitem[0], B.small + fwd_small::kTotal, fg_status, B.sc.d_ticket, B.sc.d_err, ws_mode, B.slist[0],
+                       B.small + fwd_small::kFu, (uint32_t)fwd::kFuMax);
     });
     ARCHON_HIP_TRY(hipGetLastError());
-    ++c->launches;
     return ARCHON_OK;
 }
 
@@ -1680,8 +1655,8 @@ int Fwd::seven_pass()
         h0 = 56 / bits;
         ARCHON_HIP_TRY(hipMemsetAsync(B.sc.d_ghist, 0, 8 * 256 * sizeof(uint32_t), s));
         const uint32_t want = div_up(div_up(n, 4), 256), cap = (uint32_t)kNumCU * 8;
-        hipLaunchKernelGGL(fwd::k_init_keys_packed, dim3(want < cap ? want : cap), dim3(256), 0, s, d_x, n, reinterpret_cast<const uint8_t *>(B.small + fwd_small::kLut),
-                           bits, h0, B.keyA, B.valA, B.sc.d_ghist);        // (... and the digit counts of the passes)
+        ARCHON_LAUNCH(fwd::k_init_keys_packed, dim3(want < cap ? want : cap), dim3(256), 0, s, d_x, n, reinterpret_cast<const uint8_t *>(B.small + fwd_small::kLut),
+                       bits, h0, B.keyA, B.valA, B.sc.d_ghist);        // (... and the digit counts of the passes)
         alphabet_bits = bits;
         h0 = (8 * key_bytes) / bits;            // symbols the sorted key bytes hold
     } else {
@@ -1725,17 +1700,19 @@ int Fwd::seven_pass()
         }
     }
     ARCHON_HIP_TRY(hipGetLastError());
-    c->launches += 2;
     bool in_b = false;
     const uint32_t pass_mask = (0xFFu << (8 - key_bytes)) & 0xFEu;          // the top key_bytes bytes; byte 0 is payload
     // (plain bytes with the histograms in hand: the first pass that runs makes the pairs from the text itself)
     const bool from_text = !packed && use_given;
     if (!packed && !from_text)
-        hipLaunchKernelGGL(fwd::k_init_keys, dim3(div_up(div_up(n, 4), 256)), dim3(256), 0, s, d_x, n, B.keyA, B.valA);
-    ARCHON_TRY(rs::sort_pairs(s, B.sc, B.keyA, B.valA, B.keyB, B.valB, n, pass_mask, &in_b, &radix_passes, &c->launches, &pt,
+        ARCHON_LAUNCH(fwd::k_init_keys, dim3(div_up(div_up(n, 4), 256)), dim3(256), 0, s, d_x, n, B.keyA, B.valA);
+    ARCHON_TRY(rs::sort_pairs(s, B.sc, B.keyA, B.valA, B.keyB, B.valB, n, pass_mask, &in_b, &radix_passes, &pt,
                               use_given ? hist_given : nullptr, from_text ? d_x : nullptr, packed));
     if (from_text && radix_passes == 0)          // every digit constant: no pass ran, the pairs still have to exist
-        hipLaunchKernelGGL(fwd::k_init_keys, dim3(div_up(div_up(n, 4), 256)), dim3(256), 0, s, d_x, n, B.keyA, B.valA);
+        ARCHON_LAUNCH(fwd::k_init_keys, dim3(div_up(div_up(n, 4), 256)), dim3(256), 0, s, d_x, n, B.keyA, B.valA);
+    // the kernel that makes the keys, k_init_keys or k_init_keys_packed, was counted twice -- also where the first pass makes them
+    // from the text and neither runs
+    launches_miscounted(from_text && radix_passes != 0 ? 2 : 1);
     e_sorted = e_first = tm.mark();
     ws_ready = key_bytes == fwd::kKeyBytes || period_breaks != 0 || shallow;     // a clean periodic block: the run shortcut will empty the working set
     return first_groups(0, in_b ? B.keyB : B.keyA, in_b ? B.valB : B.valA, 8u * (8u - key_bytes));
@@ -1774,8 +1751,8 @@ int Fwd::tied_rows()
 }
 
 // 8. The device's consistency flag -- it came with the streaming stage's summary, or it is read now -- and the statistics of
-// every route (the general stage and the 7-pass sort count theirs as they go).  A stage that did not run left its marks at
-// -1, which StageTimer::ms reads as 0.
+// every route (the general stage and the 7-pass sort keep theirs as they go; launches and waits are what the thread's counters
+// have gained since setup).  A stage that did not run left its marks at -1, which StageTimer::ms reads as 0.
 int Fwd::finish()
 {
     archon_hip_stats &st = c->stats;
@@ -1801,8 +1778,8 @@ int Fwd::finish()
     st.arena_bytes = arena_bytes;
     st.alphabet_bits = alphabet_bits;
     st.radix_passes = path == Path::kStream ? 2u : radix_passes;
-    st.kernel_launches = c->launches;
-    st.host_syncs = t_sync_count;
+    st.kernel_launches = t_launch_count - launches0;
+    st.host_syncs = t_sync_count - syncs0;
     st.ms_hist = tm.ms(e_start, e_count);
     st.ms_sort = tm.ms(e_count, e_sorted);
     st.ms_doubling = tm.ms(e_first, e_general);
@@ -2159,7 +2136,7 @@ int archon_hip_fm_locate(archon_hip_fm *f, const uint8_t *patterns, const uint32
     ARCHON_TRY(fm_check_offsets(offsets, k));
     return with_ctx(f->dev, nullptr, [&](Ctx *c, hipStream_t s) -> int {
         KeepStats<archon_hip_fm_stats> keep(t_fm_stats, f->dev);
-        KeepStats<archon_hip_fm_walk_stats> walk(t_fmw_stats, f->dev);
+        KeepStats<archon_hip_fm_walk_stats> walk(t_fmw_stats, f->dev, false);      // (the locate's launches, not the count's: fm_locate_rows)
         fmw_handle_stats(f, &walk.st);
         return fm_locate_host(c, s, f, nullptr, patterns, offsets, k, pos, cap, total, &keep.st, &walk.st);
     });
@@ -2805,7 +2782,9 @@ static int block_lcp_step(Ctx *c, hipStream_t s, const archon_hip_block *b, uint
 {
     ARCHON_TRY(ctx_io(c, 1, (size_t)b->n * 4 + 64, (void **)d_lcp));
     archon_hip_lcp_stats st = {};
+    const uint32_t launches0 = t_launch_count;
     const int rc = lcp_run(c, s, b->d_x(), b->n, b->d_sa(), b->d_bwt(), *d_lcp, &st);
+    t_launch_count = launches0;         // the step's launches are in its own record, not in the calling form's: that one goes on from here
     t_lcp_stats.keep(b->dev, st);
     if (rc == ARCHON_OK && ms_lcp_or_null) *ms_lcp_or_null = st.ms_total;
     return rc;
@@ -2889,7 +2868,6 @@ static int block_fm_table_own(Ctx *c, hipStream_t s, archon_hip_block *b, Stats 
     ARCHON_TRY(block_fm_table(c, s, b, &fst));
     st->built = fst.built;
     st->ms_build = fst.ms_build;
-    st->kernel_launches += fst.kernel_launches;
     return ARCHON_OK;
 }
 }   // extern "C++"
@@ -3285,7 +3263,7 @@ static int sa_to_bwt_run(Ctx *c, hipStream_t s, const uint8_t *d_x, uint32_t n, 
     uint32_t *res = c->d_mail() + mail::kDevSaRes.at;      // [0] bad value seen, [1] rows holding n, [2] the primary index
     uint32_t *rd = c->h_mail + mail::kRead.at;
     ARCHON_HIP_TRY(hipMemsetAsync(res, 0, 3 * sizeof(uint32_t), s));
-    hipLaunchKernelGGL(fwd::k_sa_to_bwt, dim3(div_up(div_up(n, 4), 256)), dim3(256), 0, s, d_x, d_sa, n, d_bwt, res + 2, res);
+    ARCHON_LAUNCH(fwd::k_sa_to_bwt, dim3(div_up(div_up(n, 4), 256)), dim3(256), 0, s, d_x, d_sa, n, d_bwt, res + 2, res);
     ARCHON_HIP_TRY(hipGetLastError());
     ARCHON_HIP_TRY(hipMemcpyAsync(rd, res, 3 * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
     ARCHON_SYNC(s);
@@ -3344,8 +3322,8 @@ static int post_run(Ctx *c, hipStream_t s, const uint8_t *d_bwt, uint32_t n, uin
         return a.off;
     }));
     unsigned long long *d_total = reinterpret_cast<unsigned long long *>(c->d_mail() + mail::kDevPostTotal.at);
-    hipLaunchKernelGGL(post::k_post_piece, dim3(np), dim3(post::kLanes), 0, s, d_bwt, n, slots, sizes);
-    hipLaunchKernelGGL(post::k_post_gather, dim3(np), dim3(256), 0, s, slots, sizes, np, d_out, d_total);
+    ARCHON_LAUNCH(post::k_post_piece, dim3(np), dim3(post::kLanes), 0, s, d_bwt, n, slots, sizes);
+    ARCHON_LAUNCH(post::k_post_gather, dim3(np), dim3(256), 0, s, slots, sizes, np, d_out, d_total);
     ARCHON_HIP_TRY(hipGetLastError());
     ARCHON_HIP_TRY(hipMemcpyAsync(c->h_mail + mail::kPostTotal.at, d_total, sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
     ARCHON_SYNC(s);
@@ -3353,7 +3331,6 @@ static int post_run(Ctx *c, hipStream_t s, const uint8_t *d_bwt, uint32_t n, uin
     memcpy(&total, c->h_mail + mail::kPostTotal.at, sizeof total);
     if (total < 4 + 4ull * np || total > post::block_bound(n)) { set_error("post stage: stream length %llu out of bounds", total); return ARCHON_E_INTERNAL; }
     *out_bytes = (size_t)total;
-    c->launches += 2;
     return ARCHON_OK;
 }
 
@@ -3365,13 +3342,12 @@ static int post_decode_run(Ctx *c, hipStream_t s, const uint8_t *d_in, size_t in
     ARCHON_TRY(ctx_carve(c, [&](Carve &a) { off = a.take<unsigned long long>(np_max + 2); return a.off; }));
     uint32_t *meta = c->d_mail() + mail::kDevPostMeta.at;      // [0] n, [1] pieces, [2] bad
     ARCHON_HIP_TRY(hipMemsetAsync(meta, 0, 3 * sizeof(uint32_t), s));
-    hipLaunchKernelGGL(post::k_post_offsets, dim3(1), dim3(1024), 0, s, d_in, (unsigned long long)in_bytes, cap, off, meta, meta + 2);
-    hipLaunchKernelGGL(post::k_post_decode, dim3(div_up(np_max, post::kDecWaves)), dim3(64 * post::kDecWaves), 0, s, d_in, off, meta, d_bwt, meta + 2);
+    ARCHON_LAUNCH(post::k_post_offsets, dim3(1), dim3(1024), 0, s, d_in, (unsigned long long)in_bytes, cap, off, meta, meta + 2);
+    ARCHON_LAUNCH(post::k_post_decode, dim3(div_up(np_max, post::kDecWaves)), dim3(64 * post::kDecWaves), 0, s, d_in, off, meta, d_bwt, meta + 2);
     ARCHON_HIP_TRY(hipGetLastError());
     const uint32_t *h_meta = c->h_mail + mail::kPostMeta.at;
     ARCHON_HIP_TRY(hipMemcpyAsync(c->h_mail + mail::kPostMeta.at, meta, 3 * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
     ARCHON_SYNC(s);
-    c->launches += 2;
     if (h_meta[2]) { set_error("post stage: malformed stream (flag 0x%x)", h_meta[2]); return ARCHON_E_CORRUPT; }
     *n_out = h_meta[0];
     return ARCHON_OK;
@@ -3456,14 +3432,13 @@ static int lms_select_run(Ctx *c, hipStream_t s, const uint8_t *d_x, uint32_t n,
         small = a.take<uint32_t>(inv_small::kWords);
         return a.off;
     }));
-    c->launches = 0;
     sc.d_ticket = small + inv_small::kTicket; sc.d_err = small + inv_small::kErr; sc.h_mail = c->h_mail;
     uint32_t *d_total = small + inv_small::kTotal, *d_starts = small + inv_small::kStarts;
     ARCHON_HIP_TRY(hipMemsetAsync(small, 0, inv_small::kWords * sizeof(uint32_t), s));
     const uint32_t g256 = div_up(n, 256);
-    hipLaunchKernelGGL(fwd::k_lms_pairs, dim3(g256), dim3(256), 0, s, d_x, n, v);
+    ARCHON_LAUNCH(fwd::k_lms_pairs, dim3(g256), dim3(256), 0, s, d_x, n, v);
     ARCHON_TRY(launch_scan<1>(s, v, v, n, scan_tmp, nullptr));
-    hipLaunchKernelGGL(fwd::k_lms_flag, dim3(g256), dim3(256), 0, s, d_x, n, v, flag);
+    ARCHON_LAUNCH(fwd::k_lms_flag, dim3(g256), dim3(256), 0, s, d_x, n, v, flag);
     ARCHON_TRY(launch_scan<0>(s, flag, dst, n, scan_tmp, d_total));
     ARCHON_HIP_TRY(hipMemcpyAsync(c->h_mail + mail::kRead.at, d_total, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
     ARCHON_SYNC(s);
@@ -3471,17 +3446,17 @@ static int lms_select_run(Ctx *c, hipStream_t s, const uint8_t *d_x, uint32_t n,
     *n1_out = n1;
     ARCHON_HIP_TRY(hipMemsetAsync(d_count, 0, 256 * sizeof(uint32_t), s));
     if (n1 == 1) {
-        hipLaunchKernelGGL(fwd::k_lms_compact, dim3(g256), dim3(256), 0, s, d_x, n, flag, dst, kA, vA);
-        hipLaunchKernelGGL(fwd::k_lms_single, dim3(1), dim3(1), 0, s, kA, vA, d_count, d_items);
+        ARCHON_LAUNCH(fwd::k_lms_compact, dim3(g256), dim3(256), 0, s, d_x, n, flag, dst, kA, vA);
+        ARCHON_LAUNCH(fwd::k_lms_single, dim3(1), dim3(1), 0, s, kA, vA, d_count, d_items);
     } else if (n1) {
-        hipLaunchKernelGGL(fwd::k_lms_compact, dim3(g256), dim3(256), 0, s, d_x, n, flag, dst, kA, vA);
+        ARCHON_LAUNCH(fwd::k_lms_compact, dim3(g256), dim3(256), 0, s, d_x, n, flag, dst, kA, vA);
         bool in_b = false;
         uint32_t passes = 0;
-        ARCHON_TRY(rs::sort_pairs(s, sc, kA, vA, kB, vB, n1, 0x01u, &in_b, &passes, &c->launches));
+        ARCHON_TRY(rs::sort_pairs(s, sc, kA, vA, kB, vB, n1, 0x01u, &in_b, &passes));
         // (sort_pairs has left the digit histogram of byte 0 = the per-bucket counts in d_ghist[0..255])
         ARCHON_HIP_TRY(hipMemcpyAsync(d_count, sc.d_ghist, 256 * sizeof(uint32_t), hipMemcpyDeviceToDevice, s));
-        hipLaunchKernelGGL(k_scan257, dim3(1), dim3(64), 0, s, d_count, d_starts);
-        hipLaunchKernelGGL(fwd::k_lms_place, dim3(div_up(n1, 256)), dim3(256), 0, s, in_b ? kB : kA, in_b ? vB : vA, n1, d_starts, d_items);
+        ARCHON_LAUNCH(k_scan257, dim3(1), dim3(64), 0, s, d_count, d_starts);
+        ARCHON_LAUNCH(fwd::k_lms_place, dim3(div_up(n1, 256)), dim3(256), 0, s, in_b ? kB : kA, in_b ? vB : vA, n1, d_starts, d_items);
         ARCHON_HIP_TRY(hipGetLastError());
     }
     ARCHON_SYNC(s);
@@ -3519,11 +3494,11 @@ int archon_hip_radix_scatter_dev(const uint8_t *d_src, size_t n, uint8_t *d_dst,
     return with_ctx(dev, stream, [&](Ctx *c, hipStream_t s) -> int {
         uint32_t *d_counts = c->d_mail() + mail::kDevCounts.at, *d_starts = c->d_mail() + mail::kDevStarts.at;
         ARCHON_TRY(launch_hist256(s, d_src, n, d_counts, n));
-        hipLaunchKernelGGL(k_scan257, dim3(1), dim3(64), 0, s, d_counts, d_starts);
+        ARCHON_LAUNCH(k_scan257, dim3(1), dim3(64), 0, s, d_counts, d_starts);
         uint32_t grid = div_up(n, 256 * 16);
         if (grid < 1) grid = 1;
         if (grid > (uint32_t)kNumCU * 8) grid = kNumCU * 8;
-        hipLaunchKernelGGL(k_fill_runs, dim3(grid), dim3(256), 0, s, d_starts, d_dst, n);
+        ARCHON_LAUNCH(k_fill_runs, dim3(grid), dim3(256), 0, s, d_starts, d_dst, n);
         ARCHON_HIP_TRY(hipGetLastError());
         ARCHON_SYNC(s);
         return ARCHON_OK;

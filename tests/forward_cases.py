@@ -121,6 +121,8 @@ _NO_BREAK = {"ARCHON_NO_BREAK_ROUND": "1"}
 _NO_WRITER = {"ARCHON_NO_RANK_WRITER": "1"}
 _GROUP_16MI = {"ARCHON_NO_CHAINS": "1", "ARCHON_NO_CLOSED_FORM": "1"}
 _LSB = {"ARCHON_FORCE_PATH": "0"}
+_SMALL = {"ARCHON_SMALL_BLOCK": "-1"}
+PRIMER = "ARCHON_PRIMER"       # no route of the library: the block of CENSUS_BLOCKS that census_run sends ahead of the case instead of `primer`
 
 
 def _shape(shape, n):
@@ -147,6 +149,8 @@ CENSUS_BLOCKS = {
     "one_duplicate": lambda: _dup_cases()["one_duplicate"],
     "word_soup_5mi": lambda: _word_soup((5 << 20) + 12345, 7, 24, 14),
     "a_16mi": lambda: np.full(16 << 20, 97, np.uint8),
+    "dna_64ki": lambda: _shape("dna", 64 << 10),
+    "dna_64": lambda: _shape("dna", 64),
 }
 
 CENSUS_CASES = [
@@ -178,15 +182,27 @@ CENSUS_CASES = [
     ("writer_log-off", "word_soup_5mi", _NO_WRITER),
     ("writer_b_log", "a_16mi", _GROUP_16MI),
     ("writer_b_log-off", "a_16mi", dict(_GROUP_16MI, **_NO_WRITER)),
+    # first-stage routes: the product's small-block rule (the row sets SMALL_BLOCK back to the library's default itself), the closed
+    # form, and a poor alphabet on the streaming machinery -- found by the count that gives up, or shown first behind a dna primer
+    ("small-random", "random_64ki", _SMALL),
+    ("small-text", "text_64ki", _SMALL),
+    ("small-dna", "dna_64ki", _SMALL),
+    ("small-closed_form", "ab", _SMALL),
+    ("closed_form", "ab", {}),
+    ("dna_stream", "dna_64", {}),
+    ("dna_stream-hinted", "dna_64", {PRIMER: "dna_64"}),
 ]
 
 
 def census_run(archon, x, env, primer):
     """the statistics and the suffix array of one forward of x with the routes of env set for that call alone.  A forward of
     `primer` (CENSUS_BLOCKS["random_64ki"]) goes first: what a context remembers of its last block (a poor alphabet or a period
-    sends the next block to its alphabet first) is then the same whichever call came before, and so are the figures."""
+    sends the next block to its alphabet first) is then the same whichever call came before, and so are the figures.  A case
+    that is about that memory names its own primer (env[PRIMER])."""
     import os
-    archon.forward(primer, want_sa=False)
+    env = dict(env)
+    own = env.pop(PRIMER, None)
+    archon.forward(CENSUS_BLOCKS[own]() if own else primer, want_sa=False)
     saved = {k: os.environ.get(k) for k in env}
     os.environ.update(env)
     try:

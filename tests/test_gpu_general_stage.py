@@ -18,7 +18,15 @@ Where the branches were found, on the parent:
     route of the tests: the shortcut settles every tied row of the first, and takes none of the second (its period's defects
     go to the break rounds).  Both stay, pinned, as what they are; the recount is reached by archon_synth's random block with
     a copy (64 Ki, 7-pass route) and by _dup_cases()["duplicate_behind_runs"].
-  * the group of 16 Mi rows reaches the rank writer's B log as it stands (seg_big_items >= n, 268 launches against 174)."""
+  * the group of 16 Mi rows reaches the rank writer's B log as it stands (seg_big_items >= n, 268 launches against 174).
+
+The last seven cases pin first-stage routes instead: the product's small-block rule (the row sets SMALL_BLOCK back to the library's
+default), the closed form with its nested transform, and a block of four distinct bytes on the streaming machinery, found by the
+count that gives up or -- behind a primer of its own -- shown by the presence map first.  Their figures are the library's at the
+commit before the one that counts launches where they are made (profiles/launch_count/census_parent.txt and
+census_parent_second_process.txt: two processes, every field of every case agreed, none is left out).  A dna block takes the
+packed streaming stage at every size that was tried, from 64 bytes (the case) to 1 MiB; from 64 Ki on the period probe adds its
+three launches (29 and 17 instead of 26 and 14)."""
 import pytest
 
 import forward_cases as F
@@ -57,7 +65,15 @@ PINNED = {
     "writer_log-off":              (0, 7, 84, 19, 0, 5, 0, 0, 0, 0, 0, 9120122, 5579314, 5255212, 21626139),
     "writer_b_log":                (1, 2, 268, 54, 0, 23, 0, 0, 0, 0, 0, 0, 369098777, 16777215, 369098777),
     "writer_b_log-off":            (1, 2, 174, 54, 0, 23, 0, 0, 0, 0, 0, 0, 369098777, 16777215, 369098777),
+    "small-random":                (0, 3, 11, 4, 1, 0, 0, 0, 0, 0, 0, 0, 0, 252, 252),
+    "small-text":                  (0, 7, 15, 4, 1, 0, 0, 0, 0, 0, 0, 0, 0, 10, 10),
+    "small-dna":                   (0, 7, 14, 5, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0),
+    "small-closed_form":           (2, 0, 33, 6, 0, 0, 0, 0, 2, 300000, 0, 0, 0, 0, 0),
+    "closed_form":                 (2, 0, 44, 6, 0, 0, 0, 0, 2, 300000, 0, 0, 0, 0, 0),
+    "dna_stream":                  (1, 2, 26, 4, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0),
+    "dna_stream-hinted":           (1, 2, 14, 3, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0),
 }
+_LAUNCHES = F.CENSUS_FIELDS.index("kernel_launches")
 
 _tied_rounds = lambda st: st["text_rounds"] + st["doubling_rounds"]
 _breaks = lambda st, n: st["break_rounds"] >= 1 and st["break_settled"] > 0
@@ -65,6 +81,8 @@ _no_breaks = lambda st, n: st["break_rounds"] == 0 and st["period"] > 0
 _mid_and_big = lambda st, n: st["mid_items"] > 0 and st["seg_big_items"] > 0
 _recount = lambda st, n: 0 < st["chain_items"] < st["unresolved_initial"] and _tied_rounds(st) > 0
 _s_text_rounds = lambda st, n: st["text_rounds"] > 0 and st["mid_items"] == 0 and st["seg_big_items"] == 0
+_closed = lambda st, n: st["path"] == 2 and st["period"] == 2 and st["chain_items"] == n
+_packed_stream = lambda st, n: st["path"] == 1 and st["alphabet_bits"] == 2
 WITNESS = {
     "nothing_tied": lambda st, n: st["text_rounds"] == st["doubling_rounds"] == 0,
     "text_rounds": _s_text_rounds,
@@ -91,6 +109,16 @@ WITNESS = {
     "writer_log-off": lambda st, n: n >= 1 << 22,
     "writer_b_log": lambda st, n: st["seg_big_items"] >= n,
     "writer_b_log-off": lambda st, n: st["seg_big_items"] >= n,
+    # the small-block rule: no streaming stage (path 0 on blocks that take it otherwise); the shallow key depth comes from the
+    # byte count's histogram alone; the closed form behind a byte count makes fewer launches than behind the streaming stage
+    "small-random": lambda st, n: st["path"] == 0 and 0 < st["radix_passes"] < 7 and st["alphabet_bits"] == 0,
+    "small-text": lambda st, n: st["path"] == 0 and st["alphabet_bits"] == 0,
+    "small-dna": lambda st, n: st["path"] == 0 and st["alphabet_bits"] == 2,
+    "small-closed_form": lambda st, n: _closed(st, n) and st["kernel_launches"] < PINNED["closed_form"][_LAUNCHES],
+    "closed_form": lambda st, n: _closed(st, n) and st["kernel_launches"] > PINNED["small-closed_form"][_LAUNCHES],
+    # the first attempt (count, streaming stage, round trip) is what the hint saves
+    "dna_stream": lambda st, n: _packed_stream(st, n) and st["kernel_launches"] > PINNED["dna_stream-hinted"][_LAUNCHES],
+    "dna_stream-hinted": lambda st, n: _packed_stream(st, n) and st["kernel_launches"] < PINNED["dna_stream"][_LAUNCHES],
 }
 
 
