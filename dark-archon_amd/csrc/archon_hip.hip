@@ -23,6 +23,7 @@
 #include "fm_host.hiph"
 #include "repeats.hiph"
 #include "lz.hiph"
+#include "kmers.hiph"
 
 #include <stdarg.h>
 #include <atomic>
@@ -97,6 +98,7 @@ static thread_local LastStats<archon_hip_fm_text_stats> t_fmt_stats;    // text 
 static thread_local LastStats<archon_hip_fm_doc_stats> t_fmd_stats;     // documents calls: attach_docs, docs, docs_ranges, doc_of
 static thread_local LastStats<archon_hip_repeat_stats> t_rep_stats;     // repeats calls
 static thread_local LastStats<archon_hip_lz_stats> t_lz_stats;          // LZ calls: lpf, lz_parse, block_lz
+static thread_local LastStats<archon_hip_kmer_stats> t_kmer_stats;      // k-mer calls: kmers, kmer_occ, sus
 
 // The record of one FM call: kept for the calling thread when the scope ends, on whichever path the call leaves it, with the
 // host waits and the kernel launches since the scope began.  A record that covers less than its call takes its launches
@@ -2051,6 +2053,117 @@ int archon_hip_get_lz_stats(int dev, archon_hip_lz_stats *out)
     return t_lz_stats.get(dev, out, "LZ call");
 }
 
+// ---- k-mers, per-position counts and shortest unique substrings (kmers.hiph: the kernels and their drivers; here the argument
+// checks and the statistics).  *total is written whenever it is given: 0 before any refusal
+static int kmers_check(const void *sa, const void *lcp, uint64_t *total, uint32_t n, uint32_t k, const void *hist, uint32_t bins)
+{
+    if (total) *total = 0;
+    if (!sa || !lcp || !total) { set_error("null pointer"); return ARCHON_E_ARG; }
+    ARCHON_TRY(check_n(n));
+    return kmer_check_args(k, hist, bins);
+}
+
+int archon_hip_kmers_dev(const uint32_t *d_sa, const uint32_t *d_lcp, uint32_t n, uint32_t k, uint32_t min_occ, uint32_t max_occ,
+                         archon_hip_kmer *d_out_or_null, uint64_t cap, uint64_t *total, uint32_t *d_hist_or_null, uint32_t bins, int dev, void *stream)
+{
+    ARCHON_TRY(kmers_check(d_sa, d_lcp, total, n, k, d_hist_or_null, bins));
+    return with_ctx(dev, stream, [&](Ctx *c, hipStream_t s) -> int {
+        KeepStats<archon_hip_kmer_stats> keep(t_kmer_stats, dev);
+        kmer_call_stats(&keep.st, n, k, min_occ, max_occ, bins, 0);
+        KmerCall q = {d_sa, d_lcp, n, k, min_occ, max_occ, bins};
+        return kmer_list(c, s, q, d_out_or_null, cap, total, d_hist_or_null, false, &keep.st);
+    });
+}
+
+// sa and lcp of host buffers through staging buffers 0 and 1
+static int kmer_stage(Ctx *c, hipStream_t s, const uint32_t *sa, const uint32_t *lcp, uint32_t n, uint32_t **d_sa, uint32_t **d_lcp)
+{
+    ARCHON_TRY(ctx_io(c, 0, (size_t)n * 4 + 64, (void **)d_sa));
+    ARCHON_TRY(ctx_io(c, 1, (size_t)n * 4 + 64, (void **)d_lcp));
+    ARCHON_HIP_TRY(hipMemcpyAsync(*d_sa, sa, (size_t)n * 4, hipMemcpyHostToDevice, s));
+    ARCHON_HIP_TRY(hipMemcpyAsync(*d_lcp, lcp, (size_t)n * 4, hipMemcpyHostToDevice, s));
+    return ARCHON_OK;
+}
+
+int archon_hip_kmers(const uint32_t *sa, const uint32_t *lcp, uint32_t n, uint32_t k, uint32_t min_occ, uint32_t max_occ, archon_hip_kmer *out_or_null,
+                     uint64_t cap, uint64_t *total, uint32_t *hist_or_null, uint32_t bins, int dev)
+{
+    ARCHON_TRY(kmers_check(sa, lcp, total, n, k, hist_or_null, bins));
+    return with_ctx(dev, nullptr, [&](Ctx *c, hipStream_t s) -> int {
+        KeepStats<archon_hip_kmer_stats> keep(t_kmer_stats, dev);
+        kmer_call_stats(&keep.st, n, k, min_occ, max_occ, bins, 0);
+        uint32_t *d_sa = nullptr, *d_lcp = nullptr;
+        ARCHON_TRY(kmer_stage(c, s, sa, lcp, n, &d_sa, &d_lcp));
+        KmerCall q = {d_sa, d_lcp, n, k, min_occ, max_occ, bins};
+        return kmer_list(c, s, q, out_or_null, cap, total, hist_or_null, true, &keep.st);
+    });
+}
+
+static int kmer_occ_check(const void *sa, const void *lcp, const void *occ, uint32_t n, uint32_t k)
+{
+    if (!sa || !lcp || !occ) { set_error("null pointer"); return ARCHON_E_ARG; }
+    ARCHON_TRY(check_n(n));
+    return kmer_check_args(k, nullptr, 0);
+}
+
+int archon_hip_kmer_occ_dev(const uint32_t *d_sa, const uint32_t *d_lcp, uint32_t n, uint32_t k, uint32_t *d_occ, int dev, void *stream)
+{
+    ARCHON_TRY(kmer_occ_check(d_sa, d_lcp, d_occ, n, k));
+    return with_ctx(dev, stream, [&](Ctx *c, hipStream_t s) -> int {
+        KeepStats<archon_hip_kmer_stats> keep(t_kmer_stats, dev);
+        kmer_call_stats(&keep.st, n, k, 0, 0, 0, 1);
+        KmerCall q = {d_sa, d_lcp, n, k};
+        return kmer_occ_run(c, s, q, d_occ, false, &keep.st);
+    });
+}
+
+int archon_hip_kmer_occ(const uint32_t *sa, const uint32_t *lcp, uint32_t n, uint32_t k, uint32_t *occ, int dev)
+{
+    ARCHON_TRY(kmer_occ_check(sa, lcp, occ, n, k));
+    return with_ctx(dev, nullptr, [&](Ctx *c, hipStream_t s) -> int {
+        KeepStats<archon_hip_kmer_stats> keep(t_kmer_stats, dev);
+        kmer_call_stats(&keep.st, n, k, 0, 0, 0, 1);
+        uint32_t *d_sa = nullptr, *d_lcp = nullptr;
+        ARCHON_TRY(kmer_stage(c, s, sa, lcp, n, &d_sa, &d_lcp));
+        KmerCall q = {d_sa, d_lcp, n, k};
+        return kmer_occ_run(c, s, q, occ, true, &keep.st);
+    });
+}
+
+static int sus_check(const void *sa, const void *lcp, const void *sus, uint32_t n)
+{
+    if (!sa || !lcp || !sus) { set_error("null pointer"); return ARCHON_E_ARG; }
+    return check_n(n);
+}
+
+int archon_hip_sus_dev(const uint32_t *d_sa, const uint32_t *d_lcp, uint32_t n, uint32_t *d_sus, int dev, void *stream)
+{
+    ARCHON_TRY(sus_check(d_sa, d_lcp, d_sus, n));
+    return with_ctx(dev, stream, [&](Ctx *c, hipStream_t s) -> int {
+        KeepStats<archon_hip_kmer_stats> keep(t_kmer_stats, dev);
+        kmer_call_stats(&keep.st, n, 0, 0, 0, 0, 2);
+        return kmer_sus_run(c, s, d_sa, d_lcp, n, d_sus, false, &keep.st);
+    });
+}
+
+int archon_hip_sus(const uint32_t *sa, const uint32_t *lcp, uint32_t n, uint32_t *sus, int dev)
+{
+    ARCHON_TRY(sus_check(sa, lcp, sus, n));
+    return with_ctx(dev, nullptr, [&](Ctx *c, hipStream_t s) -> int {
+        KeepStats<archon_hip_kmer_stats> keep(t_kmer_stats, dev);
+        kmer_call_stats(&keep.st, n, 0, 0, 0, 0, 2);
+        uint32_t *d_sa = nullptr, *d_lcp = nullptr;
+        ARCHON_TRY(kmer_stage(c, s, sa, lcp, n, &d_sa, &d_lcp));
+        return kmer_sus_run(c, s, d_sa, d_lcp, n, sus, true, &keep.st);
+    });
+}
+
+int archon_hip_get_kmer_stats(int dev, archon_hip_kmer_stats *out)
+{
+    if (!out) { set_error("null pointer"); return ARCHON_E_ARG; }
+    return t_kmer_stats.get(dev, out, "k-mer call");
+}
+
 // ---- the FM index (fm_host.hiph: the handle and every driver; here the argument checks and the statistics)
 int archon_hip_fm_create(const uint8_t *bwt, uint32_t n, uint32_t base_id, int dev, archon_hip_fm **out)
 {
@@ -2845,6 +2958,55 @@ int archon_hip_block_lz(archon_hip_block *b, uint32_t dir, archon_hip_lpf_rec *l
         if (lpf_or_null) ARCHON_HIP_TRY(hipMemcpyAsync(lpf_or_null, d_lpf, (size_t)b->n * 8, hipMemcpyDeviceToHost, s));
         ParseCall q = {reinterpret_cast<const uint32_t *>(d_lpf), b->n};
         return parse_to_host(c, s, tm, q, out_or_null, cap, total, &keep.st);     // (its count waits for the stream: the records have arrived)
+    });
+}
+
+// the LCP array into staging buffer 1 and, with the resident suffix array, into the k-mer passes; the results through buffer 2
+int archon_hip_block_kmers(archon_hip_block *b, uint32_t k, uint32_t min_occ, uint32_t max_occ, archon_hip_kmer *out_or_null, uint64_t cap, uint64_t *total,
+                           uint32_t *hist_or_null, uint32_t bins)
+{
+    if (total) *total = 0;
+    if (!b || !total) { set_error("null pointer"); return ARCHON_E_ARG; }
+    ARCHON_TRY(kmer_check_args(k, hist_or_null, bins));
+    std::lock_guard<std::mutex> lkb(b->mu);
+    ARCHON_TRY(block_check(b, true));
+    return with_ctx(b->dev, nullptr, [&](Ctx *c, hipStream_t s) -> int {
+        KeepStats<archon_hip_kmer_stats> keep(t_kmer_stats, b->dev);
+        kmer_call_stats(&keep.st, b->n, k, min_occ, max_occ, bins, 0);
+        uint32_t *d_lcp = nullptr;
+        ARCHON_TRY(block_lcp_step(c, s, b, &d_lcp, &keep.st.ms_lcp));
+        KmerCall q = {b->d_sa(), d_lcp, b->n, k, min_occ, max_occ, bins};
+        return kmer_list(c, s, q, out_or_null, cap, total, hist_or_null, true, &keep.st);
+    });
+}
+
+int archon_hip_block_kmer_occ(archon_hip_block *b, uint32_t k, uint32_t *occ)
+{
+    if (!b || !occ) { set_error("null pointer"); return ARCHON_E_ARG; }
+    ARCHON_TRY(kmer_check_args(k, nullptr, 0));
+    std::lock_guard<std::mutex> lkb(b->mu);
+    ARCHON_TRY(block_check(b, true));
+    return with_ctx(b->dev, nullptr, [&](Ctx *c, hipStream_t s) -> int {
+        KeepStats<archon_hip_kmer_stats> keep(t_kmer_stats, b->dev);
+        kmer_call_stats(&keep.st, b->n, k, 0, 0, 0, 1);
+        uint32_t *d_lcp = nullptr;
+        ARCHON_TRY(block_lcp_step(c, s, b, &d_lcp, &keep.st.ms_lcp));
+        KmerCall q = {b->d_sa(), d_lcp, b->n, k};
+        return kmer_occ_run(c, s, q, occ, true, &keep.st);
+    });
+}
+
+int archon_hip_block_sus(archon_hip_block *b, uint32_t *sus)
+{
+    if (!b || !sus) { set_error("null pointer"); return ARCHON_E_ARG; }
+    std::lock_guard<std::mutex> lkb(b->mu);
+    ARCHON_TRY(block_check(b, true));
+    return with_ctx(b->dev, nullptr, [&](Ctx *c, hipStream_t s) -> int {
+        KeepStats<archon_hip_kmer_stats> keep(t_kmer_stats, b->dev);
+        kmer_call_stats(&keep.st, b->n, 0, 0, 0, 0, 2);
+        uint32_t *d_lcp = nullptr;
+        ARCHON_TRY(block_lcp_step(c, s, b, &d_lcp, &keep.st.ms_lcp));
+        return kmer_sus_run(c, s, b->d_sa(), d_lcp, b->n, sus, true, &keep.st);
     });
 }
 
@@ -3728,6 +3890,14 @@ int archon_hip_test_route(const char *name, long value)
             return ARCHON_E_ARG;
         }
         g_route.lz_tile = (int)value;
+        return ARCHON_OK;
+    }
+    if (!strcmp(name, "KMER_TILE")) {
+        if (value && (value < (long)kmer::kMinTile || value > (long)kmer::kDefaultTile || (value & (value - 1)))) {
+            set_error("KMER_TILE=%ld: not a power of two in [%u, %u]", value, kmer::kMinTile, kmer::kDefaultTile);
+            return ARCHON_E_ARG;
+        }
+        g_route.kmer_tile = (int)value;
         return ARCHON_OK;
     }
     if (!strcmp(name, "MS_CHUNK")) {

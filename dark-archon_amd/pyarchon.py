@@ -51,6 +51,8 @@ SYMBOLS = [
     "archon_hip_fm_docs_ranges", "archon_hip_fm_docs_ranges_dev", "archon_hip_fm_doc_of", "archon_hip_fm_doc_of_dev", "archon_hip_get_fm_doc_stats",
     "archon_hip_repeats", "archon_hip_repeats_dev", "archon_hip_block_repeats", "archon_hip_get_repeat_stats",
     "archon_hip_lpf", "archon_hip_lpf_dev", "archon_hip_lz_parse", "archon_hip_lz_parse_dev", "archon_hip_block_lz", "archon_hip_get_lz_stats",
+    "archon_hip_kmers", "archon_hip_kmers_dev", "archon_hip_block_kmers", "archon_hip_kmer_occ", "archon_hip_kmer_occ_dev", "archon_hip_block_kmer_occ",
+    "archon_hip_sus", "archon_hip_sus_dev", "archon_hip_block_sus", "archon_hip_get_kmer_stats",
 ]
 
 # archon_hip_fm_hit: one distinct string within the distance of a pattern (FmIndex.approx, Block.fm_approx)
@@ -69,6 +71,8 @@ LPF = np.dtype([("len", "<u4"), ("src", "<u4")])
 PHRASE = np.dtype([("end", "<u4"), ("len", "<u4"), ("src", "<u4")])
 # one phrase of lz77(): it starts at z[pos] and copies len bytes from z[src] (len 0: the literal z[pos])
 LZ77 = np.dtype([("pos", "<u4"), ("len", "<u4"), ("src", "<u4")])
+# archon_hip_kmer: one k-mer of a block (kmers, Block.kmers): rows [lo, hi) of its occurrences, item = sa[lo]: the bytes x[item-k .. item)
+KMER = np.dtype([("lo", "<u4"), ("hi", "<u4"), ("item", "<u4")])
 
 
 class Stats(ctypes.Structure):
@@ -257,6 +261,21 @@ class LzStats(ctypes.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_}
 
 
+class KmerStats(ctypes.Structure):
+    """archon_hip_kmer_stats: the calling thread's last k-mer call (kmers, kmer_occ, sus) on a device"""
+    _fields_ = [
+        ("n", ctypes.c_uint32), ("k", ctypes.c_uint32), ("min_occ", ctypes.c_uint32), ("max_occ", ctypes.c_uint32),
+        ("bins", ctypes.c_uint32), ("tile", ctypes.c_uint32), ("what", ctypes.c_uint32), ("kernel_launches", ctypes.c_uint32),
+        ("host_syncs", ctypes.c_uint32), ("most", ctypes.c_uint32),
+        ("groups", ctypes.c_uint64), ("short_rows", ctypes.c_uint64), ("distinct", ctypes.c_uint64), ("kmers", ctypes.c_uint64),
+        ("occurrences", ctypes.c_uint64), ("unique", ctypes.c_uint64),
+        ("ms_lcp", ctypes.c_float), ("ms_count", ctypes.c_float), ("ms_emit", ctypes.c_float), ("ms_scatter", ctypes.c_float),
+    ]
+
+    def asdict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
 class ArchonError(RuntimeError):
     def __init__(self, code, msg):
         super().__init__("archon_hip error %d: %s" % (code, msg))
@@ -391,6 +410,16 @@ def load():
         "archon_hip_lz_parse_dev": [vp, u32, vp, ctypes.c_uint64, vp, i32, vp],
         "archon_hip_block_lz": [vp, u32, vp, vp, ctypes.c_uint64, vp],
         "archon_hip_get_lz_stats": [i32, ctypes.POINTER(LzStats)],
+        "archon_hip_kmers": [vp, vp, u32, u32, u32, u32, vp, ctypes.c_uint64, vp, vp, u32, i32],
+        "archon_hip_kmers_dev": [vp, vp, u32, u32, u32, u32, vp, ctypes.c_uint64, vp, vp, u32, i32, vp],
+        "archon_hip_block_kmers": [vp, u32, u32, u32, vp, ctypes.c_uint64, vp, vp, u32],
+        "archon_hip_kmer_occ": [vp, vp, u32, u32, vp, i32],
+        "archon_hip_kmer_occ_dev": [vp, vp, u32, u32, vp, i32, vp],
+        "archon_hip_block_kmer_occ": [vp, u32, vp],
+        "archon_hip_sus": [vp, vp, u32, vp, i32],
+        "archon_hip_sus_dev": [vp, vp, u32, vp, i32, vp],
+        "archon_hip_block_sus": [vp, vp],
+        "archon_hip_get_kmer_stats": [i32, ctypes.POINTER(KmerStats)],
     }.items():
         fn = getattr(lib, name)
         fn.argtypes = args
@@ -415,7 +444,7 @@ _ROUTE_NAMES = ("FORCE_PATH", "SMALL_BLOCK", "PASS_RANGES", "INV_ROWS", "INV_SLA
                 "NO_PACK", "NO_PACK_STREAM", "NO_PAIR_CHAINS", "NO_PERIOD_HINT", "NO_BREAK_ROUND", "NO_PERIOD_PROBE", "NO_PERIOD_STREAM", "NO_PROBE",
                 "NO_RANK_WRITER", "NO_TEXT_ROUNDS", "NO_MID", "NO_SHALLOW", "NO_CLOSED_FORM", "NO_REL_RECORDS", "ALIGNED_MIN", "REL_MIN_SEG", "KEY_BYTES",
                 "LCP_CAP", "LCP_WINDOW", "FM_SUB_ROWS", "FM_SUPER_ROWS", "FM_SAMPLE_WALK", "REP_FAN", "LZ_FAN", "LZ_TILE", "MS_CHUNK",
-                "EDIT_TILE", "EDIT_BATCH", "DOC_TILE")
+                "EDIT_TILE", "EDIT_BATCH", "DOC_TILE", "KMER_TILE")
 
 
 def _sync_routes(L):
@@ -726,6 +755,83 @@ def lz77(z, dev=0):
     out["len"] = ph["len"]
     out["src"] = np.where(ph["len"] > 0, n - ph["src"], 0)
     return out
+
+
+def kmer_stats(dev=0):
+    """KmerStats of the calling thread's last k-mer call (kmers, kmer_occ, sus) on dev"""
+    s = KmerStats()
+    _check(lib().archon_hip_get_kmer_stats(dev, ctypes.byref(s)))
+    return s
+
+
+def _kmers(call, count_only, bins):
+    """call(out pointer or None, cap, total pointer, hist pointer or None, bins) -> rc: the count, or the k-mers in an array of
+    the size a first call gave; with bins the pair (that result, the histogram).  Both calls take the histogram, so that the
+    call's record (kmer_stats) is that of the call the user made"""
+    total = ctypes.c_uint64(0)
+    tp = ctypes.cast(ctypes.byref(total), ctypes.c_void_p)
+    hist = np.zeros(bins, np.uint32) if bins else None
+    _check(call(None, 0, tp, _p(hist) if bins else None, bins))
+    if count_only:
+        got = total.value
+    else:
+        got = np.zeros(total.value, KMER)
+        if total.value:
+            _check(call(_p(got), got.size, tp, _p(hist) if bins else None, bins))
+    return (got, hist) if bins else got
+
+
+def _sa_lcp(what, sa, lcp):
+    sa = np.ascontiguousarray(sa, dtype=np.uint32)
+    lcp = np.ascontiguousarray(lcp, dtype=np.uint32)
+    if sa.size != lcp.size:
+        raise ValueError("%s: sa has %d rows, lcp %d" % (what, sa.size, lcp.size))
+    return sa, lcp
+
+
+def kmers(sa, lcp, k, min_occ=1, max_occ=0, count_only=False, bins=0, dev=0):
+    """the k-mers of a block from its suffix array and LCP array (include/archon_hip.h: archon_hip_kmers): a KMER array in
+    ascending row, those with min_occ <= hi - lo <= max_occ (0: no limit), or their number with count_only; with bins the pair
+    (that, hist): hist[c] = distinct k-mers with c occurrences, the last bin those with at least bins - 1 -- over ALL k-mers"""
+    sa, lcp = _sa_lcp("kmers", sa, lcp)
+    fn = lib().archon_hip_kmers
+    return _kmers(lambda out, cap, tp, hp, nb: fn(_p(sa), _p(lcp), sa.size, int(k), int(min_occ), int(max_occ), out, cap, tp, hp, nb, dev),
+                  count_only, int(bins))
+
+
+def kmer_occ(sa, lcp, k, dev=0):
+    """occ[p], p in 0 .. n-k: the number of occurrences of x[p .. p+k) in x (archon_hip_kmer_occ); empty when k > n"""
+    sa, lcp = _sa_lcp("kmer_occ", sa, lcp)
+    words = max(sa.size - int(k) + 1, 0)
+    out = np.zeros(max(words, 1), np.uint32)
+    _check(lib().archon_hip_kmer_occ(_p(sa), _p(lcp), sa.size, int(k), _p(out), dev))
+    return out[:words]
+
+
+def sus(sa, lcp, dev=0):
+    """sus[e-1]: the length of the shortest substring ending at item e that occurs once, 0 when there is none (archon_hip_sus)"""
+    sa, lcp = _sa_lcp("sus", sa, lcp)
+    out = np.zeros(sa.size, np.uint32)
+    _check(lib().archon_hip_sus(_p(sa), _p(lcp), sa.size, _p(out), dev))
+    return out
+
+
+def kmer_bytes(x, recs, k):
+    """the bytes of KMER records of the block x: a uint8 array of recs.size rows of k bytes, x[item-k .. item) each (no device)"""
+    x = np.frombuffer(x, np.uint8) if isinstance(x, (bytes, bytearray)) else np.ascontiguousarray(x, dtype=np.uint8)
+    recs = np.ascontiguousarray(recs, KMER)
+    k = int(k)
+    if recs.size and (int(recs["item"].min()) < k or int(recs["item"].max()) > x.size):
+        raise ValueError("kmer_bytes: an item outside %d..%d" % (k, x.size))
+    return x[(recs["item"].astype(np.int64) - k)[:, None] + np.arange(k, dtype=np.int64)[None, :]]
+
+
+def _kmers_as_mems(recs, k):
+    """KMER records as the FM_MEM records the locate calls take: rows [lo, hi) of a piece of k bytes"""
+    recs = np.ascontiguousarray(recs, KMER)
+    mems = np.zeros(recs.size, FM_MEM)
+    mems["lo"], mems["hi"], mems["end"] = recs["lo"], recs["hi"], int(k)
+    return mems
 
 
 def _as_mems(reps):
@@ -1232,6 +1338,11 @@ class FmIndex:
         list of uint32 arrays, one per repeat, each in row order"""
         return _locate_mems(lib().archon_hip_fm_locate_mems, self.h, _as_mems(reps))
 
+    def locate_kmers(self, recs, k):
+        """the starts of every k-mer's occurrences (KMER records of the block this index was made from) from the samples: a list
+        of uint32 arrays, one per k-mer, each in row order"""
+        return _locate_mems(lib().archon_hip_fm_locate_mems, self.h, _kmers_as_mems(recs, k))
+
     def extract(self, starts, lengths):
         """x[starts[j] .. starts[j] + lengths[j]) for every j: a list of uint8 arrays"""
         starts = np.ascontiguousarray(starts, dtype=np.uint32).ravel()
@@ -1400,6 +1511,30 @@ class Block:
         """the starts of every repeat's occurrences from the resident SA: a list of uint32 arrays, one per repeat, in row order"""
         return _locate_mems(lib().archon_hip_block_fm_locate_mems, self.h, _as_mems(reps))
 
+    def kmers(self, k, min_occ=1, max_occ=0, count_only=False, bins=0):
+        """the k-mers of the resident block (needs forward(want_sa=True)): its LCP array is made and consumed on the device.
+        A KMER array in ascending row, or their number with count_only; with bins the pair (that, the histogram of ALL k-mers)"""
+        fn = lib().archon_hip_block_kmers
+        return _kmers(lambda out, cap, tp, hp, nb: fn(self.h, int(k), int(min_occ), int(max_occ), out, cap, tp, hp, nb), count_only, int(bins))
+
+    def kmer_occ(self, k):
+        """occ[p], p in 0 .. n-k: the number of occurrences of x[p .. p+k) in the resident block (needs forward(want_sa=True))"""
+        words = max(self.n - int(k) + 1, 0)
+        out = np.zeros(max(words, 1), np.uint32)
+        _check(lib().archon_hip_block_kmer_occ(self.h, int(k), _p(out)))
+        return out[:words]
+
+    def sus(self):
+        """sus[e-1]: the length of the shortest substring ending at item e of the resident block that occurs once, 0 when there
+        is none (needs forward(want_sa=True))"""
+        out = np.zeros(self.n, np.uint32)
+        _check(lib().archon_hip_block_sus(self.h, _p(out)))
+        return out
+
+    def locate_kmers(self, recs, k):
+        """the starts of every k-mer's occurrences from the resident SA: a list of uint32 arrays, one per k-mer, in row order"""
+        return _locate_mems(lib().archon_hip_block_fm_locate_mems, self.h, _kmers_as_mems(recs, k))
+
     def lz(self, dir=0, want_lpf=False, count_only=False):
         """the LZ77 parse of the resident block (needs forward(want_sa=True)): its LCP array and its LPF records are made and
         consumed on the device.  A PHRASE array in chain order (the phrase ending at n first), or the number of phrases with
@@ -1507,6 +1642,33 @@ def lz_parse_dev(lpf_t, out_t=None):
     _check(lib().archon_hip_lz_parse_dev(ctypes.c_void_p(lpf_t.data_ptr()), lpf_t.numel() // 2, ctypes.c_void_p(out_t.data_ptr()) if out_t is not None else None,
                                          cap, ctypes.cast(ctypes.byref(total), ctypes.c_void_p), dev, _stream_ptr()))
     return total.value
+
+
+def kmers_dev(sa_t, lcp_t, k, min_occ=1, max_occ=0, out_t=None, hist_t=None):
+    """torch CUDA tensors: sa and lcp int32[n], out an int32 tensor of 3 words per k-mer or None (counting only), hist an int32
+    tensor of 2 .. 4096 bins or None; on the current stream.  Returns the number of k-mers (raises when out_t holds fewer)"""
+    dev = sa_t.device.index or 0
+    total = ctypes.c_uint64(0)
+    cap = out_t.numel() // 3 if out_t is not None else 0
+    _check(lib().archon_hip_kmers_dev(ctypes.c_void_p(sa_t.data_ptr()), ctypes.c_void_p(lcp_t.data_ptr()), sa_t.numel(), int(k), int(min_occ), int(max_occ),
+                                      ctypes.c_void_p(out_t.data_ptr()) if out_t is not None else None, cap, ctypes.cast(ctypes.byref(total), ctypes.c_void_p),
+                                      ctypes.c_void_p(hist_t.data_ptr()) if hist_t is not None else None, hist_t.numel() if hist_t is not None else 0,
+                                      dev, _stream_ptr()))
+    return total.value
+
+
+def kmer_occ_dev(sa_t, lcp_t, k, occ_t):
+    """torch CUDA tensors: sa and lcp int32[n], occ int32[n - k + 1] (written); on the current stream"""
+    dev = sa_t.device.index or 0
+    _check(lib().archon_hip_kmer_occ_dev(ctypes.c_void_p(sa_t.data_ptr()), ctypes.c_void_p(lcp_t.data_ptr()), sa_t.numel(), int(k),
+                                         ctypes.c_void_p(occ_t.data_ptr()), dev, _stream_ptr()))
+
+
+def sus_dev(sa_t, lcp_t, sus_t):
+    """torch CUDA tensors: sa and lcp int32[n], sus int32[n] (written); on the current stream"""
+    dev = sa_t.device.index or 0
+    _check(lib().archon_hip_sus_dev(ctypes.c_void_p(sa_t.data_ptr()), ctypes.c_void_p(lcp_t.data_ptr()), sa_t.numel(), ctypes.c_void_p(sus_t.data_ptr()),
+                                    dev, _stream_ptr()))
 
 
 def validate_resident_dev(x_t, sa_t, bwt_t, base_id):

@@ -24,6 +24,8 @@
  *                           that occurs, and its rows -- with the block's LCP array beside the index (archon_hip_fm_attach_lcp)
  *   archon_hip_repeats*     nothing: the LCP intervals, maximal and supermaximal repeats of a block from its LCP array and BWT
  *   archon_hip_lpf*, _lz_*  nothing: the longest previous factor of every item and the LZ77 parse, from the SA and LCP array
+ *   archon_hip_kmers*, _kmer_occ*, _sus*   nothing: the k-mers of a block with their counts, the count of the k-mer at every
+ *                           position and the shortest unique substring ending at every item, from the SA and LCP array
  *
  * Ordering convention ("a7 order"): item s in 1..N names the
  * reversed prefix x[s-1],x[s-2],...,x[0],INF with INF > 255; sa[0..N) lists the
@@ -934,6 +936,102 @@ typedef struct archon_hip_lz_stats {
     float ms_emit;              /* device time of the scan and the emit pass */
 } archon_hip_lz_stats;
 int  archon_hip_get_lz_stats(int dev, archon_hip_lz_stats *out);
+
+/* ---- the k-mers of a block: their counts, the count at every position, the shortest unique substrings (no counterpart in the
+ * reference) ----------------------------------------------------------------------------------------------------------------
+ * What a caller asks of a suffix-sorted block first: how often does each k-mer occur?  Which k-mers exist and with what counts
+ * (the spectrum), how often the k-mer at each text position occurs (the mappability track of genomics), and which substrings
+ * are unique -- seed selection, error thresholds, repeat masking, unique markers.  All of it follows from sa and lcp in a few
+ * streaming passes, with no search structure.  Rows, items, sa, lcp and a7 order are those above: row r holds item sa[r] in
+ * 1..n, the key of item s is x[s-1], x[s-2], ..., x[0], INF; lcp[0] is taken as 0 whatever it holds, and lcp[n] as 0.
+ * k-mer groups, for k >= 1: row i STARTS A GROUP when i == 0 or lcp[i] < k; group g is the rows [starts[g], starts[g+1]), with n
+ * after the last group.  A group is a k-mer exactly when sa[lo] >= k: then all its rows hold the string w = x[e-k .. e), e =
+ * sa[r]; [lo, hi) is what archon_hip_fm_count(w) returns, and the occurrences start at sa[r] - k.  A group with sa[lo] < k is a
+ * single SHORT ROW, whose key ends in INF before k symbols: there are exactly min(k - 1, n) of them.  k > n gives no k-mers;
+ * k = 0 is ARCHON_E_ARG.  Output order is ascending row: ascending order of the reversed k-mer, a7 order.
+ * Example "banana" (sa = 2 4 6 1 3 5, lcp = 0 1 3 0 0 2), as (lo, hi, item): k = 1 gives (0,3,2) "a", (3,4,1) "b", (4,6,3) "n";
+ * k = 2 gives (0,1,2) "ba", (1,3,4) "na", (4,6,3) "an" (a7 order: by the reversed bytes ab, an, na); k = 3 gives (1,3,4) "ana", (4,5,3) "ban", (5,6,5) "nan", rows 0 and 3
+ * being short.
+ * Filters: min_occ <= hi - lo <= max_occ is kept; min_occ 0 behaves as 1, max_occ 0 means no limit.  They change the output and
+ * the `kmers` and `occurrences` counters only.
+ * Histogram: hist[c], c in 1 .. bins-1, is the number of distinct k-mers with exactly c occurrences; the last bin holds every
+ * k-mer with >= bins-1 occurrences, bin 0 stays 0.  It covers ALL k-mers, not only those the filters keep: the spectrum of the
+ * block for that k.  bins is in 2 .. 4096, or 0 with a NULL hist; anything else is ARCHON_E_ARG.
+ * Cap rule (that of archon_hip_repeats): *total is a host pointer and always written.  out NULL: counting only, no emit pass.
+ * cap < *total with out given: ARCHON_E_ARG, *total and the histogram written, out untouched.
+ * Per-position counts: occ[p], p in 0 .. n-k, is the number of occurrences of x[p .. p+k) in x: for a row r of a k-mer group,
+ * occ[sa[r] - k] = hi - lo.  n - k + 1 words in text order; with k > n nothing is written.  "banana": k = 1 gives 1 3 2 3 2 3,
+ * k = 2 gives 1 2 2 2 2, k = 3 gives 1 2 1 2.
+ * Shortest unique substring ending at an item: with r the row of item e and m = max(lcp[r], lcp[r+1]), sus[e-1] = m + 1 if
+ * m + 1 <= e, else 0: the whole prefix x[0 .. e) occurs again, so nothing that ends at e is unique.  n words in text order.
+ * x[e-L .. e) with L = sus[e-1] > 0 occurs once and every shorter suffix of it at least twice; and occ[p] == 1 exactly when
+ * 0 < sus[p+k-1] <= k.  "banana": 1 2 3 4 3 4.  A caller who wants the shortest unique substring STARTING at a position passes
+ * the reversed text, as for the textbook LZ77 parse above: item e of reverse(z) is position n - e of z.
+ * Invariants of the record: distinct + short_rows == groups; the counts of all k-mers sum to n - k + 1 when k <= n; hist sums
+ * to distinct.
+ * Work: bounds (reads sa and lcp, 8 n bytes), a one-workgroup scan of the tile words, starts (reads lcp, writes 4 G), then
+ *   kmers      the count pass over the G groups (two words of starts and one item each), and with out given a scan and the same
+ *              pass again storing 12 bytes per k-mer: 4 launches counting, 6 with the emit pass; 1 host wait, 2 when a
+ *              histogram is given or the emit pass runs (out given and *total > 0)
+ *   kmer_occ   one pass over the rows (sa and lcp again, two cached words of starts, one scattered 4-byte store per row):
+ *              4 launches; 1 host wait, 2 in the host and block forms
+ *   sus        a check of sa and one pass (lcp, sa, one scattered store per row): 2 launches; 1 host wait, 2 in the host and
+ *              block forms
+ * (the block forms add the waits of their LCP step, not its launches).
+ * Bad input.  An sa value outside 1..n is never used as an index: ARCHON_E_CORRUPT, the outputs untouched (*total is 0).  A
+ * value that occurs twice, or an lcp that is not the LCP array of anything, returns ARCHON_OK with unspecified contents; every
+ * access stays inside the buffers and every emitted record has lo < hi <= n.
+ * Workspace, from the calling thread's context arena: 4 (n + 1) bytes of starts, n / 256 bytes of tile words and 16 KiB of
+ * histogram; sus takes none.  The host forms stage sa, lcp and the result besides.
+ * Locating and document frequency need no new call: a k-mer (lo, hi) is located by archon_hip_block_fm_locate_mems /
+ * archon_hip_fm_locate_mems with an archon_hip_fm_mem {lo, hi, start 0, end k}, and archon_hip_fm_docs_ranges over lo and hi
+ * lists the documents of every k-mer. */
+typedef struct archon_hip_kmer {
+    uint32_t lo, hi;            /* the rows of the k-mer's occurrences */
+    uint32_t item;              /* sa[lo], the end of one of them: the bytes are x[item-k .. item) */
+} archon_hip_kmer;
+/* device sa[n], lcp[n], out and hist (any 4-byte aligned address); on `stream` (NULL = the context's own), complete on return */
+int  archon_hip_kmers_dev(const uint32_t *d_sa, const uint32_t *d_lcp, uint32_t n, uint32_t k, uint32_t min_occ, uint32_t max_occ,
+                          archon_hip_kmer *d_out_or_null, uint64_t cap, uint64_t *total, uint32_t *d_hist_or_null, uint32_t bins, int dev,
+                          void *stream);
+/* host sa[n], lcp[n], out and hist */
+int  archon_hip_kmers(const uint32_t *sa, const uint32_t *lcp, uint32_t n, uint32_t k, uint32_t min_occ, uint32_t max_occ,
+                      archon_hip_kmer *out_or_null, uint64_t cap, uint64_t *total, uint32_t *hist_or_null, uint32_t bins, int dev);
+/* the resident block of the handle's last forward and its suffix array (ARCHON_E_ARG when that forward kept none): its LCP array
+ * is computed on the device (as archon_hip_block_lcp does, and with the same record in archon_hip_lcp_stats) and consumed there,
+ * it never visits the host.  out and hist are host buffers. */
+int  archon_hip_block_kmers(archon_hip_block *b, uint32_t k, uint32_t min_occ, uint32_t max_occ, archon_hip_kmer *out_or_null, uint64_t cap,
+                            uint64_t *total, uint32_t *hist_or_null, uint32_t bins);
+/* occ[n - k + 1] on the device, on the host, of the resident block (host occ) */
+int  archon_hip_kmer_occ_dev(const uint32_t *d_sa, const uint32_t *d_lcp, uint32_t n, uint32_t k, uint32_t *d_occ, int dev, void *stream);
+int  archon_hip_kmer_occ(const uint32_t *sa, const uint32_t *lcp, uint32_t n, uint32_t k, uint32_t *occ, int dev);
+int  archon_hip_block_kmer_occ(archon_hip_block *b, uint32_t k, uint32_t *occ);
+/* sus[n] on the device, on the host, of the resident block (host sus) */
+int  archon_hip_sus_dev(const uint32_t *d_sa, const uint32_t *d_lcp, uint32_t n, uint32_t *d_sus, int dev, void *stream);
+int  archon_hip_sus(const uint32_t *sa, const uint32_t *lcp, uint32_t n, uint32_t *sus, int dev);
+int  archon_hip_block_sus(archon_hip_block *b, uint32_t *sus);
+/* the CALLING THREAD's last call of this family on `dev`; these calls leave every other record alone (the block forms also keep
+ * the LCP record of their LCP step).  A kmer_occ call fills `groups` and leaves the other work counters 0, a sus call all of them */
+typedef struct archon_hip_kmer_stats {
+    uint32_t n, k, min_occ, max_occ;        /* of the call, as given (k 0 for sus) */
+    uint32_t bins;              /* of the call, as given */
+    uint32_t tile;              /* rows of a tile of the passes */
+    uint32_t what;              /* 0 kmers, 1 kmer_occ, 2 sus */
+    uint32_t kernel_launches;   /* launches issued by the call (block form: without those of its LCP step) */
+    uint32_t host_syncs;        /* times the host waited for the stream inside the call (block form: the LCP step's included) */
+    uint32_t most;              /* the largest count of a k-mer */
+    uint64_t groups;            /* G: rows that start a group */
+    uint64_t short_rows;        /* groups that are a short row */
+    uint64_t distinct;          /* groups that are a k-mer: all k-mers of the block */
+    uint64_t kmers;             /* those that passed the filters: *total */
+    uint64_t occurrences;       /* hi - lo summed over them */
+    uint64_t unique;            /* k-mers with one occurrence */
+    float ms_lcp;               /* block form: device time of the LCP step */
+    float ms_count;             /* device time of bounds, scan and starts, and of the count pass of kmers */
+    float ms_emit;              /* device time of the scan of the group tiles and the emit pass */
+    float ms_scatter;           /* device time of the occ pass; of the check and the pass of sus */
+} archon_hip_kmer_stats;
+int  archon_hip_get_kmer_stats(int dev, archon_hip_kmer_stats *out);
 
 /* ---- matching statistics of a long text, and its relative LZ parse against the block ------------------------------------------
  * archon_hip_fm_ms runs one wave per pattern, so one long pattern runs on one wave.  These calls take ONE text P of m bytes --

@@ -34,6 +34,9 @@
  *   LZ_FAN         2..64 / 0      LZ: fan-out of the two hierarchies of the LPF pass, a power of two (0: 16).  It changes no result
  *   LZ_TILE        2..4096 / 0    LZ: items of a tile of the parse, a power of two (0: 256).  It changes no result: at 2, blocks of
  *                                 seven bytes cross three parse levels
+ *   KMER_TILE      4..2048 / 0    k-mers: rows of a tile of the passes (and groups of a tile of the group passes), a power of two
+ *                                 (0: 2048).  It changes no result: at 4, blocks of seven bytes cross a tile boundary, and
+ *                                 65536 rows at 16 give every lane of the tile scan four words
  *   MS_CHUNK       1.. / 0        text matching statistics: bytes of a chunk of the walk, any C >= 1 (0: 1024).  It changes no
  *                                 record: at 1 every end after the first is a join
  *   EDIT_TILE      1..64 / 0      edit-distance search: ends a tile owns, W (0: 32).  A call whose K makes W + 2K > 64 is ARCHON_E_ARG.
