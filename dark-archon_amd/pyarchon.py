@@ -75,7 +75,14 @@ LZ77 = np.dtype([("pos", "<u4"), ("len", "<u4"), ("src", "<u4")])
 KMER = np.dtype([("lo", "<u4"), ("hi", "<u4"), ("item", "<u4")])
 
 
-class Stats(ctypes.Structure):
+class _Record(ctypes.Structure):
+    """what every statistics structure shares: its fields as a dict, without the padding (names that start with `_`)"""
+
+    def asdict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_ if not k.startswith("_")}
+
+
+class Stats(_Record):
     _fields_ = [
         ("n", ctypes.c_uint32), ("radix_passes", ctypes.c_uint32), ("doubling_rounds", ctypes.c_uint32),
         ("_pad0", ctypes.c_uint32),
@@ -94,11 +101,8 @@ class Stats(ctypes.Structure):
         ("host_syncs", ctypes.c_uint32), ("_pad2", ctypes.c_uint32),
     ]
 
-    def asdict(self):
-        return {k: getattr(self, k) for k, _ in self._fields_ if not k.startswith("_")}
 
-
-class LcpStats(ctypes.Structure):
+class LcpStats(_Record):
     """archon_hip_lcp_stats: the calling thread's last LCP call on a device"""
     _fields_ = [
         ("n", ctypes.c_uint32), ("long_rounds", ctypes.c_uint32), ("max_lcp", ctypes.c_uint32), ("kernel_launches", ctypes.c_uint32),
@@ -106,11 +110,8 @@ class LcpStats(ctypes.Structure):
         ("host_syncs", ctypes.c_uint32), ("ms_total", ctypes.c_float),
     ]
 
-    def asdict(self):
-        return {k: getattr(self, k) for k, _ in self._fields_}
 
-
-class FmStats(ctypes.Structure):
+class FmStats(_Record):
     """archon_hip_fm_stats: the calling thread's last FM call on a device"""
     _fields_ = [
         ("n", ctypes.c_uint32), ("patterns", ctypes.c_uint32), ("pattern_bytes", ctypes.c_uint64), ("steps", ctypes.c_uint64),
@@ -118,11 +119,8 @@ class FmStats(ctypes.Structure):
         ("table_bytes", ctypes.c_uint64), ("ms_build", ctypes.c_float), ("ms_query", ctypes.c_float),
     ]
 
-    def asdict(self):
-        return {k: getattr(self, k) for k, _ in self._fields_}
 
-
-class FmWalkStats(ctypes.Structure):
+class FmWalkStats(_Record):
     """archon_hip_fm_walk_stats: the calling thread's last sample / locate / extract call on a device"""
     _fields_ = [
         ("n", ctypes.c_uint32), ("rate", ctypes.c_uint32), ("route", ctypes.c_uint32), ("kernel_launches", ctypes.c_uint32),
@@ -131,11 +129,8 @@ class FmWalkStats(ctypes.Structure):
         ("ms_query", ctypes.c_float),
     ]
 
-    def asdict(self):
-        return {k: getattr(self, k) for k, _ in self._fields_}
 
-
-class FmApproxStats(ctypes.Structure):
+class FmApproxStats(_Record):
     """archon_hip_fm_approx_stats: the calling thread's last approximate call (approx, locate_hits) on a device"""
     _fields_ = [
         ("n", ctypes.c_uint32), ("patterns", ctypes.c_uint32), ("max_mismatches", ctypes.c_uint32), ("built", ctypes.c_uint32),
@@ -144,11 +139,8 @@ class FmApproxStats(ctypes.Structure):
         ("ms_build", ctypes.c_float), ("ms_count", ctypes.c_float), ("ms_emit", ctypes.c_float), ("ms_locate", ctypes.c_float),
     ]
 
-    def asdict(self):
-        return {k: getattr(self, k) for k, _ in self._fields_}
 
-
-class FmClassStats(ctypes.Structure):
+class FmClassStats(_Record):
     """archon_hip_fm_class_stats: the calling thread's last class call (classes, classes_dev, fm_classes) on a device"""
     _fields_ = [
         ("n", ctypes.c_uint32), ("patterns", ctypes.c_uint32), ("max_width", ctypes.c_uint32), ("built", ctypes.c_uint32),
@@ -157,11 +149,8 @@ class FmClassStats(ctypes.Structure):
         ("ms_build", ctypes.c_float), ("ms_width", ctypes.c_float), ("ms_count", ctypes.c_float), ("ms_emit", ctypes.c_float),
     ]
 
-    def asdict(self):
-        return {k: getattr(self, k) for k, _ in self._fields_}
 
-
-class FmEditStats(ctypes.Structure):
+class FmEditStats(_Record):
     """archon_hip_fm_edit_stats: the calling thread's last edit-distance call (edit, edit_dev, fm_edit) on a device"""
     _fields_ = [
         ("n", ctypes.c_uint32), ("patterns", ctypes.c_uint32), ("max_errors", ctypes.c_uint32), ("tile", ctypes.c_uint32),
@@ -172,11 +161,8 @@ class FmEditStats(ctypes.Structure):
         ("ms_emit", ctypes.c_float),
     ]
 
-    def asdict(self):
-        return {k: getattr(self, k) for k, _ in self._fields_}
 
-
-class FmMemStats(ctypes.Structure):
+class FmMemStats(_Record):
     """archon_hip_fm_mem_stats: the calling thread's last SMEM call (mirror, smems, locate_mems) on a device"""
     _fields_ = [
         ("n", ctypes.c_uint32), ("patterns", ctypes.c_uint32), ("min_len", ctypes.c_uint32), ("built", ctypes.c_uint32),
@@ -186,11 +172,8 @@ class FmMemStats(ctypes.Structure):
         ("ms_emit", ctypes.c_float), ("ms_locate", ctypes.c_float),
     ]
 
-    def asdict(self):
-        return {k: getattr(self, k) for k, _ in self._fields_}
 
-
-class FmMsStats(ctypes.Structure):
+class FmMsStats(_Record):
     """archon_hip_fm_ms_stats: the calling thread's last attach or matching-statistics call (attach_lcp, ms) on a device"""
     _fields_ = [
         ("n", ctypes.c_uint32), ("patterns", ctypes.c_uint32), ("fan", ctypes.c_uint32), ("levels", ctypes.c_uint32), ("attached", ctypes.c_uint32),
@@ -199,11 +182,8 @@ class FmMsStats(ctypes.Structure):
         ("host_syncs", ctypes.c_uint32), ("ms_lcp", ctypes.c_float), ("ms_attach", ctypes.c_float), ("ms_query", ctypes.c_float),
     ]
 
-    def asdict(self):
-        return {k: getattr(self, k) for k, _ in self._fields_}
 
-
-class FmTextStats(ctypes.Structure):
+class FmTextStats(_Record):
     """archon_hip_fm_text_stats: the calling thread's last attach_sa, ms_text or rlz call on a device"""
     _fields_ = [
         ("n", ctypes.c_uint32), ("m", ctypes.c_uint32), ("chunk", ctypes.c_uint32), ("chunks", ctypes.c_uint32), ("fan", ctypes.c_uint32),
@@ -214,11 +194,8 @@ class FmTextStats(ctypes.Structure):
         ("ms_parse", ctypes.c_float),
     ]
 
-    def asdict(self):
-        return {k: getattr(self, k) for k, _ in self._fields_}
 
-
-class FmDocStats(ctypes.Structure):
+class FmDocStats(_Record):
     """archon_hip_fm_doc_stats: the calling thread's last documents call (attach_docs, docs, docs_ranges, doc_of) on a device"""
     _fields_ = [
         ("n", ctypes.c_uint32), ("docs", ctypes.c_uint32), ("ranges", ctypes.c_uint32), ("tile", ctypes.c_uint32), ("attached", ctypes.c_uint32),
@@ -228,11 +205,8 @@ class FmDocStats(ctypes.Structure):
         ("ms_attach", ctypes.c_float), ("ms_search", ctypes.c_float), ("ms_count", ctypes.c_float), ("ms_emit", ctypes.c_float),
     ]
 
-    def asdict(self):
-        return {k: getattr(self, k) for k, _ in self._fields_}
 
-
-class RepeatStats(ctypes.Structure):
+class RepeatStats(_Record):
     """archon_hip_repeat_stats: the calling thread's last repeats call on a device"""
     _fields_ = [
         ("n", ctypes.c_uint32), ("kind", ctypes.c_uint32), ("min_len", ctypes.c_uint32), ("min_occ", ctypes.c_uint32),
@@ -243,11 +217,8 @@ class RepeatStats(ctypes.Structure):
         ("ms_lcp", ctypes.c_float), ("ms_count", ctypes.c_float), ("ms_emit", ctypes.c_float), ("reserved1", ctypes.c_float),
     ]
 
-    def asdict(self):
-        return {k: getattr(self, k) for k, _ in self._fields_}
 
-
-class LzStats(ctypes.Structure):
+class LzStats(_Record):
     """archon_hip_lz_stats: the calling thread's last LZ call on a device"""
     _fields_ = [
         ("n", ctypes.c_uint32), ("dir", ctypes.c_uint32), ("fan", ctypes.c_uint32), ("levels", ctypes.c_uint32),
@@ -257,11 +228,8 @@ class LzStats(ctypes.Structure):
         ("ms_lcp", ctypes.c_float), ("ms_lpf", ctypes.c_float), ("ms_parse", ctypes.c_float), ("ms_emit", ctypes.c_float),
     ]
 
-    def asdict(self):
-        return {k: getattr(self, k) for k, _ in self._fields_}
 
-
-class KmerStats(ctypes.Structure):
+class KmerStats(_Record):
     """archon_hip_kmer_stats: the calling thread's last k-mer call (kmers, kmer_occ, sus) on a device"""
     _fields_ = [
         ("n", ctypes.c_uint32), ("k", ctypes.c_uint32), ("min_occ", ctypes.c_uint32), ("max_occ", ctypes.c_uint32),
@@ -271,9 +239,6 @@ class KmerStats(ctypes.Structure):
         ("occurrences", ctypes.c_uint64), ("unique", ctypes.c_uint64),
         ("ms_lcp", ctypes.c_float), ("ms_count", ctypes.c_float), ("ms_emit", ctypes.c_float), ("ms_scatter", ctypes.c_float),
     ]
-
-    def asdict(self):
-        return {k: getattr(self, k) for k, _ in self._fields_}
 
 
 class ArchonError(RuntimeError):
@@ -440,8 +405,8 @@ _routes_seen = None
 # Test routing (include/archon_hip_test.h): the library reads nothing from the environment; the tests, bench.py and the
 # tools keep saying ARCHON_<NAME>=<value> in os.environ, and this binding hands what it finds to archon_hip_test_route
 # before the next call into the library.
-_ROUTE_NAMES = ("FORCE_PATH", "SMALL_BLOCK", "PASS_RANGES", "INV_ROWS", "INV_SLAB", "INV_SBITS", "INV_WALK_WGS", "NO_ALIGNED", "NO_CHAINS", "NO_DEEP_HINT",
-                "NO_PACK", "NO_PACK_STREAM", "NO_PAIR_CHAINS", "NO_PERIOD_HINT", "NO_BREAK_ROUND", "NO_PERIOD_PROBE", "NO_PERIOD_STREAM", "NO_PROBE",
+_ROUTE_NAMES = ("FORCE_PATH", "SMALL_BLOCK", "PASS_RANGES", "INV_ROWS", "INV_SLAB", "INV_SBITS", "INV_WALK_WGS", "NO_ALIGNED", "NO_CHAINS",
+                "NO_PACK", "NO_PAIR_CHAINS", "NO_PERIOD_HINT", "NO_BREAK_ROUND", "NO_PERIOD_STREAM",
                 "NO_RANK_WRITER", "NO_TEXT_ROUNDS", "NO_MID", "NO_SHALLOW", "NO_CLOSED_FORM", "NO_REL_RECORDS", "ALIGNED_MIN", "REL_MIN_SEG", "KEY_BYTES",
                 "LCP_CAP", "LCP_WINDOW", "FM_SUB_ROWS", "FM_SUPER_ROWS", "FM_SAMPLE_WALK", "REP_FAN", "LZ_FAN", "LZ_TILE", "MS_CHUNK",
                 "EDIT_TILE", "EDIT_BATCH", "DOC_TILE", "KMER_TILE")
@@ -550,74 +515,61 @@ def lcp(x, sa, dev=0):
     return out
 
 
+def _last_stats(cls, getter_name, dev):
+    """the record `cls` of the calling thread's last call of one kind on dev, from the library's getter of that name"""
+    s = cls()
+    _check(getattr(lib(), getter_name)(dev, ctypes.byref(s)))
+    return s
+
+
 def lcp_stats(dev=0):
     """LcpStats of the calling thread's last LCP call on dev"""
-    s = LcpStats()
-    _check(lib().archon_hip_get_lcp_stats(dev, ctypes.byref(s)))
-    return s
+    return _last_stats(LcpStats, "archon_hip_get_lcp_stats", dev)
 
 
 def fm_stats(dev=0):
     """FmStats of the calling thread's last FM call on dev"""
-    s = FmStats()
-    _check(lib().archon_hip_get_fm_stats(dev, ctypes.byref(s)))
-    return s
+    return _last_stats(FmStats, "archon_hip_get_fm_stats", dev)
 
 
 def fm_walk_stats(dev=0):
     """FmWalkStats of the calling thread's last sample / locate / extract call on dev"""
-    s = FmWalkStats()
-    _check(lib().archon_hip_get_fm_walk_stats(dev, ctypes.byref(s)))
-    return s
+    return _last_stats(FmWalkStats, "archon_hip_get_fm_walk_stats", dev)
 
 
 def fm_approx_stats(dev=0):
     """FmApproxStats of the calling thread's last approximate call (approx, locate_hits) on dev"""
-    s = FmApproxStats()
-    _check(lib().archon_hip_get_fm_approx_stats(dev, ctypes.byref(s)))
-    return s
+    return _last_stats(FmApproxStats, "archon_hip_get_fm_approx_stats", dev)
 
 
 def fm_class_stats(dev=0):
     """FmClassStats of the calling thread's last class call (classes, classes_dev, fm_classes) on dev"""
-    s = FmClassStats()
-    _check(lib().archon_hip_get_fm_class_stats(dev, ctypes.byref(s)))
-    return s
+    return _last_stats(FmClassStats, "archon_hip_get_fm_class_stats", dev)
 
 
 def fm_edit_stats(dev=0):
     """FmEditStats of the calling thread's last edit-distance call (edit, edit_dev, fm_edit) on dev"""
-    s = FmEditStats()
-    _check(lib().archon_hip_get_fm_edit_stats(dev, ctypes.byref(s)))
-    return s
+    return _last_stats(FmEditStats, "archon_hip_get_fm_edit_stats", dev)
 
 
 def fm_mem_stats(dev=0):
     """FmMemStats of the calling thread's last SMEM call (mirror, smems, locate_mems) on dev"""
-    s = FmMemStats()
-    _check(lib().archon_hip_get_fm_mem_stats(dev, ctypes.byref(s)))
-    return s
+    return _last_stats(FmMemStats, "archon_hip_get_fm_mem_stats", dev)
 
 
 def fm_ms_stats(dev=0):
     """FmMsStats of the calling thread's last attach or matching-statistics call (attach_lcp, ms) on dev"""
-    s = FmMsStats()
-    _check(lib().archon_hip_get_fm_ms_stats(dev, ctypes.byref(s)))
-    return s
+    return _last_stats(FmMsStats, "archon_hip_get_fm_ms_stats", dev)
 
 
 def fm_text_stats(dev=0):
     """FmTextStats of the calling thread's last attach_sa, ms_text or rlz call on dev"""
-    s = FmTextStats()
-    _check(lib().archon_hip_get_fm_text_stats(dev, ctypes.byref(s)))
-    return s
+    return _last_stats(FmTextStats, "archon_hip_get_fm_text_stats", dev)
 
 
 def fm_doc_stats(dev=0):
     """FmDocStats of the calling thread's last documents call (attach_docs, docs, docs_ranges, doc_of) on dev"""
-    s = FmDocStats()
-    _check(lib().archon_hip_get_fm_doc_stats(dev, ctypes.byref(s)))
-    return s
+    return _last_stats(FmDocStats, "archon_hip_get_fm_doc_stats", dev)
 
 
 def rlz_decode(x, phrases, m, literals=None):
@@ -669,9 +621,7 @@ def ms_smems(len, lo, hi, offsets, min_len=1):
 
 def repeat_stats(dev=0):
     """RepeatStats of the calling thread's last repeats call on dev"""
-    s = RepeatStats()
-    _check(lib().archon_hip_get_repeat_stats(dev, ctypes.byref(s)))
-    return s
+    return _last_stats(RepeatStats, "archon_hip_get_repeat_stats", dev)
 
 
 def _repeats(call, count_only):
@@ -701,9 +651,7 @@ def repeats(lcp, bwt, base_id, kind=1, min_len=1, min_occ=2, count_only=False, d
 
 def lz_stats(dev=0):
     """LzStats of the calling thread's last LZ call on dev"""
-    s = LzStats()
-    _check(lib().archon_hip_get_lz_stats(dev, ctypes.byref(s)))
-    return s
+    return _last_stats(LzStats, "archon_hip_get_lz_stats", dev)
 
 
 def lpf(sa, lcp, dir=0, dev=0):
@@ -759,9 +707,7 @@ def lz77(z, dev=0):
 
 def kmer_stats(dev=0):
     """KmerStats of the calling thread's last k-mer call (kmers, kmer_occ, sus) on dev"""
-    s = KmerStats()
-    _check(lib().archon_hip_get_kmer_stats(dev, ctypes.byref(s)))
-    return s
+    return _last_stats(KmerStats, "archon_hip_get_kmer_stats", dev)
 
 
 def _kmers(call, count_only, bins):

@@ -13,6 +13,7 @@
  *   SMALL_BLOCK  bytes / -1   blocks below this size take the byte count + LSB passes instead of the streaming stage (-1: 8 MiB)
  *   ALIGNED_MIN  bytes / -1   blocks from this size on may run pass B in bucket mode (-1: 16 MiB)
  *   REL_MIN_SEG  places / -1  bucket mode moves range-relative records when a bucket's segments average at least this many places (-1: 4096)
+ *   KEY_BYTES    3..6 / 0     7-pass first stage: key bytes the LSB passes sort on (0, or any other value: the library's own choice)
  *   INV_SLAB, INV_SBITS, INV_WALK_WGS   inverse: slab bytes per chain, log2 rows per chain head, walk workgroups per CU.
  *                                       INV_SBITS is clamped to 3..12 (any value >= 0 counts as set; negative: the product's rule).
  *                                       INV_SLAB is cut to a multiple of 16 and taken only where it is at least 16 and below the
@@ -45,8 +46,8 @@
  *                                 no match: at 1 every pattern is marked, swept and checked alone
  *   DOC_TILE       64..2^20 / 0   document listing: rows of a tile, a multiple of 64 (0: 4096).  It changes no record: at 64 a range of
  *                                 65 rows is two tiles
- *   NO_ALIGNED NO_BREAK_ROUND NO_CHAINS NO_DEEP_HINT NO_PACK NO_PACK_STREAM NO_PAIR_CHAINS NO_PERIOD_HINT NO_PERIOD_PROBE
- *   NO_PERIOD_STREAM NO_PROBE NO_RANK_WRITER NO_TEXT_ROUNDS NO_MID NO_SHALLOW NO_CLOSED_FORM NO_REL_RECORDS      nonzero switches the named step off
+ *   NO_ALIGNED NO_BREAK_ROUND NO_CHAINS NO_PACK NO_PAIR_CHAINS NO_PERIOD_HINT NO_PERIOD_STREAM NO_RANK_WRITER NO_TEXT_ROUNDS
+ *   NO_MID NO_SHALLOW NO_CLOSED_FORM NO_REL_RECORDS      nonzero switches the named step off
  * Returns 0, or ARCHON_E_ARG for an unknown name / a value out of range.  Process-wide; not thread-safe against
  * concurrent transforms (tests run one at a time).
  */

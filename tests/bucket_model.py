@@ -44,7 +44,7 @@ LS_MAX_BIN = 64                # kLsMaxBin
 TIE_GROUP_MAX = 32             # kTieGroupMax
 BIG_ROWS = 32768               # kBigRows
 UNPACK_CHUNK = 4096            # kUnpackChunk
-LIST_CAP = 1 << 20             # kTieListCap (archon_hip.hip)
+LIST_CAP = 1 << 20             # kTieListCap (forward_driver.hiph)
 TIE_SAMPLE = 1 << 16           # kTieSample
 KEY_BYTES = 5                  # key bytes the stage sorts on
 RESOLVE_BYTES = 64             # further key bytes k_resolve_ties compares

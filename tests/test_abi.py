@@ -45,6 +45,56 @@ def test_library_reads_no_routing_from_the_environment():
     assert lib.archon_hip_test_route(b"NO_SUCH_ROUTE", 1) < 0 and lib.archon_hip_test_route(b"PASS_RANGES", 5000) < 0
 
 
+def test_abi_file_launches_nothing():
+    """archon_hip.hip is the translation unit and the C ABI: an entry point checks arguments, takes a context, stages host
+    buffers and keeps the record; everything that launches a kernel lives in a .hiph file beside its kernels."""
+    text = open(os.path.join(ROOT, "dark-archon_amd", "csrc", "archon_hip.hip")).read()
+    for word in ("ARCHON_LAUNCH", "hipLaunchKernelGGL", "<<<"):
+        assert text.count(word) == 0, word
+
+
+# what each archon_hip_get_*_stats calls its family when the calling thread has no record of it
+STATS_GETTERS = {
+    "archon_hip_get_stats": "transform", "archon_hip_get_lcp_stats": "LCP call", "archon_hip_get_fm_stats": "FM call",
+    "archon_hip_get_fm_walk_stats": "sampled FM call", "archon_hip_get_fm_approx_stats": "approximate FM call",
+    "archon_hip_get_fm_class_stats": "class FM call", "archon_hip_get_fm_edit_stats": "edit-distance FM call",
+    "archon_hip_get_fm_mem_stats": "SMEM call", "archon_hip_get_fm_ms_stats": "matching-statistics call",
+    "archon_hip_get_fm_text_stats": "text call", "archon_hip_get_fm_doc_stats": "documents call",
+    "archon_hip_get_repeat_stats": "repeats call", "archon_hip_get_lz_stats": "LZ call", "archon_hip_get_kmer_stats": "k-mer call",
+}
+
+_GETTER_PROBE = r"""
+import ctypes, json, sys
+L = ctypes.CDLL(sys.argv[1])
+L.archon_hip_last_error.restype = ctypes.c_char_p
+out = ctypes.create_string_buffer(4096)
+res = {}
+for name in sys.argv[2:]:
+    fn = getattr(L, name)
+    fn.argtypes = [ctypes.c_int, ctypes.c_void_p]
+    fn.restype = ctypes.c_int
+    res[name] = [[fn(dev, buf), L.archon_hip_last_error().decode()] for dev, buf in ((0, None), (0, out), (-1, out), (64, out))]
+assert out.raw == bytes(4096)
+print(json.dumps(res))
+"""
+
+
+def test_stats_getters_before_any_call():
+    """On a thread that has made no call, every archon_hip_get_*_stats the header declares refuses a null `out`, and refuses
+    device 0, -1 and 64 by saying what the thread has not run there; nothing is written."""
+    import json
+    import sys
+    import pyarchon
+    getters = [f for f in declared_functions("archon_hip.h") if re.fullmatch(r"archon_hip_get_\w+_stats|archon_hip_get_stats", f)]
+    assert sorted(getters) == sorted(STATS_GETTERS)
+    r = subprocess.run([sys.executable, "-c", _GETTER_PROBE, pyarchon.LIB_PATH] + getters, check=True, capture_output=True, text=True)
+    res = json.loads(r.stdout)
+    for name in getters:
+        no_run = "the calling thread has run no %s on device %%d" % STATS_GETTERS[name]
+        assert res[name] == [[pyarchon.E_ARG, "null pointer"], [pyarchon.E_ARG, no_run % 0], [pyarchon.E_ARG, no_run % -1],
+                             [pyarchon.E_ARG, no_run % 64]], name
+
+
 def test_host_library_exports_header():
     path = os.path.join(ROOT, "dark-archon_amd", "libarchon.so")
     if not os.path.exists(path):

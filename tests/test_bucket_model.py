@@ -172,7 +172,7 @@ def test_constants_follow_the_kernels():
     import re
     csrc = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "dark-archon_amd", "csrc")
     bs = open(os.path.join(csrc, "bucket_sort.hiph")).read()
-    drv = open(os.path.join(csrc, "archon_hip.hip")).read()
+    drv = open(os.path.join(csrc, "forward_driver.hiph")).read()
     num = lambda src, name: int(re.search(r"constexpr\s+\w+\s+" + name + r"\s*=\s*([0-9]+)", src).group(1))
     assert num(bs, "kLsBlock") == M.LS_BLOCK and num(bs, "kLsIPT") * M.LS_BLOCK == M.LS_CAP
     assert num(bs, "kLsMaxBin") == M.LS_MAX_BIN and num(bs, "kTieGroupMax") == M.TIE_GROUP_MAX

@@ -549,7 +549,7 @@ def test_compacted_alphabet_with_repeats(archon, oracle):
 
 @pytest.mark.streaming_machinery
 def test_alphabet_hint_between_blocks(archon, oracle):
-    """a context whose last block had <= 4 distinct bytes looks at the next block's alphabet before counting it (archon_hip.hip,
+    """a context whose last block had <= 4 distinct bytes looks at the next block's alphabet before counting it (forward_driver.hiph,
     hint_poor_alphabet): the same order and the same route whatever block came before -- DNA after DNA, then blocks that break the
     promise (256 symbols, 5 symbols, 4 symbols and one stray byte at the end), clean periodic blocks, DNA again"""
     rng = np.random.default_rng(5)

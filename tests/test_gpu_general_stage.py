@@ -1,4 +1,4 @@
-"""GPU: census of the general stage -- the host driver of everything the first stage leaves tied (archon_hip.hip,
+"""GPU: census of the general stage -- the host driver of everything the first stage leaves tied (general_stage.hiph,
 Fwd::general_stage: run shortcut, lists, text rounds, rank table, certified break rounds, break and doubling rounds with the pair
 chains), in the manner of test_gpu_block_calls.py.  One forward per case of forward_cases.CENSUS_CASES, at the smallest block
 that reaches the branch the case is named after; the statistics that say which launches, waits and rounds the driver made are
