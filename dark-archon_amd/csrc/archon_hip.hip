@@ -28,6 +28,7 @@
 #include "repeats.hiph"
 #include "lz.hiph"
 #include "kmers.hiph"
+#include "maw.hiph"
 
 #include <limits.h>
 #include <stdlib.h>
@@ -101,6 +102,16 @@ static int sus_check(const void *sa, const void *lcp, const void *sus, uint32_t 
 {
     if (!sa || !lcp || !sus) { set_error("null pointer"); return ARCHON_E_ARG; }
     return check_n(n);
+}
+
+// *total is written whenever it is given: 0 before any refusal
+static int maws_check(const void *sa, const void *lcp, const void *bwt, uint64_t *total, uint32_t n, uint32_t base_id, uint32_t min_len, uint32_t max_len)
+{
+    if (total) *total = 0;
+    if (!sa || !lcp || !bwt || !total) { set_error("null pointer"); return ARCHON_E_ARG; }
+    ARCHON_TRY(check_n(n));
+    if (base_id >= n) { set_error("primary row %u out of range [0, %u)", base_id, n); return ARCHON_E_ARG; }
+    return maw_check_filters(min_len, max_len);
 }
 
 // ---- the FM index: text calls, documents
@@ -606,6 +617,34 @@ int archon_hip_sus(const uint32_t *sa, const uint32_t *lcp, uint32_t n, uint32_t
 }
 
 int archon_hip_get_kmer_stats(int dev, archon_hip_kmer_stats *out) { return t_kmer_stats.get(dev, out, "k-mer call"); }
+
+// ---- minimal absent words (maw.hiph: the kernel and its drivers; here the argument checks and the statistics)
+int archon_hip_maws_dev(const uint32_t *d_sa, const uint32_t *d_lcp, const uint8_t *d_bwt, uint32_t n, uint32_t base_id, uint32_t min_len,
+                        uint32_t max_len, archon_hip_maw *d_out_or_null, uint64_t cap, uint64_t *total, int dev, void *stream)
+{
+    ARCHON_TRY(maws_check(d_sa, d_lcp, d_bwt, total, n, base_id, min_len, max_len));
+    return with_ctx(dev, stream, [&](Ctx *c, hipStream_t s) -> int {
+        KeepStats<archon_hip_maw_stats> keep(t_maw_stats, dev);
+        maw_call_stats(&keep.st, n, min_len, max_len);
+        return maw_over_copy(c, s, d_sa, d_lcp, nullptr, d_bwt, n, base_id, min_len, max_len, d_out_or_null, cap, total, false, &keep.st);
+    });
+}
+
+// host buffers: sa and lcp through staging buffers 0 and 1, the BWT straight into the call's table, the words through buffer 2
+int archon_hip_maws(const uint32_t *sa, const uint32_t *lcp, const uint8_t *bwt, uint32_t n, uint32_t base_id, uint32_t min_len, uint32_t max_len,
+                    archon_hip_maw *out_or_null, uint64_t cap, uint64_t *total, int dev)
+{
+    ARCHON_TRY(maws_check(sa, lcp, bwt, total, n, base_id, min_len, max_len));
+    return with_ctx(dev, nullptr, [&](Ctx *c, hipStream_t s) -> int {
+        KeepStats<archon_hip_maw_stats> keep(t_maw_stats, dev);
+        maw_call_stats(&keep.st, n, min_len, max_len);
+        uint32_t *d_sa = nullptr, *d_lcp = nullptr;
+        ARCHON_TRY(kmer_stage(c, s, sa, lcp, n, &d_sa, &d_lcp));
+        return maw_over_copy(c, s, d_sa, d_lcp, bwt, nullptr, n, base_id, min_len, max_len, out_or_null, cap, total, true, &keep.st);
+    });
+}
+
+int archon_hip_maw_last_stats(int dev, archon_hip_maw_stats *out) { return t_maw_stats.get(dev, out, "minimal-absent-words call"); }
 
 // ---- the FM index (fm_host.hiph: the handle and every driver; here the argument checks and the statistics)
 int archon_hip_fm_create(const uint8_t *bwt, uint32_t n, uint32_t base_id, int dev, archon_hip_fm **out)
@@ -1316,6 +1355,25 @@ int archon_hip_block_sus(archon_hip_block *b, uint32_t *sus)
         uint32_t *d_lcp = nullptr;
         ARCHON_TRY(block_lcp_step(c, s, b, &d_lcp, &keep.st.ms_lcp));
         return kmer_sus_run(c, s, b->d_sa(), d_lcp, b->n, sus, true, &keep.st);
+    });
+}
+
+// the LCP array into staging buffer 1, the block's own rank table (built here when no FM call has), the words through buffer 2
+int archon_hip_block_maws(archon_hip_block *b, uint32_t min_len, uint32_t max_len, archon_hip_maw *out_or_null, uint64_t cap, uint64_t *total)
+{
+    if (total) *total = 0;
+    if (!b || !total) { set_error("null pointer"); return ARCHON_E_ARG; }
+    ARCHON_TRY(maw_check_filters(min_len, max_len));
+    std::lock_guard<std::mutex> lkb(b->mu);
+    ARCHON_TRY(block_check(b, true));
+    return with_ctx(b->dev, nullptr, [&](Ctx *c, hipStream_t s) -> int {
+        KeepStats<archon_hip_maw_stats> keep(t_maw_stats, b->dev);
+        maw_call_stats(&keep.st, b->n, min_len, max_len);
+        uint32_t *d_lcp = nullptr;
+        ARCHON_TRY(block_lcp_step(c, s, b, &d_lcp, &keep.st.ms_lcp));
+        ARCHON_TRY(block_fm_table_own(c, s, b, &keep.st));
+        const MawCall q = {b->d_sa(), d_lcp, b->fm->table(), min_len, max_len};
+        return maw_run(c, s, q, out_or_null, cap, total, true, &keep.st);
     });
 }
 

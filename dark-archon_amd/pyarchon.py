@@ -53,6 +53,7 @@ SYMBOLS = [
     "archon_hip_lpf", "archon_hip_lpf_dev", "archon_hip_lz_parse", "archon_hip_lz_parse_dev", "archon_hip_block_lz", "archon_hip_get_lz_stats",
     "archon_hip_kmers", "archon_hip_kmers_dev", "archon_hip_block_kmers", "archon_hip_kmer_occ", "archon_hip_kmer_occ_dev", "archon_hip_block_kmer_occ",
     "archon_hip_sus", "archon_hip_sus_dev", "archon_hip_block_sus", "archon_hip_get_kmer_stats",
+    "archon_hip_maws", "archon_hip_maws_dev", "archon_hip_block_maws", "archon_hip_maw_last_stats",
 ]
 
 # archon_hip_fm_hit: one distinct string within the distance of a pattern (FmIndex.approx, Block.fm_approx)
@@ -73,6 +74,9 @@ PHRASE = np.dtype([("end", "<u4"), ("len", "<u4"), ("src", "<u4")])
 LZ77 = np.dtype([("pos", "<u4"), ("len", "<u4"), ("src", "<u4")])
 # archon_hip_kmer: one k-mer of a block (kmers, Block.kmers): rows [lo, hi) of its occurrences, item = sa[lo]: the bytes x[item-k .. item)
 KMER = np.dtype([("lo", "<u4"), ("hi", "<u4"), ("item", "<u4")])
+# archon_hip_maw: one minimal absent word of a block (maws, Block.maws): rows [lo, hi) of the word without its last byte, the
+# word's length, item = sa[lo]: the bytes x[item-len+1 .. item) followed by `last`
+MAW = np.dtype([("lo", "<u4"), ("hi", "<u4"), ("len", "<u4"), ("item", "<u4"), ("last", "<u4")])
 
 
 class _Record(ctypes.Structure):
@@ -241,6 +245,18 @@ class KmerStats(_Record):
     ]
 
 
+class MawStats(_Record):
+    """archon_hip_maw_stats: the calling thread's last minimal-absent-words call on a device"""
+    _fields_ = [
+        ("n", ctypes.c_uint32), ("min_len", ctypes.c_uint32), ("max_len", ctypes.c_uint32), ("fan", ctypes.c_uint32),
+        ("levels", ctypes.c_uint32), ("direct_rows", ctypes.c_uint32), ("built", ctypes.c_uint32), ("kernel_launches", ctypes.c_uint32),
+        ("host_syncs", ctypes.c_uint32), ("absent_bytes", ctypes.c_uint32), ("shortest", ctypes.c_uint32), ("longest", ctypes.c_uint32),
+        ("intervals", ctypes.c_uint64), ("nodes", ctypes.c_uint64), ("children", ctypes.c_uint64), ("sets_direct", ctypes.c_uint64),
+        ("sets_table", ctypes.c_uint64), ("words", ctypes.c_uint64), ("probes", ctypes.c_uint64),
+        ("ms_lcp", ctypes.c_float), ("ms_build", ctypes.c_float), ("ms_count", ctypes.c_float), ("ms_emit", ctypes.c_float),
+    ]
+
+
 class ArchonError(RuntimeError):
     def __init__(self, code, msg):
         super().__init__("archon_hip error %d: %s" % (code, msg))
@@ -385,6 +401,10 @@ def load():
         "archon_hip_sus_dev": [vp, vp, u32, vp, i32, vp],
         "archon_hip_block_sus": [vp, vp],
         "archon_hip_get_kmer_stats": [i32, ctypes.POINTER(KmerStats)],
+        "archon_hip_maws": [vp, vp, vp, u32, u32, u32, u32, vp, ctypes.c_uint64, vp, i32],
+        "archon_hip_maws_dev": [vp, vp, vp, u32, u32, u32, u32, vp, ctypes.c_uint64, vp, i32, vp],
+        "archon_hip_block_maws": [vp, u32, u32, vp, ctypes.c_uint64, vp],
+        "archon_hip_maw_last_stats": [i32, ctypes.POINTER(MawStats)],
     }.items():
         fn = getattr(lib, name)
         fn.argtypes = args
@@ -770,6 +790,44 @@ def kmer_bytes(x, recs, k):
     if recs.size and (int(recs["item"].min()) < k or int(recs["item"].max()) > x.size):
         raise ValueError("kmer_bytes: an item outside %d..%d" % (k, x.size))
     return x[(recs["item"].astype(np.int64) - k)[:, None] + np.arange(k, dtype=np.int64)[None, :]]
+
+
+def maw_stats(dev=0):
+    """MawStats of the calling thread's last minimal-absent-words call on dev"""
+    return _last_stats(MawStats, "archon_hip_maw_last_stats", dev)
+
+
+def _maws(call, count_only):
+    """call(out pointer or None, cap, total pointer) -> rc: the count, or the words in an array of the size a first call gave"""
+    total = ctypes.c_uint64(0)
+    tp = ctypes.cast(ctypes.byref(total), ctypes.c_void_p)
+    _check(call(None, 0, tp))
+    if count_only:
+        return total.value
+    out = np.zeros(total.value, MAW)
+    if total.value:
+        _check(call(_p(out), out.size, tp))
+    return out[:total.value]
+
+
+def maws(sa, lcp, bwt, base_id, min_len=2, max_len=0, count_only=False, dev=0):
+    """the minimal absent words of a block from its suffix array, LCP array and BWT (include/archon_hip.h: archon_hip_maws): a MAW
+    array in the rule's order, those with min_len <= len <= max_len (0: no limit), or their number with count_only"""
+    sa, lcp = _sa_lcp("maws", sa, lcp)
+    bwt = np.ascontiguousarray(bwt, dtype=np.uint8)
+    if bwt.size != sa.size:
+        raise ValueError("maws: sa has %d rows, bwt %d" % (sa.size, bwt.size))
+    fn = lib().archon_hip_maws
+    return _maws(lambda out, cap, tp: fn(_p(sa), _p(lcp), _p(bwt), sa.size, int(base_id), int(min_len), int(max_len), out, cap, tp, dev), count_only)
+
+
+def maw_bytes(x, rec):
+    """the bytes of one MAW record of the block x: x[item-len+1 .. item) followed by `last` (no device)"""
+    x = bytes(x) if isinstance(x, (bytes, bytearray)) else np.ascontiguousarray(x, dtype=np.uint8).tobytes()
+    item, ln, last = int(rec["item"]), int(rec["len"]), int(rec["last"])
+    if ln < 2 or item < ln - 1 or item > len(x) or last > 255:
+        raise ValueError("maw_bytes: a record outside the block (item %d, len %d, last %d)" % (item, ln, last))
+    return x[item - ln + 1:item] + bytes([last])
 
 
 def _kmers_as_mems(recs, k):
@@ -1481,6 +1539,13 @@ class Block:
         """the starts of every k-mer's occurrences from the resident SA: a list of uint32 arrays, one per k-mer, in row order"""
         return _locate_mems(lib().archon_hip_block_fm_locate_mems, self.h, _kmers_as_mems(recs, k))
 
+    def maws(self, min_len=2, max_len=0, count_only=False):
+        """the minimal absent words of the resident block (needs forward(want_sa=True)): its LCP array is made and consumed on
+        the device, the rank table is the block's own (built here when no FM call has).  A MAW array in the rule's order, those
+        with min_len <= len <= max_len (0: no limit), or their number with count_only"""
+        fn = lib().archon_hip_block_maws
+        return _maws(lambda out, cap, tp: fn(self.h, int(min_len), int(max_len), out, cap, tp), count_only)
+
     def lz(self, dir=0, want_lpf=False, count_only=False):
         """the LZ77 parse of the resident block (needs forward(want_sa=True)): its LCP array and its LPF records are made and
         consumed on the device.  A PHRASE array in chain order (the phrase ending at n first), or the number of phrases with
@@ -1615,6 +1680,18 @@ def sus_dev(sa_t, lcp_t, sus_t):
     dev = sa_t.device.index or 0
     _check(lib().archon_hip_sus_dev(ctypes.c_void_p(sa_t.data_ptr()), ctypes.c_void_p(lcp_t.data_ptr()), sa_t.numel(), ctypes.c_void_p(sus_t.data_ptr()),
                                     dev, _stream_ptr()))
+
+
+def maws_dev(sa_t, lcp_t, bwt_t, base_id, min_len=2, max_len=0, out_t=None):
+    """torch CUDA tensors: sa and lcp int32[n], bwt uint8[n], out an int32 tensor of 5 words per word or None (counting only); on
+    the current stream.  Returns the number of minimal absent words (raises when out_t holds fewer)"""
+    dev = sa_t.device.index or 0
+    total = ctypes.c_uint64(0)
+    cap = out_t.numel() // 5 if out_t is not None else 0
+    _check(lib().archon_hip_maws_dev(ctypes.c_void_p(sa_t.data_ptr()), ctypes.c_void_p(lcp_t.data_ptr()), ctypes.c_void_p(bwt_t.data_ptr()), sa_t.numel(),
+                                     int(base_id), int(min_len), int(max_len), ctypes.c_void_p(out_t.data_ptr()) if out_t is not None else None, cap,
+                                     ctypes.cast(ctypes.byref(total), ctypes.c_void_p), dev, _stream_ptr()))
+    return total.value
 
 
 def validate_resident_dev(x_t, sa_t, bwt_t, base_id):

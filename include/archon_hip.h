@@ -26,6 +26,7 @@
  *   archon_hip_lpf*, _lz_*  nothing: the longest previous factor of every item and the LZ77 parse, from the SA and LCP array
  *   archon_hip_kmers*, _kmer_occ*, _sus*   nothing: the k-mers of a block with their counts, the count of the k-mer at every
  *                           position and the shortest unique substring ending at every item, from the SA and LCP array
+ *   archon_hip_maws*        nothing: the minimal absent words of a block, from the SA, the LCP array and the BWT
  *
  * Ordering convention ("a7 order"): item s in 1..N names the
  * reversed prefix x[s-1],x[s-2],...,x[0],INF with INF > 255; sa[0..N) lists the
@@ -1032,6 +1033,98 @@ typedef struct archon_hip_kmer_stats {
     float ms_scatter;           /* device time of the occ pass; of the check and the pass of sus */
 } archon_hip_kmer_stats;
 int  archon_hip_get_kmer_stats(int dev, archon_hip_kmer_stats *out);
+
+/* ---- the minimal absent words of a block (no counterpart in the reference) ----------------------------------------------------
+ * The calls above say what occurs in a block, how often and where; this one gives the complement.  A MINIMAL ABSENT WORD (MAW)
+ * of x is a string that does not occur in x while every proper substring of it does: the nullomers of a genome, a negative
+ * dictionary, the basis of alignment-free comparison.  Rows, items, sa, lcp, bwt, the primary row `base` and a7 order are those
+ * of the repeats section; lcp[0] reads as 0.
+ * Definition.  A MAW of x of length at least 2 is a.w.b (bytes a, b, a string w, possibly empty) such that a.w occurs in x, w.b
+ * occurs in x and a.w.b does not.  Bytes that do not occur in x at all (the absent words of length 1) are not reported: they are
+ * the empty buckets, and the record counts them (absent_bytes).
+ * The same in rows.  A NODE is the root -- l = 0, rows [0, n), ordered as row 0 -- or an LCP interval (lo, hi, l, k) exactly as
+ * archon_hip_repeats kind 0 defines it, k its representative row.  The CHILDREN of a node are the pieces of [lo, hi) cut at every
+ * row q in (lo, hi) with lcp[q] == l.  All rows of a child [clo, chi) hold the same symbol at depth l of their key: the byte
+ * a = x[sa[clo] - l - 1], and then [clo, chi) is what archon_hip_fm_count(a.w) returns; or INF, when sa[clo] == l: a single row,
+ * the occurrence of w at the start of the text, which names no a and yields no word.  B([p, q)) is the set of bwt[r] for r in
+ * [p, q) with r != base; for the root only, B(node) also takes bwt[base] = x[0], which follows no item, so that B(root) is the
+ * set of bytes that occur in x.  The words of a node are, for each child with a byte a, the words a.w.b for every b in
+ * B(node) \ B(child).  Only the root and the nodes that are maximal repeats (kind 1: bwt[lo .. hi) not all equal, or base
+ * inside) can yield a word: a right-uniform node has B(child) == B(node) for every child.
+ * Output order: nodes in ascending representative row, the root first; within a node the children in ascending row; within a
+ * child b ascending.  The order is the same on every run.
+ * Examples.  "banana" (sa 2 4 6 1 3 5, lcp 0 1 3 0 0 2, BWT nnbaaa, base 2) gives seven words, as (lo, hi, len, item, last):
+ * (0,3,2,2,'a') "aa", (0,3,2,2,'b') "ab", (3,4,2,1,'b') "bb", (3,4,2,1,'n') "bn", (4,6,2,3,'b') "nb", (4,6,2,3,'n') "nn" from
+ * the root, and (2,3,5,6,'n') "nanan" from the node (1,3,3,2) "ana".  "abracadabra" gives 25: 18 of length 2; cab, cac, dac,
+ * dad, rab, rad from the node (0,5,1,1) "a", whose fourth child is the INF row of item 1; dabrac from the node (2,4,4,3) "abra".
+ * A block of n equal bytes c gives exactly one word, c repeated n + 1 times (n = 1 included).
+ * Filters: min_len <= len <= max_len is kept; min_len 0 or 1 behaves as 2, max_len 0 means no limit; min_len > max_len with
+ * max_len != 0 is ARCHON_E_ARG.  A node with l + 2 outside the filter does no set work (the root counts as l = 0): words up to
+ * a small length is the common use, and cheap.
+ * Cap rule (that of archon_hip_repeats): *total is a host pointer and always written.  out NULL: counting only.  cap < *total
+ * with out given: ARCHON_E_ARG, out untouched.  (More than 2^32 - 1 words are counted but not emitted: ARCHON_E_ARG.)
+ * Bad input.  An sa value outside 1..n: ARCHON_E_CORRUPT, the outputs untouched (*total is 0).  Arrays that are not the SA, LCP
+ * array or BWT of anything return ARCHON_OK with unspecified contents; every access stays inside the buffers, and a node is
+ * left after 257 children.  Null pointers, n = 0, base_id >= n or the filter above: ARCHON_E_ARG with *total = 0.
+ * Method (csrc/maw.hiph).  The check of sa; the minimum hierarchy over lcp and the flag sums S of a repeats call of kind 1, so
+ * that right-uniform is S[hi] == S[lo + 1]; a rank table over the BWT (the FM index's; the host and device forms build one over
+ * a copy of bwt for the call, the block form uses and keeps the block's own).  Then one pass, run twice (count, and emit behind
+ * a scan of the tile words): every lane settles one row as the repeats pass does, and the wave then takes the rows that are
+ * nodes one after the other: B(node), then child by child (one right search for the next cut) B(child) and
+ * popc(B(node) & ~B(child)) words.  A set over at most direct_rows (64) rows is read from bwt, a row per lane; a longer one is
+ * ONE expansion of the rank table (all 256 children of the range at once; the ones that are nonempty are the set).
+ * Bounds, for any arrays: the children of all nodes together are at most 2n; per row one left search, per node and per child
+ * one right search, each within the repeats bound of 2F - 1 entries per level; a set costs at most 64 row reads or one
+ * expansion.  A block of one byte has n - 1 nested intervals of which all but [0, n) are right-uniform: they are dropped after
+ * the left search and one comparison of S, and [0, n) gives the one word.
+ * Launches: 1 (check) + levels + 3 (flag sums) + 1 counting, 2 more with the emit pass; the host and device forms add the 3 of
+ * the table, the block form only when it builds the block's.  Host waits: 1 counting, 2 with the emit pass; 1 more for a table
+ * that is built; the block form adds those of its LCP step.
+ * Workspace, from the calling thread's context arena: that of a repeats call of kind 1 (4 (n + 1) bytes of S, about 4 n / (F-1)
+ * of hierarchy) and n / 64 bytes of tile words; the host and device forms hold a copy of the BWT and its table (about 1.5 n
+ * bytes) for the duration of the call. */
+typedef struct archon_hip_maw {
+    uint32_t lo, hi;            /* the rows of a.w: the occurrences of the word without its last byte */
+    uint32_t len;               /* the length of the word, l + 2 */
+    uint32_t item;              /* sa[lo]: a.w = x[item-len+1 .. item) */
+    uint32_t last;              /* b (0..255) */
+} archon_hip_maw;               /* 20 bytes; the word is x[item-len+1 .. item) followed by `last` */
+/* device sa[n], lcp[n], bwt[n] and out (any 4-byte aligned address); on `stream` (NULL = the context's own), complete on return */
+int  archon_hip_maws_dev(const uint32_t *d_sa, const uint32_t *d_lcp, const uint8_t *d_bwt, uint32_t n, uint32_t base_id, uint32_t min_len,
+                         uint32_t max_len, archon_hip_maw *d_out_or_null, uint64_t cap, uint64_t *total, int dev, void *stream);
+/* host sa[n], lcp[n], bwt[n] and out */
+int  archon_hip_maws(const uint32_t *sa, const uint32_t *lcp, const uint8_t *bwt, uint32_t n, uint32_t base_id, uint32_t min_len, uint32_t max_len,
+                     archon_hip_maw *out_or_null, uint64_t cap, uint64_t *total, int dev);
+/* the resident block of the handle's last forward and its suffix array (ARCHON_E_ARG when that forward kept none): its LCP array
+ * is computed on the device as archon_hip_block_repeats does; the rank table is the block's own, built on the first FM call
+ * after a forward and kept -- this call builds it when it is missing and says so (`built`).  out is a host buffer. */
+int  archon_hip_block_maws(archon_hip_block *b, uint32_t min_len, uint32_t max_len, archon_hip_maw *out_or_null, uint64_t cap, uint64_t *total);
+/* the CALLING THREAD's last call of this family on `dev`; these calls leave every other record alone (the block form also keeps
+ * the LCP record of its LCP step).  Every counter but the two sets_* and probes follows from x and the filters alone; sets_*
+ * from x, the filters and direct_rows; probes also from the fan-out */
+typedef struct archon_hip_maw_stats {
+    uint32_t n, min_len, max_len;   /* of the call, as given */
+    uint32_t fan, levels;       /* fan-out and levels of the minimum hierarchy over lcp */
+    uint32_t direct_rows;       /* a set over at most this many rows is read from bwt, a longer one from the rank table */
+    uint32_t built;             /* 1 when this call built a rank table */
+    uint32_t kernel_launches;   /* launches issued by the call (block form: without those of its LCP step) */
+    uint32_t host_syncs;        /* times the host waited for the stream inside the call (block form: the LCP step's included) */
+    uint32_t absent_bytes;      /* 256 less the bytes that occur in x: the absent words of length 1 */
+    uint32_t shortest, longest; /* of the words that passed; 0 when there is none */
+    uint64_t intervals;         /* all LCP intervals, as a repeats call reports them */
+    uint64_t nodes;             /* the root and the maximal repeats, of those whose l + 2 passes the filter */
+    uint64_t children;          /* children visited over those nodes, the INF ones included */
+    uint64_t sets_direct;       /* byte sets read from bwt: one per node and one per child with a byte */
+    uint64_t sets_table;        /* ... taken from the rank table */
+    uint64_t words;             /* *total */
+    uint64_t probes;            /* entries of the hierarchy the searches read */
+    float ms_lcp;               /* block form: device time of the LCP step */
+    float ms_build;             /* device time of the table build, when built */
+    float ms_count;             /* device time of the check, the hierarchy, the flag sums and the count pass */
+    float ms_emit;              /* device time of the scan of the tile words and the emit pass */
+} archon_hip_maw_stats;
+/* (not named archon_hip_get_*_stats: it behaves as those do) */
+int  archon_hip_maw_last_stats(int dev, archon_hip_maw_stats *out);
 
 /* ---- matching statistics of a long text, and its relative LZ parse against the block ------------------------------------------
  * archon_hip_fm_ms runs one wave per pattern, so one long pattern runs on one wave.  These calls take ONE text P of m bytes --
