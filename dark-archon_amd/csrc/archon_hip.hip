@@ -29,6 +29,7 @@
 #include "lz.hiph"
 #include "kmers.hiph"
 #include "maw.hiph"
+#include "entropy.hiph"
 
 #include <limits.h>
 #include <stdlib.h>
@@ -112,6 +113,32 @@ static int maws_check(const void *sa, const void *lcp, const void *bwt, uint64_t
     ARCHON_TRY(check_n(n));
     if (base_id >= n) { set_error("primary row %u out of range [0, %u)", base_id, n); return ARCHON_E_ARG; }
     return maw_check_filters(min_len, max_len);
+}
+
+// the records are zeroed by any refusal of the arguments
+static int entropy_args(const void *sa, const void *lcp, const void *bwt, uint32_t n, uint32_t base_id, const uint32_t *ks, uint32_t nk, const void *out)
+{
+    ARCHON_TRY(ent_check_orders(ks, nk, out));
+    if (!sa || !lcp || !bwt) { set_error("null pointer"); return ARCHON_E_ARG; }
+    ARCHON_TRY(check_n(n));
+    if (base_id >= n) { set_error("primary row %u out of range [0, %u)", base_id, n); return ARCHON_E_ARG; }
+    return ARCHON_OK;
+}
+static int entropy_check(const void *sa, const void *lcp, const void *bwt, uint32_t n, uint32_t base_id, const uint32_t *ks, uint32_t nk, struct archon_hip_entropy *out)
+{
+    return ent_refused(entropy_args(sa, lcp, bwt, n, base_id, ks, nk, out), out, nk);
+}
+
+static int complexity_args(const void *lcp, uint32_t n, const void *rec)
+{
+    if (!lcp || !rec) { set_error("null pointer"); return ARCHON_E_ARG; }
+    return check_n(n);
+}
+static int complexity_check(const void *lcp, uint32_t n, struct archon_hip_complexity *rec)
+{
+    const int rc = complexity_args(lcp, n, rec);
+    if (rc != ARCHON_OK && rec) memset(rec, 0, sizeof *rec);
+    return rc;
 }
 
 // ---- the FM index: text calls, documents
@@ -645,6 +672,66 @@ int archon_hip_maws(const uint32_t *sa, const uint32_t *lcp, const uint8_t *bwt,
 }
 
 int archon_hip_maw_last_stats(int dev, archon_hip_maw_stats *out) { return t_maw_stats.get(dev, out, "minimal-absent-words call"); }
+
+// ---- order-k entropy, substring complexity and BWT runs (entropy.hiph: the kernels and their drivers; here the argument checks
+// and the statistics)
+int archon_hip_entropy_dev(const uint32_t *d_sa, const uint32_t *d_lcp, const uint8_t *d_bwt, uint32_t n, uint32_t base_id, const uint32_t *ks,
+                           uint32_t nk, struct archon_hip_entropy *out, int dev, void *stream)
+{
+    ARCHON_TRY(entropy_check(d_sa, d_lcp, d_bwt, n, base_id, ks, nk, out));
+    return with_ctx(dev, stream, [&](Ctx *c, hipStream_t s) -> int {
+        KeepStats<archon_hip_entropy_stats> keep(t_ent_stats, dev);
+        ent_call_stats(&keep.st, n, nk, 0);
+        return ent_over_copy(c, s, d_sa, d_lcp, nullptr, d_bwt, n, base_id, ks, nk, out, &keep.st);
+    });
+}
+
+// host buffers: sa and lcp through staging buffers 0 and 1, the BWT straight into the call's table
+int archon_hip_entropy(const uint32_t *sa, const uint32_t *lcp, const uint8_t *bwt, uint32_t n, uint32_t base_id, const uint32_t *ks, uint32_t nk,
+                       struct archon_hip_entropy *out, int dev)
+{
+    ARCHON_TRY(entropy_check(sa, lcp, bwt, n, base_id, ks, nk, out));
+    return with_ctx(dev, nullptr, [&](Ctx *c, hipStream_t s) -> int {
+        KeepStats<archon_hip_entropy_stats> keep(t_ent_stats, dev);
+        ent_call_stats(&keep.st, n, nk, 0);
+        uint32_t *d_sa = nullptr, *d_lcp = nullptr;
+        ARCHON_TRY(kmer_stage(c, s, sa, lcp, n, &d_sa, &d_lcp));
+        return ent_over_copy(c, s, d_sa, d_lcp, bwt, nullptr, n, base_id, ks, nk, out, &keep.st);
+    });
+}
+
+int archon_hip_complexity_dev(const uint32_t *d_lcp, const uint8_t *d_bwt_or_null, uint32_t n, uint32_t max_len, uint32_t *d_counts_or_null,
+                              struct archon_hip_complexity *rec, int dev, void *stream)
+{
+    ARCHON_TRY(complexity_check(d_lcp, n, rec));
+    return with_ctx(dev, stream, [&](Ctx *c, hipStream_t s) -> int {
+        KeepStats<archon_hip_entropy_stats> keep(t_ent_stats, dev);
+        ent_call_stats(&keep.st, n, 0, 1);
+        return cx_run(c, s, d_lcp, d_bwt_or_null, n, max_len, d_counts_or_null, false, rec, &keep.st);
+    });
+}
+
+// host buffers: lcp through staging buffer 1, the BWT through buffer 0
+int archon_hip_complexity(const uint32_t *lcp, const uint8_t *bwt_or_null, uint32_t n, uint32_t max_len, uint32_t *counts_or_null,
+                          struct archon_hip_complexity *rec, int dev)
+{
+    ARCHON_TRY(complexity_check(lcp, n, rec));
+    return with_ctx(dev, nullptr, [&](Ctx *c, hipStream_t s) -> int {
+        KeepStats<archon_hip_entropy_stats> keep(t_ent_stats, dev);
+        ent_call_stats(&keep.st, n, 0, 1);
+        uint32_t *d_lcp = nullptr;
+        uint8_t *d_bwt = nullptr;
+        ARCHON_TRY(ctx_io(c, 1, (size_t)n * 4 + 64, (void **)&d_lcp));
+        ARCHON_HIP_TRY(hipMemcpyAsync(d_lcp, lcp, (size_t)n * 4, hipMemcpyHostToDevice, s));
+        if (bwt_or_null) {
+            ARCHON_TRY(ctx_io(c, 0, (size_t)n + 64, (void **)&d_bwt));
+            ARCHON_HIP_TRY(hipMemcpyAsync(d_bwt, bwt_or_null, n, hipMemcpyHostToDevice, s));
+        }
+        return cx_run(c, s, d_lcp, d_bwt, n, max_len, counts_or_null, true, rec, &keep.st);
+    });
+}
+
+int archon_hip_entropy_last_stats(int dev, archon_hip_entropy_stats *out) { return t_ent_stats.get(dev, out, "entropy call"); }
 
 // ---- the FM index (fm_host.hiph: the handle and every driver; here the argument checks and the statistics)
 int archon_hip_fm_create(const uint8_t *bwt, uint32_t n, uint32_t base_id, int dev, archon_hip_fm **out)
@@ -1374,6 +1461,45 @@ int archon_hip_block_maws(archon_hip_block *b, uint32_t min_len, uint32_t max_le
         ARCHON_TRY(block_fm_table_own(c, s, b, &keep.st));
         const MawCall q = {b->d_sa(), d_lcp, b->fm->table(), min_len, max_len};
         return maw_run(c, s, q, out_or_null, cap, total, true, &keep.st);
+    });
+}
+
+// the LCP array into staging buffer 1, the block's own rank table (built here when no FM call has); one wait for all orders
+int archon_hip_block_entropy(archon_hip_block *b, const uint32_t *ks, uint32_t nk, struct archon_hip_entropy *out)
+{
+    ARCHON_TRY(ent_refused(ent_check_orders(ks, nk, out), out, nk));
+    if (!b) { set_error("null pointer"); return ent_refused(ARCHON_E_ARG, out, nk); }
+    std::lock_guard<std::mutex> lkb(b->mu);
+    ARCHON_TRY(ent_refused(block_check(b, true), out, nk));
+    return with_ctx(b->dev, nullptr, [&](Ctx *c, hipStream_t s) -> int {
+        KeepStats<archon_hip_entropy_stats> keep(t_ent_stats, b->dev);
+        ent_call_stats(&keep.st, b->n, nk, 0);
+        uint32_t *d_lcp = nullptr;
+        ARCHON_TRY(block_lcp_step(c, s, b, &d_lcp, &keep.st.ms_lcp));
+        ARCHON_TRY(block_fm_table_own(c, s, b, &keep.st));
+        return ent_run(c, s, b->d_sa(), d_lcp, b->fm->table(), ks, nk, out, &keep.st);
+    });
+}
+
+// the LCP array into staging buffer 1; the runs are those of the resident BWT
+int archon_hip_block_complexity(archon_hip_block *b, uint32_t max_len, uint32_t *counts_or_null, struct archon_hip_complexity *rec)
+{
+    if (!b || !rec) {
+        if (rec) memset(rec, 0, sizeof *rec);
+        set_error("null pointer");
+        return ARCHON_E_ARG;
+    }
+    std::lock_guard<std::mutex> lkb(b->mu);
+    if (block_check(b, true) != ARCHON_OK) {
+        memset(rec, 0, sizeof *rec);
+        return ARCHON_E_ARG;
+    }
+    return with_ctx(b->dev, nullptr, [&](Ctx *c, hipStream_t s) -> int {
+        KeepStats<archon_hip_entropy_stats> keep(t_ent_stats, b->dev);
+        ent_call_stats(&keep.st, b->n, 0, 1);
+        uint32_t *d_lcp = nullptr;
+        ARCHON_TRY(block_lcp_step(c, s, b, &d_lcp, &keep.st.ms_lcp));
+        return cx_run(c, s, d_lcp, b->d_bwt(), b->n, max_len, counts_or_null, true, rec, &keep.st);
     });
 }
 

@@ -54,6 +54,8 @@ SYMBOLS = [
     "archon_hip_kmers", "archon_hip_kmers_dev", "archon_hip_block_kmers", "archon_hip_kmer_occ", "archon_hip_kmer_occ_dev", "archon_hip_block_kmer_occ",
     "archon_hip_sus", "archon_hip_sus_dev", "archon_hip_block_sus", "archon_hip_get_kmer_stats",
     "archon_hip_maws", "archon_hip_maws_dev", "archon_hip_block_maws", "archon_hip_maw_last_stats",
+    "archon_hip_entropy", "archon_hip_entropy_dev", "archon_hip_block_entropy", "archon_hip_complexity", "archon_hip_complexity_dev",
+    "archon_hip_block_complexity", "archon_hip_entropy_last_stats",
 ]
 
 # archon_hip_fm_hit: one distinct string within the distance of a pattern (FmIndex.approx, Block.fm_approx)
@@ -77,6 +79,10 @@ KMER = np.dtype([("lo", "<u4"), ("hi", "<u4"), ("item", "<u4")])
 # archon_hip_maw: one minimal absent word of a block (maws, Block.maws): rows [lo, hi) of the word without its last byte, the
 # word's length, item = sa[lo]: the bytes x[item-len+1 .. item) followed by `last`
 MAW = np.dtype([("lo", "<u4"), ("hi", "<u4"), ("len", "<u4"), ("item", "<u4"), ("last", "<u4")])
+# struct archon_hip_entropy: the order-k statistics of a block (entropy, Block.entropy): the contexts of length k that a byte
+# follows, those always followed by the same byte, the distinct (context, byte) pairs, n - k, and bits = n * H_k
+ENTROPY = np.dtype([("k", "<u4"), ("reserved", "<u4"), ("contexts", "<u8"), ("deterministic", "<u8"), ("pairs", "<u8"), ("symbols", "<u8"),
+                    ("bits", "<f8")])
 
 
 class _Record(ctypes.Structure):
@@ -257,6 +263,25 @@ class MawStats(_Record):
     ]
 
 
+class Complexity(_Record):
+    """struct archon_hip_complexity: the substring complexity of a block and the runs of its BWT (complexity, Block.complexity)"""
+    _fields_ = [
+        ("n", ctypes.c_uint32), ("max_len", ctypes.c_uint32), ("lcp_max", ctypes.c_uint32), ("delta_len", ctypes.c_uint32),
+        ("delta_count", ctypes.c_uint32), ("delta_exact", ctypes.c_uint32), ("longest_run", ctypes.c_uint32), ("reserved", ctypes.c_uint32),
+        ("lcp_sum", ctypes.c_uint64), ("substrings", ctypes.c_uint64), ("runs", ctypes.c_uint64),
+    ]
+
+
+class EntropyStats(_Record):
+    """archon_hip_entropy_stats: the calling thread's last entropy or complexity call on a device"""
+    _fields_ = [
+        ("n", ctypes.c_uint32), ("nk", ctypes.c_uint32), ("what", ctypes.c_uint32), ("tile", ctypes.c_uint32),
+        ("direct_rows", ctypes.c_uint32), ("built", ctypes.c_uint32), ("kernel_launches", ctypes.c_uint32), ("host_syncs", ctypes.c_uint32),
+        ("groups_direct", ctypes.c_uint64), ("groups_table", ctypes.c_uint64), ("groups_in_wave", ctypes.c_uint64),
+        ("ms_lcp", ctypes.c_float), ("ms_build", ctypes.c_float), ("ms_count", ctypes.c_float),
+    ]
+
+
 class ArchonError(RuntimeError):
     def __init__(self, code, msg):
         super().__init__("archon_hip error %d: %s" % (code, msg))
@@ -405,6 +430,13 @@ def load():
         "archon_hip_maws_dev": [vp, vp, vp, u32, u32, u32, u32, vp, ctypes.c_uint64, vp, i32, vp],
         "archon_hip_block_maws": [vp, u32, u32, vp, ctypes.c_uint64, vp],
         "archon_hip_maw_last_stats": [i32, ctypes.POINTER(MawStats)],
+        "archon_hip_entropy": [vp, vp, vp, u32, u32, vp, u32, vp, i32],
+        "archon_hip_entropy_dev": [vp, vp, vp, u32, u32, vp, u32, vp, i32, vp],
+        "archon_hip_block_entropy": [vp, vp, u32, vp],
+        "archon_hip_complexity": [vp, vp, u32, u32, vp, ctypes.POINTER(Complexity), i32],
+        "archon_hip_complexity_dev": [vp, vp, u32, u32, vp, ctypes.POINTER(Complexity), i32, vp],
+        "archon_hip_block_complexity": [vp, u32, vp, ctypes.POINTER(Complexity)],
+        "archon_hip_entropy_last_stats": [i32, ctypes.POINTER(EntropyStats)],
     }.items():
         fn = getattr(lib, name)
         fn.argtypes = args
@@ -828,6 +860,49 @@ def maw_bytes(x, rec):
     if ln < 2 or item < ln - 1 or item > len(x) or last > 255:
         raise ValueError("maw_bytes: a record outside the block (item %d, len %d, last %d)" % (item, ln, last))
     return x[item - ln + 1:item] + bytes([last])
+
+
+def entropy_stats(dev=0):
+    """EntropyStats of the calling thread's last entropy or complexity call on dev"""
+    return _last_stats(EntropyStats, "archon_hip_entropy_last_stats", dev)
+
+
+def _orders(ks):
+    """(the orders as a uint32 array, an ENTROPY array for their records)"""
+    ks = np.ascontiguousarray(np.atleast_1d(ks), dtype=np.uint32)
+    return ks, np.zeros(max(ks.size, 1), ENTROPY)
+
+
+def entropy(sa, lcp, bwt, base_id, ks, dev=0):
+    """the order-k statistics of a block from its suffix array, LCP array and BWT (include/archon_hip.h: archon_hip_entropy): an
+    ENTROPY array, one record per order in ks (1 .. 64 of them), in that order; bits is n * H_k"""
+    sa, lcp = _sa_lcp("entropy", sa, lcp)
+    bwt = np.ascontiguousarray(bwt, dtype=np.uint8)
+    if bwt.size != sa.size:
+        raise ValueError("entropy: sa has %d rows, bwt %d" % (sa.size, bwt.size))
+    ks, out = _orders(ks)
+    _check(lib().archon_hip_entropy(_p(sa), _p(lcp), _p(bwt), sa.size, int(base_id), _p(ks), ks.size, _p(out), dev))
+    return out[:ks.size]
+
+
+def complexity_len(n, max_len=0):
+    """the lengths a complexity call covers: max_len 0 is min(n, 4095), more than n is n"""
+    return min(int(max_len) or 4095, int(n))
+
+
+def complexity(lcp, bwt=None, max_len=0, dev=0):
+    """the substring complexity of a block from its LCP array and, with bwt, the runs of its BWT (include/archon_hip.h:
+    archon_hip_complexity): (Complexity, counts) with counts[l-1] = the distinct substrings of length l, l = 1 .. max_len (0:
+    min(n, 4095); more than n: n)"""
+    lcp = np.ascontiguousarray(lcp, dtype=np.uint32)
+    if bwt is not None:
+        bwt = np.ascontiguousarray(bwt, dtype=np.uint8)
+        if bwt.size != lcp.size:
+            raise ValueError("complexity: lcp has %d rows, bwt %d" % (lcp.size, bwt.size))
+    rec = Complexity()
+    counts = np.zeros(max(complexity_len(lcp.size, max_len), 1), np.uint32)
+    _check(lib().archon_hip_complexity(_p(lcp), _p(bwt) if bwt is not None else None, lcp.size, int(max_len), _p(counts), ctypes.byref(rec), dev))
+    return rec, counts[:rec.max_len]
 
 
 def _kmers_as_mems(recs, k):
@@ -1546,6 +1621,21 @@ class Block:
         fn = lib().archon_hip_block_maws
         return _maws(lambda out, cap, tp: fn(self.h, int(min_len), int(max_len), out, cap, tp), count_only)
 
+    def entropy(self, ks):
+        """the order-k statistics of the resident block (needs forward(want_sa=True)): its LCP array is made and consumed on the
+        device, the rank table is the block's own (built here when no FM call has).  An ENTROPY array, one record per order"""
+        ks, out = _orders(ks)
+        _check(lib().archon_hip_block_entropy(self.h, _p(ks), ks.size, _p(out)))
+        return out[:ks.size]
+
+    def complexity(self, max_len=0):
+        """the substring complexity of the resident block and the runs of its BWT (needs forward(want_sa=True)): (Complexity,
+        counts) with counts[l-1] = the distinct substrings of length l, l = 1 .. max_len (0: min(n, 4095); more than n: n)"""
+        rec = Complexity()
+        counts = np.zeros(max(complexity_len(self.n, max_len), 1), np.uint32)
+        _check(lib().archon_hip_block_complexity(self.h, int(max_len), _p(counts), ctypes.byref(rec)))
+        return rec, counts[:rec.max_len]
+
     def lz(self, dir=0, want_lpf=False, count_only=False):
         """the LZ77 parse of the resident block (needs forward(want_sa=True)): its LCP array and its LPF records are made and
         consumed on the device.  A PHRASE array in chain order (the phrase ending at n first), or the number of phrases with
@@ -1692,6 +1782,29 @@ def maws_dev(sa_t, lcp_t, bwt_t, base_id, min_len=2, max_len=0, out_t=None):
                                      int(base_id), int(min_len), int(max_len), ctypes.c_void_p(out_t.data_ptr()) if out_t is not None else None, cap,
                                      ctypes.cast(ctypes.byref(total), ctypes.c_void_p), dev, _stream_ptr()))
     return total.value
+
+
+def entropy_dev(sa_t, lcp_t, bwt_t, base_id, ks):
+    """torch CUDA tensors: sa and lcp int32[n], bwt uint8[n]; ks on the host; on the current stream.  An ENTROPY array, one record
+    per order"""
+    dev = sa_t.device.index or 0
+    ks, out = _orders(ks)
+    _check(lib().archon_hip_entropy_dev(ctypes.c_void_p(sa_t.data_ptr()), ctypes.c_void_p(lcp_t.data_ptr()), ctypes.c_void_p(bwt_t.data_ptr()), sa_t.numel(),
+                                        int(base_id), _p(ks), ks.size, _p(out), dev, _stream_ptr()))
+    return out[:ks.size]
+
+
+def complexity_dev(lcp_t, bwt_t=None, max_len=0, counts_t=None):
+    """torch CUDA tensors: lcp int32[n], bwt uint8[n] or None, counts an int32 tensor of at least complexity_len(n, max_len) words or
+    None; on the current stream.  Returns the Complexity record"""
+    dev = lcp_t.device.index or 0
+    if counts_t is not None and counts_t.numel() < complexity_len(lcp_t.numel(), max_len):
+        raise ValueError("complexity_dev: counts holds %d words, the call writes %d" % (counts_t.numel(), complexity_len(lcp_t.numel(), max_len)))
+    rec = Complexity()
+    _check(lib().archon_hip_complexity_dev(ctypes.c_void_p(lcp_t.data_ptr()), ctypes.c_void_p(bwt_t.data_ptr()) if bwt_t is not None else None, lcp_t.numel(),
+                                           int(max_len), ctypes.c_void_p(counts_t.data_ptr()) if counts_t is not None else None, ctypes.byref(rec), dev,
+                                           _stream_ptr()))
+    return rec
 
 
 def validate_resident_dev(x_t, sa_t, bwt_t, base_id):

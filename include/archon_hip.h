@@ -27,6 +27,8 @@
  *   archon_hip_kmers*, _kmer_occ*, _sus*   nothing: the k-mers of a block with their counts, the count of the k-mer at every
  *                           position and the shortest unique substring ending at every item, from the SA and LCP array
  *   archon_hip_maws*        nothing: the minimal absent words of a block, from the SA, the LCP array and the BWT
+ *   archon_hip_entropy*, _complexity*   nothing: the order-k statistics and entropy of a block, its substring complexity and the
+ *                           runs of its BWT, from the SA, the LCP array and the BWT
  *
  * Ordering convention ("a7 order"): item s in 1..N names the
  * reversed prefix x[s-1],x[s-2],...,x[0],INF with INF > 255; sa[0..N) lists the
@@ -1125,6 +1127,112 @@ typedef struct archon_hip_maw_stats {
 } archon_hip_maw_stats;
 /* (not named archon_hip_get_*_stats: it behaves as those do) */
 int  archon_hip_maw_last_stats(int dev, archon_hip_maw_stats *out);
+
+/* ---- order-k entropy, substring complexity and BWT runs of a block (no counterpart in the reference) ----------------------------
+ * How compressible is this block, and at which context order?  Block-sorting coders are judged against the empirical entropy H_k;
+ * the usual measures of repetitiveness are z (LZ77 phrases: archon_hip_block_lz), r (the runs of the BWT) and delta (the substring
+ * complexity).  Rows, items, sa, lcp, bwt, the primary row `base` and a7 order are those of the repeats and k-mer sections;
+ * lcp[0] reads as 0.
+ * 1. Order-k statistics, k >= 0.  By the text: for every string w of length k let F_w be the multiset of the bytes x[p] with
+ * k <= p < n and x[p-k .. p) = w (an occurrence of w at the very end of x is followed by nothing and adds nothing).  contexts =
+ * the w with F_w not empty; deterministic = the w with exactly one distinct byte in F_w; pairs = the sum over w of the distinct
+ * bytes of F_w, which is the number of distinct (k+1)-mers of x; symbols = the sum of |F_w| = max(n - k, 0); bits = the sum over
+ * w and c of n_wc log2(|F_w| / n_wc) = n H_k(x).  By rows, k >= 1: the groups are those of archon_hip_kmers; a group with
+ * sa[lo] < k is a short row and adds nothing; for a k-mer group [lo, hi), F is bwt[r] for r in [lo, hi), r != base; a group left
+ * empty by that (the single row base) is no context.  k = 0: one group [0, n), and bwt[base] = x[0] counts, so that bits is
+ * n H_0(x).  k > n: the record is all zero but for k.
+ * Examples.  "banana" (BWT nnbaaa, base 2): k = 0 gives contexts 1, deterministic 0, pairs 3, symbols 6, bits 8.754887502163468;
+ * k = 1, 2, 3 give (3, 3, 3, 6 - k, 0.0).  "abracadabra": k = 0 (1, 0, 5, 11, 22.44410733057346), k = 1 (5, 4, 7, 10, 6.0),
+ * k = 2 (7, 7, 7, 9, 0.0).  pairs at k equals `distinct` of an archon_hip_kmers call at k + 1; bits never grows with k.
+ * 2. Substring complexity.  d_l, the number of distinct substrings of length l, is n - l + 1 - #{i >= 1 : lcp[i] >= l}: each of the
+ * n - l + 1 items of length at least l starts a new l-mer unless it shares l symbols with the row before it.  counts[l-1] = d_l for
+ * l = 1 .. max_len; max_len 0 behaves as min(n, 4095), a value above n as n.  substrings = n (n + 1) / 2 - lcp_sum is the number
+ * of all distinct substrings.  delta = max over l of d_l / l is reported as (delta_len, delta_count), compared exactly by 64-bit
+ * cross-multiplication, ties to the smallest l, over l <= max_len; delta_exact = 1 when max_len == n or
+ * delta_count (max_len + 1) >= (n - max_len) delta_len: no longer l can beat it, since d_l <= n - l + 1.
+ * 3. BWT runs.  runs = 1 + #{i >= 1 : bwt[i] != bwt[i-1]} over the n stored bytes, the one at base included: what the -m stage
+ * sees.  longest_run is the length of the longest one.  Without a bwt both are 0.
+ * Examples.  "banana": d = 3 3 3 3 2 1, substrings 15, lcp_sum 6, lcp_max 3, delta (1, 3), runs 3, longest_run 3.
+ * "abracadabra": d = 5 7 7 7 7 6 5 4 3 2 1, substrings 54, lcp_sum 12, lcp_max 4, delta (1, 5), runs 7, longest_run 4.
+ * Arguments.  ks[nk] and out[nk] are host arrays, 1 <= nk <= 64; the records come in the order of ks.  rec is a host pointer.
+ * Bad input.  Null pointers (counts and, for complexity, bwt may be null), n = 0, nk outside 1..64 and base_id >= n:
+ * ARCHON_E_ARG, with the records zeroed.  An sa value outside 1..n: ARCHON_E_CORRUPT, the outputs untouched.  Arrays that are
+ * not the SA, LCP array or BWT of anything return ARCHON_OK with unspecified contents; every access stays inside the buffers.  No
+ * GPU: ARCHON_E_NODEVICE; there is no CPU fallback.
+ * Method (csrc/entropy.hiph).  Per order k >= 1 the bounds, scan and starts passes of a k-mer call, then the follower pass over
+ * tiles of rows (the tile is that of the k-mer passes) and a reduction.  The 64 rows a wave holds in one step are its window.  A
+ * group inside the window is settled by the wave without a loop over rows: each lane holds (group, byte), and the classes of
+ * equal pairs are peeled by a ballot and a popcount, the first lane of a class adding c log2(m / c); a group of one row costs
+ * nothing (groups_in_wave).  A group of at most direct_rows (64) rows that ends past the window belongs to the wave that holds
+ * its first row, which reads bwt[lo .. hi), a row per lane (groups_direct).  A longer group is ONE expansion of the FM index's
+ * rank table: the 256 child sizes are the follower counts, the primary row left out (groups_table), so a block of one byte at
+ * k = 5 is one expansion, not n row reads.  No group is read by two waves.  Order 0 is one expansion of [0, n) and x[0].  bits is
+ * summed in doubles without floating-point atomics -- lanes, wave, tile slot, then a fixed-order reduction --, so the same call
+ * with the same tile gives the same 64 bits on every run.  The host and device forms build a rank table over a copy of bwt for
+ * the call, the block form uses and keeps the block's own.  Complexity: a histogram of lcp (bins below 4096 in LDS per workgroup,
+ * higher ones by global atomics, values of max_len and above in the last bin), one streaming pass over bwt for the runs, and one
+ * workgroup for the suffix sums, the arg-max and the longest run.
+ * Launches: entropy 5 per order in 1..n, 1 for order 0, none for an order above n; the host and device forms add the 3 of the
+ * table, the block form only when it builds the block's.  Complexity 2, 3 with a bwt.  Host waits: ONE per call, however many
+ * orders it takes -- the words of the orders stay on the device until the end; the host and device forms of entropy add 1 for the
+ * table they build, the block forms those of their LCP step (and 1 for a table that is built).
+ * Workspace, from the calling thread's context arena: entropy that of a k-mer call, 8 bytes per tile and 4 KiB of records;
+ * complexity 8 max_len bytes and 12 bytes per tile of rows. */
+/* (the two records share their names with the host forms below, as struct stat does with stat(): they have no typedef and are
+ * written `struct archon_hip_entropy`, `struct archon_hip_complexity`) */
+struct archon_hip_entropy {               /* 48 bytes */
+    uint32_t k, reserved;
+    uint64_t contexts;          /* the k-mers that are followed by a byte somewhere */
+    uint64_t deterministic;     /* ... always by the same one */
+    uint64_t pairs;             /* distinct (context, byte) pairs: the distinct (k+1)-mers */
+    uint64_t symbols;           /* max(n - k, 0) */
+    double   bits;              /* n * H_k */
+};
+struct archon_hip_complexity {            /* 56 bytes */
+    uint32_t n, max_len;        /* max_len as the call used it */
+    uint32_t lcp_max;
+    uint32_t delta_len, delta_count;    /* the l <= max_len with the largest d_l / l (the smallest such l), and d_l */
+    uint32_t delta_exact;       /* 1: no l above max_len can beat it */
+    uint32_t longest_run, reserved;
+    uint64_t lcp_sum, substrings;
+    uint64_t runs;              /* runs, longest_run 0 without a bwt */
+};
+/* device sa[n], lcp[n], bwt[n]; ks and out on the host; on `stream` (NULL = the context's own), complete on return */
+int  archon_hip_entropy_dev(const uint32_t *d_sa, const uint32_t *d_lcp, const uint8_t *d_bwt, uint32_t n, uint32_t base_id, const uint32_t *ks,
+                            uint32_t nk, struct archon_hip_entropy *out, int dev, void *stream);
+/* host sa[n], lcp[n], bwt[n] */
+int  archon_hip_entropy(const uint32_t *sa, const uint32_t *lcp, const uint8_t *bwt, uint32_t n, uint32_t base_id, const uint32_t *ks, uint32_t nk,
+                        struct archon_hip_entropy *out, int dev);
+/* the resident block of the handle's last forward and its suffix array (ARCHON_E_ARG when that forward kept none): its LCP array
+ * is computed on the device as archon_hip_block_kmers does; the rank table is the block's own, built on the first FM call after
+ * a forward and kept -- this call builds it when it is missing and says so (`built`) */
+int  archon_hip_block_entropy(archon_hip_block *b, const uint32_t *ks, uint32_t nk, struct archon_hip_entropy *out);
+/* device lcp[n], bwt[n] or NULL, counts[max_len as used] or NULL (any 4-byte aligned address); rec on the host */
+int  archon_hip_complexity_dev(const uint32_t *d_lcp, const uint8_t *d_bwt_or_null, uint32_t n, uint32_t max_len, uint32_t *d_counts_or_null,
+                               struct archon_hip_complexity *rec, int dev, void *stream);
+/* host lcp[n], bwt[n] or NULL, counts or NULL */
+int  archon_hip_complexity(const uint32_t *lcp, const uint8_t *bwt_or_null, uint32_t n, uint32_t max_len, uint32_t *counts_or_null,
+                           struct archon_hip_complexity *rec, int dev);
+/* the resident block, its suffix array and its BWT; counts is a host buffer */
+int  archon_hip_block_complexity(archon_hip_block *b, uint32_t max_len, uint32_t *counts_or_null, struct archon_hip_complexity *rec);
+/* the CALLING THREAD's last call of this family on `dev`; these calls leave every other record alone (the block forms also keep
+ * the LCP record of their LCP step).  The three groups_* follow from x, the orders, the tile and direct_rows */
+typedef struct archon_hip_entropy_stats {
+    uint32_t n, nk;             /* of the call (nk 0 for complexity) */
+    uint32_t what;              /* 0 entropy, 1 complexity */
+    uint32_t tile;              /* rows of a tile of the passes (test route KMER_TILE) */
+    uint32_t direct_rows;       /* a group of at most this many rows is read from bwt, a longer one from the rank table */
+    uint32_t built;             /* 1 when this call built a rank table */
+    uint32_t kernel_launches;   /* launches issued by the call (block forms: without those of the LCP step) */
+    uint32_t host_syncs;        /* times the host waited for the stream inside the call (block forms: the LCP step's included) */
+    uint64_t groups_direct;     /* summed over the orders: k-mer groups of 2 .. direct_rows rows that end past their wave's window */
+    uint64_t groups_table;      /* ... of more rows: one expansion each; order 0 counts one */
+    uint64_t groups_in_wave;    /* ... inside their wave's window, those of one row included */
+    float ms_lcp;               /* block forms: device time of the LCP step */
+    float ms_build;             /* device time of the table build, when built */
+    float ms_count;             /* device time of the passes */
+} archon_hip_entropy_stats;
+int  archon_hip_entropy_last_stats(int dev, archon_hip_entropy_stats *out);
 
 /* ---- matching statistics of a long text, and its relative LZ parse against the block ------------------------------------------
  * archon_hip_fm_ms runs one wave per pattern, so one long pattern runs on one wave.  These calls take ONE text P of m bytes --
