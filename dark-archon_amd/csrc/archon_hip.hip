@@ -30,6 +30,7 @@
 #include "kmers.hiph"
 #include "maw.hiph"
 #include "entropy.hiph"
+#include "runs.hiph"
 
 #include <limits.h>
 #include <stdlib.h>
@@ -139,6 +140,39 @@ static int complexity_check(const void *lcp, uint32_t n, struct archon_hip_compl
     const int rc = complexity_args(lcp, n, rec);
     if (rc != ARCHON_OK && rec) memset(rec, 0, sizeof *rec);
     return rc;
+}
+
+// *total is written whenever it is given: 0 before any refusal
+static int runs_check(const void *sa, const void *lcp, const void *sa_c, uint64_t *total, uint32_t n, uint32_t min_period, uint32_t max_period,
+                      uint32_t min_copies)
+{
+    if (total) *total = 0;
+    if (!sa || !lcp || !sa_c || !total) { set_error("null pointer"); return ARCHON_E_ARG; }
+    ARCHON_TRY(check_n(n));
+    return run_check_filters(min_period, max_period, min_copies);
+}
+
+static int lce_check(const void *sa, const void *lcp, uint32_t n, const void *s, const void *t, uint32_t k, const void *out)
+{
+    if (!sa || !lcp || (k && (!s || !t || !out))) { set_error("null pointer"); return ARCHON_E_ARG; }
+    return check_n(n);
+}
+
+// host items: one above n refuses the call before anything runs
+static int lce_check_items(const uint32_t *s, const uint32_t *t, uint32_t k, uint32_t n)
+{
+    for (uint32_t i = 0; i < k; ++i)
+        if (s[i] > n || t[i] > n) { set_error("lce: pair %u is (%u, %u), an item above %u", i, s[i], t[i], n); return ARCHON_E_ARG; }
+    return ARCHON_OK;
+}
+
+// host queries through staging buffer 2: s, t and the answers, k words each
+static int lce_stage(Ctx *c, hipStream_t st, const uint32_t *s, const uint32_t *t, uint32_t k, uint32_t **d_q)
+{
+    ARCHON_TRY(ctx_io(c, 2, (size_t)k * 12 + 64, (void **)d_q));
+    ARCHON_HIP_TRY(hipMemcpyAsync(*d_q, s, (size_t)k * 4, hipMemcpyHostToDevice, st));
+    ARCHON_HIP_TRY(hipMemcpyAsync(*d_q + k, t, (size_t)k * 4, hipMemcpyHostToDevice, st));
+    return ARCHON_OK;
 }
 
 // ---- the FM index: text calls, documents
@@ -732,6 +766,71 @@ int archon_hip_complexity(const uint32_t *lcp, const uint8_t *bwt_or_null, uint3
 }
 
 int archon_hip_entropy_last_stats(int dev, archon_hip_entropy_stats *out) { return t_ent_stats.get(dev, out, "entropy call"); }
+
+// ---- runs and longest common extensions (runs.hiph: the kernels and their drivers; here the argument checks and the statistics)
+int archon_hip_lce_dev(const uint32_t *d_sa, const uint32_t *d_lcp, uint32_t n, const uint32_t *d_s, const uint32_t *d_t, uint32_t k, uint32_t *d_out,
+                       int dev, void *stream)
+{
+    ARCHON_TRY(lce_check(d_sa, d_lcp, n, d_s, d_t, k, d_out));
+    if (!k) return ARCHON_OK;
+    return with_ctx(dev, stream, [&](Ctx *c, hipStream_t s) -> int {
+        KeepStats<archon_hip_run_stats> keep(t_run_stats, dev);
+        run_call_stats(&keep.st, n, 0, 0, 0, 0, 1);
+        return lce_run(c, s, d_sa, d_lcp, n, d_s, d_t, k, d_out, &keep.st);
+    });
+}
+
+// host buffers: sa and lcp through staging buffers 0 and 1, the queries and their answers through buffer 2
+int archon_hip_lce(const uint32_t *sa, const uint32_t *lcp, uint32_t n, const uint32_t *s, const uint32_t *t, uint32_t k, uint32_t *out, int dev)
+{
+    ARCHON_TRY(lce_check(sa, lcp, n, s, t, k, out));
+    if (!k) return ARCHON_OK;
+    ARCHON_TRY(lce_check_items(s, t, k, n));
+    return with_ctx(dev, nullptr, [&](Ctx *c, hipStream_t st) -> int {
+        KeepStats<archon_hip_run_stats> keep(t_run_stats, dev);
+        run_call_stats(&keep.st, n, 0, 0, 0, 0, 1);
+        uint32_t *d_sa = nullptr, *d_lcp = nullptr, *d_q = nullptr;
+        ARCHON_TRY(kmer_stage(c, st, sa, lcp, n, &d_sa, &d_lcp));
+        ARCHON_TRY(lce_stage(c, st, s, t, k, &d_q));
+        ARCHON_TRY(lce_run(c, st, d_sa, d_lcp, n, d_q, d_q + k, k, d_q + 2 * (size_t)k, &keep.st));
+        ARCHON_HIP_TRY(hipMemcpyAsync(out, d_q + 2 * (size_t)k, (size_t)k * 4, hipMemcpyDeviceToHost, st));
+        ARCHON_SYNC(st);
+        return ARCHON_OK;
+    });
+}
+
+int archon_hip_runs_dev(const uint32_t *d_sa, const uint32_t *d_lcp, const uint32_t *d_sa_c, uint32_t n, uint32_t min_period, uint32_t max_period,
+                        uint32_t min_copies, uint32_t min_len, archon_hip_run *d_out_or_null, uint64_t cap, uint64_t *total, int dev, void *stream)
+{
+    ARCHON_TRY(runs_check(d_sa, d_lcp, d_sa_c, total, n, min_period, max_period, min_copies));
+    return with_ctx(dev, stream, [&](Ctx *c, hipStream_t s) -> int {
+        KeepStats<archon_hip_run_stats> keep(t_run_stats, dev);
+        run_call_stats(&keep.st, n, min_period, max_period, min_copies, min_len, 0);
+        ARCHON_TRY(run_begin(c, s));
+        RunCall q = {d_sa, d_lcp, d_sa_c, nullptr, n, {min_period, max_period, min_copies, min_len}};
+        return run_list(c, s, q, d_out_or_null, cap, total, false, 0, &keep.st);
+    });
+}
+
+// host buffers: sa, lcp and sa_c through staging buffers 0, 1 and 2; the records through buffer 0, which sa has left by then
+int archon_hip_runs(const uint32_t *sa, const uint32_t *lcp, const uint32_t *sa_c, uint32_t n, uint32_t min_period, uint32_t max_period,
+                    uint32_t min_copies, uint32_t min_len, archon_hip_run *out_or_null, uint64_t cap, uint64_t *total, int dev)
+{
+    ARCHON_TRY(runs_check(sa, lcp, sa_c, total, n, min_period, max_period, min_copies));
+    return with_ctx(dev, nullptr, [&](Ctx *c, hipStream_t s) -> int {
+        KeepStats<archon_hip_run_stats> keep(t_run_stats, dev);
+        run_call_stats(&keep.st, n, min_period, max_period, min_copies, min_len, 0);
+        uint32_t *d_sa = nullptr, *d_lcp = nullptr, *d_sa_c = nullptr;
+        ARCHON_TRY(kmer_stage(c, s, sa, lcp, n, &d_sa, &d_lcp));
+        ARCHON_TRY(ctx_io(c, 2, (size_t)n * 4 + 64, (void **)&d_sa_c));
+        ARCHON_HIP_TRY(hipMemcpyAsync(d_sa_c, sa_c, (size_t)n * 4, hipMemcpyHostToDevice, s));
+        ARCHON_TRY(run_begin(c, s));
+        RunCall q = {d_sa, d_lcp, d_sa_c, nullptr, n, {min_period, max_period, min_copies, min_len}};
+        return run_list(c, s, q, out_or_null, cap, total, true, 0, &keep.st);
+    });
+}
+
+int archon_hip_runs_last_stats(int dev, archon_hip_run_stats *out) { return t_run_stats.get(dev, out, "runs or LCE call"); }
 
 // ---- the FM index (fm_host.hiph: the handle and every driver; here the argument checks and the statistics)
 int archon_hip_fm_create(const uint8_t *bwt, uint32_t n, uint32_t base_id, int dev, archon_hip_fm **out)
@@ -1500,6 +1599,52 @@ int archon_hip_block_complexity(archon_hip_block *b, uint32_t max_len, uint32_t 
         uint32_t *d_lcp = nullptr;
         ARCHON_TRY(block_lcp_step(c, s, b, &d_lcp, &keep.st.ms_lcp));
         return cx_run(c, s, d_lcp, b->d_bwt(), b->n, max_len, counts_or_null, true, rec, &keep.st);
+    });
+}
+
+// the LCP array into staging buffer 1, the queries and their answers through buffer 2
+int archon_hip_block_lce(archon_hip_block *b, const uint32_t *s, const uint32_t *t, uint32_t k, uint32_t *out)
+{
+    if (!b || (k && (!s || !t || !out))) { set_error("null pointer"); return ARCHON_E_ARG; }
+    std::lock_guard<std::mutex> lkb(b->mu);
+    ARCHON_TRY(block_check(b, true));
+    if (!k) return ARCHON_OK;
+    ARCHON_TRY(lce_check_items(s, t, k, b->n));
+    return with_ctx(b->dev, nullptr, [&](Ctx *c, hipStream_t st) -> int {
+        KeepStats<archon_hip_run_stats> keep(t_run_stats, b->dev);
+        run_call_stats(&keep.st, b->n, 0, 0, 0, 0, 1);
+        uint32_t *d_lcp = nullptr, *d_q = nullptr;
+        ARCHON_TRY(block_lcp_step(c, st, b, &d_lcp, &keep.st.ms_lcp));
+        ARCHON_TRY(lce_stage(c, st, s, t, k, &d_q));
+        ARCHON_TRY(lce_run(c, st, b->d_sa(), d_lcp, b->n, d_q, d_q + k, k, d_q + 2 * (size_t)k, &keep.st));
+        ARCHON_HIP_TRY(hipMemcpyAsync(out, d_q + 2 * (size_t)k, (size_t)k * 4, hipMemcpyDeviceToHost, st));
+        ARCHON_SYNC(st);
+        return ARCHON_OK;
+    });
+}
+
+// The second sort first -- the complemented text, a forward transform on it, rank1 into memory of the call's own, the three
+// buffers of the sort freed --, so that its arena and buffers are not live beside the LCP step's; then the LCP array into staging
+// buffer 1 and the passes; the records through buffer 2
+int archon_hip_block_runs(archon_hip_block *b, uint32_t min_period, uint32_t max_period, uint32_t min_copies, uint32_t min_len,
+                          archon_hip_run *out_or_null, uint64_t cap, uint64_t *total)
+{
+    if (total) *total = 0;
+    if (!b || !total) { set_error("null pointer"); return ARCHON_E_ARG; }
+    ARCHON_TRY(run_check_filters(min_period, max_period, min_copies));
+    std::lock_guard<std::mutex> lkb(b->mu);
+    ARCHON_TRY(block_check(b, true));
+    return with_ctx(b->dev, nullptr, [&](Ctx *c, hipStream_t s) -> int {
+        KeepStats<archon_hip_run_stats> keep(t_run_stats, b->dev);
+        run_call_stats(&keep.st, b->n, min_period, max_period, min_copies, min_len, 0);
+        DevBuf rank1;
+        ARCHON_TRY(rank1.alloc(((size_t)b->n + 1) * 4 + 64, "runs: rank of the complemented block"));
+        ARCHON_TRY(run_begin(c, s));
+        ARCHON_TRY(run_second_sort(c, s, b->d_x(), b->n, reinterpret_cast<uint32_t *>(rank1.p), &keep.st));
+        uint32_t *d_lcp = nullptr;
+        ARCHON_TRY(block_lcp_step(c, s, b, &d_lcp, &keep.st.ms_lcp));
+        RunCall q = {b->d_sa(), d_lcp, nullptr, reinterpret_cast<const uint32_t *>(rank1.p), b->n, {min_period, max_period, min_copies, min_len}};
+        return run_list(c, s, q, out_or_null, cap, total, true, 2, &keep.st);
     });
 }
 

@@ -56,6 +56,8 @@ SYMBOLS = [
     "archon_hip_maws", "archon_hip_maws_dev", "archon_hip_block_maws", "archon_hip_maw_last_stats",
     "archon_hip_entropy", "archon_hip_entropy_dev", "archon_hip_block_entropy", "archon_hip_complexity", "archon_hip_complexity_dev",
     "archon_hip_block_complexity", "archon_hip_entropy_last_stats",
+    "archon_hip_lce", "archon_hip_lce_dev", "archon_hip_block_lce", "archon_hip_runs", "archon_hip_runs_dev", "archon_hip_block_runs",
+    "archon_hip_runs_last_stats",
 ]
 
 # archon_hip_fm_hit: one distinct string within the distance of a pattern (FmIndex.approx, Block.fm_approx)
@@ -83,6 +85,9 @@ MAW = np.dtype([("lo", "<u4"), ("hi", "<u4"), ("len", "<u4"), ("item", "<u4"), (
 # follows, those always followed by the same byte, the distinct (context, byte) pairs, n - k, and bits = n * H_k
 ENTROPY = np.dtype([("k", "<u4"), ("reserved", "<u4"), ("contexts", "<u8"), ("deterministic", "<u8"), ("pairs", "<u8"), ("symbols", "<u8"),
                     ("bits", "<f8")])
+# archon_hip_run: one run (maximal repetition) of a block (runs, Block.runs): x[start .. end) has smallest period `period`, holds at
+# least two copies of it and extends neither way; root is the item of the rule that found it, and the output ascends in it
+RUN = np.dtype([("start", "<u4"), ("end", "<u4"), ("period", "<u4"), ("root", "<u4")])
 
 
 class _Record(ctypes.Structure):
@@ -282,6 +287,19 @@ class EntropyStats(_Record):
     ]
 
 
+class RunStats(_Record):
+    """archon_hip_run_stats: the calling thread's last runs or LCE call on a device"""
+    _fields_ = [
+        ("n", ctypes.c_uint32), ("min_period", ctypes.c_uint32), ("max_period", ctypes.c_uint32), ("min_copies", ctypes.c_uint32),
+        ("min_len", ctypes.c_uint32), ("what", ctypes.c_uint32), ("fan", ctypes.c_uint32), ("lcp_fan", ctypes.c_uint32),
+        ("levels", ctypes.c_uint32), ("longest_period", ctypes.c_uint32), ("kernel_launches", ctypes.c_uint32), ("host_syncs", ctypes.c_uint32),
+        ("candidates", ctypes.c_uint64), ("roots", ctypes.c_uint64), ("lce_queries", ctypes.c_uint64), ("probes", ctypes.c_uint64),
+        ("runs", ctypes.c_uint64), ("emitted", ctypes.c_uint64),
+        ("ms_forward", ctypes.c_float), ("ms_lcp", ctypes.c_float), ("ms_build", ctypes.c_float), ("ms_count", ctypes.c_float),
+        ("ms_emit", ctypes.c_float),
+    ]
+
+
 class ArchonError(RuntimeError):
     def __init__(self, code, msg):
         super().__init__("archon_hip error %d: %s" % (code, msg))
@@ -430,6 +448,13 @@ def load():
         "archon_hip_maws_dev": [vp, vp, vp, u32, u32, u32, u32, vp, ctypes.c_uint64, vp, i32, vp],
         "archon_hip_block_maws": [vp, u32, u32, vp, ctypes.c_uint64, vp],
         "archon_hip_maw_last_stats": [i32, ctypes.POINTER(MawStats)],
+        "archon_hip_lce": [vp, vp, u32, vp, vp, u32, vp, i32],
+        "archon_hip_lce_dev": [vp, vp, u32, vp, vp, u32, vp, i32, vp],
+        "archon_hip_block_lce": [vp, vp, vp, u32, vp],
+        "archon_hip_runs": [vp, vp, vp, u32, u32, u32, u32, u32, vp, ctypes.c_uint64, vp, i32],
+        "archon_hip_runs_dev": [vp, vp, vp, u32, u32, u32, u32, u32, vp, ctypes.c_uint64, vp, i32, vp],
+        "archon_hip_block_runs": [vp, u32, u32, u32, u32, vp, ctypes.c_uint64, vp],
+        "archon_hip_runs_last_stats": [i32, ctypes.POINTER(RunStats)],
         "archon_hip_entropy": [vp, vp, vp, u32, u32, vp, u32, vp, i32],
         "archon_hip_entropy_dev": [vp, vp, vp, u32, u32, vp, u32, vp, i32, vp],
         "archon_hip_block_entropy": [vp, vp, u32, vp],
@@ -903,6 +928,63 @@ def complexity(lcp, bwt=None, max_len=0, dev=0):
     counts = np.zeros(max(complexity_len(lcp.size, max_len), 1), np.uint32)
     _check(lib().archon_hip_complexity(_p(lcp), _p(bwt) if bwt is not None else None, lcp.size, int(max_len), _p(counts), ctypes.byref(rec), dev))
     return rec, counts[:rec.max_len]
+
+
+def run_stats(dev=0):
+    """RunStats of the calling thread's last runs or LCE call on dev"""
+    return _last_stats(RunStats, "archon_hip_runs_last_stats", dev)
+
+
+def _pairs(what, s, t):
+    s = np.ascontiguousarray(np.atleast_1d(s), dtype=np.uint32)
+    t = np.ascontiguousarray(np.atleast_1d(t), dtype=np.uint32)
+    if s.size != t.size:
+        raise ValueError("%s: %d items s, %d items t" % (what, s.size, t.size))
+    return s, t, np.zeros(max(s.size, 1), np.uint32)
+
+
+def lce(sa, lcp, s, t, dev=0):
+    """the longest common extensions of pairs of items from a block's suffix array and LCP array (include/archon_hip.h:
+    archon_hip_lce): out[i] = the leading symbols the keys of items s[i] and t[i] (0 .. n) share, the longest common suffix of
+    x[0..s) and x[0..t)"""
+    sa, lcp = _sa_lcp("lce", sa, lcp)
+    s, t, out = _pairs("lce", s, t)
+    _check(lib().archon_hip_lce(_p(sa), _p(lcp), sa.size, _p(s), _p(t), s.size, _p(out), dev))
+    return out[:s.size]
+
+
+def _runs(call, count_only):
+    """call(out pointer or None, cap, total pointer) -> rc: the count, or the runs in an array of the size a first call gave"""
+    total = ctypes.c_uint64(0)
+    tp = ctypes.cast(ctypes.byref(total), ctypes.c_void_p)
+    _check(call(None, 0, tp))
+    if count_only:
+        return total.value
+    out = np.zeros(total.value, RUN)
+    if total.value:
+        _check(call(_p(out), out.size, tp))
+    return out[:total.value]
+
+
+def runs(sa, lcp, sa_c, min_period=0, max_period=0, min_copies=2, min_len=0, count_only=False, dev=0):
+    """the runs (maximal repetitions) of a block from its suffix array, its LCP array and the suffix array sa_c of the complemented
+    block 255 - x (include/archon_hip.h: archon_hip_runs): a RUN array in ascending root, those with min_period <= period <=
+    max_period (0: no limit), at least min_copies copies and min_len bytes, or their number with count_only"""
+    sa, lcp = _sa_lcp("runs", sa, lcp)
+    sa_c = np.ascontiguousarray(sa_c, dtype=np.uint32)
+    if sa_c.size != sa.size:
+        raise ValueError("runs: sa has %d rows, sa_c %d" % (sa.size, sa_c.size))
+    fn = lib().archon_hip_runs
+    return _runs(lambda out, cap, tp: fn(_p(sa), _p(lcp), _p(sa_c), sa.size, int(min_period), int(max_period), int(min_copies), int(min_len), out, cap,
+                                         tp, dev), count_only)
+
+
+def runs_of(x, min_period=0, max_period=0, min_copies=2, min_len=0, count_only=False, dev=0):
+    """the runs of the block x: two forwards (x and its complement), one lcp, one runs call"""
+    x = np.frombuffer(x, np.uint8) if isinstance(x, (bytes, bytearray)) else np.ascontiguousarray(x, dtype=np.uint8)
+    sa = forward(x, True, dev)[0]
+    sa_c = forward(255 - x, True, dev)[0]
+    return runs(sa, lcp(x, sa, dev), sa_c, min_period, max_period, min_copies, min_len, count_only, dev)
 
 
 def _kmers_as_mems(recs, k):
@@ -1621,6 +1703,21 @@ class Block:
         fn = lib().archon_hip_block_maws
         return _maws(lambda out, cap, tp: fn(self.h, int(min_len), int(max_len), out, cap, tp), count_only)
 
+    def lce(self, s, t):
+        """the longest common extensions of pairs of items of the resident block (needs forward(want_sa=True)): out[i] = the
+        longest common suffix of x[0..s[i]) and x[0..t[i])"""
+        s, t, out = _pairs("Block.lce", s, t)
+        _check(lib().archon_hip_block_lce(self.h, _p(s), _p(t), s.size, _p(out)))
+        return out[:s.size]
+
+    def runs(self, min_period=0, max_period=0, min_copies=2, min_len=0, count_only=False):
+        """the runs of the resident block (needs forward(want_sa=True)): the complemented block is sorted on the device beside
+        the resident one, which stays as it is; the LCP array is made and consumed on the device.  A RUN array in ascending root,
+        or the number of runs with count_only.  Without count_only the block is taken twice: once for the count, once with room
+        for the records"""
+        fn = lib().archon_hip_block_runs
+        return _runs(lambda out, cap, tp: fn(self.h, int(min_period), int(max_period), int(min_copies), int(min_len), out, cap, tp), count_only)
+
     def entropy(self, ks):
         """the order-k statistics of the resident block (needs forward(want_sa=True)): its LCP array is made and consumed on the
         device, the rank table is the block's own (built here when no FM call has).  An ENTROPY array, one record per order"""
@@ -1780,6 +1877,26 @@ def maws_dev(sa_t, lcp_t, bwt_t, base_id, min_len=2, max_len=0, out_t=None):
     cap = out_t.numel() // 5 if out_t is not None else 0
     _check(lib().archon_hip_maws_dev(ctypes.c_void_p(sa_t.data_ptr()), ctypes.c_void_p(lcp_t.data_ptr()), ctypes.c_void_p(bwt_t.data_ptr()), sa_t.numel(),
                                      int(base_id), int(min_len), int(max_len), ctypes.c_void_p(out_t.data_ptr()) if out_t is not None else None, cap,
+                                     ctypes.cast(ctypes.byref(total), ctypes.c_void_p), dev, _stream_ptr()))
+    return total.value
+
+
+def lce_dev(sa_t, lcp_t, s_t, t_t, out_t):
+    """torch CUDA tensors: sa and lcp int32[n], items s and t int32[k], out int32[k] (written); on the current stream"""
+    dev = sa_t.device.index or 0
+    _check(lib().archon_hip_lce_dev(ctypes.c_void_p(sa_t.data_ptr()), ctypes.c_void_p(lcp_t.data_ptr()), sa_t.numel(), ctypes.c_void_p(s_t.data_ptr()),
+                                    ctypes.c_void_p(t_t.data_ptr()), s_t.numel(), ctypes.c_void_p(out_t.data_ptr()), dev, _stream_ptr()))
+
+
+def runs_dev(sa_t, lcp_t, sa_c_t, min_period=0, max_period=0, min_copies=2, min_len=0, out_t=None):
+    """torch CUDA tensors: sa, lcp and sa_c int32[n], out an int32 tensor of 4 words per run or None (counting only); on the current
+    stream.  Returns the number of runs (raises when out_t holds fewer)"""
+    dev = sa_t.device.index or 0
+    total = ctypes.c_uint64(0)
+    cap = out_t.numel() // 4 if out_t is not None else 0
+    _check(lib().archon_hip_runs_dev(ctypes.c_void_p(sa_t.data_ptr()), ctypes.c_void_p(lcp_t.data_ptr()), ctypes.c_void_p(sa_c_t.data_ptr()), sa_t.numel(),
+                                     int(min_period), int(max_period), int(min_copies), int(min_len),
+                                     ctypes.c_void_p(out_t.data_ptr()) if out_t is not None else None, cap,
                                      ctypes.cast(ctypes.byref(total), ctypes.c_void_p), dev, _stream_ptr()))
     return total.value
 

@@ -1234,6 +1234,112 @@ typedef struct archon_hip_entropy_stats {
 } archon_hip_entropy_stats;
 int  archon_hip_entropy_last_stats(int dev, archon_hip_entropy_stats *out);
 
+/* ---- the runs (maximal repetitions, tandem repeats) of a block, and longest-common-extension queries -----------------------------
+ * (no counterpart in the reference)  archon_hip_repeats lists WHICH strings recur; these calls list where a string recurs back to
+ * back: `anana` in `banana`, a microsatellite in DNA, a repeated record in a log.  Rows, items, sa, lcp and a7 order are those of
+ * the repeats section; lcp[0] reads as 0.
+ * LCE.  For items s, t in 0..n, lce(s, t) is the number of leading symbols in which the a7 keys of s and t agree: the length of
+ * the longest common suffix of x[0..s) and x[0..t).  lce(s, s) = s; lce(0, .) = 0; for s != t, both >= 1, it is
+ * min lcp[min(r_s, r_t) + 1 .. max(r_s, r_t)] with r = isa[.], the row of the item.
+ * Run.  (start, end, period) is a run of x when x[start..end) has smallest period p = period, end - start >= 2p, and it can be
+ * extended neither way: start == 0 or x[start-1] != x[start-1+p], and end == n or x[end] != x[end-p].  A block has fewer than n
+ * runs.
+ * The rule.  It fixes the output order and the work counters, and needs only LCEs in the key direction and one second sort.
+ * rank0[s] is the row of item s in the a7 suffix array of x, rank1[s] its row in the a7 suffix array of the complemented block
+ * xc[i] = 255 - x[i]; every LCE is that of x.  For s = 1..n ascending, and for l = 0 then l = 1:
+ *   1. t is the greatest item in 1..s-1 with rank_l[t] > rank_l[s]; none: no candidate.  p = s - t; a period filter that
+ *      excludes p: no candidate.  Count `candidates`.
+ *   2. R = lce(s, t).  R == 0: stop.
+ *   3. If s + p <= n and lce(s + p, s) >= p: stop (this root is not the outermost one).  Otherwise count `roots`.
+ *   4. L is the greatest l' in 0..min(p-1, n-s) with lce(s + l', t + l') >= l' (monotone in l'), found by
+ *      lo = 0, hi = min(p-1, n-s); while lo < hi: m = (lo+hi+1)>>1; lce(s+m, t+m) >= m ? lo = m : hi = m-1.  R + L < p: stop.
+ *   5. start = t - R, end = s + L.  The run is kept when start == 0 and l == 0; or start >= 1, l == 0 and
+ *      rank0[start] > rank0[start+p]; or start >= 1, l == 1 and rank0[start] < rank0[start+p].  (The keys' first bytes
+ *      x[start-1] and x[start-1+p] differ, so rank0 orders them.)  Count `runs`.
+ *   6. The filters; emit (start, end, period, root = s).
+ * Behind it is the runs theorem of Bannai et al.: descending rank0 is the suffix order of the reversed block under reversed byte
+ * order with the end smallest, descending rank1 the same under plain byte order; step 1 is the longest Lyndon word that ends at
+ * s; step 3 keeps one root per run, step 5 one order per run.  Every run is emitted exactly once, in ascending root.
+ * lce_queries counts one per step 2, one per step 3 that is evaluated (s + p <= n), one per iteration of the loop of step 4.
+ * Examples, as records (start, end, period, root), then candidates / roots / lce_queries:
+ *   "banana"       (1,6,2,6)                                        7 / 1 / 8
+ *   "mississippi"  (2,4,1,4) (5,7,1,7) (1,8,3,8) (8,10,1,10)       16 / 6 / 24
+ *   "aaaa"         (0,4,1,4)                                        6 / 2 / 10
+ *   "abracadabra"  none                                            18 / 5 / 26
+ * Filters: min_period <= period, period <= max_period (0: no upper bound), end - start >= min_copies * period
+ * (min_copies >= 2) and end - start >= min_len.  min_copies < 2, or min_period > max_period with max_period != 0:
+ * ARCHON_E_ARG with *total = 0.
+ * Cap rule (that of archon_hip_repeats): *total is a host pointer and always written.  out NULL: counting only.  cap < *total
+ * with out given: ARCHON_E_ARG, *total written, out untouched.
+ * Bad input.  sa or sa_c not a permutation of 1..n: ARCHON_E_CORRUPT, the outputs untouched (*total is 0).  A permutation that
+ * is not the right suffix array, or an lcp that is no LCP array, returns ARCHON_OK with unspecified records; every access stays
+ * inside the buffers.  An LCE item above n: ARCHON_E_ARG with nothing written (the device form finds it on the device); k = 0
+ * writes nothing.  Null pointers, n = 0: ARCHON_E_ARG.  No GPU: ARCHON_E_NODEVICE; there is no CPU fallback.
+ * Method (csrc/runs.hiph).  The inverse arrays rank0 and rank1 by a scatter that flags values outside 1..n and, in a second
+ * kernel, leftovers; one minimum hierarchy over ~rank_l in item order per order (fan-out: test route LZ_FAN, default 16), so that
+ * step 1 is one nearest-smaller-value walk to the left; the minimum hierarchy over lcp of a repeats call (test route REP_FAN),
+ * so that an LCE is one range minimum.  Then one pass over tiles of 2048 items, run twice (count, and emit behind a scan of the
+ * tile words): a lane takes an item and both orders.  The emit pass runs the rule again.  No atomics on the output.
+ * Work, for any data: per item and order one left search of at most 31 ceil(log16 n) probes (2F - 1 per level) and at most
+ * 2 + ceil(log2 p) LCEs, each one range minimum of at most 2(F - 1) entries per level.  A block of one byte drops every
+ * candidate but the last at step 3.
+ * Launches: 1 + 1 (scatter, leftovers) per array, the levels of the three hierarchies, 1 counting; 2 more with the emit pass.
+ * The block form adds the complement kernel; the launches of its second forward transform and of its LCP step stay out of the
+ * record.  Host waits: 1 counting, 2 with the emit pass
+ * (the host form's copy back rides on the second); the block form adds those of its forward and LCP steps.  An LCE call: the
+ * scatter, the leftovers, the lcp hierarchy, the check of the items and the query kernel; one wait, two in the host and block forms.
+ * Workspace, from the calling thread's context arena: 8 (n + 1) bytes of inverse arrays, about 12 n / (F-1) of hierarchies,
+ * n / 512 bytes of tile words (an LCE call: 4 (n + 1) and one hierarchy).  The host form stages sa, lcp and sa_c (12 n bytes). */
+typedef struct archon_hip_run {
+    uint32_t start, end;        /* x[start .. end) */
+    uint32_t period;            /* its smallest period */
+    uint32_t root;              /* the item s of the rule that found it, start + period <= root <= end; the output ascends in it */
+} archon_hip_run;               /* 16 bytes */
+/* host sa[n], lcp[n], items s[k], t[k] and out[k] */
+int  archon_hip_lce(const uint32_t *sa, const uint32_t *lcp, uint32_t n, const uint32_t *s, const uint32_t *t, uint32_t k, uint32_t *out, int dev);
+/* device arrays (any 4-byte aligned address); on `stream` (NULL = the context's own), complete on return */
+int  archon_hip_lce_dev(const uint32_t *d_sa, const uint32_t *d_lcp, uint32_t n, const uint32_t *d_s, const uint32_t *d_t, uint32_t k, uint32_t *d_out,
+                        int dev, void *stream);
+/* the resident block of the handle's last forward and its suffix array (ARCHON_E_ARG when that forward kept none); s, t and out
+ * are host buffers */
+int  archon_hip_block_lce(archon_hip_block *b, const uint32_t *s, const uint32_t *t, uint32_t k, uint32_t *out);
+/* host sa[n], lcp[n], sa_c[n] (the a7 suffix array of the complemented block) and out */
+int  archon_hip_runs(const uint32_t *sa, const uint32_t *lcp, const uint32_t *sa_c, uint32_t n, uint32_t min_period, uint32_t max_period,
+                     uint32_t min_copies, uint32_t min_len, archon_hip_run *out_or_null, uint64_t cap, uint64_t *total, int dev);
+/* device arrays and out (any 4-byte aligned address); on `stream`, complete on return */
+int  archon_hip_runs_dev(const uint32_t *d_sa, const uint32_t *d_lcp, const uint32_t *d_sa_c, uint32_t n, uint32_t min_period, uint32_t max_period,
+                         uint32_t min_copies, uint32_t min_len, archon_hip_run *d_out_or_null, uint64_t cap, uint64_t *total, int dev, void *stream);
+/* The resident block and its suffix array.  The call complements the resident text into memory of its own (outside the arena),
+ * runs a forward transform on that copy in the block's context -- archon_hip_get_stats and the resident block are left as they
+ * were -- and keeps only rank1 of it; then the LCP step of archon_hip_block_repeats and the passes.  out is a host buffer. */
+int  archon_hip_block_runs(archon_hip_block *b, uint32_t min_period, uint32_t max_period, uint32_t min_copies, uint32_t min_len,
+                           archon_hip_run *out_or_null, uint64_t cap, uint64_t *total);
+/* the CALLING THREAD's last runs or LCE call on `dev`; these calls leave every other record alone (the block forms also keep the
+ * LCP record of their LCP step).  candidates, roots, lce_queries, runs, emitted and longest_period follow from x and the filters
+ * alone; probes also from the fan-out */
+typedef struct archon_hip_run_stats {
+    uint32_t n;                 /* of the call */
+    uint32_t min_period, max_period, min_copies, min_len;   /* the filters, as given (an LCE call: 0) */
+    uint32_t what;              /* 0 runs, 1 LCE */
+    uint32_t fan, lcp_fan;      /* fan-out of the rank hierarchies and of the hierarchy over lcp */
+    uint32_t levels;            /* levels of the hierarchy over lcp */
+    uint32_t longest_period;    /* of the records that passed every filter */
+    uint32_t kernel_launches;   /* launches issued by the call (block forms: without those of the second sort and the LCP step) */
+    uint32_t host_syncs;        /* times the host waited for the stream inside the call (block forms: the second sort's and the LCP step's included) */
+    uint64_t candidates;        /* step 1 */
+    uint64_t roots;             /* step 3 */
+    uint64_t lce_queries;       /* steps 2, 3 and 4 (an LCE call: k) */
+    uint64_t probes;            /* entries of the rank hierarchies the left searches read */
+    uint64_t runs;              /* step 5: the runs whose period passes, before the copies and length filters */
+    uint64_t emitted;           /* *total */
+    float ms_forward;           /* block form: device time of the second sort */
+    float ms_lcp;               /* block forms: device time of the LCP step */
+    float ms_build;             /* device time of the inverse arrays and the hierarchies */
+    float ms_count;             /* device time of the count pass (an LCE call: of the query kernel) */
+    float ms_emit;              /* device time of the scan of the tile words and the emit pass */
+} archon_hip_run_stats;
+int  archon_hip_runs_last_stats(int dev, archon_hip_run_stats *out);
+
 /* ---- matching statistics of a long text, and its relative LZ parse against the block ------------------------------------------
  * archon_hip_fm_ms runs one wave per pattern, so one long pattern runs on one wave.  These calls take ONE text P of m bytes --
  * another version of a file, a read set, the next block of a container -- and spread it over the device.  The result is defined
