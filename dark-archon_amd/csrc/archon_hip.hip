@@ -417,6 +417,7 @@ static const RouteRow kRoutes[] = {
     {"MS_CHUNK", RouteKind::kRange, ROUTE_FIELD(ms_chunk), 0, 0xFFFFFFFFl, 0, ": not a chunk of 1 .. 2^32 - 1 bytes (0: the default)"},
     {"EDIT_TILE", RouteKind::kRange, ROUTE_FIELD(edit_tile), 0, 64, 0, ": not a tile of 1 .. 64 ends (0: the default)"},
     {"EDIT_BATCH", RouteKind::kRange, ROUTE_FIELD(edit_batch), 0, 0x7FFFFFFFl, 0, ": not a batch of 1 .. 2^31 - 1 patterns (0: the budget's own)"},
+    {"STRIDE_GRID", RouteKind::kRange, ROUTE_FIELD(stride_grid), 0, 2048, 0, ": not a grid of 1 .. 2048 workgroups (0: the default)"},
     {"DOC_TILE", RouteKind::kMul64, ROUTE_FIELD(doc_tile), (long)fmd::kMinTile, (long)fmd::kMaxTile, 0, ": not a tile of 64 .. 2^20 rows, a multiple of 64 (0: the default)"},
 };
 #undef ROUTE_FLAG

@@ -486,7 +486,7 @@ _ROUTE_NAMES = ("FORCE_PATH", "SMALL_BLOCK", "PASS_RANGES", "INV_ROWS", "INV_SLA
                 "NO_PACK", "NO_PAIR_CHAINS", "NO_PERIOD_HINT", "NO_BREAK_ROUND", "NO_PERIOD_STREAM",
                 "NO_RANK_WRITER", "NO_TEXT_ROUNDS", "NO_MID", "NO_SHALLOW", "NO_CLOSED_FORM", "NO_REL_RECORDS", "ALIGNED_MIN", "REL_MIN_SEG", "KEY_BYTES",
                 "LCP_CAP", "LCP_WINDOW", "FM_SUB_ROWS", "FM_SUPER_ROWS", "FM_SAMPLE_WALK", "REP_FAN", "LZ_FAN", "LZ_TILE", "MS_CHUNK",
-                "EDIT_TILE", "EDIT_BATCH", "DOC_TILE", "KMER_TILE")
+                "EDIT_TILE", "EDIT_BATCH", "DOC_TILE", "KMER_TILE", "STRIDE_GRID")
 
 
 def _sync_routes(L):

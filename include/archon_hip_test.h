@@ -46,6 +46,13 @@
  *                                 no match: at 1 every pattern is marked, swept and checked alone
  *   DOC_TILE       64..2^20 / 0   document listing: rows of a tile, a multiple of 64 (0: 4096).  It changes no record: at 64 a range of
  *                                 65 rows is two tiles
+ *   STRIDE_GRID    1..2048 / 0    analyses (FM count / locate / walk, approximate, class, edit, SMEM, matching statistics, text MS /
+ *                                 RLZ, document listing, repeats, LZ, k-mers, MAW, entropy, runs / LCE): the most workgroups a stride
+ *                                 kernel is launched with (0: 2048; k_fm_locate keeps its own 8192 where that is less).  It changes no
+ *                                 result and no counter: at 1 one workgroup (four waves) takes every tile and every pattern.  No
+ *                                 kernel of these families waits on another workgroup.  The entropy sums are added per tile in tile
+ *                                 order (k_ent_follow fills one slot per tile, k_ent_reduce adds the slots in a fixed order), so
+ *                                 `bits` is the same 64 bits at every grid
  *   NO_ALIGNED NO_BREAK_ROUND NO_CHAINS NO_PACK NO_PAIR_CHAINS NO_PERIOD_HINT NO_PERIOD_STREAM NO_RANK_WRITER NO_TEXT_ROUNDS
  *   NO_MID NO_SHALLOW NO_CLOSED_FORM NO_REL_RECORDS      nonzero switches the named step off
  * Returns 0, or ARCHON_E_ARG for an unknown name / a value out of range.  Process-wide; not thread-safe against

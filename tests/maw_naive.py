@@ -110,3 +110,42 @@ def word(x, rec):
     x = bytes(x)
     lo, hi, ln, item, last = (int(v) for v in rec)
     return x[item - ln + 1:item] + bytes([last])
+
+
+def _codes(c, m):
+    """the 2-bit codes of every m-mer of the letters c (values 0 .. 3), first letter in the highest bits"""
+    count = c.size - m + 1
+    code = np.zeros(max(count, 0), np.int64)
+    for i in range(m):
+        code = code * 4 + c[i:count + i]
+    return code
+
+
+def words_of_length(x, L, first=97):
+    """the minimal absent words of exactly L >= 2 bytes of a block over the four letters first .. first + 3, by the definition
+    and without the arrays, as ascending 2-bit codes (the first byte in the highest bits): presence bitmaps of all (L-1)-mers
+    and all L-mers; a code is a word when it is absent while its first and its last L - 1 letters are present"""
+    c = np.asarray(x, np.uint8).astype(np.int64) - first
+    assert L >= 2 and c.size and c.min() >= 0 and c.max() <= 3
+    present = []
+    for m in (L - 1, L):
+        P = np.zeros(4 ** m, bool)
+        P[_codes(c, m)] = True
+        present.append(P)
+    short, full = present
+    return np.flatnonzero(~full & np.repeat(short, 4) & np.tile(short, 4))
+
+
+def record_codes(x, recs, L, first=97):
+    """the 2-bit codes of the words of records that all have len L: x[item - L + 1 .. item) followed by last"""
+    c = np.asarray(x, np.uint8).astype(np.int64) - first
+    assert (recs["len"] == L).all()
+    start = recs["item"].astype(np.int64) - L + 1
+    code = np.zeros(recs.size, np.int64)
+    for i in range(L - 1):
+        code = code * 4 + c[start + i]
+    return code * 4 + (recs["last"].astype(np.int64) - first)
+
+
+def code_bytes(code, L, first=97):
+    return bytes(first + ((int(code) >> (2 * (L - 1 - i))) & 3) for i in range(L))

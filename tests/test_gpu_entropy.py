@@ -17,6 +17,7 @@ import pytest
 import archon_synth as S
 import entropy_naive as E
 import repeats_naive as R
+import stride_util as G
 
 pytestmark = pytest.mark.gpu
 
@@ -396,3 +397,74 @@ def test_arrays_of_nothing_stay_inside(archon):
             _check_complexity(rec, counts[1:used + 1], want_rec, want_counts, "trial %d max_len %d" % (trial, L))
     x, sa, lcp, bwt, base = _shape(archon, "text", 1000)
     _check_orders(archon.entropy(sa, lcp, bwt, base, [2]), [2], [E.order_windows(x, 2)], 1000, "after garbage")
+
+
+@pytest.mark.parametrize("grid", G.GRIDS)
+def test_stride_grid(archon, grid, monkeypatch):
+    """at most 1 and 3 workgroups (ARCHON_STRIDE_GRID) on text and dna at 65 536 (32 tiles): the six orders 0, 1, 2, 3, 8, 16 in
+    one call through the host and block forms -- the integers exactly, bits in its bound, the groups against the model -- and
+    complexity with max_len 0 and 5000; byte-equal to the same calls without the route, so that `bits` is the same 64 bits (the
+    sums are kept per tile and added in tile order, whatever workgroup took the tile), with their counters, launches and waits"""
+    ks = [0, 1, 2, 3, 8, 16]
+    for shape in ("text", "dna"):
+        x, sa, lcp, bwt, base = _shape(archon, shape, 65536)
+        n = x.size
+        wants = [E.order_windows(x, k) for k in ks]
+        model = _model_groups(sa, lcp, bwt, base, ks, E.DEFAULT_TILE)
+        blk = archon.Block()
+        try:
+            blk.forward(x, want_sa=True)
+            blk.fm_count([b"a"])                     # (the block's table built: `built` is 0 in every block call below)
+
+            def call():
+                out, stats = [], []
+                got = archon.entropy(sa, lcp, bwt, base, ks)
+                _check_orders(got, ks, wants, n, shape)
+                st = archon.entropy_stats()
+                assert _groups(st) == model and (st.kernel_launches, st.host_syncs, st.built) == (3 + _launches(ks, n), 2, 1)
+                got_b = blk.entropy(ks)
+                assert got_b.tobytes() == got.tobytes() and _groups(archon.entropy_stats()) == model
+                out += [got, got_b]
+                stats += [st, archon.entropy_stats()]
+                for L in (0, 5000):
+                    want_rec, want_counts = E.complexity_rows(lcp, bwt, L)
+                    for form in (lambda: archon.complexity(lcp, bwt, L), lambda: blk.complexity(L)):
+                        rec, counts = form()
+                        _check_complexity(rec, counts, want_rec, want_counts, shape)
+                        out += [rec, counts]
+                        stats.append(archon.entropy_stats())
+                return out, stats
+            G.same_under(monkeypatch, grid, call)
+        finally:
+            blk.close()
+
+
+@pytest.mark.parametrize("shape", ["a", "dna"])
+def test_second_trip_at_the_product_grid(archon, shape):
+    """no route: 2048 * 2048 + 3 * 2048 + 5 rows are 2052 tiles, so workgroups 0-3 of the 2048 take a second tile and the last
+    tile has 5 rows.  One byte: the tuples of test_one_byte_block.  DNA at k = 12 against the windows of the text, and
+    complexity at max_len 5000 against the rule over the LCP array"""
+    n = G.N2
+    x = S.gen_shape(shape, n)
+    blk = archon.Block()
+    try:
+        sa, base = blk.forward(x, want_sa=True)
+        assert blk.validate() == 1
+        if shape == "a":
+            ks = [0, 1, 5, n - 1, n, n + 1]
+            _check_orders(blk.entropy(ks), ks, [(1, 1, 1, n - k, 0.0) if k < n else (0, 0, 0, 0, 0.0) for k in ks], n, "a")
+            assert _groups(archon.entropy_stats()) == (0, 3, 2)
+            rec, counts = blk.complexity(5000)
+            assert (counts == 1).all() and counts.size == 5000 and (rec.delta_len, rec.delta_count, rec.delta_exact) == (1, 1, 0)
+            assert (rec.runs, rec.longest_run, rec.lcp_max, rec.lcp_sum, rec.substrings) == (1, n, n - 1, n * (n - 1) // 2, n)
+        else:
+            ks = [0, 12]
+            got = blk.entropy(ks)
+            _check_orders(got, ks, [E.order_windows(x, k) for k in ks], n, "dna")
+            assert blk.entropy(ks).tobytes() == got.tobytes()
+            lcp, bwt = blk.lcp(), blk.read_bwt()
+            want_rec, want_counts = E.complexity_rows(lcp, bwt, 5000)
+            rec, counts = blk.complexity(5000)
+            _check_complexity(rec, counts, want_rec, want_counts, "dna")
+    finally:
+        blk.close()

@@ -10,6 +10,7 @@ import pytest
 
 import archon_synth as S
 import fm_naive
+import stride_util as G
 
 pytestmark = pytest.mark.gpu
 
@@ -55,19 +56,33 @@ def _patterns(x, rng, long=False):
     return pats
 
 
-def _check(archon, naive, x, pats, lo, hi, locate_block=None):
+def _want(naive, x, pats, locate=False):
+    """the KMP scan's (count, matched lengths, the rarer patterns, their sorted starts)"""
     count, L = naive(x, pats)
+    some, starts = [], []
+    if locate:
+        some = [p for p, c in zip(pats, count) if c <= LOCATE_MAX // 64][:64]
+        _, _, starts = naive(x, some, starts=True)
+    return count, L, some, starts
+
+
+def _check_against(archon, want, x, pats, lo, hi, locate_block=None):
+    count, L, some, starts = want
     assert ((hi.astype(np.int64) - lo) == count).all()
     assert (lo <= hi).all() and (hi <= x.size).all()
     st = archon.fm_stats()
     assert st.steps == _steps(L, pats, x.size)
     assert st.shared_steps <= st.steps
     if locate_block is not None:
-        some = [p for p, c in zip(pats, count) if c <= LOCATE_MAX // 64][:64]
-        _, _, starts = naive(x, some, starts=True)
         got = locate_block.fm_locate(some)
         for p, g, w in zip(some, got, starts):
             assert (np.sort(g) == w).all(), p
+        return got
+    return None
+
+
+def _check(archon, naive, x, pats, lo, hi, locate_block=None):
+    _check_against(archon, _want(naive, x, pats, locate_block is not None), x, pats, lo, hi, locate_block)
 
 
 def test_exhaustive_tiny(archon, oracle):
@@ -302,3 +317,67 @@ def test_bad_offsets_and_empty_calls(archon):
     assert lo_t.cpu().tolist() == [4, 1, 0] and hi_t.cpu().tolist() == [6, 3, 6]
     assert archon.fm_stats().steps == 3
     f.close()
+
+
+@pytest.mark.parametrize("grid", G.GRIDS)
+def test_stride_grid(archon, naive, grid, monkeypatch):
+    """at most 1 and 3 workgroups (ARCHON_STRIDE_GRID): the 260 patterns of text and dna at 65 536 and of one byte x (MiB + 3)
+    with its long patterns, so that every wave counts 20 to 65 patterns one behind another -- counts and the exact rank steps
+    against the KMP scan through the block and a host-built index, the starts of the rarer patterns, byte-equal to the same
+    calls without the route, with their counters"""
+    for shape, n in (("text", 65536), ("dna", 65536), ("a", MiB + 3)):
+        x = S.gen_shape(shape, n)
+        pats = _patterns(x, np.random.default_rng(n + len(shape)), long=shape == "a")
+        want = _want(naive, x, pats, locate=True)
+        b = archon.Block()
+        try:
+            _, base = b.forward(x)
+            f = archon.FmIndex(b.read_bwt(), base)
+            b.fm_count([b"a"])
+            f.count([b"a"])                  # (both tables built: `built` is 0 in every call below)
+
+            def call():
+                lo, hi = b.fm_count(pats)
+                st = [archon.fm_stats()]
+                starts = _check_against(archon, want, x, pats, lo, hi, locate_block=b)
+                st.append(archon.fm_stats())
+                lo2, hi2 = f.count(pats)
+                st.append(archon.fm_stats())
+                _check_against(archon, want, x, pats, lo2, hi2)
+                return [lo, hi, lo2, hi2] + list(starts), st
+            G.same_under(monkeypatch, grid, call)
+            f.close()
+        finally:
+            b.close()
+
+
+def test_second_trip_at_the_product_grid(archon, naive):
+    """no route: 8192 + 13 patterns of 1-24 bytes on 64 KiB of text, so that waves 0-12 of the 2048 workgroups count a second
+    pattern -- counts and the exact rank steps against the KMP scan through the block and a host-built index, and the sorted
+    starts of the 7700 patterns with at most four occurrences"""
+    n = 65536
+    x = S.gen_shape("text", n)
+    pats = G.k2_patterns(x)
+    count, L = naive(x, pats)
+    assert len(pats) == G.K2 > 4 * 2048 and (count[-13:] > 0).any() and (count == 0).sum() > 1000
+    b = archon.Block()
+    try:
+        _, base = b.forward(x)
+        lo, hi = b.fm_count(pats)
+        _check_against(archon, (count, L, [], []), x, pats, lo, hi)
+        st = archon.fm_stats()
+        assert st.patterns == G.K2 and st.kernel_launches >= 1
+        f = archon.FmIndex(b.read_bwt(), base)
+        lo2, hi2 = f.count(pats)
+        _check_against(archon, (count, L, [], []), x, pats, lo2, hi2)
+        f.close()
+        assert (lo2 == lo).all() and (hi2 == hi).all()
+        rare = [p for p, c in zip(pats, count) if c <= 4]
+        assert len(rare) > 7000
+        _, _, starts = naive(x, rare, starts=True)
+        got = b.fm_locate(rare)
+        assert len(got) == len(rare)
+        for p, g, w in zip(rare, got, starts):
+            assert (np.sort(g) == w).all(), p
+    finally:
+        b.close()

@@ -13,6 +13,7 @@ import archon_synth as S
 import fm_approx_naive as A
 import fm_naive
 import fm_sampled_naive as M
+import stride_util as G
 
 pytestmark = pytest.mark.gpu
 
@@ -303,3 +304,47 @@ def test_repeatable_and_two_threads(archon):
     for r in out:
         assert r is not None and all((u == v).all() for u, v in zip(r, one))
     f0.close()
+
+
+@pytest.mark.parametrize("grid", G.GRIDS)
+def test_stride_grid(archon, grid, monkeypatch):
+    """at most 1 and 3 workgroups (ARCHON_STRIDE_GRID) at K = 1, 2 on 64 KiB of text: every wave takes several patterns, and a
+    three-byte pattern with 150 (K = 1) and 4500 (K = 2) hits lies directly ahead of patterns with none on the same wave (patterns j, j + 4 under
+    one workgroup, j, j + 12 under three) -- the rule's hits and counters from the count pass alone and with the emit pass,
+    through a block and a host-built index, byte-equal to the same call without the route, with its counters"""
+    n = 64 * KiB
+    x = _shape("text", n)
+    rng = np.random.default_rng(n + 99)
+    b = archon.Block()
+    try:
+        _, base = b.forward(x, want_sa=False)
+        bwt = b.read_bwt()
+        rule = A.Rule(bwt, base)
+        f = archon.FmIndex(bwt, base)
+        f.count([b"a"])
+        b.fm_count([b"a"])                       # (both tables built: `built` is 0 in every call below)
+        absent = bytes([1, 2, 3, 4, 5, 6])
+        for K in (1, 2):
+            pats = _patterns(x, rng, K, (1, 2, 5, 12, 30, 70), 8)
+            pats[0] = pats[1] = pats[2] = pats[3] = b"the"
+            for j in (4, 5, 6, 7, 12, 13, 14, 15):
+                pats[j] = absent
+            want = [rule.search(p, K) for p in pats]
+            assert len(pats) > 48 and len(want[0][0]) > 100 and not want[4][0] and not want[12][0]
+
+            def call():
+                out, st = [], []
+                for search in (b.fm_approx, f.approx):
+                    nhits, nocc, none = search(pats, K, hits=False)
+                    assert none is None
+                    st.append(archon.fm_approx_stats())
+                    got = search(pats, K)
+                    _check_against_rule(archon, want, got, pats, K)
+                    assert (got[0] == nhits).all() and (got[1] == nocc).all()
+                    st.append(archon.fm_approx_stats())
+                    out += [nhits, nocc, got[0], got[1], got[2]]
+                return out, st
+            G.same_under(monkeypatch, grid, call)
+        f.close()
+    finally:
+        b.close()

@@ -14,6 +14,7 @@ import fm_approx_naive as A
 import fm_class_naive as C
 import fm_naive
 import fm_sampled_naive as M
+import stride_util as G
 
 pytestmark = pytest.mark.gpu
 
@@ -462,3 +463,55 @@ def test_repeatable_and_two_threads(archon):
     for r in out:
         assert r is not None and all((u == v).all() for u, v in zip(r, one))
     f0.close()
+
+
+@pytest.mark.parametrize("grid", G.GRIDS)
+def test_stride_grid(archon, grid, monkeypatch):
+    """at most 1 and 3 workgroups (ARCHON_STRIDE_GRID): the fold-case table on 64 KiB of text and the IUPAC table on 64 KiB of
+    DNA with some seventy patterns each, so that every wave takes several; and on the de Bruijn block of test_deep_stack the
+    pattern NNNNNN -- 4096 hits, 18 frames pending on the LDS stack -- directly ahead of plain six-byte patterns on the same
+    wave (patterns j, j + 4 under one workgroup, j, j + 12 under three).  The rule's hits, counters and largest width from the
+    count pass alone and with the emit pass, through a block and a host-built index, byte-equal to the same calls without
+    the route, with their counters"""
+    tables = _tables(archon)
+    seq = _de_bruijn(4, 6)
+    cases = [(_shape("text", 64 * KiB), "fold", None), (_shape("dna", 64 * KiB), "iupac", None),
+             (np.array([b"ACGT"[s] for s in seq + seq[:5]], np.uint8), "iupac", b"NNNNNN")]
+    for x, name, wide in cases:
+        table = tables[name]
+        sets = C.table_sets(table)
+        rng = np.random.default_rng(x.size + len(name))
+        b = archon.Block()
+        try:
+            _, base = b.forward(x, want_sa=False)
+            bwt = b.read_bwt()
+            rule = A.Rule(bwt, base)
+            f = archon.FmIndex(bwt, base)
+            b.fm_count([b"a"])
+            f.count([b"a"])                  # (both tables built: `built` is 0 in every call below)
+            if wide is None:
+                pats = [p for _ in range(4) for p in _patterns(x, rng, sets, False)]
+                assert len(pats) > 48
+            else:
+                narrow = [x[q:q + 6].tobytes() for q in rng.integers(0, x.size - 6, 8)]
+                pats = [wide] * 4 + narrow[:4] + [wide] * 4 + narrow[4:]
+            want, width = _predict(rule, pats, table, sets)
+            if wide is not None:
+                assert width == 18 and len(want[0][0]) == 4096 and all(len(want[j][0]) == 1 for j in (4, 5, 6, 7, 12, 13, 14, 15))
+
+            def call():
+                out, st = [], []
+                for search in (b.fm_classes, f.classes):
+                    nhits, nocc, none = search(pats, table, hits=False)
+                    assert none is None
+                    st.append(archon.fm_class_stats())
+                    got = search(pats, table)
+                    _check_against_rule(archon, want, width, got, pats)
+                    assert (got[0] == nhits).all() and (got[1] == nocc).all()
+                    st.append(archon.fm_class_stats())
+                    out += [nhits, nocc, got[0], got[1], got[2]]
+                return out, st
+            G.same_under(monkeypatch, grid, call)
+            f.close()
+        finally:
+            b.close()

@@ -11,6 +11,7 @@ import pytest
 
 import archon_synth as S
 import fm_doc_naive as N
+import stride_util as G
 
 pytestmark = pytest.mark.gpu
 
@@ -412,3 +413,52 @@ def test_other_statistics_records_are_left_alone(archon, oracle):
         assert archon.fm_doc_stats().n == n
     finally:
         f.close()
+
+
+@pytest.mark.parametrize("grid", G.GRIDS)
+def test_stride_grid(archon, oracle, grid, monkeypatch):
+    """at most 1 and 3 workgroups (ARCHON_STRIDE_GRID) with tiles of 64 rows, text and dna at 64 KiB in 257 documents: ranges
+    of 65, 4096 and 12 345 rows, the raw ranges and the ranges of the patterns in ONE call, so that a wave takes many tiles of
+    one range and then tiles of the next -- attach_docs under the route, docs_ranges and docs with and without the records
+    against the numpy model with its counters; byte-equal to the same calls without the route, with their counters"""
+    monkeypatch.setenv("ARCHON_DOC_TILE", "64")
+    T, D = 64, 257
+    for shape in ("text", "dna"):
+        x, sa, bwt, base = _reference(oracle, shape)
+        n = x.size
+        rng = np.random.default_rng(n + 3 * len(shape))
+        bounds = _bounds(n, D, rng)
+        patterns = _patterns(x, rng)
+        f = archon.FmIndex(bwt, base).attach_sa(sa)
+        try:
+            plo, phi = f.count(patterns)
+            pranges = [(int(a), int(b)) if a < b else (0, 0) for a, b in zip(plo, phi)]
+            ranges = [(1001, 1001 + 65), (5003, 5003 + 4096), (20011, 20011 + 12345)] + _raw_ranges(n, rng)[1:] + pranges
+            lo, hi = [r[0] for r in ranges], [r[1] for r in ranges]
+            want, wnd, ctr = N.listing(sa, bounds, ranges, T)
+            pwant, pwnd, pctr = N.listing(sa, bounds, pranges, T)
+            assert ctr["tiles"] > 2 + 64 + 192 and want.size > 3 * D // 2
+
+            def call():
+                f.attach_docs(bounds)
+                stats = [archon.fm_doc_stats()]
+                ndocs, got = f.docs_ranges(lo, hi)
+                st = archon.fm_doc_stats()
+                _same(got, want)
+                assert (ndocs == wnd).all()
+                _check_stats(st.asdict(), n, D, len(ranges), T, ctr, want)
+                only, none = f.docs_ranges(lo, hi, emit=False)
+                assert none is None and (only == wnd).all()
+                stats += [st, archon.fm_doc_stats()]
+                pdocs, pgot = f.docs(patterns)
+                st = archon.fm_doc_stats()
+                _same(pgot, pwant)
+                assert (pdocs == pwnd).all()
+                _check_stats(st.asdict(), n, D, len(patterns), T, pctr, pwant)
+                ponly, none = f.docs(patterns, emit=False)
+                assert none is None and (ponly == pwnd).all()
+                stats += [st, archon.fm_doc_stats()]
+                return [ndocs, got, only, pdocs, pgot, ponly], stats
+            G.same_under(monkeypatch, grid, call)
+        finally:
+            f.close()

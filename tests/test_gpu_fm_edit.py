@@ -13,6 +13,7 @@ import archon_synth as S
 import fm_edit_naive as E
 import fm_naive
 import fm_sampled_naive as M
+import stride_util as G
 
 pytestmark = pytest.mark.gpu
 
@@ -395,3 +396,44 @@ def test_repeatable_and_two_threads(archon):
     for r in out:
         assert r is not None and all((u == v).all() for u, v in zip(r, one))
     f0.close()
+
+
+@pytest.mark.parametrize("batch", [0, 1])
+@pytest.mark.parametrize("grid", G.GRIDS)
+def test_stride_grid(archon, grid, batch, monkeypatch):
+    """at most 1 and 3 workgroups (ARCHON_STRIDE_GRID) at K = 2 and 4 on 64 KiB of text, 22 patterns, in one batch and with
+    ARCHON_EDIT_BATCH=1: every wave of the piece count, the tile count, the tile list and the banded check takes item after
+    item -- matches from rule_np, counters from tile_model, through the block and a sampled handle, counting only and
+    emitting; byte-equal to the same calls without the route, with their counters, launches and host waits"""
+    if batch:
+        monkeypatch.setenv("ARCHON_EDIT_BATCH", str(batch))
+    x = _shape("text", 64 * KiB)
+    rng = np.random.default_rng(64 * KiB + 77)
+    b = archon.Block()
+    try:
+        b.forward(x)
+        f = b.fm_index(32)
+        b.fm_count([b"a"])                   # (the table built before the calls that are compared)
+        for K in (2, 4):
+            pats = _patterns(x, rng, K, (K + 1, 7, 33, 64, 65, 130) * 3)
+            want = _want(archon, [E.rule_cells(x, p) for p in pats], K)
+            counters = _counters(x, pats, K, 32)
+            assert len(pats) == 22 and want[1].size > 22
+
+            def call():
+                out, stats = [], []
+                for search in (b.fm_edit, f.edit):
+                    nhits, none = search(pats, K, emit=False)
+                    assert none is None and (nhits == want[0]).all()
+                    stats.append(archon.fm_edit_stats())
+                    got = search(pats, K)
+                    _same(got, want)
+                    st = _check_stats(archon, want, counters, K, 32, len(pats))
+                    assert st.batches == (len(pats) if batch else 1) and (st.lf_steps > 0) == (search == f.edit)
+                    stats.append(st)
+                    out += [nhits, got[0], got[1]]
+                return out, stats
+            G.same_under(monkeypatch, grid, call)
+        f.close()
+    finally:
+        b.close()

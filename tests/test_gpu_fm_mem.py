@@ -12,6 +12,7 @@ import pytest
 import archon_synth as S
 import fm_mem_naive as N
 import fm_naive
+import stride_util as G
 
 pytestmark = pytest.mark.gpu
 
@@ -377,3 +378,51 @@ def test_other_statistics_unchanged(archon):
         f.close()
     finally:
         b.close()
+
+
+@pytest.mark.parametrize("grid", G.GRIDS)
+def test_stride_grid(archon, oracle, naive, grid, monkeypatch):
+    """at most 1 and 3 workgroups (ARCHON_STRIDE_GRID) on text and dna at 64 KiB with some ninety patterns, so that every wave
+    takes pattern after pattern (one with hundreds of SMEMs ahead of one with none): the brute force's SMEMs, counts and
+    step counters at min_len 1 and 20, counting only and emitting; byte-equal to the same calls without the route, with
+    their counters"""
+    for shape in ("text", "dna"):
+        x = _shape(shape, 64 * KiB)
+        sa, bwt, base = oracle.forward(x)
+        f = archon.FmIndex(bwt, base)
+        try:
+            f.mirror()
+            pats = _patterns(x, np.random.default_rng(64 * KiB + len(shape)))
+            f.smems(pats[:1])                # (both tables in use before the calls that are compared)
+
+            def call():
+                out, stats = [], []
+                for min_len in (1, 20):
+                    nmems, nocc, none = f.smems(pats, min_len, mems=False)
+                    assert none is None
+                    stats.append(archon.fm_mem_stats())
+                    mems = _check(archon, naive, f, x, sa, pats, min_len)
+                    stats.append(archon.fm_mem_stats())
+                    got = f.smems(pats, min_len)
+                    assert (got[0] == nmems).all() and (got[1] == nocc).all()
+                    out += [nmems, nocc, mems, got[0], got[1]]
+                return out, stats
+            G.same_under(monkeypatch, grid, call)
+        finally:
+            f.close()
+
+
+def test_second_trip_at_the_product_grid(archon, oracle, naive):
+    """no route: 8192 + 13 patterns of 1-24 bytes on 64 KiB of text, so that waves 0-12 of the 2048 workgroups take a second
+    pattern: the brute force's SMEMs, counts and step counters"""
+    x = _shape("text", 64 * KiB)
+    sa, bwt, base = oracle.forward(x)
+    f = archon.FmIndex(bwt, base)
+    try:
+        f.mirror()
+        pats = G.k2_patterns(x)
+        assert len(pats) == G.K2 > 4 * 2048
+        mems = _check(archon, naive, f, x, sa, pats)
+        assert (mems["pattern"] >= 8192).any()
+    finally:
+        f.close()

@@ -11,6 +11,7 @@ import archon_synth as S
 import fm_ms_naive as N
 import fm_naive
 import lcp_kasai
+import stride_util as G
 
 pytestmark = pytest.mark.gpu
 
@@ -389,3 +390,46 @@ def test_other_statistics_unchanged(archon):
         assert (after[0], after[3], after[4], after[5], after[6]) == (before[0], before[3], before[4], before[5], before[6])
     finally:
         b.close()
+
+
+@pytest.mark.parametrize("grid", G.GRIDS)
+def test_stride_grid(archon, oracle, naive, kasai, grid, monkeypatch):
+    """at most 1 and 3 workgroups (ARCHON_STRIDE_GRID) on text and dna at 64 KiB with some ninety patterns, so that every wave
+    takes pattern after pattern: every record, the work counters and the probe bound against the brute force, with and
+    without the rows; byte-equal to the same calls without the route, with their counters"""
+    for shape in ("text", "dna"):
+        x = _shape(shape, 64 * KiB)
+        sa, bwt, base = oracle.forward(x)
+        lcp = kasai(x, sa)
+        f = archon.FmIndex(bwt, base)
+        try:
+            f.attach_lcp(lcp)
+            pats = _patterns(x, np.random.default_rng(64 * KiB + len(shape)))
+            f.ms(pats[:1])
+
+            def call():
+                length, lo, hi, off = _check(archon, naive, f, x, sa, lcp, pats)
+                st = archon.fm_ms_stats()
+                only = f.ms(pats, rows=False)
+                assert only[1] is None and only[2] is None and (only[0] == length).all()
+                return [length, lo, hi, off, only[0]], [st, archon.fm_ms_stats()]
+            G.same_under(monkeypatch, grid, call)
+        finally:
+            f.close()
+
+
+def test_second_trip_at_the_product_grid(archon, oracle, naive, kasai):
+    """no route: 8192 + 13 patterns of 1-24 bytes on 64 KiB of text, so that waves 0-12 of the 2048 workgroups take a second
+    pattern: every record and the work counters against the brute force"""
+    x = _shape("text", 64 * KiB)
+    sa, bwt, base = oracle.forward(x)
+    lcp = kasai(x, sa)
+    f = archon.FmIndex(bwt, base)
+    try:
+        f.attach_lcp(lcp)
+        pats = G.k2_patterns(x)
+        assert len(pats) == G.K2 > 4 * 2048
+        length, _, _, off = _check(archon, naive, f, x, sa, lcp, pats)
+        assert length[off[-14]:].max() > 0
+    finally:
+        f.close()

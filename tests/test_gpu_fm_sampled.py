@@ -7,6 +7,7 @@ import pytest
 
 import archon_synth as S
 import fm_sampled_naive as M
+import stride_util as G
 
 pytestmark = pytest.mark.gpu
 
@@ -265,3 +266,40 @@ def test_limits_and_bad_input(archon, oracle):
     f.sample(2)
     assert (f.samples() == M.expected_isa(P, b0, 2)).all()
     f.close()
+
+
+@pytest.mark.parametrize("grid", G.GRIDS)
+def test_stride_grid(archon, oracle, grid, monkeypatch):
+    """at most 1 and 3 workgroups (ARCHON_STRIDE_GRID) on text at 1 MiB, rate 32: locate through an index sampled from the BWT
+    alone and through the block's (some eighty patterns and thousands of rows, so every wave walks row after row) with the
+    exact LF steps, extract of 28 requests -- the whole text among them, 32 768 segments -- in both forms; byte-equal to the
+    same calls without the route, with their counters"""
+    n, rate = MiB, 32
+    x = _shape("text", n)
+    P, B, b0 = oracle.forward(x)
+    b = archon.Block()
+    try:
+        sa, base = b.forward(x)
+        assert base == b0 and (sa == P).all()
+        f1 = archon.FmIndex(b.read_bwt(), base).sample(rate)
+        f2 = b.fm_index(rate)
+        b.fm_count([b"a"])                   # (the block's table built before the calls that are compared)
+        some = _within_budget(f2, _patterns(x, np.random.default_rng(n + 5)), rate, n)
+        assert len(some) > 40
+
+        def call():
+            out, stats = [], []
+            for f in (f1, f2):
+                _check_locate(archon, f, b, P, some, rate)
+                stats.append(archon.fm_walk_stats())
+                out += list(f.locate(some))
+                _check_extract(archon, f, x, rate, np.random.default_rng(n + 6))
+                stats.append(archon.fm_walk_stats())
+                starts, lengths = _requests(n, np.random.default_rng(n + 6))
+                out += list(f.extract(starts, lengths))
+            return out, stats
+        G.same_under(monkeypatch, grid, call)
+        f1.close()
+        f2.close()
+    finally:
+        b.close()

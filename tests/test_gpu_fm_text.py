@@ -11,6 +11,7 @@ import archon_synth as S
 import fm_ms_naive as N
 import fm_text_naive as T
 import lcp_kasai
+import stride_util as G
 
 pytestmark = pytest.mark.gpu
 
@@ -408,3 +409,43 @@ def test_block_form(archon, oracle, naive, kasai):
     finally:
         h.close()
         b.close()
+
+
+@pytest.mark.parametrize("chunk", [0, 64])
+@pytest.mark.parametrize("grid", G.GRIDS)
+def test_stride_grid(archon, oracle, naive, kasai, grid, chunk, monkeypatch):
+    """at most 1 and 3 workgroups (ARCHON_STRIDE_GRID) at the default chunk (32 chunks: every wave walks several) and at
+    ARCHON_MS_CHUNK=64 (512 chunks), on text and dna: every len, lo and hi of ms_text against the brute force, the counters of
+    the model, and the phrases of rlz against the chain over the expected records, counted and emitted; byte-equal to the same
+    calls without the route, with their counters, launches and host waits"""
+    if chunk:
+        monkeypatch.setenv("ARCHON_MS_CHUNK", str(chunk))
+    C = chunk or DEFAULT_CHUNK
+    for shape in ("text", "dna"):
+        x, sa, bwt, base, lcp, text, (w_len, w_lo, w_hi) = _reference(oracle, naive, kasai, shape)
+        n, m = x.size, text.size
+        rec = np.zeros(m, archon.LPF)
+        rec["len"] = w_len
+        rec["src"] = np.where(w_len > 0, sa[np.minimum(w_lo, n - 1)], 0)
+        chain = T.chain(list(zip(w_len.tolist(), rec["src"].tolist())))
+        want_counters = T.counters(T.walk_len_of(w_len, C), C)
+        f = _index(archon, bwt, base, lcp, sa)
+        try:
+            def call():
+                length, lo, hi = f.ms_text(text)
+                st = archon.fm_text_stats()
+                assert (length == w_len).all() and (lo == w_lo).all() and (hi == w_hi).all()
+                _check_stats(st, n, m, C, want_counters)
+                assert (st.matched, st.longest) == (int(w_len.sum(dtype=np.uint64)), int(w_len.max()))
+                assert (st.kernel_launches, st.host_syncs) == (4, 1)
+                only = f.ms_text(text, rows=False)
+                assert (only[0] == w_len).all() and only[1] is None
+                st2 = archon.fm_text_stats()
+                got = f.rlz(text)
+                st3 = archon.fm_text_stats()
+                assert got.size == len(chain) == st3.phrases and [tuple(int(v) for v in p) for p in got] == chain
+                assert f.rlz(text, count_only=True) == got.size
+                return [length, lo, hi, only[0], got], [st, st2, st3, archon.fm_text_stats()]
+            G.same_under(monkeypatch, grid, call)
+        finally:
+            f.close()

@@ -12,6 +12,7 @@ import pytest
 import archon_synth as S
 import kmers_naive as K
 import repeats_naive as R
+import stride_util as G
 
 pytestmark = pytest.mark.gpu
 
@@ -111,15 +112,16 @@ def test_exhaustive_tiny(archon, tiny, tile, part, monkeypatch):
             assert got[b:b + words].tolist() == occ.tolist(), (x, k)
 
 
-def _check_block(archon, x, ks, sample=24):
+def _check_block(archon, x, ks, sample=24, tile=DEFAULT_TILE, keep=None):
     """Block.kmers, Block.kmer_occ and Block.sus of x against the text: records, histogram, counters and their invariants,
-    filters, count_only, occ, sus (the rule in numpy, and the identity "least L with count 1" on a sample of items)"""
+    filters, count_only, occ, sus (the rule in numpy, and the identity "least L with count 1" on a sample of items).  keep: a
+    list that takes every output and the stats record of every call"""
     n = x.size
     blk = archon.Block()
     sa, _ = blk.forward(x, want_sa=True)
     lcp = blk.lcp()
     sus = blk.sus()
-    st = archon.kmer_stats()
+    st0 = st = archon.kmer_stats()
     assert (st.what, st.n, st.ms_lcp > 0, st.ms_scatter > 0) == (2, n, True, True)
     assert (sus == K.sus_arrays(sa, lcp)).all()
     rng = np.random.default_rng(n)
@@ -132,7 +134,7 @@ def _check_block(archon, x, ks, sample=24):
         got, hist = blk.kmers(k, bins=16)
         st = archon.kmer_stats()
         assert got.size == want.size and (got == want).all(), k
-        assert (st.what, st.n, st.k, st.bins, st.tile) == (0, n, k, 16, DEFAULT_TILE) and st.ms_lcp > 0 and st.ms_count > 0
+        assert (st.what, st.n, st.k, st.bins, st.tile) == (0, n, k, 16, tile) and st.ms_lcp > 0 and st.ms_count > 0
         # the three invariants of the header
         assert st.distinct + st.short_rows == st.groups == groups and st.short_rows == min(k - 1, n)
         assert int(sizes.sum()) == max(n - k + 1, 0) == st.occurrences
@@ -153,6 +155,10 @@ def _check_block(archon, x, ks, sample=24):
         assert (st3.what, st3.k, st3.groups) == (1, k, groups) and st3.ms_scatter > 0
         assert occ.size == max(n - k + 1, 0) and (occ == K.occ_windows(x, k)).all(), k
         assert ((occ == 1) == ((sus[k - 1:] > 0) & (sus[k - 1:] <= k))).all(), k
+        if keep is not None:
+            keep += [got, hist, twice, once, occ, st, st2, archon.kmer_stats(), st3]
+    if keep is not None:
+        keep += [sus, st0]
     return blk, sa, lcp
 
 
@@ -467,3 +473,42 @@ def test_bad_sa_is_corrupt(archon, dna, bad):
             call()
         assert e.value.code == archon.E_CORRUPT
     assert (buf_t == -1).all()
+
+
+@pytest.mark.parametrize("tile", [0, 16])
+@pytest.mark.parametrize("grid", G.GRIDS)
+def test_stride_grid(archon, grid, tile, monkeypatch):
+    """at most 1 and 3 workgroups (ARCHON_STRIDE_GRID) on text and dna at 65 536 + 3, with the default tile (33 tiles, the last
+    of 3 rows) and with tiles of 16 rows (4097 tiles; 17 words of the tile scan): kmers with the histogram and the filters,
+    kmer_occ and sus at k = 2 and 12 against the text, byte-equal to the same calls without the route, with their counters,
+    launches and host waits"""
+    if tile:
+        monkeypatch.setenv("ARCHON_KMER_TILE", str(tile))
+    for shape in ("text", "dna"):
+        x = S.gen_shape(shape, 65536 + 3)
+
+        def call():
+            keep = []
+            _check_block(archon, x, (2, 12), sample=4, tile=tile or DEFAULT_TILE, keep=keep)[0].close()
+            return [v for v in keep if isinstance(v, np.ndarray)], [v for v in keep if not isinstance(v, np.ndarray)]
+        G.same_under(monkeypatch, grid, call)
+
+
+@pytest.mark.parametrize("shape", ["a", "dna"])
+def test_second_trip_at_the_product_grid(archon, shape):
+    """no route: 2048 * 2048 + 3 * 2048 + 5 rows are 2052 tiles, so workgroups 0-3 of the 2048 take a second tile in every pass
+    and the last tile has 5 rows.  One byte at k = 5: one group of n - 4 rows.  DNA at k = 12 against the text"""
+    n = G.N2
+    x = S.gen_shape(shape, n)
+    blk, _, _ = _check_block(archon, x, (5,) if shape == "a" else (12,), sample=4)
+    try:
+        assert blk.validate() == 1
+        if shape == "a":
+            got = blk.kmers(5)
+            st = archon.kmer_stats()
+            assert got.tolist() == [(0, n - 4, n)] and (st.groups, st.short_rows, st.distinct, st.most, st.unique) == (5, 4, 1, n - 4, 0)
+            assert (blk.kmer_occ(5) == n - 4).all()
+            sus = blk.sus()
+            assert sus[n - 1] == n and not sus[:n - 1].any()
+    finally:
+        blk.close()

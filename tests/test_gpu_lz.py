@@ -10,6 +10,7 @@ import pytest
 
 import archon_synth as S
 import lz_naive as Z
+import stride_util as G
 
 pytestmark = pytest.mark.gpu
 
@@ -121,8 +122,9 @@ def test_exhaustive_tiny(archon, naive, tiny, fan, tile, dir, monkeypatch):
         assert got[:3 * total].view(archon.PHRASE).tolist() == phrases.tolist(), (sa, lcp)
 
 
-def _block_lz(archon, naive, x, dirs=(0, 1), tile=DEFAULT_TILE, fan=DEFAULT_FAN):
-    """x through Block.lz in the given directions against the helper; returns {dir: phrases}"""
+def _block_lz(archon, naive, x, dirs=(0, 1), tile=DEFAULT_TILE, fan=DEFAULT_FAN, keep=None):
+    """x through Block.lz in the given directions against the helper; returns {dir: phrases} (keep: a list that takes the
+    records, the phrases and the stats records of every call)"""
     n = x.size
     blk = archon.Block()
     sa, _ = blk.forward(x, want_sa=True)
@@ -141,6 +143,8 @@ def _block_lz(archon, naive, x, dirs=(0, 1), tile=DEFAULT_TILE, fan=DEFAULT_FAN)
         assert st.ms_lcp > 0 and st.ms_lpf > 0 and st.ms_parse > 0 and st.ms_emit > 0
         assert blk.lz(d, count_only=True) == phrases.size and archon.lz_stats().ms_emit == 0
         out[d] = got
+        if keep is not None:
+            keep += [rec, got, st, archon.lz_stats()]
     blk.close()
     return out, sa
 
@@ -434,3 +438,64 @@ def test_two_contexts_concurrently(archon):
     for k in (0, 1):
         assert (got[k][1] == solo[k][1]).all()
         assert stats[k].n == blocks[k].size and stats[k].phrases == solo[k][1].size
+
+
+def _decode_ends(phrases, x):
+    """the text of (end, len, src) phrases of direction 0 in chain order (ends descending), literals taken from x: the len
+    bytes before item end are the len bytes before the earlier item src"""
+    out = np.zeros(x.size, np.uint8)
+    for e, m, s in phrases[::-1].tolist():
+        if m == 0:
+            out[e - 1] = x[e - 1]
+        elif s <= e - m:
+            out[e - m:e] = out[s - m:s]
+        else:                               # the copy overlaps what it writes: it repeats the e - s bytes before e - m
+            out[e - m:e] = np.resize(out[s - m:e - m], m)
+    return out
+
+
+@pytest.mark.parametrize("grid", G.GRIDS)
+def test_stride_grid(archon, naive, grid, monkeypatch):
+    """at most 1 and 3 workgroups (ARCHON_STRIDE_GRID) on text and a random block with a long copy at 65 536 + 3 (33 tiles of
+    the LPF pass, the last of 3 rows; 257 tiles of the parse): the LPF records in both directions, the parse counted and
+    emitted through Block.lz against the helper, and lpf / lz_parse on host arrays, byte-equal to the same calls without the
+    route, with their counters, launches and host waits"""
+    for shape in ("text", "random_copy"):
+        x = S.gen_shape(shape, 65536 + 3)
+
+        def call():
+            keep = []
+            _, sa = _block_lz(archon, naive, x, keep=keep)
+            rec = archon.lpf(sa, archon.lcp(x, sa), 1)
+            keep += [rec, archon.lz_stats(), _parse_once(archon, rec), archon.lz_stats()]
+            return [v for v in keep if isinstance(v, np.ndarray)], [v for v in keep if not isinstance(v, np.ndarray)]
+        G.same_under(monkeypatch, grid, call)
+
+
+@pytest.mark.parametrize("shape", ["a", "dna"])
+def test_second_trip_at_the_product_grid(archon, naive, shape):
+    """no route: 2048 * 2048 + 3 * 2048 + 5 rows are 2052 tiles of the LPF pass, so workgroups 0-3 of the 2048 take a second
+    tile and the last tile has 5 rows (the parse's tiles of 256 items go round eight times).  One byte: two phrases.  DNA: the
+    LPF records and the phrases against the helper, and decoding the phrases gives the block back"""
+    n = G.N2
+    x = S.gen_shape(shape, n)
+    blk = archon.Block()
+    try:
+        sa, _ = blk.forward(x, want_sa=True)
+        assert blk.validate() == 1
+        rec, got = blk.lz(0, want_lpf=True)
+        st = archon.lz_stats()
+        if shape == "a":
+            assert got.tolist() == [(n, n - 1, n - 1), (1, 0, 0)]
+            assert (rec["len"] == np.arange(n)).all()
+            assert blk.lz(1).tolist() == [(n, 0, 0), (n - 1, n - 1, n)]
+        else:
+            want = naive.lpf(sa, blk.lcp(), 0)
+            phrases = naive.parse(want)
+            assert (rec == want).all() and got.size == phrases.size and (got == phrases).all()
+            assert (_decode_ends(got, x) == x).all()
+            assert blk.lz(0, count_only=True) == phrases.size
+        _check_parse_stats(st, n, got, DEFAULT_TILE)
+        assert st.probes <= _probe_bound(n, DEFAULT_FAN)
+    finally:
+        blk.close()

@@ -14,6 +14,7 @@ import pytest
 import archon_synth as S
 import maw_naive as M
 import repeats_naive as R
+import stride_util as G
 
 pytestmark = pytest.mark.gpu
 
@@ -404,3 +405,59 @@ def test_other_records_stay(archon):
     assert (archon.kmer_stats().asdict(), archon.repeat_stats().asdict()) == before
     st = archon.maw_stats()
     assert st.n == 513 and archon.lib().archon_hip_maw_last_stats(0, None) == archon.E_ARG
+
+
+@pytest.mark.parametrize("grid", G.GRIDS)
+def test_stride_grid(archon, grid, monkeypatch):
+    """at most 1 and 3 workgroups (ARCHON_STRIDE_GRID; a wave takes a tile of 256 rows, so four and twelve waves share the 65
+    tiles of 16 385 rows, 16 and 5 each, the last tile of one row): random blocks over 2 and 4 letters, one byte x 1025, the
+    README under a length window, and the block whose words lie in the last tile only -- the model's records and counters
+    through the host, device and block forms, byte-equal to the same calls without the route, with their counters, launches
+    and host waits.  (The random blocks are 16 385 bytes, not the 70 001 of test_many_tiles: at 70 001 this test alone took as
+    long as the rest of the file.)"""
+    for name, lo, hi in (("rand:2:16385", 2, 0), ("rand:4:16385", 2, 0), ("same:1025", 2, 0), ("readme:6000", 2, 4), ("lasttile", 4, 0)):
+        def call():
+            got_h, st_h = _host(archon, name, lo, hi)
+            got_d, st_d = _dev(archon, name, lo, hi, odd=True)
+            got_b, st_b = _block(archon, name, lo, hi)
+            assert st_h.probes == st_d.probes == st_b.probes
+            return [got_h, got_d, got_b], [st_h, st_d, st_b]
+        G.same_under(monkeypatch, grid, call)
+
+
+def test_second_trip_at_the_product_grid_one_byte(archon):
+    """no route: 8192 * 256 + 5 * 256 + 7 rows are 8198 tiles of 256, so waves 0-5 of the 2048 workgroups take a second tile
+    and the last tile has 7 rows.  One byte: the one word of n + 1 bytes"""
+    n = G.N_MAW
+    blk = archon.Block()
+    try:
+        blk.forward(np.full(n, ord("c"), np.uint8), want_sa=True)
+        assert blk.validate() == 1
+        assert blk.maws().tolist() == [(0, 1, n + 1, n, ord("c"))]
+        st = archon.maw_stats()
+        assert (st.n, st.words, st.shortest, st.longest, st.absent_bytes, st.intervals) == (n, 1, n + 1, n + 1, 255, n - 1)
+        assert blk.maws(count_only=True) == 1
+    finally:
+        blk.close()
+
+
+def test_second_trip_at_the_product_grid_four_letters(archon):
+    """no route, 8198 tiles: a random block over four letters with min_len = max_len = 11, 12, 13 (1.5, 1.4 and 0.5
+    million words), as a set against the definition by the text (maw_naive.words_of_length, pinned by
+    test_maw_abi.py): every word once, none missing"""
+    n = G.N_MAW
+    x = _text("rand:4:%d" % n)
+    blk = archon.Block()
+    try:
+        blk.forward(x, want_sa=True)
+        assert blk.validate() == 1
+        for L in (11, 12, 13):
+            got = blk.maws(L, L)
+            want = M.words_of_length(x, L)
+            codes = np.sort(M.record_codes(x, got, L))
+            assert want.size > 10000 and got.size == want.size and (codes == want).all(), L
+            st = archon.maw_stats()
+            assert (st.n, st.min_len, st.max_len, st.words, st.shortest, st.longest) == (n, L, L, want.size, L, L)
+            assert blk.maws(L, L, count_only=True) == want.size
+    finally:
+        blk.close()

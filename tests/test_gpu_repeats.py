@@ -10,6 +10,7 @@ import pytest
 
 import archon_synth as S
 import repeats_naive as R
+import stride_util as G
 
 pytestmark = pytest.mark.gpu
 
@@ -104,17 +105,13 @@ def _numpy_counters(lcp):
     return intervals, int(v[1:].sum())
 
 
-@pytest.mark.parametrize("shape", S.SHAPES)
-@pytest.mark.parametrize("n", [1000, 65536, MiB + 3])
-def test_shapes(archon, naive, shape, n, monkeypatch):
-    """every synthetic shape through Block.repeats, kinds 1 and 2 with both filters, against the helper; the counters against
-    numpy on the LCP array; at 65536 once more with a fan-out of 4"""
-    x = S.gen_shape(shape, n)
-    blk = archon.Block()
-    _, base = blk.forward(x, want_sa=True)
-    lcp, bwt = blk.lcp(), blk.read_bwt()
+def _check_kinds(archon, naive, blk, lcp, bwt, base, kinds):
+    """Block.repeats of the given kinds with both filters against the helper, the counters against numpy on the LCP array;
+    returns the records and the stats records of every call"""
+    n = bwt.size
     intervals, sum_lcp = _numpy_counters(lcp)
-    for kind in (1, 2):
+    out, stats = [], []
+    for kind in kinds:
         for min_len in (1, 8):
             for min_occ in (2, 3):
                 want, w_int, w_occ, w_long = naive(lcp, bwt, base, kind, min_len, min_occ)
@@ -129,6 +126,21 @@ def test_shapes(archon, naive, shape, n, monkeypatch):
                 assert st.probes <= _bound(n, DEFAULT_FAN)[0] and st.levels == _bound(n, DEFAULT_FAN)[1]
                 assert blk.repeats(kind, min_len, min_occ, count_only=True) == want.size
                 assert archon.repeat_stats().ms_emit == 0 and archon.repeat_stats().ms_lcp > 0
+                out.append(got)
+                stats += [st, archon.repeat_stats()]
+    return out, stats
+
+
+@pytest.mark.parametrize("shape", S.SHAPES)
+@pytest.mark.parametrize("n", [1000, 65536, MiB + 3])
+def test_shapes(archon, naive, shape, n, monkeypatch):
+    """every synthetic shape through Block.repeats, kinds 1 and 2 with both filters, against the helper; the counters against
+    numpy on the LCP array; at 65536 once more with a fan-out of 4"""
+    x = S.gen_shape(shape, n)
+    blk = archon.Block()
+    _, base = blk.forward(x, want_sa=True)
+    lcp, bwt = blk.lcp(), blk.read_bwt()
+    _check_kinds(archon, naive, blk, lcp, bwt, base, (1, 2))
     if n == 65536:
         monkeypatch.setenv("ARCHON_REP_FAN", "4")
         want = naive(lcp, bwt, base, 1)[0]
@@ -309,3 +321,51 @@ def test_garbage_lcp(archon, naive):
         assert (got["lo"] < got["row"]).all() and (got["row"] < got["hi"]).all() and (got["hi"] <= n).all()
         assert (got == naive(lcp, bwt, 12345, kind)[0]).all()
         assert archon.repeat_stats().probes <= _bound(n, DEFAULT_FAN)[0]
+
+
+@pytest.mark.parametrize("grid", G.GRIDS)
+def test_stride_grid(archon, naive, grid, monkeypatch):
+    """at most 1 and 3 workgroups (ARCHON_STRIDE_GRID) on text and motif_defects at 65 536 (32 tiles: 32 and 11, 11, 10 trips):
+    kinds 0, 1, 2 with both filters through Block.repeats against the helper, counting only and with the emit pass, byte-equal
+    to the same calls without the route, with their counters, launches and host waits"""
+    for shape in ("text", "motif_defects"):
+        x = S.gen_shape(shape, 65536)
+        blk = archon.Block()
+        try:
+            _, base = blk.forward(x, want_sa=True)
+            lcp, bwt = blk.lcp(), blk.read_bwt()
+            G.same_under(monkeypatch, grid, lambda: _check_kinds(archon, naive, blk, lcp, bwt, base, (0, 1, 2)))
+        finally:
+            blk.close()
+
+
+@pytest.mark.parametrize("shape", ["a", "dna"])
+def test_second_trip_at_the_product_grid(archon, naive, shape):
+    """no route: 2048 * 2048 + 3 * 2048 + 5 rows are 2052 tiles, so workgroups 0-3 of the 2048 take a second tile and the
+    last tile has 5 rows.  One byte: the counts of the three kinds and the one supermaximal record, as in
+    test_worst_case_depth.  DNA: the maximal repeats emitted, against the helper, with its counters"""
+    n = G.N2
+    x = S.gen_shape(shape, n)
+    blk = archon.Block()
+    try:
+        _, base = blk.forward(x, want_sa=True)
+        assert blk.validate() == 1
+        bound, levels = _bound(n, DEFAULT_FAN)
+        if shape == "a":
+            for kind, want in ((0, n - 1), (1, n - 1), (2, 1)):
+                assert blk.repeats(kind, count_only=True) == want
+                st = archon.repeat_stats()
+                assert st.intervals == n - 1 and st.probes <= bound and st.levels == levels and st.longest == n - 1
+                assert st.sum_lcp == n * (n - 1) // 2 and st.distinct_substrings == n
+            assert blk.repeats(2).tolist() == [(0, 2, n - 1, 1)]
+        else:
+            lcp, bwt = blk.lcp(), blk.read_bwt()
+            want, w_int, w_occ, w_long = naive(lcp, bwt, base, 1)
+            got = blk.repeats(1)
+            assert got.size == want.size > n // 8 and (got == want).all()
+            st = archon.repeat_stats()
+            assert (st.intervals, st.repeats, st.occurrences, st.longest) == (w_int, want.size, w_occ, w_long)
+            assert st.probes <= bound and st.levels == levels
+            assert st.distinct_substrings == n * (n + 1) // 2 - int(lcp[1:].astype(np.int64).sum())
+    finally:
+        blk.close()

@@ -15,6 +15,7 @@ import pytest
 import archon_synth as S
 import repeats_naive as R
 import runs_naive as N
+import stride_util as G
 
 pytestmark = pytest.mark.gpu
 
@@ -506,3 +507,71 @@ def test_resident_block_survives(archon):
     finally:
         blk.close()
     _independent(x, got)
+
+
+@pytest.mark.parametrize("grid", G.GRIDS)
+def test_stride_grid(archon, grid, monkeypatch):
+    """at most 1 and 3 workgroups (ARCHON_STRIDE_GRID): random binary at 16^3 + 1 (9 tiles), the Fibonacci string of length
+    10 946 (6 tiles, the last one ragged), text under period, copies and length filters (17 tiles) and 70 000 LCE queries
+    (274 workgroups by themselves) -- the rule's records and counters through the host and device forms, byte-equal to the same
+    call without the route, with its counters, launches and host waits"""
+    for name, filters in (("binary:16385", (0, 0, 2, 0)), ("fib:21", (0, 0, 2, 0)), ("text:33333", (2, 40, 2, 4))):
+        x, sa, lcp, sa_c = _case(archon, name)
+        want, c = _rule(archon, name, filters)
+        assert want.size > 50
+
+        def call():
+            got_h, st_h = _host(archon, sa, lcp, sa_c, want, c, filters)
+            got_d, st_d = _dev(archon, sa, lcp, sa_c, want, c, filters, odd=True)
+            count = archon.runs(sa, lcp, sa_c, *filters, count_only=True)
+            return (got_h, got_d, count), (st_h, st_d, archon.run_stats())
+        got = G.same_under(monkeypatch, grid, call)
+        assert all(N.is_run_fast(x.tobytes(), int(r["start"]), int(r["end"]), int(r["period"])) for r in got[0])
+    x, sa, lcp, _ = _case(archon, "defects:70000")
+    n = x.size
+    rng = np.random.default_rng(70000)
+    s, t = rng.integers(0, n + 1, 70000).astype(np.uint32), rng.integers(0, n + 1, 70000).astype(np.uint32)
+    rows = rng.integers(0, n - 1, 20000)
+    s[:20000], t[:20000] = sa[rows], sa[rows + 1]
+    want = N.SparseLce(sa, lcp).many(s, t)
+
+    def lce():
+        got = archon.lce(sa, lcp, s, t)
+        assert got.tolist() == want.tolist()
+        return got, archon.run_stats()
+    G.same_under(monkeypatch, grid, lce)
+
+
+@pytest.mark.parametrize("shape", ["same", "dna"])
+def test_second_trip_at_the_product_grid(archon, shape):
+    """no route: 2048 * 2048 + 3 * 2048 + 5 items are 2052 tiles, so workgroups 0-3 of the 2048 take a second tile in the count
+    and the emit pass and the last tile has 5 items.  One byte: the single record and the exact counters of test_one_byte.
+    DNA with max_period 8: a million records, as a set those of the vectorised finder, in ascending root, and a sample of
+    10 000 checked as runs by slices"""
+    n = G.N2
+    x = np.ascontiguousarray(_text("%s:%d" % (shape, n)))
+    blk = archon.Block()
+    try:
+        blk.forward(x, want_sa=True)
+        assert blk.validate() == 1
+        if shape == "same":
+            assert blk.runs().tolist() == [(0, n, 1, n)]
+            st = archon.run_stats()
+            assert (st.roots, st.candidates, st.runs, st.emitted, st.longest_period) == (2, 2 * (n - 1), 1, 1, 1)
+            assert st.lce_queries == 2 * (n - 1) + 2 * (n - 2)
+            assert st.probes <= 2 * n * 31 * _levels(n + 1, DEFAULT_FAN)
+        else:
+            got = blk.runs(max_period=8)
+            st = archon.run_stats()
+            xb = x.tobytes()
+            want = N.runs_short(xb, 8)
+            triples = set(zip(got["start"].tolist(), got["end"].tolist(), got["period"].tolist()))
+            assert got.size == len(triples) == len(want) > 500000 and triples == want
+            assert st.emitted == st.runs == got.size and st.longest_period == int(got["period"].max()) == 8
+            root = got["root"].astype(np.int64)
+            assert (np.diff(root) >= 0).all() and (got["start"] + got["period"] <= root).all() and (root <= got["end"]).all()
+            for i in np.random.default_rng(n).integers(0, got.size, 10000).tolist():
+                assert N.is_run_fast(xb, int(got["start"][i]), int(got["end"][i]), int(got["period"][i]))
+            assert blk.runs(max_period=8, count_only=True) == got.size
+    finally:
+        blk.close()

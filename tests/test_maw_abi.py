@@ -201,3 +201,25 @@ def test_model_is_the_definition():
             assert c["absent_bytes"] == 256 - len(set(x)) and c["children"] <= 2 * n
             for r, w in zip(recs, words):
                 assert w not in x and w[:-1] in x and w[1:] in x
+
+
+def test_bitmap_helper_is_the_definition():
+    """words_of_length (presence bitmaps of 2-bit codes, what the GPU test at two million rows compares with) against the
+    definition by the text on the random strings over 2, 3 and 4 letters, at every length from 2 to n + 1; record_codes gives
+    the codes of the model's records"""
+    rng = np.random.default_rng(20261021)
+    for sigma in (2, 3, 4):
+        for i in range(90):
+            n = 1 + i % 18
+            x = bytes(rng.integers(0, sigma, n).astype(np.uint8) + 97)
+            xa = np.frombuffer(x, np.uint8)
+            words = M.definition(x)
+            recs = M.model(*R.a7_arrays(x))[0]
+            seen = 0
+            for L in range(2, min(n + 2, 12)):
+                codes = M.words_of_length(xa, L)
+                assert {M.code_bytes(c, L) for c in codes.tolist()} == {w for w in words if len(w) == L}, (x, L)
+                assert (np.diff(codes) > 0).all()
+                assert sorted(M.record_codes(xa, recs[recs["len"] == L], L).tolist()) == codes.tolist(), (x, L)
+                seen += codes.size
+            assert seen == sum(len(w) < 12 for w in words)

@@ -23,6 +23,7 @@ RANGE = {
     "MS_CHUNK": (0xFFFFFFFF, ": not a chunk of 1 .. 2^32 - 1 bytes (0: the default)", True),
     "EDIT_TILE": (64, ": not a tile of 1 .. 64 ends (0: the default)", True),
     "EDIT_BATCH": (0x7FFFFFFF, ": not a batch of 1 .. 2^31 - 1 patterns (0: the budget's own)", True),
+    "STRIDE_GRID": (2048, ": not a grid of 1 .. 2048 workgroups (0: the default)", True),
 }
 DOC_TILE = (64, 1 << 20, ": not a tile of 64 .. 2^20 rows, a multiple of 64 (0: the default)")
 
