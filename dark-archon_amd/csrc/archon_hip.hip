@@ -24,6 +24,7 @@
 #include "fm_ms.hiph"
 #include "fm_text.hiph"
 #include "fm_doc.hiph"
+#include "fm_win.hiph"
 #include "fm_host.hiph"
 #include "repeats.hiph"
 #include "lz.hiph"
@@ -212,6 +213,14 @@ static int fmd_doc_of_check(const archon_hip_fm *f, const void *items, uint64_t 
     if (!f || (!items && count) || (!doc && count)) { set_error("null pointer"); return ARCHON_E_ARG; }
     if (count >> 32) { set_error("FM doc of: %llu items in one call", (unsigned long long)count); return ARCHON_E_ARG; }
     return fmd_check_attached(f);
+}
+
+// a window call's pointers: lo, hi and the answer whenever there are queries, a and b both given or both null
+static int fmwin_check(const archon_hip_fm *f, const void *lo, const void *hi, const void *a, const void *b, const void *answer, uint32_t k)
+{
+    if (!f || (k && (!lo || !hi || !answer))) { set_error("null pointer"); return ARCHON_E_ARG; }
+    if (!a != !b) { set_error("FM window: a and b are both given or both null"); return ARCHON_E_ARG; }
+    return ARCHON_OK;
 }
 
 // ---- resident blocks
@@ -1365,6 +1374,84 @@ int archon_hip_fm_doc_of_dev(archon_hip_fm *f, const uint32_t *d_items, uint64_t
 
 int archon_hip_get_fm_doc_stats(int dev, archon_hip_fm_doc_stats *out) { return t_fmd_stats.get(dev, out, "documents call"); }
 
+// ---- windows
+int archon_hip_fm_attach_wm(archon_hip_fm *f)
+{
+    if (!f) { set_error("null pointer"); return ARCHON_E_ARG; }
+    if (!f->sa.mem) { set_error("FM attach wm: the handle has no suffix array (archon_hip_fm_attach_sa)"); return ARCHON_E_ARG; }
+    return with_ctx(f->dev, nullptr, [&](Ctx *c, hipStream_t s) -> int {
+        KeepStats<archon_hip_fm_win_stats> keep(t_fmwin_stats, f->dev);
+        fmwin_call_stats(&keep.st, f, 0, 0);
+        return fmwin_attach_run(c, s, f, f->sa.sa, &keep.st);
+    });
+}
+
+// one window call of either kind, host or device arrays: the checks every form shares, the context, the record
+static int fmwin_call(archon_hip_fm *f, FmWinCall q, void *stream, uint64_t *total)
+{
+    q.f = f;
+    ARCHON_TRY(fmwin_check_attached(f));
+    if (q.host) ARCHON_TRY(fmwin_check_queries(f->n, q.lo, q.hi, q.a, q.b, q.k));
+    if (!q.k) return ARCHON_OK;
+    return with_ctx(f->dev, stream, [&](Ctx *c, hipStream_t s) -> int {
+        KeepStats<archon_hip_fm_win_stats> keep(t_fmwin_stats, f->dev);
+        fmwin_call_stats(&keep.st, f, q.k, q.most);
+        return fmwin_run(c, s, q, total, &keep.st);
+    });
+}
+
+int archon_hip_fm_win_count(archon_hip_fm *f, const uint32_t *lo, const uint32_t *hi, const uint32_t *a_or_null, const uint32_t *b_or_null, uint32_t k,
+                            uint32_t *count)
+{
+    ARCHON_TRY(fmwin_check(f, lo, hi, a_or_null, b_or_null, count, k));
+    return fmwin_call(f, FmWinCall{f, k, 0, lo, hi, a_or_null, b_or_null, nullptr, true, false, false, count, nullptr, nullptr, 0}, nullptr, nullptr);
+}
+
+int archon_hip_fm_win_count_dev(archon_hip_fm *f, const uint32_t *d_lo, const uint32_t *d_hi, const uint32_t *d_a_or_null, const uint32_t *d_b_or_null,
+                                uint32_t k, uint32_t *d_count, void *stream)
+{
+    ARCHON_TRY(fmwin_check(f, d_lo, d_hi, d_a_or_null, d_b_or_null, d_count, k));
+    return fmwin_call(f, FmWinCall{f, k, 0, d_lo, d_hi, d_a_or_null, d_b_or_null, nullptr, false, false, false, d_count, nullptr, nullptr, 0}, stream, nullptr);
+}
+
+int archon_hip_fm_win_select(archon_hip_fm *f, const uint32_t *lo, const uint32_t *hi, const uint32_t *a_or_null, const uint32_t *b_or_null,
+                             const uint32_t *idx, uint32_t k, uint32_t *item)
+{
+    ARCHON_TRY(fmwin_check(f, lo, hi, a_or_null, b_or_null, item, k));
+    if (k && !idx) { set_error("null pointer"); return ARCHON_E_ARG; }
+    return fmwin_call(f, FmWinCall{f, k, 0, lo, hi, a_or_null, b_or_null, idx, true, true, false, nullptr, item, nullptr, 0}, nullptr, nullptr);
+}
+
+int archon_hip_fm_win_select_dev(archon_hip_fm *f, const uint32_t *d_lo, const uint32_t *d_hi, const uint32_t *d_a_or_null, const uint32_t *d_b_or_null,
+                                 const uint32_t *d_idx, uint32_t k, uint32_t *d_item, void *stream)
+{
+    ARCHON_TRY(fmwin_check(f, d_lo, d_hi, d_a_or_null, d_b_or_null, d_item, k));
+    if (k && !d_idx) { set_error("null pointer"); return ARCHON_E_ARG; }
+    return fmwin_call(f, FmWinCall{f, k, 0, d_lo, d_hi, d_a_or_null, d_b_or_null, d_idx, false, true, false, nullptr, d_item, nullptr, 0}, stream, nullptr);
+}
+
+int archon_hip_fm_win_list(archon_hip_fm *f, const uint32_t *lo, const uint32_t *hi, const uint32_t *a_or_null, const uint32_t *b_or_null, uint32_t k,
+                           uint32_t most, uint32_t *count, archon_hip_fm_win *out_or_null, uint64_t cap, uint64_t *total)
+{
+    if (total) *total = 0;
+    if (!total) { set_error("null pointer"); return ARCHON_E_ARG; }
+    ARCHON_TRY(fmwin_check(f, lo, hi, a_or_null, b_or_null, count, k));
+    return fmwin_call(f, FmWinCall{f, k, most, lo, hi, a_or_null, b_or_null, nullptr, true, false, true, count, nullptr,
+                                   reinterpret_cast<fmwin::FmWin *>(out_or_null), cap}, nullptr, total);
+}
+
+int archon_hip_fm_win_list_dev(archon_hip_fm *f, const uint32_t *d_lo, const uint32_t *d_hi, const uint32_t *d_a_or_null, const uint32_t *d_b_or_null,
+                               uint32_t k, uint32_t most, uint32_t *d_count, archon_hip_fm_win *d_out_or_null, uint64_t cap, uint64_t *total, void *stream)
+{
+    if (total) *total = 0;
+    if (!total) { set_error("null pointer"); return ARCHON_E_ARG; }
+    ARCHON_TRY(fmwin_check(f, d_lo, d_hi, d_a_or_null, d_b_or_null, d_count, k));
+    return fmwin_call(f, FmWinCall{f, k, most, d_lo, d_hi, d_a_or_null, d_b_or_null, nullptr, false, false, true, d_count, nullptr,
+                                   reinterpret_cast<fmwin::FmWin *>(d_out_or_null), cap}, stream, total);
+}
+
+int archon_hip_fm_win_last_stats(int dev, archon_hip_fm_win_stats *out) { return t_fmwin_stats.get(dev, out, "window call"); }
+
 // ---- resident blocks ---------------------------------------------------------------------------------------------------
 int archon_hip_block_create(int dev, archon_hip_block **out)
 {
@@ -1825,6 +1912,20 @@ int archon_hip_block_fm_attach_docs(archon_hip_block *b, archon_hip_fm *f, const
         KeepStats<archon_hip_fm_doc_stats> keep(t_fmd_stats, b->dev);
         fmd_call_stats(&keep.st, f, 0);
         return fmd_attach_run(c, s, f, b->d_sa(), bounds, nullptr, ndocs, &keep.st);
+    });
+}
+
+// the resident suffix array read where it is, device to device, as the documents' block form reads it
+int archon_hip_block_fm_attach_wm(archon_hip_block *b, archon_hip_fm *f)
+{
+    if (!b || !f) { set_error("null pointer"); return ARCHON_E_ARG; }
+    std::lock_guard<std::mutex> lkb(b->mu);
+    ARCHON_TRY(block_check(b, true));
+    ARCHON_TRY(block_check_handle(b, f, "FM attach wm"));
+    return with_ctx(b->dev, nullptr, [&](Ctx *c, hipStream_t s) -> int {
+        KeepStats<archon_hip_fm_win_stats> keep(t_fmwin_stats, b->dev);
+        fmwin_call_stats(&keep.st, f, 0, 0);
+        return fmwin_attach_run(c, s, f, b->d_sa(), &keep.st);
     });
 }
 

@@ -58,6 +58,8 @@ SYMBOLS = [
     "archon_hip_block_complexity", "archon_hip_entropy_last_stats",
     "archon_hip_lce", "archon_hip_lce_dev", "archon_hip_block_lce", "archon_hip_runs", "archon_hip_runs_dev", "archon_hip_block_runs",
     "archon_hip_runs_last_stats",
+    "archon_hip_fm_attach_wm", "archon_hip_block_fm_attach_wm", "archon_hip_fm_win_count", "archon_hip_fm_win_count_dev", "archon_hip_fm_win_select",
+    "archon_hip_fm_win_select_dev", "archon_hip_fm_win_list", "archon_hip_fm_win_list_dev", "archon_hip_fm_win_last_stats",
 ]
 
 # archon_hip_fm_hit: one distinct string within the distance of a pattern (FmIndex.approx, Block.fm_approx)
@@ -68,6 +70,8 @@ FM_EDIT = np.dtype([("start", "<u4"), ("end", "<u4"), ("distance", "<u4"), ("pat
 FM_MEM = np.dtype([("lo", "<u4"), ("hi", "<u4"), ("start", "<u4"), ("end", "<u4"), ("pattern", "<u4"), ("reserved0", "<u4")])
 # archon_hip_fm_doc: one document of a pattern or a row range (FmIndex.docs, docs_ranges): tf rows of the range lie in it, the first is `row`
 FM_DOC = np.dtype([("doc", "<u4"), ("tf", "<u4"), ("row", "<u4"), ("range", "<u4")])
+# archon_hip_fm_win: one occurrence of a row range inside its item window (FmIndex.win_list): the item where it ends, its range
+FM_WIN = np.dtype([("item", "<u4"), ("range", "<u4")])
 # archon_hip_repeat: one repeat of a block (repeats, Block.repeats): rows [lo, hi) of a string of len bytes, its representative row
 REPEAT = np.dtype([("lo", "<u4"), ("hi", "<u4"), ("len", "<u4"), ("row", "<u4")])
 # struct archon_hip_lpf: the longest previous factor that ends at an item and the item where a copy of it ends (lpf, Block.lz)
@@ -218,6 +222,16 @@ class FmDocStats(_Record):
         ("pattern_bytes", ctypes.c_uint64), ("rows", ctypes.c_uint64), ("tiles", ctypes.c_uint64), ("listed", ctypes.c_uint64),
         ("probes", ctypes.c_uint64), ("doc_bytes", ctypes.c_uint64), ("kernel_launches", ctypes.c_uint32), ("host_syncs", ctypes.c_uint32),
         ("ms_attach", ctypes.c_float), ("ms_search", ctypes.c_float), ("ms_count", ctypes.c_float), ("ms_emit", ctypes.c_float),
+    ]
+
+
+class FmWinStats(_Record):
+    """archon_hip_fm_win_stats: the calling thread's last window call (attach_wm, win_count, win_select, win_list) on a device"""
+    _fields_ = [
+        ("n", ctypes.c_uint32), ("levels", ctypes.c_uint32), ("ranges", ctypes.c_uint32), ("most", ctypes.c_uint32), ("attached", ctypes.c_uint32),
+        ("reserved0", ctypes.c_uint32), ("rows", ctypes.c_uint64), ("in_window", ctypes.c_uint64), ("listed", ctypes.c_uint64),
+        ("walks", ctypes.c_uint64), ("wm_bytes", ctypes.c_uint64), ("kernel_launches", ctypes.c_uint32), ("host_syncs", ctypes.c_uint32),
+        ("ms_attach", ctypes.c_float), ("ms_count", ctypes.c_float), ("ms_emit", ctypes.c_float),
     ]
 
 
@@ -424,6 +438,15 @@ def load():
         "archon_hip_fm_doc_of": [vp, vp, ctypes.c_uint64, vp, vp],
         "archon_hip_fm_doc_of_dev": [vp, vp, ctypes.c_uint64, vp, vp, vp],
         "archon_hip_get_fm_doc_stats": [i32, ctypes.POINTER(FmDocStats)],
+        "archon_hip_fm_attach_wm": [vp],
+        "archon_hip_block_fm_attach_wm": [vp, vp],
+        "archon_hip_fm_win_count": [vp, vp, vp, vp, vp, u32, vp],
+        "archon_hip_fm_win_count_dev": [vp, vp, vp, vp, vp, u32, vp, vp],
+        "archon_hip_fm_win_select": [vp, vp, vp, vp, vp, vp, u32, vp],
+        "archon_hip_fm_win_select_dev": [vp, vp, vp, vp, vp, vp, u32, vp, vp],
+        "archon_hip_fm_win_list": [vp, vp, vp, vp, vp, u32, u32, vp, vp, ctypes.c_uint64, vp],
+        "archon_hip_fm_win_list_dev": [vp, vp, vp, vp, vp, u32, u32, vp, vp, ctypes.c_uint64, vp, vp],
+        "archon_hip_fm_win_last_stats": [i32, ctypes.POINTER(FmWinStats)],
         "archon_hip_repeats": [vp, vp, u32, u32, u32, u32, u32, vp, ctypes.c_uint64, vp, i32],
         "archon_hip_repeats_dev": [vp, vp, u32, u32, u32, u32, u32, vp, ctypes.c_uint64, vp, i32, vp],
         "archon_hip_block_repeats": [vp, u32, u32, u32, vp, ctypes.c_uint64, vp],
@@ -647,6 +670,11 @@ def fm_text_stats(dev=0):
 def fm_doc_stats(dev=0):
     """FmDocStats of the calling thread's last documents call (attach_docs, docs, docs_ranges, doc_of) on dev"""
     return _last_stats(FmDocStats, "archon_hip_get_fm_doc_stats", dev)
+
+
+def fm_win_stats(dev=0):
+    """the calling thread's last window call (attach_wm, win_count, win_select, win_list) on `dev` as a dict"""
+    return _last_stats(FmWinStats, "archon_hip_fm_win_last_stats", dev)
 
 
 def rlz_decode(x, phrases, m, literals=None):
@@ -1123,6 +1151,21 @@ def _docs(call, k, emit):
     return ndocs[:k], out[:total.value]
 
 
+def _win_queries(lo, hi, a, b, idx=None):
+    """the queries of a window call as uint32 arrays of one length k (never of size 0: a pointer is always there) and k"""
+    if (a is None) != (b is None):
+        raise ValueError("window: a and b are both given or both None")
+    arrs = [np.ascontiguousarray(v, dtype=np.uint32).ravel() if v is not None else None for v in (lo, hi, a, b, idx)]
+    k = arrs[0].size
+    if any(v is not None and v.size != k for v in arrs):
+        raise ValueError("window: lo, hi, a, b and idx differ in length")
+    return [(v if k else np.zeros(1, np.uint32)) if v is not None else None for v in arrs], k
+
+
+def _tp(t):
+    return ctypes.c_void_p(t.data_ptr()) if t is not None else None
+
+
 def _bounds(bounds):
     bounds = np.ascontiguousarray(bounds, dtype=np.uint32).ravel()
     if bounds.size < 1:
@@ -1490,6 +1533,96 @@ class FmIndex:
         _check(lib().archon_hip_fm_doc_of(self.h, _p(items) if items.size else None, items.size, _p(doc), _p(off) if offsets else None))
         return doc[:items.size], (off[:items.size] if offsets else None)
 
+    def attach_wm(self):
+        """builds the wavelet matrix over the attached suffix array for win_count(), win_select(), win_list(), first() and
+        locate_sorted(): about bits(n) * (n/8 + n/64) bytes on the device.  Needs attach_sa(); replaces an earlier one; returns self"""
+        _check(lib().archon_hip_fm_attach_wm(self.h))
+        return self
+
+    def win_count(self, lo, hi, a=None, b=None):
+        """count[j] = how many rows r of [lo[j], hi[j]) have a[j] <= sa[r] < b[j] (a and b None: all of them).  Needs attach_wm()"""
+        (lo, hi, a, b, _), k = _win_queries(lo, hi, a, b)
+        count = np.zeros(max(k, 1), np.uint32)
+        _check(lib().archon_hip_fm_win_count(self.h, _p(lo), _p(hi), _p(a) if a is not None else None, _p(b) if b is not None else None, k, _p(count)))
+        return count[:k]
+
+    def win_count_dev(self, lo_t, hi_t, count_t, a_t=None, b_t=None):
+        """torch int32 tensors on the device: lo, hi [k], a, b [k] or None, count [k] (written); current stream"""
+        _check(lib().archon_hip_fm_win_count_dev(self.h, _tp(lo_t), _tp(hi_t), _tp(a_t), _tp(b_t), lo_t.numel(), _tp(count_t), _stream_ptr()))
+
+    def win_select(self, lo, hi, idx, a=None, b=None):
+        """item[j] = the idx[j]-th smallest sa[r] (0-based) of the rows of [lo[j], hi[j]) with a[j] <= sa[r] < b[j], 0 when there
+        are idx[j] of them or fewer"""
+        (lo, hi, a, b, idx), k = _win_queries(lo, hi, a, b, idx)
+        item = np.zeros(max(k, 1), np.uint32)
+        _check(lib().archon_hip_fm_win_select(self.h, _p(lo), _p(hi), _p(a) if a is not None else None, _p(b) if b is not None else None, _p(idx), k,
+                                              _p(item)))
+        return item[:k]
+
+    def win_select_dev(self, lo_t, hi_t, idx_t, item_t, a_t=None, b_t=None):
+        """torch int32 tensors on the device: lo, hi, idx [k], a, b [k] or None, item [k] (written); current stream"""
+        _check(lib().archon_hip_fm_win_select_dev(self.h, _tp(lo_t), _tp(hi_t), _tp(a_t), _tp(b_t), _tp(idx_t), lo_t.numel(), _tp(item_t),
+                                                  _stream_ptr()))
+
+    def win_list(self, lo, hi, a=None, b=None, most=0, emit=True):
+        """(count, records): count[j] the size of window j, records an FM_WIN array with the min(count[j], most) smallest items of
+        every window (most 0: all), range by range and ascending within a range (None with emit=False: counts only)"""
+        (lo, hi, a, b, _), k = _win_queries(lo, hi, a, b)
+        count = np.zeros(max(k, 1), np.uint32)
+        total = ctypes.c_uint64(0)
+        tp = ctypes.cast(ctypes.byref(total), ctypes.c_void_p)
+        fn = lib().archon_hip_fm_win_list
+        call = lambda out, cap: fn(self.h, _p(lo), _p(hi), _p(a) if a is not None else None, _p(b) if b is not None else None, k, int(most),  # noqa: E731
+                                   _p(count), out, cap, tp)
+        if not emit:
+            _check(call(None, 0))
+            return count[:k], None
+        out = np.zeros(max(4 * k, 1), FM_WIN)
+        rc = call(_p(out), out.size)
+        if rc == E_ARG and total.value > out.size:
+            out = np.zeros(total.value, FM_WIN)
+            rc = call(_p(out), out.size)
+        _check(rc)
+        return count[:k], out[:total.value]
+
+    def win_list_dev(self, lo_t, hi_t, count_t, out_t=None, a_t=None, b_t=None, most=0):
+        """torch int32 tensors on the device: lo, hi [k], a, b [k] or None, count [k] (written), out 2 words per record or None;
+        current stream.  Returns the number of records"""
+        total = ctypes.c_uint64(0)
+        cap = out_t.numel() // 2 if out_t is not None else 0
+        _check(lib().archon_hip_fm_win_list_dev(self.h, _tp(lo_t), _tp(hi_t), _tp(a_t), _tp(b_t), lo_t.numel(), int(most), _tp(count_t), _tp(out_t), cap,
+                                                ctypes.cast(ctypes.byref(total), ctypes.c_void_p), _stream_ptr()))
+        return total.value
+
+    def count_ranges(self, patterns):
+        """count() as valid row ranges: a pattern that does not occur has an empty range wherever it lies, here [0, 0)"""
+        lo, hi = self.count(patterns)
+        occurs = lo < hi
+        return np.where(occurs, lo, 0).astype(np.uint32), np.where(occurs, hi, 0).astype(np.uint32)
+
+    def first(self, patterns, after=0):
+        """the first start of every pattern at or after `after`, -1 when there is none: an int64 array.  The count, then select 0
+        with a = after + m"""
+        _, offsets = _pack_patterns(patterns)
+        m = np.diff(offsets.astype(np.int64))
+        lo, hi = self.count_ranges(patterns)
+        a = np.minimum(int(after) + m, self.n + 1).astype(np.uint32)
+        b = np.full(lo.size, self.n + 1, np.uint32)
+        item = self.win_select(lo, hi, np.zeros(lo.size, np.uint32), a, b).astype(np.int64)
+        return np.where(item > 0, item - m, -1)
+
+    def locate_sorted(self, patterns, most=0):
+        """the starts of every pattern's occurrences in ascending order, the first `most` of them (0: all): a list of uint32
+        arrays -- sorted(locate()) without the locate"""
+        _, offsets = _pack_patterns(patterns)
+        m = np.diff(offsets.astype(np.int64))
+        lo, hi = self.count_ranges(patterns)
+        count, recs = self.win_list(lo, hi, most=most)
+        cuts = np.zeros(lo.size + 1, np.int64)
+        np.cumsum(np.minimum(count, most) if most else count, out=cuts[1:])
+        starts = (recs["item"].astype(np.int64) - m[recs["range"]]).astype(np.uint32)
+        return [starts[cuts[j]:cuts[j + 1]] for j in range(lo.size)]
+
     def locate_mems(self, mems):
         """the starts of every SMEM's occurrences from the samples (a list of uint32 arrays, one per SMEM, each in row order)"""
         return _locate_mems(lib().archon_hip_fm_locate_mems, self.h, mems)
@@ -1743,12 +1876,13 @@ class Block:
         got = _phrases(lambda out, cap, tp: fn(self.h, int(dir), _p(rec) if rec is not None and out is None else None, out, cap, tp), count_only)
         return (rec, got) if want_lpf else got
 
-    def fm_index(self, rate, mirror=False, sa=False, docs=None, lcp=False):
+    def fm_index(self, rate, mirror=False, sa=False, docs=None, wm=False, lcp=False):
         """a standalone sampled FmIndex of the last forward's BWT (samples from the SA when that forward kept one, else by the
         LF walk); it outlives later forwards and close().  mirror=True: with its mirror, built from the resident block.
         lcp=True: with the block's LCP array attached (needs forward(want_sa=True)); the array is made on the device.
         sa=True: with the block's suffix array attached, device to device (needs forward(want_sa=True)).
-        docs=bounds: cut into documents (FmIndex.attach_docs) from the resident suffix array (needs forward(want_sa=True))"""
+        docs=bounds: cut into documents (FmIndex.attach_docs) from the resident suffix array (needs forward(want_sa=True)).
+        wm=True: with the wavelet matrix (FmIndex.attach_wm) built from the resident suffix array (needs forward(want_sa=True))"""
         h = ctypes.c_void_p(None)
         _check(lib().archon_hip_block_fm_index(self.h, int(rate), ctypes.byref(h)))
         f = FmIndex(_handle=h)
@@ -1763,6 +1897,8 @@ class Block:
         if docs is not None:
             bounds = _bounds(docs)
             _check(lib().archon_hip_block_fm_attach_docs(self.h, f.h, _p(bounds), bounds.size - 1))
+        if wm:
+            _check(lib().archon_hip_block_fm_attach_wm(self.h, f.h))
         return f
 
     def stats(self):

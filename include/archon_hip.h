@@ -1530,6 +1530,104 @@ typedef struct archon_hip_fm_doc_stats {
 } archon_hip_fm_doc_stats;
 int  archon_hip_get_fm_doc_stats(int dev, archon_hip_fm_doc_stats *out);
 
+/* ---- windows: count, select and list a row range's occurrences in text order ----------------------------------------------------
+ * Every search above ends in a row range [lo, hi) of the suffix array, and a locate lists it in row order.  These calls answer
+ * in TEXT order without listing the range: how many of its occurrences end inside a window of the block, which is the first one
+ * at or after a position, the next, the last, the first ten.  The cost of an answer is ceil(log2(n+1)) rank steps however many
+ * rows the range has.
+ * Rows and items.  Rows are 0 .. n-1.  Items sa[r] are 1 .. n.
+ * Query.  A row range [lo, hi) with lo <= hi <= n and an item window [a, b) with a <= b <= n + 1.  Anything else is ARCHON_E_ARG.
+ * a and b both NULL mean the whole block (a = 0, b = n + 1); one of them NULL alone is ARCHON_E_ARG.
+ * Window of a query: the multiset { sa[r] : lo <= r < hi, a <= sa[r] < b }, in ascending item order.
+ * Occurrences.  An occurrence of an m-byte pattern at row r is x[sa[r]-m .. sa[r]), as everywhere else: the item is its END.
+ * Starts in [p, q) are items in [p + m, q + m).  Document d is items [bounds[d] + 1, bounds[d+1] + 1).
+ * count:  count[j] is the size of the window.
+ * select: item[j] is the idx[j]-th smallest item of the window (0-based), and 0 when the window has idx[j] items or fewer: 0 is no
+ *         item, so it is the sentinel.  idx = 0 gives the first occurrence at or after a, idx = count - 1 the last one before b.
+ * list:   range j emits its min(count[j], most) smallest items (most = 0: all of them) as records {item, range}, range by range
+ *         and ascending within a range.  count[j] is always the full window size; *total is the number of records.
+ * Examples: "banana", sa = 2 4 6 1 3 5.
+ *   rows [0, 3) ("a"), no window: count 3, list 2 4 6
+ *   rows [0, 3), window [3, 7): count 2, select 0 -> 4, select 1 -> 6, select 2 -> 0
+ *   rows [4, 6) ("an"), window [1, 4): count 1, list 3
+ *   rows [0, 6), window [2, 6), most 3: count 4, list 2 3 4
+ *   rows [2, 2), window [0, 7): count 0, list nothing, select 0 -> 0
+ * Structure: a wavelet matrix over the suffix array, one more device allocation of the handle.  L = ceil(log2(n+1)) levels (the
+ * bit length of n, at least 1), most significant bit first: level l holds bit L-1-l of every value in the level's order, and the
+ * order of level l+1 is the stable partition of level l, zeros first.  With B = ceil(n / 256) a level is 8 B words of bits and
+ * B + 1 directory words -- entry i the ones before bit 256 i, the last entry all ones of the level -- padded to 256 bytes:
+ *   wm_bytes = L * 256 * ceil(4 (9 B + 1) / 256)
+ * about L (n/8 + n/64) bytes: 4.1 n at n = 2^28, 3.5 n at 16 MiB.  It is built on the device, level by level, from two n-word
+ * buffers in the calling thread's context arena (a ballot per 64 values, a scan of the 256-bit blocks' popcounts, a stable scatter).
+ * archon_hip_fm_destroy frees it; handles without one behave exactly as before and refuse these calls with ARCHON_E_ARG.
+ * Method.  less(lo, hi, v), the items below v among the rows, walks the levels with two ranks each: a one bit of v adds the zeros
+ * of the range and maps it to z + rank1, a zero bit maps it to rank0.  v = 0 is 0 and v >= 2^L is hi - lo, both with no walk (at
+ * n = 2^k - 1 the bound n + 1 has L + 1 bits).  count = less(b) - less(a).  select walks once more with idx + less(a), taking the
+ * zero side while the index is below the zeros of the range; it is refused (item 0) when idx + less(a) >= less(b).  One lane
+ * answers one query; a list counts, scans min(count, most) and emits with one lane per record.
+ * walks (statistics) counts root-to-leaf walks: an empty range makes none; in a nonempty range a bound of 0 or >= 2^L makes none
+ * and every other bound makes one; every select and every emitted record makes one more, a refused select (item 0) none: it
+ * is settled by the two bounds.  So the walks of the bounds follow from n and the queries alone, while those of the selects and
+ * of the records, like in_window and listed, depend on the suffix array as the answers do.
+ * A handle serves one thread at a time (as above). */
+typedef struct archon_hip_fm_win {
+    uint32_t item;     /* sa[r] of a row of the range inside the window: the occurrence is x[item-m .. item) */
+    uint32_t range;    /* j: the range it belongs to */
+} archon_hip_fm_win;
+/* Builds the matrix from the handle's attached suffix array (archon_hip_fm_attach_sa; a handle without one is ARCHON_E_ARG).
+ * Replaces an earlier matrix; a refused attach leaves it in place.  The suffix array may be attached again or not afterwards,
+ * the matrix keeps what it made. */
+int  archon_hip_fm_attach_wm(archon_hip_fm *f);
+/* f a handle from archon_hip_block_fm_index of this block's last forward, which kept its suffix array: reads the resident array
+ * device to device and needs no archon_hip_fm_attach_sa; preconditions and ARCHON_E_ARG cases of archon_hip_block_fm_attach_docs */
+int  archon_hip_block_fm_attach_wm(archon_hip_block *b, archon_hip_fm *f);
+/* k queries on the host: lo[k], hi[k], a_or_null[k], b_or_null[k] -> count[k].  k = 0 does nothing. */
+int  archon_hip_fm_win_count(archon_hip_fm *f, const uint32_t *lo, const uint32_t *hi, const uint32_t *a_or_null, const uint32_t *b_or_null,
+                             uint32_t k, uint32_t *count);
+/* device arrays; on `stream` (NULL = the context's own), complete on return.  A bad query is found on the device: ARCHON_E_ARG,
+ * and what d_count holds then is unspecified */
+int  archon_hip_fm_win_count_dev(archon_hip_fm *f, const uint32_t *d_lo, const uint32_t *d_hi, const uint32_t *d_a_or_null,
+                                 const uint32_t *d_b_or_null, uint32_t k, uint32_t *d_count, void *stream);
+/* k queries and idx[k] on the host -> item[k] */
+int  archon_hip_fm_win_select(archon_hip_fm *f, const uint32_t *lo, const uint32_t *hi, const uint32_t *a_or_null, const uint32_t *b_or_null,
+                              const uint32_t *idx, uint32_t k, uint32_t *item);
+/* device arrays; on `stream`, complete on return; a bad query as in archon_hip_fm_win_count_dev */
+int  archon_hip_fm_win_select_dev(archon_hip_fm *f, const uint32_t *d_lo, const uint32_t *d_hi, const uint32_t *d_a_or_null,
+                                  const uint32_t *d_b_or_null, const uint32_t *d_idx, uint32_t k, uint32_t *d_item, void *stream);
+/* The list of k queries on the host.  The cap rule is that of archon_hip_fm_docs: count[k] and *total (the number of records) are
+ * always written; out_or_null NULL: counts only, no emit pass; cap < *total with out_or_null given is ARCHON_E_ARG with out
+ * untouched; k = 0 writes *total = 0 and nothing else.  *total is 0 after any other refusal.  More than 2^32 - 1 records is
+ * ARCHON_E_ARG. */
+int  archon_hip_fm_win_list(archon_hip_fm *f, const uint32_t *lo, const uint32_t *hi, const uint32_t *a_or_null, const uint32_t *b_or_null,
+                            uint32_t k, uint32_t most, uint32_t *count, archon_hip_fm_win *out_or_null, uint64_t cap, uint64_t *total);
+/* device queries, counts and records, *total on the host; on `stream`, complete on return.  A bad query is found on the device:
+ * ARCHON_E_ARG, nothing emitted */
+int  archon_hip_fm_win_list_dev(archon_hip_fm *f, const uint32_t *d_lo, const uint32_t *d_hi, const uint32_t *d_a_or_null,
+                                const uint32_t *d_b_or_null, uint32_t k, uint32_t most, uint32_t *d_count, archon_hip_fm_win *d_out_or_null,
+                                uint64_t cap, uint64_t *total, void *stream);
+/* the CALLING THREAD's last window call (attach, count, select or list) on `dev`; these calls leave every other statistics record
+ * alone.  n, levels, ranges, most, rows and wm_bytes follow from n and the queries alone; in_window, listed and walks also from the
+ * suffix array (the rule above); none but the times from anything else. */
+typedef struct archon_hip_fm_win_stats {
+    uint32_t n;                 /* block size of the index */
+    uint32_t levels;            /* L */
+    uint32_t ranges;            /* k */
+    uint32_t most;              /* of a list */
+    uint32_t attached;          /* 1 when the call built the matrix */
+    uint32_t reserved0;
+    uint64_t rows;              /* the sum of hi - lo */
+    uint64_t in_window;         /* the sum of the counts */
+    uint64_t listed;            /* records emitted */
+    uint64_t walks;             /* root-to-leaf walks made (the rule above) */
+    uint64_t wm_bytes;          /* bytes of the matrix (the formula above) */
+    uint32_t kernel_launches;   /* launches issued by the call */
+    uint32_t host_syncs;        /* times the host waited for the stream inside the call */
+    float ms_attach;            /* device time of the build (HIP events) */
+    float ms_count;             /* of the count or select kernel, and of a list's scan */
+    float ms_emit;              /* of the emit pass */
+} archon_hip_fm_win_stats;
+int  archon_hip_fm_win_last_stats(int dev, archon_hip_fm_win_stats *out);
+
 /* ---- measurement ------------------------------------------------------------- */
 
 /* Per-stage device times (HIP events on the stream the kernels ran on) and
