@@ -26,6 +26,7 @@
 #include "fm_doc.hiph"
 #include "fm_win.hiph"
 #include "fm_host.hiph"
+#include "analysis.hiph"
 #include "repeats.hiph"
 #include "lz.hiph"
 #include "kmers.hiph"
@@ -84,8 +85,8 @@ static int kmers_check(const void *sa, const void *lcp, uint64_t *total, uint32_
     return kmer_check_args(k, hist, bins);
 }
 
-// sa and lcp of host buffers through staging buffers 0 and 1
-static int kmer_stage(Ctx *c, hipStream_t s, const uint32_t *sa, const uint32_t *lcp, uint32_t n, uint32_t **d_sa, uint32_t **d_lcp)
+// sa and lcp of host buffers through staging buffers 0 and 1 (k-mers, minimal absent words, entropy, runs, LCE)
+static int stage_sa_lcp(Ctx *c, hipStream_t s, const uint32_t *sa, const uint32_t *lcp, uint32_t n, uint32_t **d_sa, uint32_t **d_lcp)
 {
     ARCHON_TRY(ctx_io(c, 0, (size_t)n * 4 + 64, (void **)d_sa));
     ARCHON_TRY(ctx_io(c, 1, (size_t)n * 4 + 64, (void **)d_lcp));
@@ -521,7 +522,7 @@ int archon_hip_repeats_dev(const uint32_t *d_lcp, const uint8_t *d_bwt, uint32_t
         KeepStats<archon_hip_repeat_stats> keep(t_rep_stats, dev);
         rep_call_stats(&keep.st, n, kind, min_len, min_occ);
         RepCall q = {d_lcp, d_bwt, n, base_id, kind, min_len, min_occ};
-        return rep_dev(c, s, q, d_out_or_null, cap, total, &keep.st);
+        return rep_list(c, s, q, d_out_or_null, cap, total, false, &keep.st);
     });
 }
 
@@ -541,7 +542,7 @@ int archon_hip_repeats(const uint32_t *lcp, const uint8_t *bwt, uint32_t n, uint
         ARCHON_HIP_TRY(hipMemcpyAsync(d_bwt, bwt, n, hipMemcpyHostToDevice, s));
         ARCHON_HIP_TRY(hipMemcpyAsync(d_lcp, lcp, (size_t)n * 4, hipMemcpyHostToDevice, s));
         RepCall q = {d_lcp, d_bwt, n, base_id, kind, min_len, min_occ};
-        return rep_to_host(c, s, q, out_or_null, cap, total, &keep.st);
+        return rep_list(c, s, q, out_or_null, cap, total, true, &keep.st);
     });
 }
 
@@ -591,7 +592,7 @@ int archon_hip_lz_parse_dev(const archon_hip_lpf_rec *d_lpf, uint32_t n, archon_
         lz_call_stats(&keep.st, n, 0);
         StageTimer tm(c, 96, s);
         ParseCall q = {reinterpret_cast<const uint32_t *>(d_lpf), n};
-        return parse_dev(c, s, tm, q, d_out_or_null, cap, total, &keep.st);
+        return parse_list(c, s, tm, q, d_out_or_null, cap, total, false, &keep.st);
     });
 }
 
@@ -607,7 +608,7 @@ int archon_hip_lz_parse(const archon_hip_lpf_rec *lpf, uint32_t n, archon_hip_ph
         ARCHON_HIP_TRY(hipMemcpyAsync(d_lpf, lpf, (size_t)n * 8, hipMemcpyHostToDevice, s));
         StageTimer tm(c, 96, s);
         ParseCall q = {d_lpf, n};
-        return parse_to_host(c, s, tm, q, out_or_null, cap, total, &keep.st);
+        return parse_list(c, s, tm, q, out_or_null, cap, total, true, &keep.st);
     });
 }
 
@@ -635,7 +636,7 @@ int archon_hip_kmers(const uint32_t *sa, const uint32_t *lcp, uint32_t n, uint32
         KeepStats<archon_hip_kmer_stats> keep(t_kmer_stats, dev);
         kmer_call_stats(&keep.st, n, k, min_occ, max_occ, bins, 0);
         uint32_t *d_sa = nullptr, *d_lcp = nullptr;
-        ARCHON_TRY(kmer_stage(c, s, sa, lcp, n, &d_sa, &d_lcp));
+        ARCHON_TRY(stage_sa_lcp(c, s, sa, lcp, n, &d_sa, &d_lcp));
         KmerCall q = {d_sa, d_lcp, n, k, min_occ, max_occ, bins};
         return kmer_list(c, s, q, out_or_null, cap, total, hist_or_null, true, &keep.st);
     });
@@ -659,7 +660,7 @@ int archon_hip_kmer_occ(const uint32_t *sa, const uint32_t *lcp, uint32_t n, uin
         KeepStats<archon_hip_kmer_stats> keep(t_kmer_stats, dev);
         kmer_call_stats(&keep.st, n, k, 0, 0, 0, 1);
         uint32_t *d_sa = nullptr, *d_lcp = nullptr;
-        ARCHON_TRY(kmer_stage(c, s, sa, lcp, n, &d_sa, &d_lcp));
+        ARCHON_TRY(stage_sa_lcp(c, s, sa, lcp, n, &d_sa, &d_lcp));
         KmerCall q = {d_sa, d_lcp, n, k};
         return kmer_occ_run(c, s, q, occ, true, &keep.st);
     });
@@ -682,7 +683,7 @@ int archon_hip_sus(const uint32_t *sa, const uint32_t *lcp, uint32_t n, uint32_t
         KeepStats<archon_hip_kmer_stats> keep(t_kmer_stats, dev);
         kmer_call_stats(&keep.st, n, 0, 0, 0, 0, 2);
         uint32_t *d_sa = nullptr, *d_lcp = nullptr;
-        ARCHON_TRY(kmer_stage(c, s, sa, lcp, n, &d_sa, &d_lcp));
+        ARCHON_TRY(stage_sa_lcp(c, s, sa, lcp, n, &d_sa, &d_lcp));
         return kmer_sus_run(c, s, d_sa, d_lcp, n, sus, true, &keep.st);
     });
 }
@@ -710,7 +711,7 @@ int archon_hip_maws(const uint32_t *sa, const uint32_t *lcp, const uint8_t *bwt,
         KeepStats<archon_hip_maw_stats> keep(t_maw_stats, dev);
         maw_call_stats(&keep.st, n, min_len, max_len);
         uint32_t *d_sa = nullptr, *d_lcp = nullptr;
-        ARCHON_TRY(kmer_stage(c, s, sa, lcp, n, &d_sa, &d_lcp));
+        ARCHON_TRY(stage_sa_lcp(c, s, sa, lcp, n, &d_sa, &d_lcp));
         return maw_over_copy(c, s, d_sa, d_lcp, bwt, nullptr, n, base_id, min_len, max_len, out_or_null, cap, total, true, &keep.st);
     });
 }
@@ -739,7 +740,7 @@ int archon_hip_entropy(const uint32_t *sa, const uint32_t *lcp, const uint8_t *b
         KeepStats<archon_hip_entropy_stats> keep(t_ent_stats, dev);
         ent_call_stats(&keep.st, n, nk, 0);
         uint32_t *d_sa = nullptr, *d_lcp = nullptr;
-        ARCHON_TRY(kmer_stage(c, s, sa, lcp, n, &d_sa, &d_lcp));
+        ARCHON_TRY(stage_sa_lcp(c, s, sa, lcp, n, &d_sa, &d_lcp));
         return ent_over_copy(c, s, d_sa, d_lcp, bwt, nullptr, n, base_id, ks, nk, out, &keep.st);
     });
 }
@@ -800,7 +801,7 @@ int archon_hip_lce(const uint32_t *sa, const uint32_t *lcp, uint32_t n, const ui
         KeepStats<archon_hip_run_stats> keep(t_run_stats, dev);
         run_call_stats(&keep.st, n, 0, 0, 0, 0, 1);
         uint32_t *d_sa = nullptr, *d_lcp = nullptr, *d_q = nullptr;
-        ARCHON_TRY(kmer_stage(c, st, sa, lcp, n, &d_sa, &d_lcp));
+        ARCHON_TRY(stage_sa_lcp(c, st, sa, lcp, n, &d_sa, &d_lcp));
         ARCHON_TRY(lce_stage(c, st, s, t, k, &d_q));
         ARCHON_TRY(lce_run(c, st, d_sa, d_lcp, n, d_q, d_q + k, k, d_q + 2 * (size_t)k, &keep.st));
         ARCHON_HIP_TRY(hipMemcpyAsync(out, d_q + 2 * (size_t)k, (size_t)k * 4, hipMemcpyDeviceToHost, st));
@@ -831,7 +832,7 @@ int archon_hip_runs(const uint32_t *sa, const uint32_t *lcp, const uint32_t *sa_
         KeepStats<archon_hip_run_stats> keep(t_run_stats, dev);
         run_call_stats(&keep.st, n, min_period, max_period, min_copies, min_len, 0);
         uint32_t *d_sa = nullptr, *d_lcp = nullptr, *d_sa_c = nullptr;
-        ARCHON_TRY(kmer_stage(c, s, sa, lcp, n, &d_sa, &d_lcp));
+        ARCHON_TRY(stage_sa_lcp(c, s, sa, lcp, n, &d_sa, &d_lcp));
         ARCHON_TRY(ctx_io(c, 2, (size_t)n * 4 + 64, (void **)&d_sa_c));
         ARCHON_HIP_TRY(hipMemcpyAsync(d_sa_c, sa_c, (size_t)n * 4, hipMemcpyHostToDevice, s));
         ARCHON_TRY(run_begin(c, s));
@@ -1555,7 +1556,7 @@ int archon_hip_block_repeats(archon_hip_block *b, uint32_t kind, uint32_t min_le
         uint32_t *d_lcp = nullptr;
         ARCHON_TRY(block_lcp_step(c, s, b, &d_lcp, &keep.st.ms_lcp));
         RepCall q = {d_lcp, b->d_bwt(), b->n, b->base, kind, min_len, min_occ};
-        return rep_to_host(c, s, q, out_or_null, cap, total, &keep.st);
+        return rep_list(c, s, q, out_or_null, cap, total, true, &keep.st);
     });
 }
 
@@ -1579,7 +1580,7 @@ int archon_hip_block_lz(archon_hip_block *b, uint32_t dir, archon_hip_lpf_rec *l
         ARCHON_TRY(lpf_run(c, s, tm, b->d_sa(), d_lcp, b->n, dir, d_lpf, &keep.st));
         if (lpf_or_null) ARCHON_HIP_TRY(hipMemcpyAsync(lpf_or_null, d_lpf, (size_t)b->n * 8, hipMemcpyDeviceToHost, s));
         ParseCall q = {reinterpret_cast<const uint32_t *>(d_lpf), b->n};
-        return parse_to_host(c, s, tm, q, out_or_null, cap, total, &keep.st);     // (its count waits for the stream: the records have arrived)
+        return parse_list(c, s, tm, q, out_or_null, cap, total, true, &keep.st);     // (its count waits for the stream: the records have arrived)
     });
 }
 

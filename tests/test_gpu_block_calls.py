@@ -23,10 +23,12 @@ LEVELS = 5                              # 256 Ki entries at F = 16: 16 Ki, 1 Ki,
 # (kernel_launches, host_syncs) of each caller's own record; a wait is one host wait for the call's stream
 LCP = (20, 10)                          # lcp_stats of a plain Block.lcp of this block (7 long rounds): every caller leaves the same
 # A caller's record counts its own launches and, as host_syncs, every wait of the call: the LCP step's ten and its own
-#   repeats   count only: one wait for the counters; with the repeats: the last C call, one wait for the counters, two for the records
-REPEATS = {"count": (9, LCP[1] + 1), "emit": (11, LCP[1] + 3)}
-#   lz        the LPF pass and the parse, count only / with the phrases (the last C call of the wrapper's two)
-LZ = {"count": (272, LCP[1] + 2), "emit": (274, LCP[1] + 4)}
+#   repeats   count only: one wait for the counters; with the repeats: the last C call, one wait for the counters, one for the records
+#             (two until the listing calls got one ending, analysis.hiph: the emit pass and the copy home had a wait each)
+REPEATS = {"count": (9, LCP[1] + 1), "emit": (11, LCP[1] + 2)}
+#   lz        the LPF pass and the parse, count only / with the phrases (the last C call of the wrapper's two; one wait for the
+#             phrases, as for the repeats)
+LZ = {"count": (272, LCP[1] + 2), "emit": (274, LCP[1] + 3)}
 #   attach    the guard and one kernel per level; one wait for the guard's flag
 ATTACH_LCP = (1 + LEVELS, LCP[1] + 1)
 
