@@ -25,6 +25,7 @@
 #include "fm_text.hiph"
 #include "fm_doc.hiph"
 #include "fm_win.hiph"
+#include "fm_ovl.hiph"
 #include "fm_host.hiph"
 #include "analysis.hiph"
 #include "repeats.hiph"
@@ -1453,6 +1454,64 @@ int archon_hip_fm_win_list_dev(archon_hip_fm *f, const uint32_t *d_lo, const uin
 
 int archon_hip_fm_win_last_stats(int dev, archon_hip_fm_win_stats *out) { return t_fmwin_stats.get(dev, out, "window call"); }
 
+// ---- overlaps
+int archon_hip_fm_attach_ends(archon_hip_fm *f, const uint32_t *ends, uint32_t ndocs)
+{
+    if (!f || !ends) { set_error("null pointer"); return ARCHON_E_ARG; }
+    ARCHON_TRY(fmo_check_ends(ends, ndocs));
+    if (!f->sa.mem) { set_error("FM attach ends: the handle has no suffix array (archon_hip_fm_attach_sa)"); return ARCHON_E_ARG; }
+    ARCHON_TRY(fmo_check_fit(f->n, ends, ndocs));
+    return with_ctx(f->dev, nullptr, [&](Ctx *c, hipStream_t s) -> int {
+        KeepStats<archon_hip_fm_ovl_stats> keep(t_fmo_stats, f->dev);
+        fmo_call_stats(&keep.st, f, 0, 0);
+        return fmo_attach_run(c, s, f, f->sa.sa, ends, nullptr, ndocs, &keep.st);
+    });
+}
+
+int archon_hip_fm_attach_ends_dev(archon_hip_fm *f, const uint32_t *d_ends, uint32_t ndocs, void *stream)
+{
+    if (!f || !d_ends) { set_error("null pointer"); return ARCHON_E_ARG; }
+    if (!ndocs) { set_error("FM attach ends: no documents"); return ARCHON_E_ARG; }
+    if (!f->sa.mem) { set_error("FM attach ends: the handle has no suffix array (archon_hip_fm_attach_sa)"); return ARCHON_E_ARG; }
+    ARCHON_TRY(fmo_check_fit(f->n, nullptr, ndocs));
+    return with_ctx(f->dev, stream, [&](Ctx *c, hipStream_t s) -> int {
+        KeepStats<archon_hip_fm_ovl_stats> keep(t_fmo_stats, f->dev);
+        fmo_call_stats(&keep.st, f, 0, 0);
+        return fmo_attach_run(c, s, f, f->sa.sa, nullptr, d_ends, ndocs, &keep.st);
+    });
+}
+
+// one overlaps call, host or device arrays: the checks both forms share, the context, the record.  *total is written whenever it
+// is given: 0 before any refusal
+static int fmo_call(archon_hip_fm *f, FmoCall q, void *stream, uint64_t *total)
+{
+    if (total) *total = 0;
+    if (!f || !q.pat || !q.off || !q.novl || !total) { set_error("null pointer"); return ARCHON_E_ARG; }
+    if (!q.min_len) { set_error("FM overlaps: min_len = 0"); return ARCHON_E_ARG; }
+    if (q.host) ARCHON_TRY(fm_check_offsets(q.off, q.k));
+    ARCHON_TRY(fmo_check_attached(f));
+    if (!q.k) return ARCHON_OK;
+    return with_ctx(f->dev, stream, [&](Ctx *c, hipStream_t s) -> int {
+        KeepStats<archon_hip_fm_ovl_stats> keep(t_fmo_stats, f->dev);
+        fmo_call_stats(&keep.st, f, q.k, q.min_len);
+        return fmo_run(c, s, q, total, &keep.st);
+    });
+}
+
+int archon_hip_fm_overlaps(archon_hip_fm *f, const uint8_t *patterns, const uint32_t *offsets, uint32_t k, uint32_t min_len, uint32_t *novl,
+                           archon_hip_fm_ovl *ovl_or_null, uint64_t cap, uint64_t *total)
+{
+    return fmo_call(f, FmoCall{f, k, min_len, patterns, offsets, true, novl, reinterpret_cast<fmo::FmOvl *>(ovl_or_null), cap}, nullptr, total);
+}
+
+int archon_hip_fm_overlaps_dev(archon_hip_fm *f, const uint8_t *d_patterns, const uint32_t *d_offsets, uint32_t k, uint32_t min_len, uint32_t *d_novl,
+                               archon_hip_fm_ovl *d_ovl_or_null, uint64_t cap, uint64_t *total, void *stream)
+{
+    return fmo_call(f, FmoCall{f, k, min_len, d_patterns, d_offsets, false, d_novl, reinterpret_cast<fmo::FmOvl *>(d_ovl_or_null), cap}, stream, total);
+}
+
+int archon_hip_fm_ovl_last_stats(int dev, archon_hip_fm_ovl_stats *out) { return t_fmo_stats.get(dev, out, "overlap call"); }
+
 // ---- resident blocks ---------------------------------------------------------------------------------------------------
 int archon_hip_block_create(int dev, archon_hip_block **out)
 {
@@ -1927,6 +1986,22 @@ int archon_hip_block_fm_attach_wm(archon_hip_block *b, archon_hip_fm *f)
         KeepStats<archon_hip_fm_win_stats> keep(t_fmwin_stats, b->dev);
         fmwin_call_stats(&keep.st, f, 0, 0);
         return fmwin_attach_run(c, s, f, b->d_sa(), &keep.st);
+    });
+}
+
+// the resident suffix array read where it is, device to device, as the documents' block form reads it
+int archon_hip_block_fm_attach_ends(archon_hip_block *b, archon_hip_fm *f, const uint32_t *ends, uint32_t ndocs)
+{
+    if (!b || !f || !ends) { set_error("null pointer"); return ARCHON_E_ARG; }
+    ARCHON_TRY(fmo_check_ends(ends, ndocs));
+    std::lock_guard<std::mutex> lkb(b->mu);
+    ARCHON_TRY(block_check(b, true));
+    ARCHON_TRY(block_check_handle(b, f, "FM attach ends"));
+    ARCHON_TRY(fmo_check_fit(f->n, ends, ndocs));
+    return with_ctx(b->dev, nullptr, [&](Ctx *c, hipStream_t s) -> int {
+        KeepStats<archon_hip_fm_ovl_stats> keep(t_fmo_stats, b->dev);
+        fmo_call_stats(&keep.st, f, 0, 0);
+        return fmo_attach_run(c, s, f, b->d_sa(), ends, nullptr, ndocs, &keep.st);
     });
 }
 

@@ -60,6 +60,8 @@ SYMBOLS = [
     "archon_hip_runs_last_stats",
     "archon_hip_fm_attach_wm", "archon_hip_block_fm_attach_wm", "archon_hip_fm_win_count", "archon_hip_fm_win_count_dev", "archon_hip_fm_win_select",
     "archon_hip_fm_win_select_dev", "archon_hip_fm_win_list", "archon_hip_fm_win_list_dev", "archon_hip_fm_win_last_stats",
+    "archon_hip_fm_attach_ends", "archon_hip_fm_attach_ends_dev", "archon_hip_block_fm_attach_ends", "archon_hip_fm_overlaps",
+    "archon_hip_fm_overlaps_dev", "archon_hip_fm_ovl_last_stats",
 ]
 
 # archon_hip_fm_hit: one distinct string within the distance of a pattern (FmIndex.approx, Block.fm_approx)
@@ -72,6 +74,8 @@ FM_MEM = np.dtype([("lo", "<u4"), ("hi", "<u4"), ("start", "<u4"), ("end", "<u4"
 FM_DOC = np.dtype([("doc", "<u4"), ("tf", "<u4"), ("row", "<u4"), ("range", "<u4")])
 # archon_hip_fm_win: one occurrence of a row range inside its item window (FmIndex.win_list): the item where it ends, its range
 FM_WIN = np.dtype([("item", "<u4"), ("range", "<u4")])
+# archon_hip_fm_ovl: one suffix-prefix overlap (FmIndex.overlaps): document `doc` ends with the first `len` bytes of query `query`; `row` its end row
+FM_OVL = np.dtype([("query", "<u4"), ("doc", "<u4"), ("len", "<u4"), ("row", "<u4")])
 # archon_hip_repeat: one repeat of a block (repeats, Block.repeats): rows [lo, hi) of a string of len bytes, its representative row
 REPEAT = np.dtype([("lo", "<u4"), ("hi", "<u4"), ("len", "<u4"), ("row", "<u4")])
 # struct archon_hip_lpf: the longest previous factor that ends at an item and the item where a copy of it ends (lpf, Block.lz)
@@ -232,6 +236,17 @@ class FmWinStats(_Record):
         ("reserved0", ctypes.c_uint32), ("rows", ctypes.c_uint64), ("in_window", ctypes.c_uint64), ("listed", ctypes.c_uint64),
         ("walks", ctypes.c_uint64), ("wm_bytes", ctypes.c_uint64), ("kernel_launches", ctypes.c_uint32), ("host_syncs", ctypes.c_uint32),
         ("ms_attach", ctypes.c_float), ("ms_count", ctypes.c_float), ("ms_emit", ctypes.c_float),
+    ]
+
+
+class FmOvlStats(_Record):
+    """archon_hip_fm_ovl_stats: the calling thread's last overlap call (attach_ends, overlaps) on a device"""
+    _fields_ = [
+        ("n", ctypes.c_uint32), ("docs", ctypes.c_uint32), ("queries", ctypes.c_uint32), ("min_len", ctypes.c_uint32), ("attached", ctypes.c_uint32),
+        ("longest", ctypes.c_uint32), ("pattern_bytes", ctypes.c_uint64), ("steps", ctypes.c_uint64), ("tested", ctypes.c_uint64),
+        ("hit", ctypes.c_uint64), ("overlaps", ctypes.c_uint64), ("emitted", ctypes.c_uint64), ("end_bytes", ctypes.c_uint64),
+        ("kernel_launches", ctypes.c_uint32), ("host_syncs", ctypes.c_uint32), ("ms_attach", ctypes.c_float), ("ms_count", ctypes.c_float),
+        ("ms_emit", ctypes.c_float), ("reserved0", ctypes.c_uint32),
     ]
 
 
@@ -447,6 +462,12 @@ def load():
         "archon_hip_fm_win_list": [vp, vp, vp, vp, vp, u32, u32, vp, vp, ctypes.c_uint64, vp],
         "archon_hip_fm_win_list_dev": [vp, vp, vp, vp, vp, u32, u32, vp, vp, ctypes.c_uint64, vp, vp],
         "archon_hip_fm_win_last_stats": [i32, ctypes.POINTER(FmWinStats)],
+        "archon_hip_fm_attach_ends": [vp, vp, u32],
+        "archon_hip_fm_attach_ends_dev": [vp, vp, u32, vp],
+        "archon_hip_block_fm_attach_ends": [vp, vp, vp, u32],
+        "archon_hip_fm_overlaps": [vp, vp, vp, u32, u32, vp, vp, ctypes.c_uint64, vp],
+        "archon_hip_fm_overlaps_dev": [vp, vp, vp, u32, u32, vp, vp, ctypes.c_uint64, vp, vp],
+        "archon_hip_fm_ovl_last_stats": [i32, ctypes.POINTER(FmOvlStats)],
         "archon_hip_repeats": [vp, vp, u32, u32, u32, u32, u32, vp, ctypes.c_uint64, vp, i32],
         "archon_hip_repeats_dev": [vp, vp, u32, u32, u32, u32, u32, vp, ctypes.c_uint64, vp, i32, vp],
         "archon_hip_block_repeats": [vp, u32, u32, u32, vp, ctypes.c_uint64, vp],
@@ -675,6 +696,48 @@ def fm_doc_stats(dev=0):
 def fm_win_stats(dev=0):
     """the calling thread's last window call (attach_wm, win_count, win_select, win_list) on `dev` as a dict"""
     return _last_stats(FmWinStats, "archon_hip_fm_win_last_stats", dev)
+
+
+def fm_ovl_stats(dev=0):
+    """the calling thread's last overlap call (attach_ends, overlaps) on `dev` as a dict"""
+    return _last_stats(FmOvlStats, "archon_hip_fm_ovl_last_stats", dev)
+
+
+def ends_from_bounds(bounds, trim=0):
+    """the ends of the documents cut by bounds[0 .. D] for FmIndex.attach_ends: bounds[1:] - trim, trim the bytes every document
+    finishes with that are no part of it (1 for a separator).  A document that `trim` would empty is refused"""
+    bounds = np.ascontiguousarray(bounds, dtype=np.int64).ravel()
+    trim = int(trim)
+    if bounds.size < 2:
+        raise ValueError("ends_from_bounds: no documents")
+    if trim < 0:
+        raise ValueError("ends_from_bounds: trim = %d" % trim)
+    short = np.flatnonzero(np.diff(bounds) <= trim)
+    if short.size:
+        raise ValueError("ends_from_bounds: document %d has %d bytes, trim = %d would empty it" % (short[0], bounds[short[0] + 1] - bounds[short[0]], trim))
+    return (bounds[1:] - trim).astype(np.uint32)
+
+
+def best_overlaps(records):
+    """the longest overlap of every (query, doc) pair of an FM_OVL array from FmIndex.overlaps, in its order.  The records come
+    by query and ascending length, so the longest of a pair is its last one"""
+    records = np.ascontiguousarray(records, FM_OVL)
+    if records.size == 0:
+        return records
+    key = (records["query"].astype(np.uint64) << np.uint64(32)) | records["doc"].astype(np.uint64)
+    rev = key[::-1]
+    _, first_rev = np.unique(rev, return_index=True)            # the first of a pair in reversed order: its last
+    return records[np.sort(records.size - 1 - first_rev)]
+
+
+def drop_self(records, query_doc):
+    """the records whose doc is not the query's own document, query_doc[j] the document query j was taken from: the
+    all-against-all case where the queries are the documents"""
+    records = np.ascontiguousarray(records, FM_OVL)
+    query_doc = np.ascontiguousarray(query_doc, dtype=np.int64).ravel()
+    if records.size == 0:
+        return records
+    return records[query_doc[records["query"]] != records["doc"]]
 
 
 def rlz_decode(x, phrases, m, literals=None):
@@ -1623,6 +1686,52 @@ class FmIndex:
         starts = (recs["item"].astype(np.int64) - m[recs["range"]]).astype(np.uint32)
         return [starts[cuts[j]:cuts[j + 1]] for j in range(lo.size)]
 
+    def attach_ends(self, ends):
+        """marks where the documents of the block end (uint32 ends[D], 1 <= ends[0] < ... < ends[D-1] <= n; ends_from_bounds) for
+        overlaps(): 256 ceil(12 D / 256) + 256 ceil(4 (9 ceil(n / 256) + 1) / 256) bytes on the device, about 0.14 n + 12 D.
+        Needs attach_sa(); replaces earlier ends; returns self"""
+        ends = np.ascontiguousarray(ends, dtype=np.uint32).ravel()
+        _check(lib().archon_hip_fm_attach_ends(self.h, _p(ends) if ends.size else None, ends.size))
+        return self
+
+    def attach_ends_dev(self, ends_t, stream=None):
+        """the same from a torch int32 tensor of D words on the device, on `stream` (a raw HIP stream; None: the current torch
+        stream); returns self"""
+        _check(lib().archon_hip_fm_attach_ends_dev(self.h, ctypes.c_void_p(ends_t.data_ptr()), ends_t.numel(),
+                                                   _stream_ptr() if stream is None else ctypes.c_void_p(stream)))
+        return self
+
+    def overlaps(self, patterns, min_len, emit=True):
+        """the suffix-prefix overlaps of every pattern with the documents: (novl, records), novl[j] the overlaps of pattern j,
+        records an FM_OVL array pattern by pattern, by ascending length and by ascending end row (None with emit=False: counts
+        only).  A record says that document `doc` ends with the first `len` >= min_len bytes of the pattern.  Needs attach_ends()"""
+        packed, offsets = _pack_patterns(patterns)
+        k = offsets.size - 1
+        novl = np.zeros(max(k, 1), np.uint32)
+        total = ctypes.c_uint64(0)
+        tp = ctypes.cast(ctypes.byref(total), ctypes.c_void_p)
+        fn = lib().archon_hip_fm_overlaps
+        call = lambda out, cap: fn(self.h, _p(packed), _p(offsets), k, int(min_len), _p(novl), out, cap, tp)  # noqa: E731
+        if not emit:
+            _check(call(None, 0))
+            return novl[:k], None
+        out = np.zeros(max(4 * k, 1), FM_OVL)
+        rc = call(_p(out), out.size)
+        if rc == E_ARG and total.value > out.size:
+            out = np.zeros(total.value, FM_OVL)
+            rc = call(_p(out), out.size)
+        _check(rc)
+        return novl[:k], out[:total.value]
+
+    def overlaps_dev(self, patterns_t, offsets_t, min_len, novl_t, ovl_t=None):
+        """torch tensors on the device: patterns uint8, offsets int32[k + 1], novl int32[k] (written), ovl an int32 tensor of 4
+        words per record or None; current stream.  Returns the number of records"""
+        total = ctypes.c_uint64(0)
+        cap = ovl_t.numel() // 4 if ovl_t is not None else 0
+        _check(lib().archon_hip_fm_overlaps_dev(self.h, _tp(patterns_t), _tp(offsets_t), novl_t.numel(), int(min_len), _tp(novl_t), _tp(ovl_t), cap,
+                                                ctypes.cast(ctypes.byref(total), ctypes.c_void_p), _stream_ptr()))
+        return total.value
+
     def locate_mems(self, mems):
         """the starts of every SMEM's occurrences from the samples (a list of uint32 arrays, one per SMEM, each in row order)"""
         return _locate_mems(lib().archon_hip_fm_locate_mems, self.h, mems)
@@ -1876,13 +1985,14 @@ class Block:
         got = _phrases(lambda out, cap, tp: fn(self.h, int(dir), _p(rec) if rec is not None and out is None else None, out, cap, tp), count_only)
         return (rec, got) if want_lpf else got
 
-    def fm_index(self, rate, mirror=False, sa=False, docs=None, wm=False, lcp=False):
+    def fm_index(self, rate, mirror=False, sa=False, docs=None, wm=False, ends=None, lcp=False):
         """a standalone sampled FmIndex of the last forward's BWT (samples from the SA when that forward kept one, else by the
         LF walk); it outlives later forwards and close().  mirror=True: with its mirror, built from the resident block.
         lcp=True: with the block's LCP array attached (needs forward(want_sa=True)); the array is made on the device.
         sa=True: with the block's suffix array attached, device to device (needs forward(want_sa=True)).
         docs=bounds: cut into documents (FmIndex.attach_docs) from the resident suffix array (needs forward(want_sa=True)).
-        wm=True: with the wavelet matrix (FmIndex.attach_wm) built from the resident suffix array (needs forward(want_sa=True))"""
+        wm=True: with the wavelet matrix (FmIndex.attach_wm) built from the resident suffix array (needs forward(want_sa=True)).
+        ends=ends: with the documents' ends (FmIndex.attach_ends) from the resident suffix array (needs forward(want_sa=True))"""
         h = ctypes.c_void_p(None)
         _check(lib().archon_hip_block_fm_index(self.h, int(rate), ctypes.byref(h)))
         f = FmIndex(_handle=h)
@@ -1899,6 +2009,9 @@ class Block:
             _check(lib().archon_hip_block_fm_attach_docs(self.h, f.h, _p(bounds), bounds.size - 1))
         if wm:
             _check(lib().archon_hip_block_fm_attach_wm(self.h, f.h))
+        if ends is not None:
+            ends = np.ascontiguousarray(ends, dtype=np.uint32).ravel()
+            _check(lib().archon_hip_block_fm_attach_ends(self.h, f.h, _p(ends) if ends.size else None, ends.size))
         return f
 
     def stats(self):

@@ -1628,6 +1628,99 @@ typedef struct archon_hip_fm_win_stats {
 } archon_hip_fm_win_stats;
 int  archon_hip_fm_win_last_stats(int dev, archon_hip_fm_win_stats *out);
 
+/* ---- overlaps: which documents of a block end with a beginning of a pattern, and how long the shared piece is -------------------
+ * The suffix-prefix overlap, the edge of an overlap or string graph: the first step of an overlap-based assembler, of joining reads
+ * to contigs, of stitching fragments of logs or records.  archon_hip_fm_count gives the rows of a whole pattern, not of each of its
+ * prefixes, and the document listing names documents that hold an occurrence anywhere, not ones that END with it.
+ * Keys, R, occ', rows and the primary row are those of the search rule of archon_hip_fm_count.
+ * Ends.  The handle gets ends[0 .. D), items with 1 <= ends[0] < ends[1] < ... < ends[D-1] <= n; anything else is ARCHON_E_ARG.
+ * Document d ENDS AT item ends[d]: its last byte is x[ends[d]-1].  ends[D-1] = n is allowed; its end row is the primary row and is
+ * found like any other.  Where documents finish with a separator the caller passes the item before the separator
+ * (bounds[d+1] - 1), otherwise bounds[d+1].
+ * Overlap.  For a query Q of m bytes and a length l with min_len <= l <= min(m, n), document d overlaps Q by l when l <= ends[d]
+ * and x[ends[d]-l .. ends[d]) = Q[0..l).  As in the document listing, the piece may begin before the document does: a document
+ * shorter than l whose predecessors end the right way overlaps too.  Collections whose documents end with a byte the queries do
+ * not hold (a newline, a 0) have no such pieces.  l = m means the whole query is a suffix of the document; it is reported like
+ * any other overlap.
+ * Walk.  Q is walked as archon_hip_fm_count walks it, P[0] first, and the walk stops when the range empties: after l bytes the
+ * range [lo, hi) holds exactly the rows r with x[sa[r]-l .. sa[r]) = Q[0..l), and document d overlaps Q by l exactly when its END
+ * ROW, the row r with sa[r] = ends[d], lies in that range.  A query longer than n is walked as its first n bytes (unlike the
+ * count it is not refused a walk).  m = 0 gives no overlap.  min_len = 0 is ARCHON_E_ARG.
+ * Records.  {query, doc, len, row}, 16 bytes; row is the end row, so sa[row] = ends[doc].  The order is query by query, within a
+ * query by ascending len, within a length by ascending row.  It is the same on every run: it comes from a count pass and an emit
+ * pass over the identical search, and no atomics decide a position.
+ * Counts.  novl[k], the overlaps of every query, and *total, their sum, are always written.  A query whose count does not fit 32
+ * bits is ARCHON_E_ARG, and so are records asked for when *total does not.
+ * Example: "banana" (sa = 2 4 6 1 3 5), ends = {3, 6} ("ban", "ana"), min_len 1.
+ *   Q = "ana": l = 1 rows [0, 3), end row 2 (item 6): (doc 1, len 1, row 2); l = 2 rows [4, 6), end row 4 (item 3): (doc 0, len 2,
+ *              row 4); l = 3 rows [1, 3), end row 2: (doc 1, len 3, row 2).  3 overlaps, 2 rank steps, 3 lengths tested, 3 hit.
+ *   Q = "nab": l = 1 rows [4, 6): (doc 0, len 1, row 4); l = 2 rows [1, 3): (doc 1, len 2, row 2); l = 3 empty.  2 overlaps.
+ * Structure: the ends, one more device allocation of the handle: ends[D] | erow[D] | edoc[D] | one bit vector over the rows.  erow
+ * holds the end rows ascending, edoc[j] the document of erow[j]; the bit vector marks the end rows in the layout of a level of the
+ * wavelet matrix above (8 B words of bits, B + 1 directory words, B = ceil(n / 256), padded to 256 bytes):
+ *   end_bytes = 256 ceil(12 D / 256) + 256 ceil(4 (9 B + 1) / 256)
+ * about 0.14 n + 12 D bytes.  It is built on the device from the suffix array: a bitmap over the items from ends, one pass over sa
+ * that ballots isend[sa[r]] into the row words, a scan of the blocks' popcounts, a compaction.  An sa value outside 1 .. n is never
+ * used as an index; a suffix array whose end rows do not number D is ARCHON_E_CORRUPT.  archon_hip_fm_destroy frees
+ * it; handles without ends behave exactly as before and refuse archon_hip_fm_overlaps with ARCHON_E_ARG.
+ * Method.  One wave per query.  Every step is the rank step of archon_hip_fm_count; after the step that completes a length
+ * l >= min_len with rows in the range, c = rank1(hi) - rank1(lo) on the bit vector: one directory word and one 32-byte block each.
+ * The count pass sums c; the emit pass writes the c records of that length, 64 at a time, lane i from erow and edoc at
+ * rank1(lo) + i, at the exclusive sum of novl before the query plus the records of its shorter lengths.
+ * Launches and waits (kernel_launches, host_syncs of the statistics): an attach is 6 launches and 1 wait.  A search with
+ * ovl_or_null NULL is 1 launch and 1 wait.  With records asked for it is 4 launches (the count pass and the 3 of the scan) and 1
+ * wait when *total is 0 or the call is refused, and one launch and one wait more otherwise; a host form whose context arena has to
+ * grow for the records runs the count pass and the scan once more (4 launches more), which a repeated call does not.
+ * A handle serves one thread at a time (as above). */
+typedef struct archon_hip_fm_ovl {
+    uint32_t query;    /* j: the query it belongs to */
+    uint32_t doc;      /* d: the document that ends with Q[0..len) */
+    uint32_t len;      /* l */
+    uint32_t row;      /* the end row of the document: sa[row] = ends[doc] */
+} archon_hip_fm_ovl;
+/* ends[ndocs] on the host, checked on the host.  Needs the handle's attached suffix array (archon_hip_fm_attach_sa; else
+ * ARCHON_E_ARG), as archon_hip_fm_attach_docs does.  Replaces earlier ends; a refused attach leaves the handle exactly as it was,
+ * and the earlier ends still answer. */
+int  archon_hip_fm_attach_ends(archon_hip_fm *f, const uint32_t *ends, uint32_t ndocs);
+/* ends on the device; on `stream` (NULL = the context's own), complete on return.  A kernel checks the entries: ARCHON_E_ARG */
+int  archon_hip_fm_attach_ends_dev(archon_hip_fm *f, const uint32_t *d_ends, uint32_t ndocs, void *stream);
+/* f a handle from archon_hip_block_fm_index of this block's last forward, which kept its suffix array: reads the resident array
+ * device to device and needs no archon_hip_fm_attach_sa; preconditions and ARCHON_E_ARG cases of archon_hip_block_fm_attach_docs */
+int  archon_hip_block_fm_attach_ends(archon_hip_block *b, archon_hip_fm *f, const uint32_t *ends, uint32_t ndocs);
+/* novl[k] and *total (the sum of novl) always written.  ovl_or_null NULL: counting only (no emit pass).  cap < *total with ovl
+ * given: ARCHON_E_ARG, counts and *total written, ovl untouched.  Patterns and offsets as for archon_hip_fm_count; k = 0 writes
+ * *total = 0 and nothing else.  *total is 0 after any other refusal. */
+int  archon_hip_fm_overlaps(archon_hip_fm *f, const uint8_t *patterns, const uint32_t *offsets, uint32_t k, uint32_t min_len, uint32_t *novl,
+                            archon_hip_fm_ovl *ovl_or_null, uint64_t cap, uint64_t *total);
+/* device patterns, offsets, novl and ovl, *total a host pointer; on `stream` (NULL = the context's own), complete on return;
+ * decreasing offsets are found on the device (ARCHON_E_ARG, nothing emitted) */
+int  archon_hip_fm_overlaps_dev(archon_hip_fm *f, const uint8_t *d_patterns, const uint32_t *d_offsets, uint32_t k, uint32_t min_len,
+                                uint32_t *d_novl, archon_hip_fm_ovl *d_ovl_or_null, uint64_t cap, uint64_t *total, void *stream);
+/* the CALLING THREAD's last overlap call (attach or search) on `dev`; these calls leave every other statistics record alone.
+ * All but the times follow from the block, the ends and the queries alone. */
+typedef struct archon_hip_fm_ovl_stats {
+    uint32_t n;                 /* block size of the index */
+    uint32_t docs;              /* D */
+    uint32_t queries;           /* k */
+    uint32_t min_len;           /* of the call (0 for an attach) */
+    uint32_t attached;          /* 1 when the call attached ends */
+    uint32_t longest;           /* the longest overlap */
+    uint64_t pattern_bytes;     /* bytes of the patterns */
+    uint64_t steps;             /* rank steps (count pass) */
+    uint64_t tested;            /* lengths l >= min_len reached with rows in the range: two rank1 each */
+    uint64_t hit;               /* of them, lengths with at least one overlap */
+    uint64_t overlaps;          /* the sum of novl */
+    uint64_t emitted;           /* records written */
+    uint64_t end_bytes;         /* bytes of the ends (the formula above) */
+    uint32_t kernel_launches;   /* launches issued by the call (the statement above) */
+    uint32_t host_syncs;        /* times the host waited for the stream inside the call */
+    float ms_attach;            /* device time of the build (HIP events) */
+    float ms_count;             /* of the count pass, and of the scan when records are asked for */
+    float ms_emit;              /* of the emit pass */
+    uint32_t reserved0;
+} archon_hip_fm_ovl_stats;
+int  archon_hip_fm_ovl_last_stats(int dev, archon_hip_fm_ovl_stats *out);
+
 /* ---- measurement ------------------------------------------------------------- */
 
 /* Per-stage device times (HIP events on the stream the kernels ran on) and
